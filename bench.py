@@ -92,7 +92,12 @@ def parse():
                     help="weak: --batch-sites per GPU per step (default); strong: --batch-sites is the WHOLE job's batch "
                          "per step and every rank takes its contiguous 1/N of it (the fixed 1 M-site job of BASELINE "
                          "configs[3] = 8 steps of 131072 sites whatever N)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (rank 0 at N > 1: the records "
+                         "of every rank, gathered) as DIR/<field>.npy in float64, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.samples <= 0:
         args.samples = 1000000 if args.tile_job else 100000
     if args.tile_job:
@@ -122,6 +127,42 @@ def self_launch(args):
         print("[bench] the %d-rank launch failed (exit code %d); see the ranks' messages above" % (args.gpus, rc),
               file=sys.stderr)
     sys.exit(rc if rc != 0 else 0)
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6  # the files of a dump, headers included
+
+
+def dump_outputs(path, recs, grecs, seed):
+    """--dump-outputs: every field of the site records `recs` (S,) as DIR/<field>.npy and, with --groups, every field of the
+    group records `grecs` (S, G) as DIR/group_<field>.npy, all in float64 (every integer field is exact in it), one row per
+    site; DIR/site_index.npy holds each row's index in the step's records.  Every array is finite: a floating-point field whose
+    record holds NaN (undefined: e.g. the rank sums of a site without a variant) or an infinity is written as 0 there, and
+    DIR/<field>_nonfinite.npy (float32, the same shape) says which of them the record held: 0 finite, 1 NaN, 2 +inf, 3 -inf.
+    Past DUMP_MAX_BYTES in all, the rows are a fixed sample of the sites drawn with `seed` (sorted), the same for the same
+    arguments."""
+    import numpy as np
+    cols = [(n, recs[n]) for n in recs.dtype.names]
+    if grecs is not None:
+        cols += [("group_" + n, grecs[n]) for n in grecs.dtype.names if not n.startswith("reserved")]
+    S = len(recs)
+    width = [(int(np.prod(a.shape[1:], dtype=np.int64)), a.dtype.kind == "f") for _, a in cols]
+    row_bytes = 8 + sum(w * (12 if f else 8) for w, f in width)
+    n_files = 1 + len(cols) + sum(f for _, f in width)
+    keep = min(S, (DUMP_MAX_BYTES - 4096 * n_files) // row_bytes)  # (an .npy header is well under 4 KB)
+    idx = np.arange(S) if keep == S else np.sort(np.random.default_rng(seed).choice(S, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "site_index.npy"), idx.astype(np.float64))
+    for n, a in cols:
+        v = np.ascontiguousarray(a[idx], dtype=np.float64)
+        if a.dtype.kind == "f":
+            cls = np.zeros(v.shape, dtype=np.float32)
+            cls[np.isnan(v)] = 1
+            cls[v == np.inf] = 2
+            cls[v == -np.inf] = 3
+            np.save(os.path.join(path, n + "_nonfinite.npy"), cls)
+            v[cls != 0] = 0.0
+        np.save(os.path.join(path, n + ".npy"), v)
+    return keep
 
 
 def host_cpu():
@@ -736,6 +777,16 @@ def main():
         st_ms += s_; p1_ms += a1; p2_ms += a2; nsub += n_
     nvar = eng.last_variant_count()
     form = eng.last_launch_form()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's records, copied before anything below submits into the same buffers
+        if dist_on:
+            drecs = torch.cat([p.cpu() for p in gatherer.parts(last_slot[0])]).numpy().view(basevar_amd.SITE_DTYPE)
+        else:
+            drecs = outs[last_slot[0]].cpu().numpy().view(basevar_amd.SITE_DTYPE)
+        dgrecs = gouts[last_slot[0]].cpu().numpy().view(basevar_amd.GROUP_DTYPE).reshape(Bl, G) if G else None
+        n_dumped = dump_outputs(args.dump_outputs, drecs, dgrecs, args.seed)
+        print("[bench] --dump-outputs: %d of %d sites of the last timed step written to %s" % (
+            n_dumped, len(drecs), args.dump_outputs), file=sys.stderr, flush=True)
     gathered_ok = None
     ranks_verified = 0
     if rank == 0 and dist_on:

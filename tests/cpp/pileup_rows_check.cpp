@@ -4,10 +4,14 @@
 // (src/basetype_caller.cpp:1027-1101), reached here through oracle/_ref/libbvcaller.so (argv[1]).  Random tiles -- uncovered
 // positions, N calls, insertions, deletions, both strands, mapq 0-255, ranks to 65,535 -- are described to both; the text must
 // be equal byte for byte.
+// argv[1] = "-" runs without the library; argv[2] / argv[3] (optional) receive the product's / the reference's rows of every
+// round ("ROUND <r> <bytes>\n" + the rows), which tests/test_host_formats.py holds against the reference's rows stored under
+// tests/golden/ (tests/golden/make_golden.py pileup_rows).
 #include <dlfcn.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 
 #include "../../basevar_amd/host/pileup.hpp"
@@ -20,12 +24,24 @@ typedef char *(*write_rows_fn)(const char *, uint32_t, uint32_t, const char *, s
 typedef void (*free_fn)(char *);
 
 int main(int argc, char **argv) {
-    if (argc < 2) { std::cerr << "usage: pileup_rows_check <libbvcaller.so>\n"; return 2; }
-    void *h = dlopen(argv[1], RTLD_NOW);
-    if (!h) { std::cerr << dlerror() << "\n"; return 2; }
-    write_rows_fn ref_rows = (write_rows_fn)dlsym(h, "bvref_write_batchfile_rows");
-    free_fn ref_free = (free_fn)dlsym(h, "bvref_caller_free");
-    if (!ref_rows || !ref_free) { std::cerr << "symbols missing\n"; return 2; }
+    if (argc < 2) { std::cerr << "usage: pileup_rows_check <libbvcaller.so | -> [product_rows_out [reference_rows_out]]\n"; return 2; }
+    const bool live = std::strcmp(argv[1], "-") != 0;
+    write_rows_fn ref_rows = nullptr;
+    free_fn ref_free = nullptr;
+    if (live) {
+        void *h = dlopen(argv[1], RTLD_NOW);
+        if (!h) { std::cerr << dlerror() << "\n"; return 2; }
+        ref_rows = (write_rows_fn)dlsym(h, "bvref_write_batchfile_rows");
+        ref_free = (free_fn)dlsym(h, "bvref_caller_free");
+        if (!ref_rows || !ref_free) { std::cerr << "symbols missing\n"; return 2; }
+    }
+    FILE *prod_out = argc > 2 ? std::fopen(argv[2], "wb") : nullptr;
+    FILE *ref_out = live && argc > 3 ? std::fopen(argv[3], "wb") : nullptr;
+    auto put = [&](FILE *f, int round, const char *p, size_t n) {
+        if (!f) return;
+        std::fprintf(f, "ROUND %d %zu\n", round, n);
+        std::fwrite(p, 1, n, f);
+    };
     uint64_t st = 0x9e3779b97f4a7c15ull;
     auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
     int fails = 0;
@@ -79,6 +95,8 @@ int main(int argc, char **argv) {
         }
         std::string got;
         pileup_rows_text(t, fa, got);
+        put(prod_out, round, got.data(), got.size());
+        if (!live) { n_rows += len; continue; }
         std::vector<const char *> p_ref, p_read;
         for (size_t k = 0; k < e_ref.size(); ++k) { p_ref.push_back(e_ref[k].c_str()); p_read.push_back(e_read[k].c_str()); }
         size_t rl = 0;
@@ -86,6 +104,7 @@ int main(int argc, char **argv) {
         char *exp = ref_rows(t.ref_id.c_str(), beg, end, fa.c_str(), n, e_ref.size(), e_sample.data(), e_pos.data(), p_ref.data(),
                              p_read.data(), e_mapq.data(), e_rpr.data(), e_strand.data(), e_qual.data(), &rl, err, sizeof(err));
         if (!exp) { std::cerr << "reference threw: " << err << "\n"; ++fails; continue; }
+        put(ref_out, round, exp, rl);
         if (got != std::string(exp, rl)) {
             ++fails;
             size_t at = 0;
@@ -96,6 +115,8 @@ int main(int argc, char **argv) {
         n_rows += len;
         ref_free(exp);
     }
+    if (prod_out) std::fclose(prod_out);
+    if (ref_out) std::fclose(ref_out);
     std::cout << "PILEUP_ROWS rounds 60 rows " << n_rows << " claimed cells " << n_cells << " indel tokens " << n_indels << " FAILS " << fails << std::endl;
     return fails ? 1 : 0;
 }

@@ -3,7 +3,9 @@
 
 Run in the build container (where /root/reference exists):
 
-    make -C oracle ref && python tests/golden/make_golden.py
+    make -C oracle ref && python tests/golden/make_golden.py          # the fixtures below + known_answers.json
+    make -C oracle ref && python tests/golden/make_golden.py fresh    # reference_fresh/: records only (see write_fresh)
+    make -C oracle ref && python tests/golden/make_golden.py pileup_rows  # reference_pileup_rows.txt.gz (see write_pileup_rows)
 
 Each fixture is data only: the seeded input planes and the per-site records that the
 reference's own code (compiled unmodified into oracle/_ref/libbvref.so, see oracle/Makefile
@@ -177,6 +179,60 @@ FIXTURES = {
 }
 
 
+# tests/test_oracle_cpu.py::test_restatement_matches_reference_fresh: slabs that the test generates itself (make_slab, seeded);
+# only the reference's records for them are stored, with a digest of the planes they were computed from
+FRESH = [(101, 1500, 0.3, 2), (102, 6000, 0.08, 0), (103, 777, 0.9, 3)]
+
+
+def fresh_slab(seed, n, cov, groups):
+    return make_slab(120, n, seed=seed, coverage=cov, n_groups=groups, ref_n_frac=0.05)
+
+
+def planes_digest(slab):
+    import hashlib
+    h = hashlib.sha256()
+    for k in ("base_strand", "qual", "mapq", "rpr", "ref_base", "group_id"):
+        if slab.get(k) is not None:
+            h.update(k.encode() + np.ascontiguousarray(slab[k]).tobytes())
+    return h.hexdigest()
+
+
+def write_fresh():
+    ref = oracle.Reference()
+    res = oracle.Restatement()
+    os.makedirs(os.path.join(HERE, "reference_fresh"), exist_ok=True)
+    for seed, n, cov, groups in FRESH:
+        slab = fresh_slab(seed, n, cov, groups)
+        sites, gsites = ref.run(slab, res.min_af(n))
+        out = {"planes_sha256": np.array(planes_digest(slab)), "expected_sites": sites.view(np.uint8)}
+        if gsites is not None:
+            out["expected_groups"] = gsites.view(np.uint8).reshape(gsites.shape[0], -1)
+        path = os.path.join(HERE, "reference_fresh", "seed%d.npz" % seed)
+        np.savez_compressed(path, **out)
+        print("%-16s sites=%d variants=%d (%d bytes)" % (os.path.relpath(path, HERE), len(sites), int(((sites["status"] & 2) != 0).sum()),
+                                                       os.path.getsize(path)))
+
+
+PILEUP_ROWS = os.path.join(HERE, "reference_pileup_rows.txt.gz")
+
+
+def write_pileup_rows():
+    """The batchfile rows that the reference's __write_record_to_batchfile (oracle/_ref/libbvcaller.so) writes for the random
+    tiles of tests/cpp/pileup_rows_check.cpp, every round framed as that harness frames them."""
+    import gzip
+    import subprocess
+    import tempfile
+    lib = os.path.join(ROOT, "oracle", "_ref", "libbvcaller.so")
+    with tempfile.TemporaryDirectory() as tmp:
+        exe, rows = os.path.join(tmp, "pileup_rows_check"), os.path.join(tmp, "rows.txt")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "tests", "cpp", "pileup_rows_check.cpp"), "-ldl", "-lz", "-o", exe])
+        subprocess.check_call([exe, lib, os.devnull, rows])
+        with open(rows, "rb") as f, open(PILEUP_ROWS, "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as z:
+            z.write(f.read())
+    print("%s (%d bytes)" % (os.path.basename(PILEUP_ROWS), os.path.getsize(PILEUP_ROWS)))
+
+
 def main():
     ref = oracle.Reference()
     res = oracle.Restatement()
@@ -212,4 +268,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    {"fresh": write_fresh, "pileup_rows": write_pileup_rows}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()

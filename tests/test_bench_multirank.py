@@ -12,6 +12,9 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# Ranks self-launched onto ONE device: a GPU node admits at most 6 processes with the GPU open at once, and beside the ranks
+# two more hold it here -- the pytest process and the torch.distributed.run agent (its launcher asks torch.cuda.is_available()).
+ONE_DEVICE_MAX_RANKS = 4
 
 
 @pytest.mark.gpu
@@ -69,22 +72,23 @@ def _run_bench(extra, world, env_extra=None, timeout=900):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("samples", [6000, 60000], ids=["short_rows", "long_rows"])
-def test_bench_eight_ranks_one_device_every_rank_verified(samples):
-    """BASELINE configs[3] in small, at the driver's largest rank count: 8 ranks (one device, gloo), every rank its
-    contiguous site range of every batch; rank 0 re-runs the first sites of EVERY rank's last batch as a one-rank job
-    and the gathered records must equal them byte for byte, in rank order (reference analogue: the fan-out and ordered
-    merge of src/basetype_caller.cpp:469-525)."""
-    d = _run_bench(["--steps", "3", "--warmup", "1", "--samples", str(samples), "--batch-sites", "512", "--verify-sites", "128"], 8)
+def test_bench_four_ranks_one_device_every_rank_verified(samples):
+    """BASELINE configs[3] in small, at the largest rank count one device takes here (ONE_DEVICE_MAX_RANKS = 4 ranks, gloo;
+    the driver's largest is 8, one per GPU), every rank its contiguous site range of every batch; rank 0 re-runs the first
+    sites of EVERY rank's last batch as a one-rank job and the gathered records must equal them byte for byte, in rank
+    order (reference analogue: the fan-out and ordered merge of src/basetype_caller.cpp:469-525)."""
+    d = _run_bench(["--steps", "3", "--warmup", "1", "--samples", str(samples), "--batch-sites", "512", "--verify-sites", "128"], ONE_DEVICE_MAX_RANKS)
     c = d["config"]
-    assert d["n_gpus"] == 8 and c["dist_world_size"] == 8 and c["job_batch_sites"] == 8 * 512
-    assert c["gathered_records_ok"] is True and c["ranks_verified"] == 8 and c["verify_sites"] == 128, d["_stderr"]
-    assert len(c["per_rank"]["step_ms"]) == 8 and all(t > 0 for t in c["per_rank"]["step_ms"])
-    assert len(c["per_rank"]["pass1_frac"]) == 8
+    W = ONE_DEVICE_MAX_RANKS
+    assert d["n_gpus"] == W and c["dist_world_size"] == W and c["job_batch_sites"] == W * 512
+    assert c["gathered_records_ok"] is True and c["ranks_verified"] == W and c["verify_sites"] == 128, d["_stderr"]
+    assert len(c["per_rank"]["step_ms"]) == W and all(t > 0 for t in c["per_rank"]["step_ms"])
+    assert len(c["per_rank"]["pass1_frac"]) == W
     assert d["ms_per_step"] == pytest.approx(max(c["per_rank"]["step_ms"]), rel=1e-9)  # the slowest rank's time
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("world", [1, 2, 8])
+@pytest.mark.parametrize("world", [1, 2, ONE_DEVICE_MAX_RANKS])
 def test_bench_tile_job_ranks_one_device(world):
     """BASELINE configs[4] in small: `--tile-job` makes the tile job THE timed workload -- every rank streams its own
     site range as tiles of --tile-width samples from pinned host memory (src/basetype_caller.cpp:419-453, 589-601), the
@@ -188,18 +192,22 @@ def _n_devices():
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_two_ranks_rccl_two_devices(scaling):
     """The driver's N = 2 run in small: `bench.py --gpus 2` with the RCCL backend, one rank per GPU, the ordered gather of
-    records over xGMI (reference analogue: the fan-out and file merge of src/basetype_caller.cpp:469-525).  Skipped on a
-    one-GPU box; the first multi-GPU lease produces evidence instead of a first run."""
-    if _n_devices() < 2:
-        pytest.skip("needs two GPUs (this box has %d)" % _n_devices())
+    records over xGMI (reference analogue: the fan-out and file merge of src/basetype_caller.cpp:469-525).  On a one-GPU box
+    the same launch cannot run (RCCL refuses two ranks on one device, and rank 1 has no device of its own): there it must end
+    the way an undersized box ends it -- rank 1's device error, relayed by the parent with a non-zero exit code, no JSON line."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BASEVAR_BENCH_BACKEND", "BASEVAR_BENCH_ONE_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--samples", "20000",
            "--batch-sites", "4096", "--no-cpu-baseline", "--scaling", scaling]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
-    assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    if _n_devices() < 2:
+        assert p.returncode != 0 and not lines, (p.returncode, p.stdout[-1000:])
+        assert "invalid device ordinal" in p.stderr and "2-rank launch failed" in p.stderr, p.stderr[-3000:]
+        assert "must be launched with" not in p.stderr and "needs a GPU" not in p.stderr
+        return
+    assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == scaling and d["value"] > 0
@@ -209,18 +217,19 @@ def test_bench_two_ranks_rccl_two_devices(scaling):
 
 
 @pytest.mark.gpu
-def test_bench_preflight_at_eight_ranks_and_a_job_that_does_not_fit():
+def test_bench_preflight_at_four_ranks_and_a_job_that_does_not_fit():
     """Before anything is allocated every rank reports what it will allocate against its free HBM, its GPU's NUMA node and the
     host memory a tile job pins; rank 0 prints the table.  A job that cannot fit ends on EVERY rank with exit code 3 and a
     message -- not with an allocator error minutes into the run."""
     d = _run_bench(["--steps", "2", "--warmup", "1", "--tile-job", "--tile-sites", "64", "--samples", "20000", "--tile-width", "200", "--tile-distinct", "8",
-                    "--verify-sites", "32"], 8)
+                    "--verify-sites", "32"], ONE_DEVICE_MAX_RANKS)
+    W = ONE_DEVICE_MAX_RANKS
     pre = [l for l in d["_stderr"].splitlines() if l.startswith("[bench preflight] ")]
     assert len(pre) == 1, d["_stderr"]
     t = json.loads(pre[0][len("[bench preflight] "):])
-    assert t["ranks"] == 8 and t["fits"] is True and len(t["hbm_free_GB_per_rank"]) == 8 and len(t["numa_node_of_gpu"]) == 8
+    assert t["ranks"] == W and t["fits"] is True and len(t["hbm_free_GB_per_rank"]) == W and len(t["numa_node_of_gpu"]) == W
     assert all(x > 0 for x in t["host_pinned_GB_per_rank"]) and all(a < b for a, b in zip(t["hbm_needed_GB_per_rank"], t["hbm_free_GB_per_rank"]))
-    assert d["config"]["ranks_verified"] == 8
+    assert d["config"]["ranks_verified"] == W
     # ... and one that cannot: 4 M sites x 100 k samples per rank = 2 TB of planes
     env = dict(os.environ, BASEVAR_BENCH_BACKEND="gloo", BASEVAR_BENCH_ONE_DEVICE="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):

@@ -550,16 +550,21 @@ def test_pileup_row_writer_against_the_references_own(tmp_path):
     """SURVEY 8 f2, the writer half: pileup_rows_text (host/pileup.hpp: dense position x sample planes + indel tokens -> batchfile
     rows) against the reference's `__write_record_to_batchfile` (basetype_caller.cpp:1027-1101, compiled where it lies:
     oracle/_ref/libbvcaller.so) on random tiles -- uncovered positions, N calls, insertions, deletions, both strands, ranks to
-    65,535: byte for byte.  (The CIGAR walk that fills the planes reads BAM records through htslib and stays unpinned.)"""
+    65,535: byte for byte.  (The CIGAR walk that fills the planes reads BAM records through htslib and stays unpinned.)
+    The reference's rows for those tiles are stored (tests/golden/reference_pileup_rows.txt.gz); the library, where it is
+    built, is compared live as well."""
     import ref_caller
     oracle.build(with_ref=True)
-    if not ref_caller.available():
-        pytest.skip("oracle/_ref/libbvcaller.so not available (no reference sources here)")
     exe = str(tmp_path / "pileup_rows_check")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", "pileup_rows_check.cpp"), "-ldl", "-lz", "-o", exe])
-    out = subprocess.run([exe, ref_caller.LIB], capture_output=True, text=True)
+    rows = str(tmp_path / "rows.txt")
+    out = subprocess.run([exe, ref_caller.LIB if ref_caller.available() else "-", rows], capture_output=True, text=True)
     assert out.returncode == 0 and "FAILS 0" in out.stdout, (out.stdout[-500:], out.stderr[-2000:])
+    assert "PILEUP_ROWS rounds 60 " in out.stdout
+    with open(rows, "rb") as f:
+        got = f.read()
+    assert got == gzip.open(os.path.join(ROOT, "tests", "golden", "reference_pileup_rows.txt.gz"), "rb").read()
 
 
 def test_tbi_reader_on_an_index_written_by_htslib():

@@ -2,14 +2,15 @@
 
 1. oracle/refcpu.c (the restatement) == committed golden vectors, which were produced by the
    REAL reference compiled from /root/reference (tests/golden/make_golden.py).
-2. restatement == real reference on fresh seeded slabs, when oracle/_ref is available
-   (always in the build container; on the GPU box too, since the built .so travels).
+2. restatement == real reference on fresh seeded slabs: the reference's records for them are stored under
+   tests/golden/reference_fresh/, and where oracle/_ref is built the live reference must still give them.
 3. known answers for the inputs of the reference's own tests/io/test_algorithm.cpp:13-31.
 4. independent cross-check of the special functions against scipy.
 """
 import glob
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -18,6 +19,8 @@ import oracle
 from basevar_amd.synth import make_slab
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+sys.path.insert(0, GOLDEN)
+import make_golden  # noqa: E402
 EXACT_SKIP = ("chi2", "em_iters", "n_em")  # not observable through the reference's public API
 
 
@@ -55,12 +58,20 @@ def test_restatement_matches_golden(restatement, path):
         assert_bit_equal(ggot, gexp)
 
 
-@pytest.mark.parametrize("seed,n,cov,groups", [(101, 1500, 0.3, 2), (102, 6000, 0.08, 0), (103, 777, 0.9, 3)])
-def test_restatement_matches_reference_fresh(restatement, reference, seed, n, cov, groups):
-    slab = make_slab(120, n, seed=seed, coverage=cov, n_groups=groups, ref_n_frac=0.05)
+@pytest.mark.parametrize("seed,n,cov,groups", make_golden.FRESH)
+def test_restatement_matches_reference_fresh(restatement, seed, n, cov, groups):
+    slab = make_golden.fresh_slab(seed, n, cov, groups)
+    d = np.load(os.path.join(GOLDEN, "reference_fresh", "seed%d.npz" % seed))
+    assert str(d["planes_sha256"]) == make_golden.planes_digest(slab), "make_slab no longer draws the slab the records were stored for"
+    b = d["expected_sites"].view(oracle.SITE_DTYPE).reshape(-1)
+    gb = d["expected_groups"].view(oracle.GROUP_DTYPE).reshape(len(b), -1) if groups else None
     maf = restatement.min_af(n)
-    a, ga = restatement.run(slab, maf)
-    b, gb = reference.run(slab, maf)
+    if oracle.ref_available():  # the stored records are still what the reference computes
+        lb, lgb = oracle.Reference().run(slab, maf)
+        assert_bit_equal(lb, b)
+        if groups:
+            assert_bit_equal(lgb, gb)
+    a, ga = oracle.Restatement().run(slab, maf)  # (the `restatement` fixture hands out the reference's records where it is built)
     assert_bit_equal(a, b, skip=EXACT_SKIP)
     if groups:
         assert_bit_equal(ga, gb)
