@@ -70,7 +70,7 @@ class SynthParams(C.Structure):
 
 # every symbol include/basevar_amd.h declares
 EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "bv_engine_submit", "bv_engine_submit_many", "bv_engine_submit_many_g", "bv_engine_wait", "bv_engine_join",
-           "bv_engine_tiles_begin", "bv_engine_tiles_add", "bv_engine_tiles_add_many", "bv_engine_tiles_add_sparse", "bv_sparse_tile_packed_layout", "bv_engine_tiles_finish", "bv_tile_packed_layout", "bv_engine_stream",
+           "bv_engine_tiles_begin", "bv_engine_tiles_add", "bv_engine_tiles_add_many", "bv_engine_tiles_add_sparse", "bv_engine_tiles_add_sparse_many", "bv_sparse_tile_packed_layout", "bv_engine_tiles_finish", "bv_tile_packed_layout", "bv_engine_stream",
            "bv_engine_kernel_ms", "bv_engine_timing_reset", "bv_engine_timing_get", "bv_engine_timing_get_ex",
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
            "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form"]
@@ -120,6 +120,8 @@ def load():
     L.bv_engine_tiles_add_many.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(Slab), C.c_void_p]
     L.bv_engine_tiles_add_sparse.restype = C.c_int
     L.bv_engine_tiles_add_sparse.argtypes = [C.c_void_p, C.POINTER(SparseTile), C.c_void_p]
+    L.bv_engine_tiles_add_sparse_many.restype = C.c_int
+    L.bv_engine_tiles_add_sparse_many.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(SparseTile), C.c_void_p]
     L.bv_sparse_tile_packed_layout.restype = C.c_int
     L.bv_sparse_tile_packed_layout.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.bv_tile_packed_layout.restype = C.c_int

@@ -428,51 +428,70 @@ struct HostPlane {
     size_t bytes;
     const uint8_t *dev;  // out: where the plane lives in the staging buffer
 };
-// Queue the host->device copies of `n` planes into a fresh staging slot (+ `extra` bytes of device scratch behind them).
-int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engine::StageSlot **slot_out, uint8_t **extra_dev, hipStream_t st) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+// Where `n` host planes go in a staging buffer: the bytes they take there, and whether they cross as ONE copy (`sp`).
+struct HostPlanes {
     HostSpan sp;
+    bool one_copy = false;
+    size_t bytes = 0;
+};
+HostPlanes plan_host_planes(const HostPlane *pl, int n) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    HostPlanes h;
     size_t sum = 0;
     for (int i = 0; i < n; ++i) {
         if (!pl[i].src || !pl[i].bytes) continue;
-        sp.add(pl[i].src, pl[i].bytes);
+        h.sp.add(pl[i].src, pl[i].bytes);
         sum += up(pl[i].bytes);
     }
     // ONE copy only for the exact layout of bv_tile_packed_layout: the planes in order, each at the 256-aligned end of the one
     // before it, in one allocation -- then every byte of [lo, hi) is the caller's.  (Planes that merely lie close together
     // are copied one by one: the bytes between them are not ours to read.)
-    bool one_copy = sp.lo != nullptr && (reinterpret_cast<uintptr_t>(sp.lo) & 15u) == 0;
+    bool one_copy = h.sp.lo != nullptr && (reinterpret_cast<uintptr_t>(h.sp.lo) & 15u) == 0;
     {
         size_t at = 0;
         for (int i = 0; i < n && one_copy; ++i) {
             if (!pl[i].src || !pl[i].bytes) continue;
-            one_copy = static_cast<const uint8_t *>(pl[i].src) == sp.lo + at;
+            one_copy = static_cast<const uint8_t *>(pl[i].src) == h.sp.lo + at;
             at += up(pl[i].bytes);
         }
     }
-    const size_t planes_bytes = one_copy ? up(sp.bytes()) : sum;
-    bv_engine::StageSlot *sl = nullptr;
-    int rc = stage_acquire(e, planes_bytes + up(extra), &sl);
-    if (rc != BV_OK) return rc;
-    rc = stage_order(e, sl, st);
-    if (rc != BV_OK) return rc;
-    uint8_t *base = static_cast<uint8_t *>(sl->buf);
-    if (one_copy) {
-        BV_HIP(e, hipMemcpyAsync(base, sp.lo, sp.bytes(), hipMemcpyHostToDevice, sl->cs));
+    h.one_copy = one_copy;
+    h.bytes = one_copy ? up(h.sp.bytes()) : sum;
+    return h;
+}
+// Queue the copies of planes planned by plan_host_planes to `base` (device) on the copy stream `cs`; pl[i].dev = where plane i lands.
+int copy_host_planes(bv_engine *e, HostPlane *pl, int n, const HostPlanes &h, uint8_t *base, hipStream_t cs) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    if (h.one_copy) {
+        BV_HIP(e, hipMemcpyAsync(base, h.sp.lo, h.sp.bytes(), hipMemcpyHostToDevice, cs));
         for (int i = 0; i < n; ++i)
-            pl[i].dev = (pl[i].src && pl[i].bytes) ? base + (static_cast<const uint8_t *>(pl[i].src) - sp.lo) : nullptr;
+            pl[i].dev = (pl[i].src && pl[i].bytes) ? base + (static_cast<const uint8_t *>(pl[i].src) - h.sp.lo) : nullptr;
     } else {
         size_t off = 0;
         for (int i = 0; i < n; ++i) {
             pl[i].dev = nullptr;
             if (!pl[i].src || !pl[i].bytes) continue;
-            BV_HIP(e, hipMemcpyAsync(base + off, pl[i].src, pl[i].bytes, hipMemcpyHostToDevice, sl->cs));
+            BV_HIP(e, hipMemcpyAsync(base + off, pl[i].src, pl[i].bytes, hipMemcpyHostToDevice, cs));
             pl[i].dev = base + off;
             off += up(pl[i].bytes);
         }
     }
+    return BV_OK;
+}
+// Queue the host->device copies of `n` planes into a fresh staging slot (+ `extra` bytes of device scratch behind them).
+int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engine::StageSlot **slot_out, uint8_t **extra_dev, hipStream_t st) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const HostPlanes h = plan_host_planes(pl, n);
+    bv_engine::StageSlot *sl = nullptr;
+    int rc = stage_acquire(e, h.bytes + up(extra), &sl);
+    if (rc != BV_OK) return rc;
+    rc = stage_order(e, sl, st);
+    if (rc != BV_OK) return rc;
+    uint8_t *base = static_cast<uint8_t *>(sl->buf);
+    rc = copy_host_planes(e, pl, n, h, base, sl->cs);
+    if (rc != BV_OK) return rc;
     *slot_out = sl;
-    if (extra_dev) *extra_dev = base + planes_bytes;
+    if (extra_dev) *extra_dev = base + h.bytes;
     return BV_OK;
 }
 }  // namespace
@@ -1383,6 +1402,164 @@ int bv_engine_tiles_add_sparse(bv_engine *e, const bv_sparse_tile *t, void *stre
         if (rc != BV_OK) return rc;
     }
     e->tile_samples_seen += t->n_samples;
+    return mark_done(e, st);
+}
+
+// Many packed tiles per call (include/basevar_amd.h): the records of n_tiles calls of bv_engine_tiles_add_sparse, but the tiles go
+// in GROUPS -- at most BV_TILE_MANY_MAX tiles and kSparseManyStage bytes of host tiles -- and a group costs one staging slot (one
+// copy per host tile into it), one descriptor table and ONE launch, where a tile cost a slot, two events, two waits and a launch of
+// its own (~48 us per 200-sample tile of a 16,384-site job, round 6).  64 MiB: ~33 such tiles (1.9 MB each) per group, so the
+// copies of the next group still run under the kernel of this one, and the four slots of the staging ring hold at most 256 MiB.
+static constexpr size_t kSparseManyStage = (size_t)64 << 20;
+int bv_engine_tiles_add_sparse_many(bv_engine *e, uint32_t n_tiles, const bv_sparse_tile *tiles, void *stream_) {
+    if (!e || !tiles || n_tiles == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: null / empty argument");
+    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: call bv_engine_tiles_begin first");
+    // every check of bv_engine_tiles_add_sparse, for every tile, before anything changes: a refused call leaves the job as it was
+    uint64_t seen = e->tile_samples_seen;
+    for (uint32_t k = 0; k < n_tiles; ++k) {
+        const bv_sparse_tile &t = tiles[k];
+        auto bad = [&](const char *why) {
+            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: tile " + std::to_string(k) + ": " + why);
+        };
+        if (t.n_sites != e->tile_sites) return bad("n_sites differs from the job's");
+        if (t.n_samples == 0 || t.n_samples > 65536u || !t.row_start || (t.n_entries && (!t.sample || !t.base_strand || !t.qual)))
+            return bad("bad tile geometry (at most 65,536 samples per tile) or missing arrays");
+        if (e->tile_ranks && t.n_entries && (!t.mapq || !t.rpr)) return bad("job was opened with rank planes");
+        if (e->tile_groups && !t.group_id) return bad("job has groups, tile has no group_id");
+        seen += t.n_samples;
+        if (seen > e->tile_samples_total) return bad("more samples than announced");
+        if ((t.layout & ~BV_SLAB_RPR_TAGGED) || t.layout != tiles[0].layout || (e->tile_layout_set && t.layout != e->tile_layout))
+            return bad("every tile of a job must have the same layout (known bits only)");
+        if (t.mem_kind == BV_MEM_HOST) {  // the kernels trust row_start: on the host it costs a pass over n_sites + 1 words
+            const uint32_t *rs = t.row_start;
+            bool ok = rs[0] == 0 && rs[t.n_sites] == t.n_entries;
+            for (uint32_t s = 0; s < t.n_sites && ok; ++s) ok = rs[s] <= rs[s + 1];
+            if (!ok) return bad("row_start must start at 0, never decrease and end at n_entries");
+        }
+    }
+    e->tile_layout = tiles[0].layout; e->tile_layout_set = true;
+    BV_HIP(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    {
+        int rc = use_stream(e, st);
+        if (rc != BV_OK) return rc;
+    }
+    const size_t S = e->tile_sites;
+    const bool ranks = e->tile_ranks, groups = e->tile_groups != 0;
+    BvSparseTileArgs a{};
+    a.n_sites = e->tile_sites;
+    a.rpr_tag = (e->tile_layout & BV_SLAB_RPR_TAGGED) ? 1u : 0u;
+    if (e->tile_join) {
+        uint8_t *jb = e->j_buf, *jq = e->j_buf + e->j_o_q, *jm = ranks ? e->j_buf + e->j_o_mq : nullptr;
+        uint16_t *jr = ranks ? reinterpret_cast<uint16_t *>(e->j_buf + e->j_o_rp) : nullptr;
+        if (!e->j_filled) {  // as bv_engine_tiles_add_sparse: the columns not delivered yet say "nobody covered", once per job
+            if (e->tile_samples_seen == 0) {
+                bv_launch_tile_fill_uncovered(jb, jq, jm, jr, (uint64_t)e->tile_sites * e->j_pitch, a.rpr_tag, st);
+                BV_HIP(e, hipGetLastError());
+            } else {
+                const size_t lo = e->tile_samples_seen, w = e->tile_samples_total - lo;
+                BV_HIP(e, hipMemset2DAsync(jb + lo, e->j_pitch, 0x08, w, S, st));
+                BV_HIP(e, hipMemset2DAsync(jq + lo, e->j_pitch, 0, w, S, st));
+                if (ranks) {
+                    BV_HIP(e, hipMemset2DAsync(jm + lo, e->j_pitch, 0, w, S, st));
+                    BV_HIP(e, hipMemset2DAsync(reinterpret_cast<uint8_t *>(jr) + 2 * lo, 2 * e->j_pitch, a.rpr_tag ? 0x80 : 0, 2 * w, S, st));
+                }
+            }
+            e->j_filled = true;
+        }
+        a.bs = jb; a.q = jq; a.mq = jm; a.rp = jr; a.pitch = e->j_pitch;
+    } else {
+        a.n_groups = e->tile_groups; a.stride = e->tile_stride; a.rank_win = e->tile_rank_win; a.hg_off = e->tile_hg_off;
+        a.ord_off = e->tile_ord_off; a.ovf_cap = bv_engine::kOvfCap; a.state = e->tile_state; a.maxr = e->tile_maxr; a.ovf = e->tile_ovf;
+    }
+    uint8_t *jgid = e->tile_join && groups ? e->j_buf + e->j_o_gid : nullptr;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    struct Staged {
+        HostPlane pl[7];
+        HostPlanes h;
+    };
+    std::vector<Staged> plan(n_tiles < (uint32_t)BV_TILE_MANY_MAX ? n_tiles : (uint32_t)BV_TILE_MANY_MAX);
+    constexpr size_t kDescBytes = sizeof(BvTileScatterPlane) * 5 * BV_TILE_MANY_MAX;  // the ring's tables (bv_engine_tiles_add_many)
+    static_assert(sizeof(BvSparseTileDesc) * BV_TILE_MANY_MAX <= kDescBytes, "a group's descriptors must fit one table of the ring");
+    for (uint32_t k0 = 0, k1 = 0; k0 < n_tiles; k0 = k1) {
+        // the group [k0, k1): its host tiles' staging bytes
+        size_t bytes = 0;
+        for (k1 = k0; k1 < n_tiles && k1 - k0 < (uint32_t)BV_TILE_MANY_MAX; ++k1) {
+            const bv_sparse_tile &t = tiles[k1];
+            Staged &p = plan[k1 - k0];
+            p.h = HostPlanes{};
+            if (t.mem_kind == BV_MEM_HOST) {
+                const size_t E = t.n_entries;
+                const uint16_t *rp = ranks ? t.rpr : nullptr;
+                const uint8_t *mq = ranks ? t.mapq : nullptr, *gid = groups ? t.group_id : nullptr;
+                HostPlane pl[7] = {{t.row_start, 4 * (S + 1), nullptr}, {t.sample, 2 * E, nullptr}, {t.base_strand, E, nullptr}, {t.qual, E, nullptr},
+                                   {mq, mq ? E : 0, nullptr}, {rp, rp ? 2 * E : 0, nullptr}, {gid, gid ? (size_t)t.n_samples : 0, nullptr}};
+                std::copy(pl, pl + 7, p.pl);
+                p.h = plan_host_planes(p.pl, 7);
+            }
+            if (k1 > k0 && bytes + p.h.bytes > kSparseManyStage) break;  // (a group holds at least one tile, however large)
+            bytes += p.h.bytes;
+        }
+        const uint32_t nk = k1 - k0;
+        bv_engine::StageSlot *slot = nullptr;
+        if (bytes) {
+            int rc = stage_acquire(e, bytes, &slot);
+            if (rc != BV_OK) return rc;
+            rc = stage_order(e, slot, st);
+            if (rc != BV_OK) return rc;
+            uint8_t *base = static_cast<uint8_t *>(slot->buf);
+            size_t off = 0;
+            for (uint32_t i = 0; i < nk; ++i) {
+                Staged &p = plan[i];
+                if (!p.h.bytes) continue;
+                rc = copy_host_planes(e, p.pl, 7, p.h, base + off, slot->cs);
+                if (rc != BV_OK) return rc;
+                off += up(p.h.bytes);
+            }
+        }
+        // the descriptor table: pinned, then one copy on `st` (ahead of the wait for the staging copies)
+        const int ds = (int)(e->desc_next++ % bv_engine::kDescRing);
+        if (!e->h_desc[ds]) {
+            BV_HIP(e, hipHostMalloc(&e->h_desc[ds], kDescBytes));
+            BV_HIP(e, hipMalloc(&e->d_desc[ds], kDescBytes));
+            BV_HIP(e, hipEventCreateWithFlags(&e->ev_desc[ds], hipEventDisableTiming));
+        }
+        if (e->desc_used[ds]) BV_HIP(e, hipEventSynchronize(e->ev_desc[ds]));  // the copy that last read this pinned table
+        BvSparseTileDesc *tab = reinterpret_cast<BvSparseTileDesc *>(e->h_desc[ds]);
+        uint64_t col = e->tile_samples_seen;
+        for (uint32_t i = 0; i < nk; ++i) {
+            const bv_sparse_tile &t = tiles[k0 + i];
+            BvSparseTileDesc &d = tab[i];
+            if (plan[i].h.bytes) {
+                const HostPlane *pl = plan[i].pl;
+                d.row_start = reinterpret_cast<const uint32_t *>(pl[0].dev); d.sample = reinterpret_cast<const uint16_t *>(pl[1].dev);
+                d.call = pl[2].dev; d.phred = pl[3].dev; d.mapq = pl[4].dev; d.rank = reinterpret_cast<const uint16_t *>(pl[5].dev);
+                d.group_id = pl[6].dev;
+            } else {
+                d.row_start = t.row_start; d.sample = t.sample; d.call = t.base_strand; d.phred = t.qual;
+                d.mapq = ranks ? t.mapq : nullptr; d.rank = ranks ? t.rpr : nullptr; d.group_id = groups ? t.group_id : nullptr;
+            }
+            if (!t.n_entries) d.mapq = nullptr;  // (as bv_engine_tiles_add_sparse: an empty tile reads no arrays but row_start)
+            d.col0 = col; d.width = t.n_samples; d.n_entries = t.n_entries;
+            col += t.n_samples;
+        }
+        BV_HIP(e, hipMemcpyAsync(e->d_desc[ds], tab, sizeof(BvSparseTileDesc) * nk, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipEventRecord(e->ev_desc[ds], st));
+        e->desc_used[ds] = true;
+        if (slot) {
+            int rc = stage_publish(e, slot, st);
+            if (rc != BV_OK) return rc;
+        }
+        const BvSparseTileDesc *dtab = reinterpret_cast<const BvSparseTileDesc *>(e->d_desc[ds]);
+        if (e->tile_join) bv_launch_tile_sparse_scatter_many(a, dtab, nk, jgid, st);
+        else bv_launch_tile_sparse_tally_many(a, dtab, nk, st);
+        BV_HIP(e, hipGetLastError());
+        if (slot) {
+            int rc = stage_release(e, slot, st);
+            if (rc != BV_OK) return rc;
+        }
+        e->tile_samples_seen = (uint32_t)col;
+    }
     return mark_done(e, st);
 }
 

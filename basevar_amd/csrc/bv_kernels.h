@@ -232,6 +232,21 @@ struct BvSparseTileArgs {
 };
 void bv_launch_tile_sparse_scatter(const BvSparseTileArgs &a, hipStream_t stream);
 void bv_launch_tile_sparse_tally(const BvSparseTileArgs &a, hipStream_t stream);
+// bv_engine_tiles_add_sparse_many: one descriptor per packed tile in a device table (at most BV_TILE_MANY_MAX per launch); the
+// job-wide fields (joined planes, pitch, rpr_tag / per-site state) come from a BvSparseTileArgs whose per-tile fields are unused
+struct BvSparseTileDesc {
+    const uint32_t *row_start;
+    const uint16_t *sample;
+    const uint8_t *call, *phred, *mapq;  // mapq NULL: no rank planes
+    const uint16_t *rank;
+    const uint8_t *group_id;             // [width] or NULL
+    uint64_t col0;                       // the tile's first column in the job
+    uint32_t width, n_entries;
+};
+// joined rows: the entries of every tile to their cells and, with `gid` (the joined group-id row), the tiles' group ids
+void bv_launch_tile_sparse_scatter_many(const BvSparseTileArgs &a, const BvSparseTileDesc *d_tab, uint32_t n_tiles, uint8_t *gid,
+                                        hipStream_t stream);
+void bv_launch_tile_sparse_tally_many(const BvSparseTileArgs &a, const BvSparseTileDesc *d_tab, uint32_t n_tiles, hipStream_t stream);
 // the whole joined planes as "nobody covered": calls 'N', phred / mapq 0, ranks 0 (tagged: 0x8000)
 void bv_launch_tile_fill_uncovered(uint8_t *bs, uint8_t *q, uint8_t *mq, uint16_t *rp, uint64_t cells, uint32_t rpr_tag, hipStream_t stream);
 void bv_launch_tile_tally(const BvTileArgs &a, hipStream_t stream);

@@ -542,6 +542,103 @@ void bv_launch_tile_sparse_tally(const BvSparseTileArgs &a, hipStream_t stream) 
     hipLaunchKernelGGL(bv_tile_sparse_tally_kernel, dim3((a.n_sites + BV_SPARSE_ROWS - 1) / BV_SPARSE_ROWS), dim3(256), 0, stream, a);
 }
 
+// bv_engine_tiles_add_sparse_many: many packed tiles, one launch -- blockIdx.y = tile, blockIdx.x = block of BV_SPARSE_ROWS
+// sites as above.  The tile's descriptor is read through the constant address space (scalar loads, as bv_tile_scatter_many_kernel);
+// the arrays it points to are ordinary global memory.  A job of 200-sample tiles paid ~48 us of host calls per tile (round 6).
+typedef const __attribute__((address_space(4))) BvSparseTileDesc *BvSparseTileDescC;
+__global__ __launch_bounds__(256) void bv_tile_sparse_scatter_many_kernel(BvSparseTileArgs a, const BvSparseTileDesc *tab, uint8_t *gid) {
+    const BvSparseTileDescC d = (BvSparseTileDescC)(uintptr_t)tab + blockIdx.y;
+    const uint32_t width = d->width, n_entries = d->n_entries;
+    const uint64_t col0 = d->col0;
+    if (gid && d->group_id) {  // the tile's group ids to its columns of the joined group-id row
+        const uint8_t *g = d->group_id;
+        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < width; i += gridDim.x * 256u) gid[col0 + i] = g[i];
+    }
+    if (n_entries == 0) return;  // (uniform over the block)
+    __shared__ uint32_t rs[BV_SPARSE_ROWS + 1];
+    const uint32_t r0 = blockIdx.x * BV_SPARSE_ROWS;
+    if (threadIdx.x <= BV_SPARSE_ROWS) rs[threadIdx.x] = d->row_start[min(r0 + threadIdx.x, a.n_sites)];
+    __syncthreads();
+    const uint16_t *sample = d->sample, *rank = d->rank;
+    const uint8_t *call = d->call, *phred = d->phred, *mapq = d->mapq;
+    const uint32_t e1 = min(rs[BV_SPARSE_ROWS], n_entries);
+    for (uint32_t e = rs[0] + threadIdx.x; e < e1; e += 256u) {
+        const uint32_t row = r0 + bv_sparse_row_of(rs, e), smp = sample[e];
+        if (smp >= width) continue;
+        const uint32_t c = call[e];
+        const size_t at = (size_t)row * a.pitch + col0 + smp;
+        a.bs[at] = (uint8_t)c;
+        a.q[at] = phred[e];
+        if (a.mq) {
+            a.mq[at] = mapq[e];
+            const uint32_t r = rank[e];
+            a.rp[at] = a.rpr_tag ? BV_RPR_TAGGED(c, r) : (uint16_t)r;
+        }
+    }
+}
+void bv_launch_tile_sparse_scatter_many(const BvSparseTileArgs &a, const BvSparseTileDesc *d_tab, uint32_t n_tiles, uint8_t *gid,
+                                        hipStream_t stream) {
+    hipLaunchKernelGGL(bv_tile_sparse_scatter_many_kernel, dim3((a.n_sites + BV_SPARSE_ROWS - 1) / BV_SPARSE_ROWS, n_tiles), dim3(256), 0, stream,
+                       a, d_tab, gid);
+}
+// per-site tallies: the atomics of bv_tile_sparse_tally_kernel.  The cells of one site now arrive from several tiles in any order;
+// the ordered cell list of a shallow site is sorted by sample index at finish (bv_tile_sorted_cells), so its order does not matter.
+__global__ __launch_bounds__(256) void bv_tile_sparse_tally_many_kernel(BvSparseTileArgs a, const BvSparseTileDesc *tab) {
+    const BvSparseTileDescC d = (BvSparseTileDescC)(uintptr_t)tab + blockIdx.y;
+    const uint32_t width = d->width, n_entries = d->n_entries, col0 = (uint32_t)d->col0;
+    if (n_entries == 0) return;
+    __shared__ uint32_t rs[BV_SPARSE_ROWS + 1];
+    const uint32_t r0 = blockIdx.x * BV_SPARSE_ROWS;
+    if (threadIdx.x <= BV_SPARSE_ROWS) rs[threadIdx.x] = d->row_start[min(r0 + threadIdx.x, a.n_sites)];
+    __syncthreads();
+    const uint16_t *sample = d->sample, *rank = d->rank;
+    const uint8_t *call = d->call, *phred = d->phred, *mapq = d->mapq, *group_id = d->group_id;
+    const uint32_t e1 = min(rs[BV_SPARSE_ROWS], n_entries);
+    for (uint32_t e = rs[0] + threadIdx.x; e < e1; e += 256u) {
+        const uint32_t site = r0 + bv_sparse_row_of(rs, e), smp = sample[e], c = call[e];
+        if (smp >= width || c > 7u) continue;
+        uint32_t *S = a.state + (size_t)site * a.stride;
+        const uint32_t q = phred[e], b = c & 3u;
+        atomicAdd(&S[BV_TS_H1 + ((c << 8) | q)], 1u);
+        if (mapq) {
+            const uint32_t mq = mapq[e], r = rank[e];
+            atomicAdd(&S[BV_TS_HM + ((b << 8) | mq)], 1u);
+            if (r) atomicMax(&a.maxr[site], r);
+            if (r < a.rank_win) atomicAdd(&S[BV_TS_HR + b * a.rank_win + r], 1u);
+            else {
+                const uint32_t k = atomicAdd(&a.ovf[0], 1u);
+                if (k < a.ovf_cap) { a.ovf[2u + 2u * k] = site; a.ovf[3u + 2u * k] = (b << 16) | r; }
+            }
+        }
+        uint32_t gi = BV_NO_GROUP;
+        if (a.n_groups) {
+            gi = group_id[smp];
+            if (gi < a.n_groups) atomicAdd(&S[a.hg_off + (((gi * 4u + b) << 7) | min(q, 127u))], 1u);
+        }
+        if (__builtin_nontemporal_load(&S[a.ord_off]) <= (uint32_t)BV_ORD_MAX) {
+            const uint32_t k = atomicAdd(&S[a.ord_off], 1u);
+            if (k < (uint32_t)BV_ORD_MAX) {
+                S[a.ord_off + 4u + 2u * k] = col0 + smp;
+                S[a.ord_off + 5u + 2u * k] = (c << 8) | q | (gi << 16);
+            }
+        }
+        if (gi < a.n_groups) {
+            uint32_t *GL = S + a.ord_off + (1u + gi) * BV_TS_ORD_WORDS;
+            if (__builtin_nontemporal_load(&GL[0]) <= (uint32_t)BV_ORD_MAX) {
+                const uint32_t k = atomicAdd(&GL[0], 1u);
+                if (k < (uint32_t)BV_ORD_MAX) {
+                    GL[4u + 2u * k] = col0 + smp;
+                    GL[5u + 2u * k] = (c << 8) | q | (gi << 16);
+                }
+            }
+        }
+    }
+}
+void bv_launch_tile_sparse_tally_many(const BvSparseTileArgs &a, const BvSparseTileDesc *d_tab, uint32_t n_tiles, hipStream_t stream) {
+    hipLaunchKernelGGL(bv_tile_sparse_tally_many_kernel, dim3((a.n_sites + BV_SPARSE_ROWS - 1) / BV_SPARSE_ROWS, n_tiles), dim3(256), 0, stream,
+                       a, d_tab);
+}
+
 void bv_launch_tile_tally(const BvTileArgs &a, hipStream_t stream) {
     const uint64_t total = (uint64_t)a.n_sites * ((a.width + 15u) >> 4);
     hipLaunchKernelGGL(bv_tile_tally_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, stream, a);

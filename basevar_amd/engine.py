@@ -202,9 +202,11 @@ class BaseTypeEngine:
         return n.value
 
     # ---- sample-axis tile mode (numpy tiles in host memory)
-    def lrt_tiles(self, slab, tile_width, max_rank=0, packed=False):
+    def lrt_tiles(self, slab, tile_width, max_rank=0, packed=False, sparse_batch=0):
         """`packed`: every tile goes as its covered cells only (bv_engine_tiles_add_sparse: 7 bytes per covered cell, one packed
         host allocation per tile); a number k > 1: every k-th tile dense, the others packed (a job may mix the two).
+        `sparse_batch` k > 0: the packed tiles go in calls of k (bv_engine_tiles_add_sparse_many; fewer before a dense tile
+        and at the end); 0: one bv_engine_tiles_add_sparse per packed tile.
         Same result as lrt(slab), but the slab is fed as column tiles of `tile_width` samples
         (the reference's `-B/--batch-count` batchfiles) that the engine accumulates in HBM.  Every tile is one packed
         host allocation (bv_tile_packed_layout), so it crosses the link as one copy.  `max_rank`: an upper bound on the
@@ -223,6 +225,15 @@ class BaseTypeEngine:
             raise RuntimeError("bv_engine_tiles_begin failed (%d): %s" % (rc, self._err()))
         keep = []  # the copies are asynchronous: every tile stays alive until the final wait
         lay = int(slab.get("layout", 0))
+        pending = []  # sparse_batch: packed tiles not sent yet
+
+        def flush():
+            if pending:
+                self.tiles_add_sparse_many(pending)
+                del pending[:]
+                if len(keep) >= 64:  # every tile held has been handed over: bound the host memory held by tiles in flight
+                    self.wait()
+                    del keep[:]
         for k_tile, lo in enumerate(range(0, N, tile_width)):
             w = min(tile_width, N - lo)
             if packed and not (packed > 1 and k_tile % int(packed) == 0):
@@ -253,6 +264,11 @@ class BaseTypeEngine:
                 keep.append(buf)
                 p = lambda a: None if a is None else a.ctypes.data
                 t = _capi.SparseTile(S, w, E, ng, p(rs), p(a_s), p(a_b), p(a_q), p(a_m), p(a_r), p(a_g), _capi.BV_MEM_HOST, lay)
+                if sparse_batch:
+                    pending.append(t)
+                    if len(pending) >= int(sparse_batch):
+                        flush()
+                    continue
                 rc = self._lib.bv_engine_tiles_add_sparse(self._h, C.byref(t), None)
                 if rc != 0:
                     raise RuntimeError("bv_engine_tiles_add_sparse failed (%d): %s" % (rc, self._err()))
@@ -260,6 +276,7 @@ class BaseTypeEngine:
                     self.wait()
                     del keep[:-1]
                 continue
+            flush()  # (the packed tiles before this dense one go first)
             pitch, total = C.c_uint64(), C.c_uint64()
             offs = (C.c_uint64 * 5)()
             rc = self._lib.bv_tile_packed_layout(S, w, 1 if ranks else 0, 1 if ng else 0, C.byref(pitch), offs, C.byref(total))
@@ -292,6 +309,7 @@ class BaseTypeEngine:
             if len(keep) >= 64:  # bound the host memory held by in-flight tiles
                 self.wait()
                 del keep[:-1]
+        flush()
         out = np.zeros(S, dtype=_capi.SITE_DTYPE)
         gout = np.zeros((S, ng), dtype=_capi.GROUP_DTYPE) if ng else None
         rc = self._lib.bv_engine_tiles_finish(self._h, ref.ctypes.data, out.ctypes.data,
@@ -308,6 +326,15 @@ class BaseTypeEngine:
         rc = self._lib.bv_engine_tiles_add_many(self._h, len(tiles), arr, C.c_void_p(stream) if stream else None)
         if rc != 0:
             raise RuntimeError("bv_engine_tiles_add_many failed (%d): %s" % (rc, self._err()))
+
+    def tiles_add_sparse_many(self, tiles, stream=0):
+        """tiles: list of _capi.SparseTile (one open tile job): n calls of bv_engine_tiles_add_sparse as one call
+        (bv_engine_tiles_add_sparse_many): one staging copy set and one launch per group of tiles.  Host tiles must stay
+        untouched until wait()."""
+        arr = (_capi.SparseTile * len(tiles))(*tiles)
+        rc = self._lib.bv_engine_tiles_add_sparse_many(self._h, len(tiles), arr, C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_tiles_add_sparse_many failed (%d): %s" % (rc, self._err()))
 
     # ---- numpy slab (host memory; the engine stages it to HBM)
     def lrt(self, slab):

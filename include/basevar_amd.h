@@ -257,6 +257,9 @@ typedef struct bv_sparse_tile {
     uint32_t mem_kind, layout;    /* bv_mem_kind; BV_SLAB_* of the job's tiles */
 } bv_sparse_tile;
 int bv_engine_tiles_add_sparse(bv_engine *e, const bv_sparse_tile *tile, void *stream);
+/* = n_tiles calls of bv_engine_tiles_add_sparse (byte-identical records; widths, mem_kind may differ; empty tiles allowed), as one
+ * staging copy set and one launch per group of tiles.  All or nothing: every tile is checked first (host tiles: row_start too). */
+int bv_engine_tiles_add_sparse_many(bv_engine *e, uint32_t n_tiles, const bv_sparse_tile *tiles, void *stream);
 int bv_sparse_tile_packed_layout(uint32_t n_sites, uint32_t n_entries, uint32_t width, int with_ranks, int with_groups,
                                  uint64_t offsets[7], uint64_t *total_bytes);
 
