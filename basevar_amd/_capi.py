@@ -57,6 +57,14 @@ class SparseTile(C.Structure):
                 ("rpr", C.c_void_p), ("group_id", C.c_void_p), ("mem_kind", C.c_uint32), ("layout", C.c_uint32)]
 
 
+class TextRows(C.Structure):  # bv_text_rows
+    _fields_ = [("text", C.c_void_p), ("row_off", C.c_void_p), ("file_samples", C.c_void_p), ("text_bytes", C.c_uint64),
+                ("n_positions", C.c_uint32), ("n_files", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+BV_TEXT_SKIP, BV_TEXT_HOST, BV_TEXT_INDEL = 1, 2, 4  # bv_engine_text_parse row states
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_sites", C.c_uint32), ("max_samples", C.c_uint32),
                 ("flags", C.c_uint32), ("min_af", C.c_double)]
@@ -73,7 +81,8 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_engine_tiles_begin", "bv_engine_tiles_add", "bv_engine_tiles_add_many", "bv_engine_tiles_add_sparse", "bv_engine_tiles_add_sparse_many", "bv_sparse_tile_packed_layout", "bv_engine_tiles_finish", "bv_tile_packed_layout", "bv_engine_stream",
            "bv_engine_kernel_ms", "bv_engine_timing_reset", "bv_engine_timing_get", "bv_engine_timing_get_ex",
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
-           "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form"]
+           "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form",
+           "bv_engine_text_parse", "bv_engine_text_submit"]
 
 _lib = None
 
@@ -163,5 +172,10 @@ def load():
     L.bv_device_numa_node.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
     L.bv_bind_thread_to_device_node.restype = C.c_int
     L.bv_bind_thread_to_device_node.argtypes = [C.c_int]
+    L.bv_engine_text_parse.restype = C.c_int
+    L.bv_engine_text_parse.argtypes = [C.c_void_p, C.POINTER(TextRows), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.bv_engine_text_submit.restype = C.c_int
+    L.bv_engine_text_submit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Slab), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
     _lib = L
     return L

@@ -272,6 +272,7 @@ struct bv_engine {
     hipEvent_t ev_desc[kDescRing] = {};
     bool desc_used[kDescRing] = {};
     unsigned desc_next = 0;
+    BvTextState *text = nullptr;       // bv_engine_text_parse / _submit (bv_text.hip)
     mutable std::mutex mu;
     std::string err;
 };
@@ -496,6 +497,11 @@ int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engin
 }
 }  // namespace
 
+BvEngineView bv_engine_view(bv_engine *e) {
+    return BvEngineView{e->cfg.device, e->cfg.max_sites, e->cfg.max_samples, e->stream, &e->text};
+}
+int bv_engine_fail(bv_engine *e, int code, const std::string &msg) { return fail(e, code, msg); }
+
 extern "C" {
 
 const char *bv_version(void) { return "basevar_amd 0.2 abi2 gfx950"; }
@@ -628,6 +634,7 @@ int bv_engine_destroy(bv_engine *e) {
     }
     if (e->ev_entry) (void)hipEventDestroy(e->ev_entry);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    bv_text_state_free(e->text);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

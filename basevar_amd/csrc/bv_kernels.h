@@ -294,3 +294,16 @@ size_t bv_pass2_lds_bytes(uint32_t n_groups);
 // planes in a.mapq / a.rpr, the variant sites' pass-2 rows -- as ONE persistent kernel (bv_pass1_fused.hip)
 bool bv_p1s_fused_takes(const BvP1ShortArgs &a);
 void bv_launch_p1s_fused(const BvP1ShortArgs &a, hipStream_t stream);
+
+// batchfile text rows (bv_text.hip): what the text entry points need from the engine (bv_engine.hip)
+#include <string>
+struct BvTextState;
+void bv_text_state_free(BvTextState *t);
+struct BvEngineView {
+    int device;
+    uint32_t max_sites, max_samples;
+    hipStream_t stream;   // the engine's own stream
+    BvTextState **text;   // the engine's text state (created by the first bv_engine_text_parse)
+};
+BvEngineView bv_engine_view(bv_engine *e);
+int bv_engine_fail(bv_engine *e, int code, const std::string &msg);  // sets bv_last_error(e) (or the global one), returns code

@@ -1,0 +1,611 @@
+// bv_text.hip -- batchfile text rows parsed on the device (bv_engine_text_parse / bv_engine_text_submit, include/basevar_amd.h;
+// the contract is INTEGRATION.md section 2e).
+//
+// The reference reads one row from every batchfile per position and splits its columns token by token on the host
+// (src/basetype_caller.cpp:586-611, 686-740).  Here the rows of a whole batch go to the device as they are: one wave per
+// (position, file) row walks the row 64 bytes at a time, finds the column and token of every byte with 64-bit ballots of its
+// tabs and spaces, and the lane that holds a token's first byte decodes it into the slab planes the calling kernels read.
+// File f's tokens land at sample offset file_samples[0] + ... + file_samples[f - 1] of the position's row.
+//
+// The device takes a row only in the narrow form every well-formed batchfile has (9 fields; CHROM, POS and REF byte-equal to
+// file 0's row; decimal Depth and POS of at most 9 digits; exactly file_samples[f] tokens per sample column; mapq 1-3 digits
+// <= 255; base one of A C G T N or a '+'/'-' token; quality one character; rank 1-5 digits <= 65,535; strand '+', '-' or '.'; a
+// covered base never with '.').  For such a row the host reader (batchfile_fast.hpp, parse_site_rows_fast) writes the same
+// bytes; anything else makes the whole position "host" and the caller re-reads it with that reader, which keeps every odd
+// case and error message of the reference.  Positions whose Depth fields sum to 0 are skipped (caller.cpp:718) -- before any
+// token is looked at, as the host reader does.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "bv_kernels.h"
+
+namespace {
+
+constexpr uint32_t kPrefixFail = 1u;  // d_pstate bits: the field count or the first four fields are not the strict form
+constexpr uint32_t kTokenFail = 2u;   //                a per-sample token is not the strict form
+constexpr uint32_t kMaxPrefix = 512;  // bytes of CHROM \t POS \t REF \t Depth \t the device looks at; longer -> host
+constexpr size_t kChunkBytes = (size_t)128 << 20;  // text bytes per staged chunk (two chunks in flight)
+
+struct TextParseArgs {
+    const char *text;          // the chunk: byte k is text byte chunk_base + k
+    const uint64_t *row_off;   // [n_rows + 1] absolute offsets (device)
+    const uint32_t *foff;      // [n_files] sample offset of file f inside the row
+    const uint32_t *fsamp;     // [n_files]
+    uint64_t chunk_base;
+    uint32_t row_first, n_rows_chunk, n_files;
+    uint64_t pitch;
+    uint8_t *bs, *q, *mq, *st, *ref, *rowflag;
+    uint16_t *rp;
+    uint32_t *depth, *pstate, *pmax;
+};
+
+__device__ __forceinline__ bool is_digit(char c) { return c >= '0' && c <= '9'; }
+__device__ __forceinline__ bool is_sep(char c) { return c == ' ' || c == '\t' || c == '\n'; }
+
+// digits [p, first separator): 1..max_digits of them, value <= max_value -> value, else -1
+__device__ __forceinline__ int parse_uint_token(const char *p, int max_digits, int max_value) {
+    int v = 0, n = 0;
+    for (;; ++n) {
+        const char c = p[n];
+        if (is_sep(c)) break;
+        if (!is_digit(c) || n == max_digits) return -1;
+        v = v * 10 + (c - '0');
+    }
+    return (n == 0 || v > max_value) ? -1 : v;
+}
+
+__device__ __forceinline__ uint8_t base_code_dev(char c) {
+    switch (c) {
+        case 'A': case 'a': return BV_BASE_A;
+        case 'C': case 'c': return BV_BASE_C;
+        case 'G': case 'g': return BV_BASE_G;
+        case 'T': case 't': return BV_BASE_T;
+        default: return BV_BASE_OTHER;
+    }
+}
+
+// One wave per (position, file) row; four rows per workgroup.
+__global__ __launch_bounds__(256) void bv_text_parse_kernel(TextParseArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t local = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (local >= a.n_rows_chunk) return;
+    const uint32_t r = a.row_first + local;
+    const uint32_t p = r / a.n_files, f = r - p * a.n_files;
+    const uint32_t r0 = p * a.n_files;  // file 0's row of the same position
+    const char *row = a.text + (a.row_off[r] - a.chunk_base);
+    const char *row0 = a.text + (a.row_off[r0] - a.chunk_base);
+    const uint32_t len = (uint32_t)(a.row_off[r + 1] - a.row_off[r]);  // the last byte is '\n' (checked by the host)
+    const uint32_t len0 = (uint32_t)(a.row_off[r0 + 1] - a.row_off[r0]);
+
+    // ---- CHROM \t POS \t REF \t Depth \t: one lane (they are a few bytes)
+    uint32_t start = 0, ok = 1, dep = 0;
+    if (lane == 0) {
+        uint32_t tabs = 0, i = 0, pos_digits = 0, dep_digits = 0, ref_at = 0;
+        const uint32_t lim = min(min(len, len0), kMaxPrefix);
+        for (; i < lim && tabs < 3; ++i) {  // CHROM, POS, REF: byte-equal to file 0's, POS decimal
+            const char c = row[i];
+            if (c != row0[i] || c == '\n') { ok = 0; break; }
+            if (c == '\t') { if (++tabs == 2) ref_at = i + 1; continue; }
+            if (tabs == 1) {
+                if (!is_digit(c) || ++pos_digits > 9) { ok = 0; break; }
+            }
+        }
+        ok = ok && tabs == 3 && pos_digits > 0;
+        if (ok) {
+            for (;; ++i) {  // Depth
+                if (i >= min(len, kMaxPrefix)) { ok = 0; break; }
+                const char c = row[i];
+                if (c == '\t') { ++i; break; }
+                if (!is_digit(c) || ++dep_digits > 9) { ok = 0; break; }
+                dep = dep * 10u + (uint32_t)(c - '0');
+            }
+            ok = ok && dep_digits > 0;
+        }
+        start = i;
+        if (ok && f == 0)  // toupper(REF[0]), 'N' when REF is empty (SlabBuilder::commit_row)
+            a.ref[p] = base_code_dev(row[ref_at] == '\t' ? 'N' : row[ref_at]);
+        if (ok) atomicAdd(&a.depth[p], dep);  // (wraps as the host reader's uint32_t sum does)
+        else atomicOr(&a.pstate[p], kPrefixFail);
+    }
+    ok = __shfl(ok, 0);
+    if (!ok) return;
+    start = __shfl(start, 0);
+
+    // ---- the five per-sample columns, 64 bytes per step
+    const uint32_t ns = a.fsamp[f];
+    const size_t cell0 = (size_t)p * a.pitch + a.foff[f];
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t fld = 4, tok = 0, prev_sep = 1, bad = 0, indel = 0, maxr = 0;
+    for (uint32_t b = start; b < len; b += 64u) {
+        const uint32_t i = b + lane;
+        const bool valid = i < len;
+        const char c = valid ? row[i] : '\0';
+        const uint64_t T = __ballot(valid && c == '\t');
+        const uint64_t S = __ballot(valid && c == ' ');
+        const uint64_t SEP = T | S | __ballot(valid && c == '\n');
+        const uint64_t tb = T & lt;
+        const uint32_t my_fld = fld + (uint32_t)__popcll(tb);
+        uint32_t my_tok;
+        if (tb) {
+            const uint32_t t = 63u - (uint32_t)__clzll(tb);
+            my_tok = (uint32_t)__popcll(S & lt & ~((2ull << t) - 1ull));
+        } else {
+            my_tok = tok + (uint32_t)__popcll(S & lt);
+        }
+        const bool after_sep = lane ? ((SEP >> (lane - 1)) & 1ull) != 0 : prev_sep != 0;
+        if (valid) {
+            if (c == '\n' && i != len - 1) bad = 1;  // a line break inside the row
+            if (is_sep(c)) {
+                // a separator ends token my_tok of field my_fld: an empty token, a tab past field 8, a row that ends early,
+                // or a column whose token count is not the file's sample count are not the strict form
+                if (after_sep) bad = 1;
+                if (c == ' ' && my_tok + 1u >= ns) bad = 1;
+                if (c == '\t' && (my_fld >= 8u || my_tok + 1u != ns)) bad = 1;
+                if (c == '\n' && (my_fld != 8u || my_tok + 1u != ns)) bad = 1;
+            } else if (after_sep && my_fld <= 8u && my_tok < ns) {
+                const char *t = row + i;
+                const size_t cell = cell0 + my_tok;
+                switch (my_fld) {
+                    case 4: {  // MappingQuality
+                        const int v = parse_uint_token(t, 3, 255);
+                        if (v < 0) bad = 1; else a.mq[cell] = (uint8_t)v;
+                        break;
+                    }
+                    case 5: {  // Readbases: the strand goes in at finish
+                        uint8_t code;
+                        if (c == '+' || c == '-') {
+                            code = c == '+' ? BV_CELL_INS : BV_CELL_DEL;
+                            indel = 1;
+                        } else if (!is_sep(t[1])) {
+                            bad = 1; code = BV_CELL_N;
+                        } else if (c == 'N') {
+                            code = BV_CELL_N;
+                        } else {
+                            code = c == 'A' ? BV_BASE_A : c == 'C' ? BV_BASE_C : c == 'G' ? BV_BASE_G : c == 'T' ? BV_BASE_T : 0xFFu;
+                            if (code == 0xFFu) { bad = 1; code = BV_CELL_N; }
+                        }
+                        a.bs[cell] = code;
+                        break;
+                    }
+                    case 6:  // ReadbasesQuality: one character, phred = char - 33
+                        if (!is_sep(t[1])) bad = 1; else a.q[cell] = (uint8_t)(c - 33);
+                        break;
+                    case 7: {  // ReadPositionRank
+                        const int v = parse_uint_token(t, 5, 65535);
+                        if (v < 0) bad = 1; else { a.rp[cell] = (uint16_t)v; maxr = max(maxr, (uint32_t)v); }
+                        break;
+                    }
+                    default: {  // Strand
+                        const uint8_t s = c == '+' ? 0u : c == '-' ? 1u : c == '.' ? 2u : 3u;
+                        if (s == 3u || !is_sep(t[1])) bad = 1; else a.st[cell] = s;
+                        break;
+                    }
+                }
+            } else if (after_sep) {
+                bad = 1;  // a token beyond the sample count, or in a tenth field
+            }
+        }
+        fld += (uint32_t)__popcll(T);
+        if (T) {
+            const uint32_t t = 63u - (uint32_t)__clzll(T);
+            tok = t == 63u ? 0u : (uint32_t)__popcll(S & ~((2ull << t) - 1ull));
+        } else {
+            tok += (uint32_t)__popcll(S);
+        }
+        prev_sep = (uint32_t)((SEP >> 63) & 1ull);
+    }
+    if (fld != 8u) {  // not 9 fields: the host reader refuses the row before it looks at Depth (a skip would be wrong)
+        if (lane == 0) atomicOr(&a.pstate[p], kPrefixFail);
+        return;
+    }
+    if (__ballot(bad)) {
+        if (lane == 0) atomicOr(&a.pstate[p], kTokenFail);
+        return;
+    }
+    const bool any_indel = __ballot(indel) != 0;
+    for (int o = 32; o > 0; o >>= 1) maxr = max(maxr, (uint32_t)__shfl_xor((int)maxr, o));
+    if (lane == 0) {
+        a.rowflag[r] = any_indel ? (uint8_t)BV_TEXT_INDEL : (uint8_t)0;
+        atomicMax(&a.pmax[p], maxr);
+    }
+}
+
+// After the last chunk: the strand of every covered call goes into its cell (REV for '-'); a covered call with strand '.'
+// makes the position "host" (the reference refuses it: basetype.cpp:272).  One workgroup per position.
+__global__ __launch_bounds__(256) void bv_text_strand_kernel(uint8_t *bs, const uint8_t *st, const uint32_t *depth, uint32_t *pstate,
+                                                             uint64_t pitch, uint32_t n_samples) {
+    const uint32_t p = blockIdx.x;
+    if (pstate[p] != 0 || depth[p] == 0) return;
+    uint8_t *row = bs + (size_t)p * pitch;
+    const uint8_t *srow = st + (size_t)p * pitch;
+    uint32_t bad = 0;
+    for (uint32_t c = threadIdx.x; c < n_samples; c += blockDim.x) {
+        const uint8_t b = row[c];
+        if (b & BV_CELL_NOCALL) continue;
+        const uint8_t s = srow[c];
+        if (s == 2u) bad = 1;
+        else if (s == 1u) row[c] = (uint8_t)(b | BV_CELL_REV);
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0) pstate[p] |= kTokenFail;
+}
+
+// Submit: output row j takes parsed row src[j] >= 0, or host row -src[j] - 1 of the caller's slab (staged to hq..); ranks are
+// written tagged when `tagged` (BV_RPR_TAGGED, what SlabBuilder::tag_ranks gives).  One workgroup per output row.
+struct TextGatherArgs {
+    const int32_t *src;
+    const uint8_t *pbs, *pq, *pmq, *pref;
+    const uint16_t *prp;
+    uint64_t ppitch;
+    const uint8_t *hbs, *hq, *hmq, *href;
+    const uint16_t *hrp;
+    uint64_t hpitch;
+    uint8_t *bs, *q, *mq, *ref;
+    uint16_t *rp;
+    uint64_t pitch;
+    uint32_t n_samples, tagged;
+};
+__global__ __launch_bounds__(256) void bv_text_gather_kernel(TextGatherArgs a) {
+    const uint32_t j = blockIdx.x;
+    const int32_t s = a.src[j];
+    const bool dev = s >= 0;
+    const size_t so = dev ? (size_t)s * a.ppitch : (size_t)(-s - 1) * a.hpitch;
+    const uint8_t *sbs = (dev ? a.pbs : a.hbs) + so, *sq = (dev ? a.pq : a.hq) + so, *smq = (dev ? a.pmq : a.hmq) + so;
+    const uint16_t *srp = (dev ? a.prp : a.hrp) + so;
+    const size_t d = (size_t)j * a.pitch;
+    for (uint32_t c = threadIdx.x; c < (uint32_t)a.pitch; c += blockDim.x) {
+        const bool in = c < a.n_samples;
+        const uint8_t b = in ? sbs[c] : (uint8_t)BV_CELL_N;
+        const uint16_t r = in ? srp[c] : (uint16_t)0;
+        a.bs[d + c] = b;
+        a.q[d + c] = in ? sq[c] : (uint8_t)0;
+        a.mq[d + c] = in ? smq[c] : (uint8_t)0;
+        a.rp[d + c] = a.tagged ? BV_RPR_TAGGED((uint32_t)b, (uint32_t)r) : r;
+    }
+    if (threadIdx.x == 0) a.ref[j] = dev ? a.pref[s] : a.href[-s - 1];
+}
+
+}  // namespace
+
+// Per-engine state of the text path: the parsed planes of the last bv_engine_text_parse, the slab handed to the calling kernels,
+// the text staging (two pinned host + two device chunks) and what the host learnt from the parse.
+struct BvTextState {
+    int device = 0;
+    hipStream_t cs = nullptr;               // copy stream of the text chunks
+    hipEvent_t ev_copied[2] = {}, ev_parsed[2] = {};
+    char *h_text[2] = {}, *d_text[2] = {};
+    size_t chunk_cap = 0;
+    uint8_t *d_planes = nullptr;            // parsed rows: bs, q, mq, st [cap][pitch], rp [cap][pitch] u16, ref [cap]
+    size_t planes_bytes = 0;
+    uint8_t *d_sub = nullptr;               // the submitted slab: bs, q, mq [cap][pitch], rp [cap][pitch] u16, ref [cap]
+    size_t sub_bytes = 0;
+    uint8_t *d_aux = nullptr;               // depth, pstate, pmax [n_pos] u32, rowflag [n_rows], row_off [n_rows + 1], foff/fsamp
+    size_t aux_bytes = 0;
+    uint8_t *d_misc = nullptr;              // submit: src [n] i32, host rows, records
+    size_t misc_bytes = 0;
+    uint8_t *d_gid = nullptr;
+    size_t gid_bytes = 0;
+    // the pending parse
+    bool parsed = false;
+    uint32_t n_pos = 0, n_files = 0, n_samples = 0, n_groups = 0;
+    uint64_t pitch = 0;
+    std::vector<uint8_t> pos_state;         // BV_TEXT_SKIP / BV_TEXT_HOST / 0 per position
+    std::vector<uint32_t> pos_max_rank;
+    std::vector<uint8_t> group_id;
+    bool has_gid = false;
+};
+
+void bv_text_state_free(BvTextState *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    if (t->cs) (void)hipStreamSynchronize(t->cs);
+    for (int k = 0; k < 2; ++k) {
+        if (t->h_text[k]) (void)hipHostFree(t->h_text[k]);
+        if (t->d_text[k]) (void)hipFree(t->d_text[k]);
+        if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
+        if (t->ev_parsed[k]) (void)hipEventDestroy(t->ev_parsed[k]);
+    }
+    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid})
+        if (b) (void)hipFree(b);
+    if (t->cs) (void)hipStreamDestroy(t->cs);
+    delete t;
+}
+
+namespace {
+#define BV_TXT_HIP(e, call)                                                                        \
+    do {                                                                                           \
+        hipError_t _s = (call);                                                                    \
+        if (_s != hipSuccess)                                                                      \
+            return bv_engine_fail((e), BV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
+    } while (0)
+
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int grow(bv_engine *e, uint8_t **buf, size_t *have, size_t need) {
+    if (need <= *have) return BV_OK;
+    if (*buf) BV_TXT_HIP(e, hipFree(*buf));
+    *buf = nullptr; *have = 0;
+    BV_TXT_HIP(e, hipMalloc(buf, need));
+    *have = need;
+    return BV_OK;
+}
+
+// The staging of text chunks: two pinned host buffers and two device buffers of `bytes` each.
+int ensure_chunks(bv_engine *e, BvTextState *t, size_t bytes) {
+    if (!t->cs) BV_TXT_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
+    for (int k = 0; k < 2; ++k) {
+        if (!t->ev_copied[k]) BV_TXT_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
+        if (!t->ev_parsed[k]) BV_TXT_HIP(e, hipEventCreateWithFlags(&t->ev_parsed[k], hipEventDisableTiming));
+    }
+    if (bytes <= t->chunk_cap) return BV_OK;
+    BV_TXT_HIP(e, hipStreamSynchronize(t->cs));
+    for (int k = 0; k < 2; ++k) {
+        if (t->h_text[k]) BV_TXT_HIP(e, hipHostFree(t->h_text[k]));
+        if (t->d_text[k]) BV_TXT_HIP(e, hipFree(t->d_text[k]));
+        t->h_text[k] = t->d_text[k] = nullptr;
+    }
+    t->chunk_cap = 0;
+    for (int k = 0; k < 2; ++k) {
+        BV_TXT_HIP(e, hipHostMalloc(&t->h_text[k], bytes));
+        BV_TXT_HIP(e, hipMalloc(&t->d_text[k], bytes));
+    }
+    t->chunk_cap = bytes;
+    return BV_OK;
+}
+
+int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
+               hipStream_t st, uint32_t n_samples) {
+    const uint32_t P = rows->n_positions, F = rows->n_files;
+    const size_t R = (size_t)P * F;
+    const uint64_t pitch = (n_samples + 255ull) & ~255ull;
+    t->parsed = false;
+    BV_TXT_HIP(e, hipSetDevice(t->device));
+    // a parse that failed part-way may have left chunk copies queued: the staging is free only once they are through
+    if (t->cs) BV_TXT_HIP(e, hipStreamSynchronize(t->cs));
+    // device buffers: planes, then the small per-position / per-row arrays
+    const size_t cells = (size_t)P * pitch;
+    int rc = grow(e, &t->d_planes, &t->planes_bytes, 6 * cells + up256(P));
+    if (rc != BV_OK) return rc;
+    const size_t o_pstate = up256(4ull * P), o_pmax = 2 * o_pstate, o_flag = 3 * o_pstate, o_off = o_flag + up256(R),
+                 o_foff = o_off + up256(8 * (R + 1)), o_fs = o_foff + up256(4ull * F), aux = o_fs + up256(4ull * F);
+    rc = grow(e, &t->d_aux, &t->aux_bytes, aux);
+    if (rc != BV_OK) return rc;
+    uint8_t *bs = t->d_planes, *q = bs + cells, *mq = q + cells, *stp = mq + cells;
+    uint16_t *rp = reinterpret_cast<uint16_t *>(stp + cells);
+    uint8_t *ref = stp + 3 * cells;
+    uint32_t *depth = reinterpret_cast<uint32_t *>(t->d_aux), *pstate = reinterpret_cast<uint32_t *>(t->d_aux + o_pstate),
+             *pmax = reinterpret_cast<uint32_t *>(t->d_aux + o_pmax), *foff = reinterpret_cast<uint32_t *>(t->d_aux + o_foff),
+             *fsamp = reinterpret_cast<uint32_t *>(t->d_aux + o_fs);
+    uint8_t *rowflag = t->d_aux + o_flag;
+    uint64_t *d_off = reinterpret_cast<uint64_t *>(t->d_aux + o_off);
+    std::vector<uint32_t> h_foff(F);
+    for (uint32_t f = 0, s = 0; f < F; s += rows->file_samples[f], ++f) h_foff[f] = s;
+    // a parsed row is all 'N' where the text leaves nothing (the padding of every row, skipped and host positions)
+    BV_TXT_HIP(e, hipMemsetAsync(bs, BV_CELL_N, cells, st));
+    BV_TXT_HIP(e, hipMemsetAsync(q, 0, 3 * cells, st));  // q, mq, strand
+    BV_TXT_HIP(e, hipMemsetAsync(rp, 0, 2 * cells, st));
+    BV_TXT_HIP(e, hipMemsetAsync(t->d_aux, 0, o_off, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(d_off, rows->row_off, 8 * (R + 1), hipMemcpyHostToDevice, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(foff, h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(fsamp, rows->file_samples, 4ull * F, hipMemcpyHostToDevice, st));
+    // the chunks: whole positions, at most kChunkBytes (or one position, if it is longer)
+    size_t need = 0;
+    for (uint32_t p = 0; p < P; ++p) need = std::max<size_t>(need, rows->row_off[(size_t)(p + 1) * F] - rows->row_off[(size_t)p * F]);
+    const size_t total = rows->row_off[R] - rows->row_off[0];
+    // (BASEVAR_AMD_TEXT_CHUNK_BYTES: a smaller chunk, for tests of the staging's reuse; never above the default)
+    size_t chunk_bytes = kChunkBytes;
+    if (const char *v = std::getenv("BASEVAR_AMD_TEXT_CHUNK_BYTES")) {
+        const unsigned long long x = std::strtoull(v, nullptr, 10);
+        if (x > 0 && x < kChunkBytes) chunk_bytes = (size_t)x;
+    }
+    rc = ensure_chunks(e, t, std::max(up256(need), std::min(chunk_bytes, up256(total))));
+    if (rc != BV_OK) return rc;
+    BV_TXT_HIP(e, hipStreamSynchronize(st));  // (the pageable uploads above are complete; the chunk buffers may be reused)
+    unsigned k = 0;
+    for (uint32_t p0 = 0; p0 < P; ++k) {
+        const uint64_t base = rows->row_off[(size_t)p0 * F];
+        uint32_t p1 = p0 + 1;
+        while (p1 < P && rows->row_off[(size_t)(p1 + 1) * F] - base <= t->chunk_cap) ++p1;
+        const size_t bytes = rows->row_off[(size_t)p1 * F] - base;
+        const unsigned s = k & 1u;
+        if (k >= 2) BV_TXT_HIP(e, hipEventSynchronize(t->ev_copied[s]));  // the pinned buffer has crossed the link
+        std::memcpy(t->h_text[s], rows->text + base, bytes);
+        if (k >= 2) BV_TXT_HIP(e, hipStreamWaitEvent(t->cs, t->ev_parsed[s], 0));  // the device buffer has been parsed
+        BV_TXT_HIP(e, hipMemcpyAsync(t->d_text[s], t->h_text[s], bytes, hipMemcpyHostToDevice, t->cs));
+        BV_TXT_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
+        BV_TXT_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
+        TextParseArgs a;
+        a.text = t->d_text[s]; a.row_off = d_off; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
+        a.row_first = p0 * F; a.n_rows_chunk = (p1 - p0) * F; a.n_files = F; a.pitch = pitch;
+        a.bs = bs; a.q = q; a.mq = mq; a.st = stp; a.ref = ref; a.rowflag = rowflag; a.rp = rp;
+        a.depth = depth; a.pstate = pstate; a.pmax = pmax;
+        hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
+        BV_TXT_HIP(e, hipGetLastError());
+        BV_TXT_HIP(e, hipEventRecord(t->ev_parsed[s], st));
+        p0 = p1;
+    }
+    hipLaunchKernelGGL(bv_text_strand_kernel, dim3(P), dim3(256), 0, st, bs, (const uint8_t *)stp, (const uint32_t *)depth, pstate, pitch,
+                       n_samples);
+    BV_TXT_HIP(e, hipGetLastError());
+    std::vector<uint32_t> h(3ull * P);
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data(), depth, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + P, pstate, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + 2ull * P, pmax, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(row_state, rowflag, R, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    // the position's state, in the host reader's order: field count / coordinates / Depth first, then Depth 0, then the tokens
+    t->pos_state.assign(P, 0);
+    t->pos_max_rank.assign(h.begin() + 2ull * P, h.end());
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t ps = h[P + p];
+        const uint8_t s = (ps & kPrefixFail) ? BV_TEXT_HOST : h[p] == 0 ? BV_TEXT_SKIP : ps ? BV_TEXT_HOST : 0;
+        t->pos_state[p] = s;
+        for (uint32_t f = 0; f < F; ++f) {
+            uint8_t &o = row_state[(size_t)p * F + f];
+            o = s ? s : (uint8_t)(o & BV_TEXT_INDEL);
+        }
+    }
+    t->n_pos = P; t->n_files = F; t->n_samples = n_samples; t->pitch = pitch; t->n_groups = n_groups;
+    t->has_gid = group_id != nullptr;
+    if (group_id) t->group_id.assign(group_id, group_id + n_samples);
+    else t->group_id.clear();
+    t->parsed = true;
+    return BV_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
+                         void *stream_) {
+    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null engine");
+    if (!rows || !row_state) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null rows/row_state");
+    if (!rows->text || !rows->row_off || !rows->file_samples)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null text/row_off/file_samples");
+    if (rows->reserved_) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: reserved_ must be zero");
+    const BvEngineView v = bv_engine_view(e);
+    if (rows->n_positions == 0 || rows->n_files == 0)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions and n_files must be > 0");
+    if (rows->n_positions > v.max_sites)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions exceeds cfg.max_sites");
+    uint64_t n_samples = 0;
+    for (uint32_t f = 0; f < rows->n_files; ++f) {
+        if (rows->file_samples[f] == 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: file_samples[f] == 0");
+        n_samples += rows->file_samples[f];
+    }
+    if (n_samples > v.max_samples)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: the files hold more samples than cfg.max_samples");
+    if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+    const size_t R = (size_t)rows->n_positions * rows->n_files;
+    for (size_t r = 0; r < R; ++r) {  // rows in order, inside the text, each ending in '\n'
+        const uint64_t a = rows->row_off[r], b = rows->row_off[r + 1];
+        if (b <= a || b > rows->text_bytes || rows->text[b - 1] != '\n')
+            return bv_engine_fail(e, BV_ERR_INVALID_ARG,
+                                  "bv_engine_text_parse: row " + std::to_string(r) + ": row_off outside text_bytes, out of order, or no final '\\n'");
+        if (b - a > 0xFFFFFFFFull) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: a row is longer than 4 GiB");
+    }
+    BvTextState *&t = *v.text;
+    if (!t) {
+        t = new BvTextState();
+        t->device = v.device;
+    }
+    const int rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : v.stream, (uint32_t)n_samples);
+    if (rc != BV_OK) t->parsed = false;
+    return rc;
+}
+
+int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab *host_rows, uint32_t n_used, bv_site_result *out,
+                          bv_group_result *gout, uint8_t *cell, uint8_t *phred, void *stream_) {
+    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null engine");
+    const BvEngineView v = bv_engine_view(e);
+    BvTextState *t = *v.text;
+    if (!t || !t->parsed) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: no bv_engine_text_parse before it");
+    if (n_used > t->n_pos) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_positions_used exceeds the parsed batch");
+    // row_state (may be NULL: as the parse left it): the host reader may have skipped a "host" position (its Depth fields, read
+    // its way, sum to 0); nothing else may change
+    std::vector<uint8_t> state(t->pos_state.begin(), t->pos_state.begin() + n_used);
+    if (row_state) {
+        for (uint32_t p = 0; p < n_used; ++p) {
+            const uint8_t s = (uint8_t)(row_state[(size_t)p * t->n_files] & (BV_TEXT_SKIP | BV_TEXT_HOST));
+            if (s != state[p] && !(state[p] == BV_TEXT_HOST && s == BV_TEXT_SKIP))
+                return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: row_state of position " + std::to_string(p) +
+                                                                 " differs from the parse (only HOST -> SKIP is allowed)");
+            state[p] = s;
+        }
+    }
+    uint32_t n_host = 0, n_out = 0;
+    uint32_t max_rank = 0;
+    for (uint32_t p = 0; p < n_used; ++p) {
+        const uint8_t s = state[p];
+        n_host += s == BV_TEXT_HOST;
+        n_out += s != BV_TEXT_SKIP;
+        if (s == 0) max_rank = std::max(max_rank, t->pos_max_rank[p]);
+    }
+    const uint32_t N = t->n_samples;
+    if (n_host) {
+        if (!host_rows || host_rows->n_sites != n_host || host_rows->n_samples != N || host_rows->pitch < N ||
+            (host_rows->pitch & 15u) || host_rows->mem_kind != BV_MEM_HOST || host_rows->layout || host_rows->reserved_ || !host_rows->base_strand ||
+            !host_rows->qual || !host_rows->mapq || !host_rows->rpr || !host_rows->ref_base)
+            return bv_engine_fail(e, BV_ERR_INVALID_ARG,
+                                  "bv_engine_text_submit: host_rows must hold the " + std::to_string(n_host) +
+                                      " host positions as a plain BV_MEM_HOST slab of n_samples = " + std::to_string(N) +
+                                      " with all five planes");
+    } else if (host_rows && host_rows->n_sites) {
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: host_rows given, but no position is marked host");
+    }
+    if (n_out && !out) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null out");
+    if (n_out && t->n_groups && !gout) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_groups > 0 needs gout");
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
+    t->parsed = false;  // one submit per parse, whatever happens below
+    if (n_out == 0) return BV_OK;
+    BV_TXT_HIP(e, hipSetDevice(t->device));
+    const uint64_t HP = n_host ? host_rows->pitch : 0;
+    for (uint32_t h = 0; h < n_host; ++h) {  // the tagged layout needs every rank <= BV_RPR_TAG_MAX_RANK, host rows' too
+        const uint16_t *r = host_rows->rpr + (size_t)h * HP;
+        for (uint32_t c = 0; c < N; ++c) max_rank = std::max<uint32_t>(max_rank, r[c]);
+    }
+    const uint64_t P = t->pitch;
+    const size_t cells = (size_t)n_out * P, hcells = (size_t)n_host * HP, G = t->n_groups;
+    int rc = grow(e, &t->d_sub, &t->sub_bytes, 5 * cells + up256(n_out));
+    if (rc != BV_OK) return rc;
+    const size_t o_host = up256(4ull * n_out), o_out = o_host + up256(5 * hcells + n_host), o_gout = o_out + up256(sizeof(bv_site_result) * n_out),
+                 misc = o_gout + up256(sizeof(bv_group_result) * n_out * G);
+    rc = grow(e, &t->d_misc, &t->misc_bytes, misc);
+    if (rc != BV_OK) return rc;
+    std::vector<int32_t> src(n_out);
+    for (uint32_t p = 0, j = 0, h = 0; p < n_used; ++p) {
+        const uint8_t s = state[p];
+        if (s == 0) src[j++] = (int32_t)p;
+        else if (s == BV_TEXT_HOST) src[j++] = -(int32_t)(h++) - 1;
+    }
+    uint8_t *hb = t->d_misc + o_host;
+    BV_TXT_HIP(e, hipMemcpyAsync(t->d_misc, src.data(), 4ull * n_out, hipMemcpyHostToDevice, st));
+    if (n_host) {
+        BV_TXT_HIP(e, hipMemcpyAsync(hb, host_rows->base_strand, hcells, hipMemcpyHostToDevice, st));
+        BV_TXT_HIP(e, hipMemcpyAsync(hb + hcells, host_rows->qual, hcells, hipMemcpyHostToDevice, st));
+        BV_TXT_HIP(e, hipMemcpyAsync(hb + 2 * hcells, host_rows->mapq, hcells, hipMemcpyHostToDevice, st));
+        BV_TXT_HIP(e, hipMemcpyAsync(hb + 3 * hcells, host_rows->rpr, 2 * hcells, hipMemcpyHostToDevice, st));
+        BV_TXT_HIP(e, hipMemcpyAsync(hb + 5 * hcells, host_rows->ref_base, n_host, hipMemcpyHostToDevice, st));
+    }
+    if (t->has_gid) {
+        rc = grow(e, &t->d_gid, &t->gid_bytes, up256(N));
+        if (rc != BV_OK) return rc;
+        BV_TXT_HIP(e, hipMemcpyAsync(t->d_gid, t->group_id.data(), N, hipMemcpyHostToDevice, st));
+    }
+    const size_t pcells = (size_t)t->n_pos * P;
+    const uint32_t tagged = max_rank <= BV_RPR_TAG_MAX_RANK ? 1u : 0u;
+    TextGatherArgs a;
+    a.src = reinterpret_cast<const int32_t *>(t->d_misc);
+    a.pbs = t->d_planes; a.pq = a.pbs + pcells; a.pmq = a.pq + pcells;
+    a.prp = reinterpret_cast<const uint16_t *>(t->d_planes + 4 * pcells); a.pref = t->d_planes + 6 * pcells; a.ppitch = P;
+    a.hbs = hb; a.hq = hb + hcells; a.hmq = hb + 2 * hcells; a.hrp = reinterpret_cast<const uint16_t *>(hb + 3 * hcells);
+    a.href = hb + 5 * hcells; a.hpitch = HP;
+    a.bs = t->d_sub; a.q = a.bs + cells; a.mq = a.q + cells; a.rp = reinterpret_cast<uint16_t *>(a.mq + cells);
+    a.ref = t->d_sub + 5 * cells; a.pitch = P; a.n_samples = N; a.tagged = tagged;
+    hipLaunchKernelGGL(bv_text_gather_kernel, dim3(n_out), dim3(256), 0, st, a);
+    BV_TXT_HIP(e, hipGetLastError());
+    bv_slab s{};
+    s.n_sites = n_out; s.n_samples = N; s.pitch = P;
+    s.base_strand = a.bs; s.qual = a.q; s.mapq = a.mq; s.rpr = a.rp; s.ref_base = a.ref;
+    s.group_id = G ? t->d_gid : nullptr; s.n_groups = (uint32_t)G;
+    s.mem_kind = BV_MEM_DEVICE; s.layout = tagged ? BV_SLAB_RPR_TAGGED : 0u;
+    bv_site_result *d_out = reinterpret_cast<bv_site_result *>(t->d_misc + o_out);
+    bv_group_result *d_gout = G ? reinterpret_cast<bv_group_result *>(t->d_misc + o_gout) : nullptr;
+    rc = bv_engine_submit(e, &s, d_out, d_gout, st);
+    if (rc != BV_OK) return rc;
+    rc = bv_engine_join(e, st);
+    if (rc != BV_OK) return rc;
+    BV_TXT_HIP(e, hipMemcpyAsync(out, d_out, sizeof(bv_site_result) * n_out, hipMemcpyDeviceToHost, st));
+    if (G) BV_TXT_HIP(e, hipMemcpyAsync(gout, d_gout, sizeof(bv_group_result) * n_out * G, hipMemcpyDeviceToHost, st));
+    if (cell) BV_TXT_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
+    if (phred) BV_TXT_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    return BV_OK;
+}
+
+}  // extern "C"

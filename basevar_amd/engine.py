@@ -360,6 +360,93 @@ class BaseTypeEngine:
         ms1, ms2 = self.kernel_ms()
         return BaseTypeBatch(out, gout, self.last_variant_count(), ms1, ms2)
 
+    # ---- batchfile text rows, parsed on the device
+    def lrt_text(self, rows, file_samples, group_id=None, n_groups=0, host_reader=None):
+        """The reference's own batchfile rows in, records out (bv_engine_text_parse + bv_engine_text_submit).
+
+        `rows`: one list per position of its row in every batchfile (bytes, without the line break), or a packed pair
+        (text, row_off) -- text bytes / uint8 array, row_off uint64 [n_positions * n_files + 1], every row ending in b"\n".
+        `file_samples`: samples per batchfile.  The device parses every position in the strict form of a well-formed row;
+        any other position comes back BV_TEXT_HOST and goes to `host_reader(list of row bytes) -> (cell, phred, mapq, rank,
+        ref_code)` numpy rows of n_samples, or None for a skipped position; without a host_reader such a position raises.
+        Returns a TextBatch: the records (one per position not skipped), `positions` (their indices), `row_state`
+        [n_positions][n_files] and the returned `cell` / `phred` planes [records][n_samples].  The engine must have been
+        created with max_samples >= sum(file_samples)."""
+        fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
+        F, N = int(fs.size), int(fs.sum())
+        if isinstance(rows, tuple):
+            text, off = rows
+            text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            P = (off.size - 1) // F
+        else:
+            P = len(rows)
+            flat = [bytes(r) + b"\n" for pos in rows for r in pos]
+            if any(len(pos) != F for pos in rows):
+                raise ValueError("lrt_text: every position needs one row per batchfile")
+            off = np.zeros(len(flat) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(r) for r in flat])
+            text = np.frombuffer(b"".join(flat), dtype=np.uint8)
+        gid = None if group_id is None else np.ascontiguousarray(group_id, dtype=np.uint8)
+        tr = _capi.TextRows(text.ctypes.data, off.ctypes.data, fs.ctypes.data, int(text.size), int(P), F, 0)
+        state = np.zeros((P, F), dtype=np.uint8)
+        rc = self._lib.bv_engine_text_parse(self._h, C.byref(tr), None if gid is None else gid.ctypes.data, int(n_groups),
+                                            state.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_parse failed (%d): %s" % (rc, self._err()))
+        host = []
+        for p in np.nonzero(state[:, 0] & _capi.BV_TEXT_HOST)[0]:
+            if host_reader is None:
+                raise RuntimeError("lrt_text: position %d is not in the strict form the device parses and no host_reader was given" % p)
+            lines = [bytes(text[int(off[p * F + f]):int(off[p * F + f + 1]) - 1]) for f in range(F)]
+            got = host_reader(lines)
+            if got is None:
+                state[p, :] = _capi.BV_TEXT_SKIP
+            else:
+                host.append(got)
+        positions = np.nonzero((state[:, 0] & _capi.BV_TEXT_SKIP) == 0)[0].astype(np.uint32)
+        R = int(positions.size)
+        hs = None
+        keep = []
+        if host:
+            pitch = (N + 15) // 16 * 16
+            planes = [np.full((len(host), pitch), 8, np.uint8), np.zeros((len(host), pitch), np.uint8),
+                      np.zeros((len(host), pitch), np.uint8), np.zeros((len(host), pitch), np.uint16)]
+            ref = np.zeros(len(host), np.uint8)
+            for h, (cell, phred, mapq, rank, ref_code) in enumerate(host):
+                for k, v in enumerate((cell, phred, mapq, rank)):
+                    planes[k][h, :N] = v
+                ref[h] = ref_code
+            keep = planes + [ref]
+            hs = _capi.Slab(len(host), N, pitch, *[a.ctypes.data for a in planes[:2]], planes[2].ctypes.data, planes[3].ctypes.data,
+                            ref.ctypes.data, None, 0, _capi.BV_MEM_HOST, 0, 0)
+        out = np.zeros(R, dtype=_capi.SITE_DTYPE)
+        gout = np.zeros((R, n_groups), dtype=_capi.GROUP_DTYPE) if n_groups else None
+        cell = np.zeros((R, N), np.uint8)
+        phred = np.zeros((R, N), np.uint8)
+        rc = self._lib.bv_engine_text_submit(self._h, state.ctypes.data, C.byref(hs) if hs is not None else None, int(P),
+                                             out.ctypes.data, gout.ctypes.data if n_groups else None, cell.ctypes.data,
+                                             phred.ctypes.data, None)
+        del keep
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_submit failed (%d): %s" % (rc, self._err()))
+        n_variant = 0
+        if R:
+            self.wait()
+            n_variant = self.last_variant_count()
+        return TextBatch(out, gout, n_variant, positions, state, cell, phred)
+
+
+class TextBatch(BaseTypeBatch):
+    """Records of BaseTypeEngine.lrt_text, plus the positions they belong to, the row states and the returned planes."""
+
+    def __init__(self, sites, groups, n_variant, positions, row_state, cell, phred):
+        super().__init__(sites, groups, n_variant, 0.0, 0.0)
+        self.positions = positions
+        self.row_state = row_state
+        self.cell = cell
+        self.phred = phred
+
 
 def tile_packed_layout(n_sites, width, with_ranks=True, with_groups=False):
     """(pitch, [offsets of base_strand, qual, mapq, rpr, group_id], total bytes) of a packed host tile: one allocation

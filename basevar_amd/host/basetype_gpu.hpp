@@ -19,10 +19,12 @@
 #include <cstdint>
 #include <stdexcept>
 #include <cstring>
+#include <exception>
 #include <string>
 #include <vector>
 
 #include "../../include/basevar_amd.h"
+#include "vcf_emit.hpp"  // SiteText
 
 namespace bvamd {
 
@@ -290,6 +292,84 @@ public:
             throw std::runtime_error(bv_last_error(e_));
         if (bv_engine_wait(e_) != BV_OK) throw std::runtime_error(bv_last_error(e_));
         return out;
+    }
+
+    // A batch of positions as the batchfiles' own text rows (bv_engine_text_parse): row (p, f) of `rows` is position p's line of
+    // batchfile f.  The device parses every position it can; the others go to `read_host` -- the host reader,
+    // bool(const std::vector<std::string> &rows, size_t n_samples, SlabBuilder &, SiteText &) as parse_site_rows_fast -- in
+    // position order.  When that reader throws, the positions before the offending one are delivered and `error` holds its
+    // exception (the caller rethrows it after emitting them: BatchfileProducer's order).
+    struct TextBatch {
+        BaseTypeBatch batch;               // one record per position that was not skipped
+        std::vector<uint32_t> position;    // ... its index in the batch
+        std::vector<SiteText> text;        // ... coordinates, REF and '+'/'-' tokens (the CVG indel column)
+        std::vector<uint8_t> cell, phred;  // ... [records][n_samples]: the GT:AB:SO:BP strings of format_vcf_line
+        std::vector<uint8_t> row_state;    // [n_positions][n_files] as bv_engine_text_parse reported it (HOST -> SKIP where the host skipped)
+        uint32_t n_positions_used = 0;
+        std::exception_ptr error;
+    };
+    template <class HostReader>
+    TextBatch lrt_text(const bv_text_rows &rows, HostReader &&read_host, const uint8_t *group_id = nullptr, uint32_t n_groups = 0) {
+        TextBatch tb;
+        const size_t F = rows.n_files;
+        tb.row_state.resize((size_t)rows.n_positions * F);
+        if (bv_engine_text_parse(e_, &rows, group_id, n_groups, tb.row_state.data(), nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+        uint32_t N = 0;
+        for (size_t f = 0; f < F; ++f) N += rows.file_samples[f];
+        auto row_text = [&](size_t p, size_t f) {  // the row without its '\n'
+            const uint64_t a = rows.row_off[p * F + f], b = rows.row_off[p * F + f + 1];
+            return std::string(rows.text + a, (size_t)(b - a - 1));
+        };
+        SlabBuilder host(N);
+        std::vector<std::string> lines(F);
+        uint32_t used = 0;
+        for (; used < rows.n_positions; ++used) {
+            uint8_t *rs = &tb.row_state[(size_t)used * F];
+            if (rs[0] & BV_TEXT_SKIP) continue;
+            SiteText st;
+            if (rs[0] & BV_TEXT_HOST) {
+                for (size_t f = 0; f < F; ++f) lines[f] = row_text(used, f);
+                bool kept = false;
+                try { kept = read_host(lines, (size_t)N, host, st); }
+                catch (...) { tb.error = std::current_exception(); break; }
+                if (!kept) { for (size_t f = 0; f < F; ++f) rs[f] = BV_TEXT_SKIP; continue; }
+            } else {
+                // device-parsed: the first three fields of file 0's row, and the '+'/'-' tokens of the flagged rows, in sample order
+                const std::string r0 = row_text(used, 0);
+                const size_t t1 = r0.find('\t'), t2 = r0.find('\t', t1 + 1), t3 = r0.find('\t', t2 + 1);
+                st.ref_id = r0.substr(0, t1);
+                st.ref_pos = (uint32_t)std::stoi(r0.substr(t1 + 1, t2 - t1 - 1));
+                st.ref_base = r0.substr(t2 + 1, t3 - t2 - 1);
+                for (size_t f = 0; f < F; ++f) {
+                    if (!(rs[f] & BV_TEXT_INDEL)) continue;
+                    const char *p = rows.text + rows.row_off[used * F + f];
+                    for (int k = 0; k < 5; ++k) { while (*p != '\t') ++p; ++p; }  // to Readbases (a parsed row has its 8 tabs)
+                    for (;;) {
+                        const char *q = p;
+                        while (*q != ' ' && *q != '\t') ++q;
+                        if (*p == '+' || *p == '-') st.indel_tokens.emplace_back(p, (size_t)(q - p));
+                        if (*q == '\t') break;
+                        p = q + 1;
+                    }
+                }
+            }
+            tb.position.push_back(used);
+            tb.text.push_back(std::move(st));
+        }
+        tb.n_positions_used = used;
+        const size_t R = tb.position.size();
+        tb.batch.sites.resize(R);
+        tb.batch.n_groups = n_groups;
+        tb.batch.groups.resize(R * n_groups);
+        tb.cell.resize(R * N);
+        tb.phred.resize(R * N);
+        const bv_slab hs = host.slab();
+        if (bv_engine_text_submit(e_, tb.row_state.data(), hs.n_sites ? &hs : nullptr, used, tb.batch.sites.data(),
+                                  n_groups ? tb.batch.groups.data() : nullptr, tb.cell.data(), tb.phred.data(), nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+        if (R && bv_engine_wait(e_) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return tb;
     }
 
 private:

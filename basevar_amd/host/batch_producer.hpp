@@ -198,10 +198,19 @@ public:
     // position order after delivering what precedes it.
     template <class Sink>
     void run(Sink &&sink) {
+        run(std::forward<Sink>(sink), [](Block &) { return true; });
+    }
+
+private:
+    struct Block;
+
+    template <class Sink, class BlockSink>
+    void run(Sink &&sink, BlockSink &&block_sink) {
         const size_t NB = rd_.size();
         if (NB == 0) return;
-        // positions per block: ~32 MB of row text, at least a few chunks per thread
+        // positions per block: ~32 MB of row text, at least a few chunks per thread (text mode: ~block_bytes of text, ~10 B per cell)
         R_ = std::max<size_t>(std::max<size_t>(64, 4 * (size_t)threads_), std::min<size_t>(4096, ((size_t)1 << 25) / std::max<size_t>(n_sample_ * 12, 1)));
+        if (text_mode_) R_ = std::min(text_max_positions_, std::max<size_t>(1, text_block_bytes_ / std::max<size_t>(n_sample_ * 10, 1)));
         chunk_ = std::max<size_t>(1, std::min<size_t>(16, R_ / (4 * (size_t)threads_)));
         bg_.resize(NB);
         blocks_.resize(kBlocks);
@@ -228,6 +237,8 @@ public:
             const double t0 = now();
             const bool last = B.n_blk < R_;
             // the chunks in position order; the first error in position order ends the run
+            if (text_mode_ && B.parts[0].error) err = B.parts[0].error;
+            else if (text_mode_ && B.n_blk) go_on = block_sink(B);
             for (Part &p : B.parts) {
                 if (go_on && !err && p.slab && p.slab->n_sites()) go_on = sink(*p.slab, p.text);
                 if (p.error && !err) err = p.error;
@@ -255,6 +266,23 @@ public:
         if (err) std::rethrow_exception(err);
     }
 
+public:
+    // Text mode (the device parses the rows, bv_engine_text_parse): instead of slab parts, every block goes to
+    // sink(std::string &text, std::vector<uint64_t> &row_off, size_t n_positions) as its rows packed position-major -- row (p, f)
+    // = text[row_off[p * NB + f], row_off[p * NB + f + 1]), each ending in '\n'.  The packing is the one copy of the bytes; pool
+    // tasks make it, a range of positions each, straight into the block's buffer.  The sink may swap the two buffers out (the
+    // producer then starts the next block in fresh ones) and returns false to stop.  Blocks hold about `block_bytes` of text
+    // and at most `max_positions` positions.  Read errors are thrown after the blocks before them; the rows are not looked at.
+    template <class Sink>
+    void run_text(Sink &&sink, size_t block_bytes, size_t max_positions) {
+        text_mode_ = true;
+        text_block_bytes_ = block_bytes;
+        text_max_positions_ = std::max<size_t>(1, max_positions);
+        run([&](SlabBuilder &, std::vector<SiteText> &) { return true; }, [&](Block &B) { return sink(B.text, B.row_off, B.n_blk); });
+        text_mode_ = false;
+    }
+
+public:
     ProducerClock clock;
     size_t block_sites() const { return R_; }
 
@@ -271,6 +299,8 @@ private:
         size_t reads_done = 0, parts_done = 0, n_blk = 0;
         std::vector<Part> parts;
         bool parsed = false;
+        std::string text;               // text mode: the block's rows, packed
+        std::vector<uint64_t> row_off;  // [n_blk * NB + 1]
     };
     static constexpr size_t kBlocks = 3;
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -467,10 +497,52 @@ private:
         B.parts.resize(std::max<size_t>(n_parts, 1));
         if (read_error_) { B.parts[0].error = read_error_; B.parsed = true; return; }
         if (n_parts == 0) { B.parsed = true; return; }
+        if (text_mode_) {
+            // where every row goes: its length is known, so the pack tasks can copy their ranges at the same time
+            const size_t NB = rd_.size();
+            B.row_off.resize(n * NB + 1);
+            uint64_t at = 0;
+            for (size_t r = 0; r < n; ++r)
+                for (size_t f = 0; f < NB; ++f) { B.row_off[r * NB + f] = at; at += B.lines[f][r].size() + 1; }
+            B.row_off[n * NB] = at;
+            // the buffer (a buffer handed to the sink comes back empty) is sized by a task of its own, outside the lock: the
+            // first touch of tens of MiB must not hold up the read tasks
+            ++in_flight_;
+            pool_->submit([this, &B, at, n_parts]() {
+                const double t0 = now();
+                B.text.resize(at);
+                std::lock_guard<std::mutex> lk(mu_);
+                clock.parse += now() - t0;
+                for (size_t p = 0; p < n_parts; ++p) {
+                    ++in_flight_;
+                    pool_->submit([this, &B, p]() { pack_task(B, p); });
+                }
+                --in_flight_;
+                cv_.notify_all();
+            });
+            return;
+        }
         for (size_t p = 0; p < n_parts; ++p) {
             ++in_flight_;
             pool_->submit([this, &B, p]() { parse_task(B, p); });
         }
+    }
+    void pack_task(Block &B, size_t p) {
+        const double t0 = now();
+        const size_t lo = p * chunk_, hi = std::min(B.n_blk, lo + chunk_), NB = rd_.size();
+        for (size_t r = lo; r < hi; ++r)
+            for (size_t f = 0; f < NB; ++f) {
+                const std::string &l = B.lines[f][r];
+                char *d = &B.text[B.row_off[r * NB + f]];
+                std::memcpy(d, l.data(), l.size());
+                d[l.size()] = '\n';
+            }
+        const double dt = now() - t0;
+        std::lock_guard<std::mutex> lk(mu_);
+        clock.parse += dt;
+        if (++B.parts_done == B.parts.size()) B.parsed = true;
+        --in_flight_;
+        cv_.notify_all();
     }
     void parse_task(Block &B, size_t p) {
         const double t0 = now();
@@ -513,6 +585,8 @@ private:
     std::vector<bool> file_busy_;
     size_t freed_ = 0, stop_at_ = (size_t)-1, in_flight_ = 0;
     std::exception_ptr read_error_;
+    bool text_mode_ = false;
+    size_t text_block_bytes_ = 0, text_max_positions_ = 0;
     TaskPool *pool_ = nullptr;
     std::mutex mu_;
     std::condition_variable cv_;

@@ -57,7 +57,16 @@ struct Batch {
     std::vector<bvamd::SiteText> text;
     bvamd::BaseTypeBatch result;
     std::string error;
+    // batchfile input: the block's rows as text (parsed on the device by the engine worker, bv_engine_text_parse), and the
+    // cell / phred rows of the records that come back; `error` then follows the records before the offending position
+    bool from_text = false;
+    std::string rows;
+    std::vector<uint64_t> row_off;
+    uint32_t n_positions = 0;
+    std::vector<uint8_t> cell, phred;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
+    const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
+    const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
 };
 typedef std::unique_ptr<Batch> BatchPtr;
 
@@ -190,12 +199,15 @@ int main(int argc, char **argv) {
         for (const auto &b : bams) sample_ids.push_back(bvamd::BamFile(b, false).sample_name());
     } catch (const std::exception &ex) { die(ex.what()); }
     std::vector<size_t> header_lines(batchfiles.size(), 0);  // lines in front of the first data row
+    std::vector<size_t> file_sample_count(batchfiles.size(), 0);
     for (size_t b = 0; b < batchfiles.size() && !from_bam; ++b) {
         if (!readers[b].open(batchfiles[b])) die("[ERROR] " + batchfiles[b] + " open failure.");
         std::string line;
         while (readers[b].getline(line)) {
             if (line.empty() || line[0] != '#') { first_row[b] = line; have_row[b] = !line.empty(); header_lines[b] += line.empty() ? 1 : 0; break; }
+            const size_t before = sample_ids.size();
             bvamd::parse_sample_ids(line, sample_ids);
+            file_sample_count[b] += sample_ids.size() - before;
             ++header_lines[b];
         }
     }
@@ -256,10 +268,19 @@ int main(int argc, char **argv) {
         const size_t by_cells = budget / std::max<size_t>(pitch, 1);
         batch_sites = (uint32_t)std::min<size_t>(65536, std::max<size_t>(by_cells, 64));
     }
+    // batchfile input: a batch is one block of rows as text, ~10 B per cell.  32 MiB blocks, the size of the host reader's
+    // blocks: larger ones left the read tasks waiting on the packing of the few blocks in flight (measured: 512 MiB blocks on
+    // 16 threads ran at 0.6 x the host reader's rate).  In flight: 4 G + 7 blocks, far below the planes' 16 GiB budget.
+    const size_t text_block_bytes = (size_t)1 << 25;
+    std::vector<uint32_t> file_samples;  // samples per batchfile, in batchfile order (the header scan)
+    for (size_t f = 0; f < file_sample_count.size(); ++f) file_samples.push_back((uint32_t)file_sample_count[f]);
 
     // ---- the pipeline: producer (this thread) -> G engine workers -> emitter, results written in batch order
     const size_t G = devices.size();
-    BatchQueue to_gpu(G + 1), to_emit(2 * G + 2);
+    // batchfile input: three engine workers per GPU -- a text batch has host work on its worker (the rows into pinned staging,
+    // the host reader for the positions the device leaves to it, the records and planes back), which the other two overlap
+    const size_t W = from_bam ? G : 3 * G;
+    BatchQueue to_gpu(W + 1), to_emit(2 * W + 2);
     std::mutex err_mu;
     std::string first_error;
     StageClock clk;
@@ -269,8 +290,9 @@ int main(int argc, char **argv) {
         if (first_error.empty()) first_error = m;
     };
     std::vector<std::thread> workers;
-    for (size_t g = 0; g < G; ++g)
-        workers.emplace_back([&, g]() {
+    for (size_t w = 0; w < W; ++w)
+        workers.emplace_back([&, w]() {
+            const size_t g = w % G;
             std::unique_ptr<bvamd::BaseTypeEngine> engine;
             // this worker feeds one GPU: keep it (and the staging memory it touches first) on the CPUs of that GPU's NUMA node
             (void)bv_bind_thread_to_device_node(devices[g]);
@@ -280,8 +302,27 @@ int main(int argc, char **argv) {
             for (BatchPtr b; (b = to_gpu.pop());) {
                 if (engine) {
                     const double t0 = StageClock::now();
-                    // (the producer's choice of layout: short reads -> the rank words carry the calls, basetype_gpu.hpp)
-                    try { b->slab.tag_ranks(); b->result = engine->lrt(b->slab); } catch (const std::exception &ex) { b->error = ex.what(); }
+                    if (b->from_text) {
+                        // the device parses the rows; the positions it leaves to the host go to the host reader in between
+                        try {
+                            const bv_text_rows rows{b->rows.data(), b->row_off.data(), file_samples.data(), b->rows.size(), b->n_positions,
+                                                    (uint32_t)file_samples.size(), 0};
+                            auto tb = engine->lrt_text(rows, [](const std::vector<std::string> &r, size_t n, bvamd::SlabBuilder &sb,
+                                                                bvamd::SiteText &st) { return bvamd::parse_site_rows_fast(r, n, sb, st); },
+                                                       group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size());
+                            b->result = std::move(tb.batch);
+                            b->text = std::move(tb.text);
+                            b->cell = std::move(tb.cell);
+                            b->phred = std::move(tb.phred);
+                            if (tb.error) {
+                                try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b->error = ex.what(); }
+                            }
+                        } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); }
+                        std::string().swap(b->rows);
+                    } else {
+                        // (the producer's choice of layout: short reads -> the rank words carry the calls, basetype_gpu.hpp)
+                        try { b->slab.tag_ranks(); b->result = engine->lrt(b->slab); } catch (const std::exception &ex) { b->error = ex.what(); }
+                    }
                     const double dt = StageClock::now() - t0;
                     std::lock_guard<std::mutex> lk(err_mu);
                     clk.engine += dt;
@@ -295,12 +336,17 @@ int main(int argc, char **argv) {
     std::thread emitter([&]() {
         std::map<uint64_t, BatchPtr> waiting;  // finished out of order
         uint64_t next_seq = 0;
+        bool stopped = false;  // a batch failed: nothing behind it is written
         for (BatchPtr b; (b = to_emit.pop());) {
             waiting[b->seq] = std::move(b);
             for (auto it = waiting.find(next_seq); it != waiting.end(); it = waiting.find(next_seq)) {
                 Batch &d = *it->second;
-                if (!d.error.empty()) fail(d.error);
-                else {
+                // (a text batch whose host reader refused a position: its records before that position are written first)
+                if (stopped) {
+                } else if (!d.error.empty() && !d.from_text) {
+                    stopped = true;
+                    fail(d.error);
+                } else {
                     const double t0 = StageClock::now();
                     // the lines of a batch are formatted by `--thread` threads (ranges of consecutive sites, a text buffer each)
                     // and written in site order
@@ -311,7 +357,7 @@ int main(int argc, char **argv) {
                         for (size_t i = lo; i < hi; ++i) {
                             cvg_txt[t] += bvamd::format_cvg_line(d.text[i], d.result.sites[i]);
                             if (d.result.has_variant(i)) {
-                                vcf_txt[t] += bvamd::format_vcf_line(d.text[i], d.slab.cell_row(i), d.slab.phred_row(i), n_sample, d.result.sites[i],
+                                vcf_txt[t] += bvamd::format_vcf_line(d.text[i], d.cell_row(i, n_sample), d.phred_row(i, n_sample), n_sample, d.result.sites[i],
                                                                      group_names.empty() ? nullptr : &d.result.group(i, 0), group_names);
                                 ++nv[t];
                             }
@@ -326,6 +372,7 @@ int main(int argc, char **argv) {
                     } catch (const std::exception &ex) { fail(ex.what()); }
                     n_sites += d.text.size();
                     clk.emit += StageClock::now() - t0;
+                    if (!d.error.empty()) { stopped = true; fail(d.error); }
                 }
                 waiting.erase(it);
                 ++next_seq;
@@ -387,24 +434,21 @@ int main(int argc, char **argv) {
         } else {
             // ---- one row from every batchfile per position (caller.cpp:586-611), on `--thread` host threads: files read and
             // positions parsed in blocks by a pipeline of tasks (batch_producer.hpp), joined here in position order
+            // Every block goes to the engines as its rows' text: the device parses them (bv_engine_text_parse), the engine worker
+            // re-reads with the host reader only the positions the device leaves to it.  A block is one batch; text is about twice
+            // the 5 B per cell of planes, so a batch carries half the cells of the planes' budget.
             bvamd::BatchfileProducer producer(readers, first_row, have_row, n_sample, threads);
             producer.set_paths(batchfiles, header_lines);  // BGZF files (what the reference writes): members inflated in parallel
             try {
-                producer.run([&](bvamd::SlabBuilder &part_, std::vector<bvamd::SiteText> &text) {
-                    bvamd::SlabBuilder *part = &part_;
-                    size_t done = 0;
-                    const size_t have = part->n_sites();
-                    while (done < have) {
-                        if (!cur) fresh();
-                        const size_t room = batch_sites - cur->slab.n_sites(), take = std::min(room, have - done);
-                        if (done == 0 && take == have) cur->slab.append(*part);
-                        else cur->slab.append_rows(*part, done, take);  // (a part that straddles a batch boundary)
-                        for (size_t i = done; i < done + take; ++i) cur->text.push_back(std::move(text[i]));
-                        done += take;
-                        if (cur->slab.n_sites() == batch_sites) ship();
-                    }
+                producer.run_text([&](std::string &rows, std::vector<uint64_t> &row_off, size_t n_positions) {
+                    fresh();
+                    cur->from_text = true;
+                    cur->rows.swap(rows);
+                    cur->row_off.swap(row_off);
+                    cur->n_positions = (uint32_t)n_positions;
+                    to_gpu.push(std::move(cur));
                     return still_ok();
-                });
+                }, text_block_bytes, batch_sites);
             } catch (...) {
                 clk.read += producer.clock.read; clk.parse += producer.clock.parse;
                 throw;
@@ -428,7 +472,7 @@ int main(int argc, char **argv) {
     char line[512];
     std::snprintf(line, sizeof line,
                   "[INFO] -- %.3f s elapsed, %.1f sites/s: read %.3f s, parse+pack %.3f s (%s; thread-seconds), engine %.3f s (%zu worker(s), batches of %u sites), emit %.3f s",
-                  total, total > 0 ? n_sites / total : 0.0, clk.read, clk.parse, from_bam ? "pileup" : "batchfile", clk.engine, G, batch_sites, clk.emit);
+                  total, total > 0 ? n_sites / total : 0.0, clk.read, clk.parse, from_bam ? "pileup" : "batchfile", clk.engine, W, batch_sites, clk.emit);
     std::cout << line << std::endl;
     if (!timing_file.empty()) {
         std::ofstream tf(timing_file);

@@ -263,6 +263,18 @@ int bv_engine_tiles_add_sparse_many(bv_engine *e, uint32_t n_tiles, const bv_spa
 int bv_sparse_tile_packed_layout(uint32_t n_sites, uint32_t n_entries, uint32_t width, int with_ranks, int with_groups,
                                  uint64_t offsets[7], uint64_t *total_bytes);
 
+/* Batchfile rows parsed on the device (src/basetype_caller.cpp:686-740; contract: INTEGRATION.md 2e).  Row (p, f) = text[row_off[
+ * p*n_files+f], row_off[p*n_files+f+1]) ends in '\n'; row_state: 0 parsed, SKIP (Depth 0), HOST (caller re-reads), | INDEL. */
+typedef struct bv_text_rows {
+    const char *text; const uint64_t *row_off; const uint32_t *file_samples; /* row_off: [n_positions * n_files + 1] */
+    uint64_t text_bytes; uint32_t n_positions, n_files, reserved_;
+} bv_text_rows;
+enum { BV_TEXT_SKIP = 1, BV_TEXT_HOST = 2, BV_TEXT_INDEL = 4 };
+int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
+                         void *stream);
+int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab *host_rows, uint32_t n_positions_used,
+                          bv_site_result *out, bv_group_result *gout, uint8_t *cell, uint8_t *phred, void *stream);
+
 /* 1 when engine e replays tie-prone shallow sites (<= 64 covered samples) with the host libm's own log() restated on the
  * device, verified bit-exact at creation (the reference takes log() with the host libm, src/algorithm.h:243); 0: the device
  * library's log() -- values within 1e-6, exact ties undecided (BV_SITE_LOG_APPROX).  Probes: basevar_amd_diag.h. */
