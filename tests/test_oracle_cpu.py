@@ -78,6 +78,29 @@ def test_restatement_matches_reference_fresh(restatement, seed, n, cov, groups):
     assert ((a["status"] & 2) != 0).sum() > 5  # the slab exercises the variant branch
 
 
+@pytest.mark.parametrize("groups", [0, 3])
+@pytest.mark.parametrize("n", [64, 500, 3000])
+def test_restatement_matches_reference_over_the_value_domain(reference, n, groups):
+    """mapq 0..255, phred 0..93 and ranks 0..65,535 on the REF and ALT reads of variant sites (tests/value_domain.py: what
+    test_gpu_value_domain.py holds the engine to), and deep rows with a dominant mapq of 60, 0 or 255: the restatement
+    gives the real reference's records on every compared field."""
+    from value_domain import assert_edges_hit, dense_slab, edge_slab
+    maf = oracle.Restatement().min_af(n)
+    slab = edge_slab(160, n, seed=7000 + n + groups, coverage=0.5 if n <= 64 else 0.2, n_groups=groups)
+    a, ga = oracle.Restatement().run(slab, maf, n_threads=4)
+    b, gb = reference.run(slab, maf, n_threads=4)
+    assert_bit_equal(a, b, skip=EXACT_SKIP)
+    if groups:
+        assert_bit_equal(ga, gb)
+    assert_edges_hit(slab, b)
+    if not groups:
+        slab = dense_slab(20, n, seed=7100 + n)
+        a, _ = oracle.Restatement().run(slab, maf, n_threads=4)
+        b, _ = reference.run(slab, maf, n_threads=4)
+        assert_bit_equal(a, b, skip=EXACT_SKIP)
+        assert ((b["status"] & 2) != 0).all()
+
+
 def test_restatement_threads_agree(restatement):
     slab = make_slab(64, 2000, seed=7, coverage=0.2, n_groups=2)
     maf = restatement.min_af(2000)
