@@ -65,6 +65,25 @@ class TextRows(C.Structure):  # bv_text_rows
 BV_TEXT_SKIP, BV_TEXT_HOST, BV_TEXT_INDEL = 1, 2, 4  # bv_engine_text_parse row states
 
 
+class BgzfMembers(C.Structure):  # bv_bgzf_members (include/basevar_amd_bgzf.h)
+    _fields_ = [("data", C.c_void_p), ("member_off", C.c_void_p), ("data_bytes", C.c_uint64), ("n_members", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+class BgzfRows(C.Structure):  # bv_bgzf_rows
+    _fields_ = [("data", C.c_void_p), ("member_off", C.c_void_p), ("data_bytes", C.c_uint64), ("file_member", C.c_void_p),
+                ("file_samples", C.c_void_p), ("skip_bytes", C.c_void_p), ("skip_lines", C.c_void_p), ("n_files", C.c_uint32),
+                ("max_positions", C.c_uint32), ("at_end", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class BgzfCursor(C.Structure):  # bv_bgzf_cursor
+    _fields_ = [("member", C.c_uint32), ("offset", C.c_uint32)]
+
+
+BV_ERR_DATA = -6  # include/basevar_amd_bgzf.h
+BV_BGZF_OK, BV_BGZF_BAD_HEADER, BV_BGZF_BAD_DEFLATE, BV_BGZF_BAD_SIZE, BV_BGZF_BAD_CRC = 0, 1, 2, 3, 4
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_sites", C.c_uint32), ("max_samples", C.c_uint32),
                 ("flags", C.c_uint32), ("min_af", C.c_double)]
@@ -83,6 +102,9 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
            "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form",
            "bv_engine_text_parse", "bv_engine_text_submit"]
+
+# every symbol include/basevar_amd_bgzf.h declares
+BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch"]
 
 _lib = None
 
@@ -177,5 +199,11 @@ def load():
     L.bv_engine_text_submit.restype = C.c_int
     L.bv_engine_text_submit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Slab), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+    L.bv_engine_bgzf_inflate.restype = C.c_int
+    L.bv_engine_bgzf_inflate.argtypes = [C.c_void_p, C.POINTER(BgzfMembers), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_engine_text_parse_bgzf.restype = C.c_int
+    L.bv_engine_text_parse_bgzf.argtypes = [C.c_void_p, C.POINTER(BgzfRows), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_engine_text_rows_fetch.restype = C.c_int
+    L.bv_engine_text_rows_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
     _lib = L
     return L

@@ -273,6 +273,7 @@ struct bv_engine {
     bool desc_used[kDescRing] = {};
     unsigned desc_next = 0;
     BvTextState *text = nullptr;       // bv_engine_text_parse / _submit (bv_text.hip)
+    BvBgzfState *bgzf = nullptr;       // bv_engine_bgzf_inflate (bv_inflate.hip)
     mutable std::mutex mu;
     std::string err;
 };
@@ -498,7 +499,7 @@ int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engin
 }  // namespace
 
 BvEngineView bv_engine_view(bv_engine *e) {
-    return BvEngineView{e->cfg.device, e->cfg.max_sites, e->cfg.max_samples, e->stream, &e->text};
+    return BvEngineView{e->cfg.device, e->cfg.max_sites, e->cfg.max_samples, e->stream, &e->text, &e->bgzf};
 }
 int bv_engine_fail(bv_engine *e, int code, const std::string &msg) { return fail(e, code, msg); }
 
@@ -635,6 +636,7 @@ int bv_engine_destroy(bv_engine *e) {
     if (e->ev_entry) (void)hipEventDestroy(e->ev_entry);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     bv_text_state_free(e->text);
+    bv_bgzf_state_free(e->bgzf);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

@@ -299,11 +299,22 @@ void bv_launch_p1s_fused(const BvP1ShortArgs &a, hipStream_t stream);
 #include <string>
 struct BvTextState;
 void bv_text_state_free(BvTextState *t);
+struct BvBgzfState;
+void bv_bgzf_state_free(BvBgzfState *t);
 struct BvEngineView {
     int device;
     uint32_t max_sites, max_samples;
     hipStream_t stream;   // the engine's own stream
     BvTextState **text;   // the engine's text state (created by the first bv_engine_text_parse)
+    BvBgzfState **bgzf;   // the engine's BGZF staging (created by the first bv_engine_bgzf_inflate; bv_inflate.hip)
 };
 BvEngineView bv_engine_view(bv_engine *e);
 int bv_engine_fail(bv_engine *e, int code, const std::string &msg);  // sets bv_last_error(e) (or the global one), returns code
+
+// BGZF members (bv_inflate.hip) for the text path (bv_text.hip): their wrappers read on the host, then inflated to chosen places
+#include <vector>
+struct bv_bgzf_members;
+struct BvBgzfMember;
+int bv_bgzf_headers(bv_engine *e, const char *who, const bv_bgzf_members *mb, std::vector<BvBgzfMember> &hd, std::vector<uint8_t> &pre);
+int bv_bgzf_inflate_placed(bv_engine *e, const bv_bgzf_members *mb, const std::vector<BvBgzfMember> &hd, const std::vector<uint8_t> &pre,
+                           const uint64_t *out_pos, uint8_t *d_dst, uint8_t *status, hipStream_t st);

@@ -22,6 +22,8 @@
 #include <string>
 #include <vector>
 
+#include "../../include/basevar_amd_bgzf.h"
+#include "bv_inflate_core.h"
 #include "bv_kernels.h"
 
 namespace {
@@ -33,7 +35,8 @@ constexpr size_t kChunkBytes = (size_t)128 << 20;  // text bytes per staged chun
 
 struct TextParseArgs {
     const char *text;          // the chunk: byte k is text byte chunk_base + k
-    const uint64_t *row_off;   // [n_rows + 1] absolute offsets (device)
+    const uint64_t *row_beg;   // [n_rows] absolute offset of every row's first byte (device) ...
+    const uint64_t *row_end;   // [n_rows] ... and of the byte behind its '\n' (bv_engine_text_parse: row_beg + 1, rows are contiguous)
     const uint32_t *foff;      // [n_files] sample offset of file f inside the row
     const uint32_t *fsamp;     // [n_files]
     uint64_t chunk_base;
@@ -77,10 +80,10 @@ __global__ __launch_bounds__(256) void bv_text_parse_kernel(TextParseArgs a) {
     const uint32_t r = a.row_first + local;
     const uint32_t p = r / a.n_files, f = r - p * a.n_files;
     const uint32_t r0 = p * a.n_files;  // file 0's row of the same position
-    const char *row = a.text + (a.row_off[r] - a.chunk_base);
-    const char *row0 = a.text + (a.row_off[r0] - a.chunk_base);
-    const uint32_t len = (uint32_t)(a.row_off[r + 1] - a.row_off[r]);  // the last byte is '\n' (checked by the host)
-    const uint32_t len0 = (uint32_t)(a.row_off[r0 + 1] - a.row_off[r0]);
+    const char *row = a.text + (a.row_beg[r] - a.chunk_base);
+    const char *row0 = a.text + (a.row_beg[r0] - a.chunk_base);
+    const uint32_t len = (uint32_t)(a.row_end[r] - a.row_beg[r]);  // the last byte is '\n' (checked by the host / the line index)
+    const uint32_t len0 = (uint32_t)(a.row_end[r0] - a.row_beg[r0]);
 
     // ---- CHROM \t POS \t REF \t Depth \t: one lane (they are a few bytes)
     uint32_t start = 0, ok = 1, dep = 0;
@@ -269,6 +272,115 @@ __global__ __launch_bounds__(256) void bv_text_gather_kernel(TextGatherArgs a) {
     if (threadIdx.x == 0) a.ref[j] = dev ? a.pref[s] : a.href[-s - 1];
 }
 
+// ---- rows that arrive compressed (bv_engine_text_parse_bgzf, include/basevar_amd_bgzf.h): the line index over the inflated runs.
+// File f's run lies at text[base .. base + len), with one spare byte behind it that holds '\n': where the runs reach the ends of
+// their files and the last line has no line break, the spare byte is its line break.  One wave per 16 KiB tile of a run counts
+// the line ends (bv_text_line_count_kernel), one thread per file sums its tiles and takes the minimum of the files' complete
+// lines (bv_text_line_scan_kernel), and the tiles are walked again to write every taken row's begin and end
+// (bv_text_line_scatter_kernel).
+constexpr uint32_t kLineTile = 16384;
+struct LineFile {
+    uint64_t base, len, skip;  // the run inside the text; inflated bytes before the file's first row
+    uint32_t skip_lines;       // further lines before it
+    uint32_t tile_first, n_tiles, reserved_;
+};
+
+__device__ __forceinline__ uint32_t line_file_of(const LineFile *fl, uint32_t F, uint32_t tile) {
+    uint32_t lo = 0, hi = F - 1u;  // the last file whose first tile is <= tile (files without a tile share the next one's)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) / 2u;
+        if (fl[mid].tile_first <= tile) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+// bytes of the run that the index looks at: the run, and the spare '\n' where it ends an unterminated last line
+__device__ __forceinline__ uint64_t line_run_end(const char *text, const LineFile &L, uint32_t at_end) {
+    return L.len + ((at_end && L.len > L.skip && text[L.base + L.len - 1] != '\n') ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(64) void bv_text_line_pad_kernel(char *text, const LineFile *fl, uint32_t F) {
+    const uint32_t f = blockIdx.x * 64u + threadIdx.x;
+    if (f < F) text[fl[f].base + fl[f].len] = '\n';
+}
+
+__global__ __launch_bounds__(64) void bv_text_line_count_kernel(const char *text, const LineFile *fl, uint32_t F, uint32_t at_end, uint32_t *tile_cnt) {
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const LineFile L = fl[line_file_of(fl, F, tile)];
+    const uint64_t end = line_run_end(text, L, at_end);
+    const uint64_t lo = L.skip + (uint64_t)(tile - L.tile_first) * kLineTile, hi = lo + kLineTile < end ? lo + kLineTile : end;
+    uint32_t cnt = 0;
+    for (uint64_t x = lo + lane; x < hi; x += 64u) cnt += text[L.base + x] == '\n';
+    for (int o = 32; o > 0; o >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, o);
+    if (lane == 0) tile_cnt[tile] = cnt;
+}
+
+// tile_cnt -> exclusive prefix inside each file; *n_pos (set to the caller's limit before) -> min over the files' lines
+__global__ __launch_bounds__(256) void bv_text_line_scan_kernel(const LineFile *fl, uint32_t F, uint32_t *tile_cnt, uint32_t *n_pos) {
+    for (uint32_t f = threadIdx.x; f < F; f += 256u) {
+        uint32_t run = 0;
+        for (uint32_t k = 0; k < fl[f].n_tiles; ++k) {
+            const uint32_t c = tile_cnt[fl[f].tile_first + k];
+            tile_cnt[fl[f].tile_first + k] = run;
+            run += c;
+        }
+        atomicMin(n_pos, run > fl[f].skip_lines ? run - fl[f].skip_lines : 0u);
+    }
+}
+
+__global__ __launch_bounds__(64) void bv_text_line_scatter_kernel(const char *text, const LineFile *fl, uint32_t F, uint32_t at_end,
+                                                                  const uint32_t *tile_pre, uint32_t P, uint64_t *row_beg, uint64_t *row_end) {
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const uint32_t f = line_file_of(fl, F, tile);
+    const LineFile L = fl[f];
+    const uint64_t end = line_run_end(text, L, at_end);
+    const uint64_t lo = L.skip + (uint64_t)(tile - L.tile_first) * kLineTile, hi = lo + kLineTile < end ? lo + kLineTile : end;
+    if (tile == L.tile_first && L.skip_lines == 0 && lane == 0) row_beg[f] = L.base + L.skip;
+    uint32_t ord = tile_pre[tile];  // line ends of this run before the tile
+    const uint64_t lt = (1ull << lane) - 1ull;
+    for (uint64_t x0 = lo; x0 < hi; x0 += 64u) {
+        const uint64_t x = x0 + lane;
+        const bool nl = x < hi && text[L.base + x] == '\n';
+        const uint64_t B = __ballot(nl);
+        if (nl) {
+            // line end number j of the run ends row j - skip_lines and begins the next one
+            const int64_t q = (int64_t)(ord + (uint32_t)__popcll(B & lt)) - (int64_t)L.skip_lines;
+            if (q >= 0 && q < (int64_t)P) row_end[(size_t)q * F + f] = L.base + x + 1u;
+            if (q + 1 >= 0 && q + 1 < (int64_t)P) row_beg[(size_t)(q + 1) * F + f] = L.base + x + 1u;
+        }
+        ord += (uint32_t)__popcll(B);
+    }
+}
+
+// ---- bv_engine_text_rows_fetch: how much of every row the host still needs, then the bytes
+__global__ __launch_bounds__(256) void bv_text_fetch_len_kernel(const char *text, const uint64_t *row_beg, const uint64_t *row_end, const uint8_t *pos_state,
+                                                                const uint8_t *rowflag, uint32_t R, uint32_t F, uint32_t *len) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t p = r / F, f = r - p * F;
+    const uint8_t s = pos_state[p];
+    const uint32_t n = (uint32_t)(row_end[r] - row_beg[r]) - 1u;  // without the line break
+    uint32_t out = 0;
+    if (s & BV_TEXT_SKIP) {
+        out = 0;
+    } else if ((s & BV_TEXT_HOST) || (rowflag[r] & BV_TEXT_INDEL)) {
+        out = n;
+    } else if (f == 0) {  // CHROM \t POS \t REF \t Depth \t
+        const char *row = text + row_beg[r];
+        uint32_t tabs = 0, i = 0;
+        for (; i < n && tabs < 4u; ++i) tabs += row[i] == '\t';
+        out = i;
+    }
+    len[r] = out;
+}
+__global__ __launch_bounds__(256) void bv_text_fetch_copy_kernel(const char *text, const uint64_t *row_beg, const uint32_t *len, const uint64_t *off,
+                                                                 uint32_t R, uint8_t *out) {
+    const uint32_t r = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (r >= R) return;
+    const char *row = text + row_beg[r];
+    uint8_t *o = out + off[r];
+    for (uint32_t i = lane; i < len[r]; i += 64u) o[i] = (uint8_t)row[i];
+}
+
 }  // namespace
 
 // Per-engine state of the text path: the parsed planes of the last bv_engine_text_parse, the slab handed to the calling kernels,
@@ -297,6 +409,17 @@ struct BvTextState {
     std::vector<uint32_t> pos_max_rank;
     std::vector<uint8_t> group_id;
     bool has_gid = false;
+    std::vector<uint32_t> h_foff;           // sample offset of every file (what parse_begin uploads)
+    // bv_engine_text_parse_bgzf: the inflated runs, the line index, and what bv_engine_text_rows_fetch gathers
+    bool bgzf_rows = false;                 // the last parse was a _parse_bgzf: d_btext and the row begins / ends stand
+    const uint64_t *bz_row_beg = nullptr, *bz_row_end = nullptr;  // ... where they stand (inside d_aux) ...
+    const uint8_t *bz_rowflag = nullptr;    // ... and the rows' BV_TEXT_INDEL flags
+    uint8_t *d_btext = nullptr;             // file f's run inflated back to back, one spare byte behind each run
+    size_t btext_bytes = 0;
+    uint8_t *d_lines = nullptr;             // LineFile [n_files], newline counts / prefixes per tile, n_pos
+    size_t lines_bytes = 0;
+    uint8_t *d_fetch = nullptr;             // rows_fetch: pos_state [n_pos], len u32 [n_rows], off u64 [n_rows + 1], the bytes
+    size_t fetch_bytes = 0;
 };
 
 void bv_text_state_free(BvTextState *t) {
@@ -309,7 +432,7 @@ void bv_text_state_free(BvTextState *t) {
         if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
         if (t->ev_parsed[k]) (void)hipEventDestroy(t->ev_parsed[k]);
     }
-    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid})
+    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch})
         if (b) (void)hipFree(b);
     if (t->cs) (void)hipStreamDestroy(t->cs);
     delete t;
@@ -357,12 +480,22 @@ int ensure_chunks(bv_engine *e, BvTextState *t, size_t bytes) {
     return BV_OK;
 }
 
-int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
-               hipStream_t st, uint32_t n_samples) {
-    const uint32_t P = rows->n_positions, F = rows->n_files;
+// The device arrays of one parse of P positions x F files.
+struct ParseBufs {
+    uint8_t *bs, *q, *mq, *stp, *ref, *rowflag;
+    uint16_t *rp;
+    uint32_t *depth, *pstate, *pmax, *foff, *fsamp;
+    uint64_t *d_off;  // [2 * (P * F + 1)]: row_off [P * F + 1] of bv_engine_text_parse; row begins [P * F], then row ends, of _parse_bgzf
+    uint64_t pitch;
+};
+
+// Sized, cleared (a parsed row is all 'N' where the text leaves nothing) and with the files' sample offsets in place.
+int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint32_t *file_samples, uint32_t n_samples, hipStream_t st,
+                ParseBufs *b) {
     const size_t R = (size_t)P * F;
     const uint64_t pitch = (n_samples + 255ull) & ~255ull;
     t->parsed = false;
+    t->bgzf_rows = false;
     BV_TXT_HIP(e, hipSetDevice(t->device));
     // a parse that failed part-way may have left chunk copies queued: the staging is free only once they are through
     if (t->cs) BV_TXT_HIP(e, hipStreamSynchronize(t->cs));
@@ -371,27 +504,45 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
     int rc = grow(e, &t->d_planes, &t->planes_bytes, 6 * cells + up256(P));
     if (rc != BV_OK) return rc;
     const size_t o_pstate = up256(4ull * P), o_pmax = 2 * o_pstate, o_flag = 3 * o_pstate, o_off = o_flag + up256(R),
-                 o_foff = o_off + up256(8 * (R + 1)), o_fs = o_foff + up256(4ull * F), aux = o_fs + up256(4ull * F);
+                 o_foff = o_off + up256(16 * (R + 1)), o_fs = o_foff + up256(4ull * F), aux = o_fs + up256(4ull * F);
     rc = grow(e, &t->d_aux, &t->aux_bytes, aux);
     if (rc != BV_OK) return rc;
-    uint8_t *bs = t->d_planes, *q = bs + cells, *mq = q + cells, *stp = mq + cells;
-    uint16_t *rp = reinterpret_cast<uint16_t *>(stp + cells);
-    uint8_t *ref = stp + 3 * cells;
-    uint32_t *depth = reinterpret_cast<uint32_t *>(t->d_aux), *pstate = reinterpret_cast<uint32_t *>(t->d_aux + o_pstate),
-             *pmax = reinterpret_cast<uint32_t *>(t->d_aux + o_pmax), *foff = reinterpret_cast<uint32_t *>(t->d_aux + o_foff),
-             *fsamp = reinterpret_cast<uint32_t *>(t->d_aux + o_fs);
-    uint8_t *rowflag = t->d_aux + o_flag;
-    uint64_t *d_off = reinterpret_cast<uint64_t *>(t->d_aux + o_off);
-    std::vector<uint32_t> h_foff(F);
-    for (uint32_t f = 0, s = 0; f < F; s += rows->file_samples[f], ++f) h_foff[f] = s;
-    // a parsed row is all 'N' where the text leaves nothing (the padding of every row, skipped and host positions)
-    BV_TXT_HIP(e, hipMemsetAsync(bs, BV_CELL_N, cells, st));
-    BV_TXT_HIP(e, hipMemsetAsync(q, 0, 3 * cells, st));  // q, mq, strand
-    BV_TXT_HIP(e, hipMemsetAsync(rp, 0, 2 * cells, st));
+    b->pitch = pitch;
+    b->bs = t->d_planes; b->q = b->bs + cells; b->mq = b->q + cells; b->stp = b->mq + cells;
+    b->rp = reinterpret_cast<uint16_t *>(b->stp + cells);
+    b->ref = b->stp + 3 * cells;
+    b->depth = reinterpret_cast<uint32_t *>(t->d_aux); b->pstate = reinterpret_cast<uint32_t *>(t->d_aux + o_pstate);
+    b->pmax = reinterpret_cast<uint32_t *>(t->d_aux + o_pmax); b->foff = reinterpret_cast<uint32_t *>(t->d_aux + o_foff);
+    b->fsamp = reinterpret_cast<uint32_t *>(t->d_aux + o_fs);
+    b->rowflag = t->d_aux + o_flag;
+    b->d_off = reinterpret_cast<uint64_t *>(t->d_aux + o_off);
+    t->h_foff.resize(F);
+    for (uint32_t f = 0, s = 0; f < F; s += file_samples[f], ++f) t->h_foff[f] = s;
+    BV_TXT_HIP(e, hipMemsetAsync(b->bs, BV_CELL_N, cells, st));
+    BV_TXT_HIP(e, hipMemsetAsync(b->q, 0, 3 * cells, st));  // q, mq, strand
+    BV_TXT_HIP(e, hipMemsetAsync(b->rp, 0, 2 * cells, st));
     BV_TXT_HIP(e, hipMemsetAsync(t->d_aux, 0, o_off, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(b->foff, t->h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(b->fsamp, file_samples, 4ull * F, hipMemcpyHostToDevice, st));
+    return BV_OK;
+}
+
+int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
+                 uint8_t *row_state, hipStream_t st, const ParseBufs &b);
+
+int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
+               hipStream_t st, uint32_t n_samples) {
+    const uint32_t P = rows->n_positions, F = rows->n_files;
+    const size_t R = (size_t)P * F;
+    ParseBufs pb;
+    int rc = parse_begin(e, t, P, F, rows->file_samples, n_samples, st, &pb);
+    if (rc != BV_OK) return rc;
+    const uint64_t pitch = pb.pitch;
+    uint8_t *bs = pb.bs, *q = pb.q, *mq = pb.mq, *stp = pb.stp, *ref = pb.ref, *rowflag = pb.rowflag;
+    uint16_t *rp = pb.rp;
+    uint32_t *depth = pb.depth, *pstate = pb.pstate, *pmax = pb.pmax, *foff = pb.foff, *fsamp = pb.fsamp;
+    uint64_t *d_off = pb.d_off;
     BV_TXT_HIP(e, hipMemcpyAsync(d_off, rows->row_off, 8 * (R + 1), hipMemcpyHostToDevice, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(foff, h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(fsamp, rows->file_samples, 4ull * F, hipMemcpyHostToDevice, st));
     // the chunks: whole positions, at most kChunkBytes (or one position, if it is longer)
     size_t need = 0;
     for (uint32_t p = 0; p < P; ++p) need = std::max<size_t>(need, rows->row_off[(size_t)(p + 1) * F] - rows->row_off[(size_t)p * F]);
@@ -419,7 +570,7 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
         BV_TXT_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
         BV_TXT_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
         TextParseArgs a;
-        a.text = t->d_text[s]; a.row_off = d_off; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
+        a.text = t->d_text[s]; a.row_beg = d_off; a.row_end = d_off + 1; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
         a.row_first = p0 * F; a.n_rows_chunk = (p1 - p0) * F; a.n_files = F; a.pitch = pitch;
         a.bs = bs; a.q = q; a.mq = mq; a.st = stp; a.ref = ref; a.rowflag = rowflag; a.rp = rp;
         a.depth = depth; a.pstate = pstate; a.pmax = pmax;
@@ -428,14 +579,21 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
         BV_TXT_HIP(e, hipEventRecord(t->ev_parsed[s], st));
         p0 = p1;
     }
-    hipLaunchKernelGGL(bv_text_strand_kernel, dim3(P), dim3(256), 0, st, bs, (const uint8_t *)stp, (const uint32_t *)depth, pstate, pitch,
+    return parse_finish(e, t, P, F, n_samples, group_id, n_groups, row_state, st, pb);
+}
+
+// The strands into the cells, then what the host needs to know of every position.
+int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
+                 uint8_t *row_state, hipStream_t st, const ParseBufs &b) {
+    const size_t R = (size_t)P * F;
+    hipLaunchKernelGGL(bv_text_strand_kernel, dim3(P), dim3(256), 0, st, b.bs, (const uint8_t *)b.stp, (const uint32_t *)b.depth, b.pstate, b.pitch,
                        n_samples);
     BV_TXT_HIP(e, hipGetLastError());
     std::vector<uint32_t> h(3ull * P);
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data(), depth, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + P, pstate, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + 2ull * P, pmax, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(row_state, rowflag, R, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data(), b.depth, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + P, b.pstate, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + 2ull * P, b.pmax, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(row_state, b.rowflag, R, hipMemcpyDeviceToHost, st));
     BV_TXT_HIP(e, hipStreamSynchronize(st));
     // the position's state, in the host reader's order: field count / coordinates / Depth first, then Depth 0, then the tokens
     t->pos_state.assign(P, 0);
@@ -449,7 +607,7 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
             o = s ? s : (uint8_t)(o & BV_TEXT_INDEL);
         }
     }
-    t->n_pos = P; t->n_files = F; t->n_samples = n_samples; t->pitch = pitch; t->n_groups = n_groups;
+    t->n_pos = P; t->n_files = F; t->n_samples = n_samples; t->pitch = b.pitch; t->n_groups = n_groups;
     t->has_gid = group_id != nullptr;
     if (group_id) t->group_id.assign(group_id, group_id + n_samples);
     else t->group_id.clear();
@@ -604,6 +762,189 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     if (G) BV_TXT_HIP(e, hipMemcpyAsync(gout, d_gout, sizeof(bv_group_result) * n_out * G, hipMemcpyDeviceToHost, st));
     if (cell) BV_TXT_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
     if (phred) BV_TXT_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    return BV_OK;
+}
+
+int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
+                              uint8_t *row_state, bv_bgzf_cursor *cursor, void *stream_) {
+    const char *who = "bv_engine_text_parse_bgzf";
+    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!rows || !row_state || !n_positions || !cursor) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
+    if (!rows->member_off || !rows->file_member || !rows->file_samples || !rows->skip_bytes || !rows->skip_lines)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null member_off/file_member/file_samples/skip_bytes/skip_lines");
+    if (rows->reserved_ || rows->at_end > 1u) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": reserved_ must be zero, at_end 0 or 1");
+    if (rows->n_files == 0 || rows->max_positions == 0)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": n_files and max_positions must be > 0");
+    const BvEngineView v = bv_engine_view(e);
+    const uint32_t F = rows->n_files;
+    uint64_t n_samples = 0;
+    if (rows->file_member[0] != 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member[0] must be 0");
+    for (uint32_t f = 0; f < F; ++f) {
+        if (rows->file_samples[f] == 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
+        if (rows->file_member[f + 1] < rows->file_member[f]) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member out of order");
+        n_samples += rows->file_samples[f];
+    }
+    if (!rows->data && rows->file_member[F]) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null data");
+    if (n_samples > v.max_samples)
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the files hold more samples than cfg.max_samples");
+    if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
+        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+    *n_positions = 0;
+    bv_bgzf_members mb{rows->data, rows->member_off, rows->data_bytes, rows->file_member[F], 0};
+    std::vector<BvBgzfMember> hd;
+    std::vector<uint8_t> pre;
+    int rc = bv_bgzf_headers(e, who, &mb, hd, pre);
+    if (rc != BV_OK) return rc;
+    BvTextState *&t = *v.text;
+    if (!t) {
+        t = new BvTextState();
+        t->device = v.device;
+    }
+    t->parsed = false;
+    t->bgzf_rows = false;
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
+    // where every member's text goes: file f's members back to back, one spare byte behind each run (16-byte aligned runs)
+    const uint32_t M = mb.n_members;
+    std::vector<uint64_t> out_pos(M + 1, 0);
+    std::vector<LineFile> fl(F);
+    uint64_t at = 0;
+    uint32_t tiles = 0;
+    for (uint32_t f = 0; f < F; ++f) {
+        LineFile &L = fl[f];
+        L.base = at;
+        for (uint32_t k = rows->file_member[f]; k < rows->file_member[f + 1]; ++k) {
+            out_pos[k] = at;
+            at += hd[k].isize;
+        }
+        L.len = at - L.base;
+        L.skip = rows->skip_bytes[f]; L.skip_lines = rows->skip_lines[f]; L.reserved_ = 0;
+        if (L.skip > L.len)
+            return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": skip_bytes of file " + std::to_string(f) + " is beyond its run");
+        L.tile_first = tiles;
+        L.n_tiles = L.len > L.skip ? (uint32_t)((L.len + rows->at_end - L.skip + kLineTile - 1) / kLineTile) : 0u;
+        tiles += L.n_tiles;
+        at = (at + 1 + 15) & ~(uint64_t)15;
+    }
+    out_pos[M] = at;
+    BV_TXT_HIP(e, hipSetDevice(t->device));
+    rc = grow(e, &t->d_btext, &t->btext_bytes, up256(at + 16));
+    if (rc != BV_OK) return rc;
+    std::vector<uint8_t> status(M ? M : 1);
+    if (M) {
+        rc = bv_bgzf_inflate_placed(e, &mb, hd, pre, out_pos.data(), t->d_btext, status.data(), st);
+        if (rc != BV_OK) return rc;
+    }
+    for (uint32_t f = 0; f < F; ++f)
+        for (uint32_t k = rows->file_member[f]; k < rows->file_member[f + 1]; ++k)
+            if (status[k] != BV_BGZF_OK)
+                return bv_engine_fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(f) + ", member " + std::to_string(k - rows->file_member[f]) +
+                                                          " of its run: BGZF status " + std::to_string(status[k]) +
+                                                          (status[k] == BV_BGZF_BAD_HEADER ? " (bad header)" : status[k] == BV_BGZF_BAD_DEFLATE ? " (invalid DEFLATE stream)"
+                                                           : status[k] == BV_BGZF_BAD_SIZE ? " (inflated size is not ISIZE)" : " (CRC32 mismatch)"));
+    auto start_cursor = [&](uint32_t f, uint64_t x) {  // inflated offset x of file f's run -> (member, offset)
+        uint32_t k = rows->file_member[f];
+        const uint32_t k1 = rows->file_member[f + 1];
+        uint64_t base = 0;
+        while (k < k1 && base + hd[k].isize <= x) base += hd[k++].isize;
+        cursor[f].member = k - rows->file_member[f];
+        cursor[f].offset = k < k1 ? (uint32_t)(x - base) : 0u;
+    };
+    for (uint32_t f = 0; f < F; ++f) start_cursor(f, fl[f].skip);
+    const uint32_t Pmax = std::min(rows->max_positions, v.max_sites);
+    if (tiles == 0) return BV_OK;  // no text behind the skips: no position
+    // the line index
+    const size_t o_cnt = up256(sizeof(LineFile) * F), o_npos = o_cnt + up256(4ull * tiles);
+    rc = grow(e, &t->d_lines, &t->lines_bytes, o_npos + 256);
+    if (rc != BV_OK) return rc;
+    LineFile *d_fl = reinterpret_cast<LineFile *>(t->d_lines);
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(t->d_lines + o_cnt), *d_npos = reinterpret_cast<uint32_t *>(t->d_lines + o_npos);
+    const char *text = reinterpret_cast<const char *>(t->d_btext);
+    BV_TXT_HIP(e, hipMemcpyAsync(d_fl, fl.data(), sizeof(LineFile) * F, hipMemcpyHostToDevice, st));
+    BV_TXT_HIP(e, hipMemcpyAsync(d_npos, &Pmax, 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_line_pad_kernel, dim3((F + 63u) / 64u), dim3(64), 0, st, (char *)t->d_btext, (const LineFile *)d_fl, F);
+    hipLaunchKernelGGL(bv_text_line_count_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, d_cnt);
+    hipLaunchKernelGGL(bv_text_line_scan_kernel, dim3(1), dim3(256), 0, st, (const LineFile *)d_fl, F, d_cnt, d_npos);
+    BV_TXT_HIP(e, hipGetLastError());
+    uint32_t P = 0;
+    BV_TXT_HIP(e, hipMemcpyAsync(&P, d_npos, 4, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    if (P == 0) return BV_OK;
+    ParseBufs pb;
+    rc = parse_begin(e, t, P, F, rows->file_samples, (uint32_t)n_samples, st, &pb);
+    if (rc != BV_OK) return rc;
+    const size_t R = (size_t)P * F;
+    uint64_t *row_beg = pb.d_off, *row_end = pb.d_off + R;
+    hipLaunchKernelGGL(bv_text_line_scatter_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, (const uint32_t *)d_cnt, P,
+                       row_beg, row_end);
+    BV_TXT_HIP(e, hipGetLastError());
+    TextParseArgs a;
+    a.text = text; a.row_beg = row_beg; a.row_end = row_end; a.foff = pb.foff; a.fsamp = pb.fsamp; a.chunk_base = 0;
+    a.row_first = 0; a.n_rows_chunk = (uint32_t)R; a.n_files = F; a.pitch = pb.pitch;
+    a.bs = pb.bs; a.q = pb.q; a.mq = pb.mq; a.st = pb.stp; a.ref = pb.ref; a.rowflag = pb.rowflag; a.rp = pb.rp;
+    a.depth = pb.depth; a.pstate = pb.pstate; a.pmax = pb.pmax;
+    hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
+    BV_TXT_HIP(e, hipGetLastError());
+    std::vector<uint64_t> last(F);
+    BV_TXT_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
+    rc = parse_finish(e, t, P, F, (uint32_t)n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
+    if (rc != BV_OK) {
+        t->parsed = false;
+        return rc;
+    }
+    for (uint32_t f = 0; f < F; ++f) start_cursor(f, std::min(last[f] - fl[f].base, fl[f].len));
+    t->bz_row_beg = row_beg; t->bz_row_end = row_end; t->bz_rowflag = pb.rowflag;
+    t->bgzf_rows = true;
+    *n_positions = P;
+    return BV_OK;
+}
+
+int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream_) {
+    const char *who = "bv_engine_text_rows_fetch";
+    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!bytes_needed) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null bytes_needed");
+    const BvEngineView v = bv_engine_view(e);
+    BvTextState *t = *v.text;
+    if (!t || !t->bgzf_rows) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": no bv_engine_text_parse_bgzf before it");
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
+    BV_TXT_HIP(e, hipSetDevice(t->device));
+    const uint32_t P = t->n_pos, F = t->n_files;
+    const size_t R = (size_t)P * F;
+    const uint64_t *row_beg = t->bz_row_beg, *row_end = t->bz_row_end;
+    const uint8_t *rowflag = t->bz_rowflag;
+    const char *text = reinterpret_cast<const char *>(t->d_btext);
+    const size_t o_len = up256(P), o_roff = o_len + up256(4 * R), o_bytes = o_roff + up256(8 * (R + 1));
+    int rc = grow(e, &t->d_fetch, &t->fetch_bytes, o_bytes);
+    if (rc != BV_OK) return rc;
+    uint32_t *d_len = reinterpret_cast<uint32_t *>(t->d_fetch + o_len);
+    BV_TXT_HIP(e, hipMemcpyAsync(t->d_fetch, t->pos_state.data(), P, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_fetch_len_kernel, dim3((uint32_t)((R + 255) / 256)), dim3(256), 0, st, text, row_beg, row_end, (const uint8_t *)t->d_fetch, rowflag,
+                       (uint32_t)R, F, d_len);
+    BV_TXT_HIP(e, hipGetLastError());
+    std::vector<uint32_t> len(R);
+    BV_TXT_HIP(e, hipMemcpyAsync(len.data(), d_len, 4 * R, hipMemcpyDeviceToHost, st));
+    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    std::vector<uint64_t> off(R + 1, 0);
+    for (size_t r = 0; r < R; ++r) off[r + 1] = off[r] + len[r];
+    *bytes_needed = off[R];
+    if (capacity < off[R]) return BV_OK;
+    if (!row_off || (!buf && off[R])) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null buf/row_off");
+    std::memcpy(row_off, off.data(), 8 * (R + 1));
+    if (off[R] == 0) return BV_OK;
+    // the gathered bytes live behind the offsets; the buffer may move when it grows, so the lengths are copied again after it
+    const size_t need = o_bytes + up256(off[R]);
+    if (need > t->fetch_bytes) {
+        rc = grow(e, &t->d_fetch, &t->fetch_bytes, need);
+        if (rc != BV_OK) return rc;
+        d_len = reinterpret_cast<uint32_t *>(t->d_fetch + o_len);
+        BV_TXT_HIP(e, hipMemcpyAsync(d_len, len.data(), 4 * R, hipMemcpyHostToDevice, st));
+    }
+    uint64_t *d_roff = reinterpret_cast<uint64_t *>(t->d_fetch + o_roff);
+    BV_TXT_HIP(e, hipMemcpyAsync(d_roff, off.data(), 8 * (R + 1), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_fetch_copy_kernel, dim3((uint32_t)((R + 3) / 4)), dim3(256), 0, st, text, row_beg, (const uint32_t *)d_len, (const uint64_t *)d_roff,
+                       (uint32_t)R, t->d_fetch + o_bytes);
+    BV_TXT_HIP(e, hipGetLastError());
+    BV_TXT_HIP(e, hipMemcpyAsync(buf, t->d_fetch + o_bytes, off[R], hipMemcpyDeviceToHost, st));
     BV_TXT_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
 }

@@ -394,11 +394,16 @@ class BaseTypeEngine:
                                             state.ctypes.data, None)
         if rc != 0:
             raise RuntimeError("bv_engine_text_parse failed (%d): %s" % (rc, self._err()))
+        return self._text_submit("lrt_text", state, P, F, N, n_groups, host_reader,
+                                 lambda p: [bytes(text[int(off[p * F + f]):int(off[p * F + f + 1]) - 1]) for f in range(F)])
+
+    def _text_submit(self, what, state, P, F, N, n_groups, host_reader, lines_of):
+        """the host positions of a parsed batch through host_reader, then bv_engine_text_submit: a TextBatch"""
         host = []
         for p in np.nonzero(state[:, 0] & _capi.BV_TEXT_HOST)[0]:
             if host_reader is None:
-                raise RuntimeError("lrt_text: position %d is not in the strict form the device parses and no host_reader was given" % p)
-            lines = [bytes(text[int(off[p * F + f]):int(off[p * F + f + 1]) - 1]) for f in range(F)]
+                raise RuntimeError("%s: position %d is not in the strict form the device parses and no host_reader was given" % (what, p))
+            lines = lines_of(int(p))
             got = host_reader(lines)
             if got is None:
                 state[p, :] = _capi.BV_TEXT_SKIP
@@ -435,6 +440,103 @@ class BaseTypeEngine:
             self.wait()
             n_variant = self.last_variant_count()
         return TextBatch(out, gout, n_variant, positions, state, cell, phred)
+
+    # ---- batchfile rows that are still compressed: inflated, split into lines and parsed on the device
+    def lrt_bgzf(self, runs, file_samples, skip_bytes=None, skip_lines=None, max_positions=None, at_end=True, group_id=None, n_groups=0,
+                 host_reader=None):
+        """lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf + bv_engine_text_rows_fetch +
+        bv_engine_text_submit).  `runs`: per batchfile the list of its consecutive whole members (bytes) from where its next row
+        starts; that row begins skip_bytes[f] inflated bytes into the run and skip_lines[f] lines further.  Takes
+        min(max_positions, max_sites, the files' complete lines) positions; `at_end`: the runs reach the ends of their files.
+        Returns what lrt_text returns plus `cursors` [n_files][2] -- (member of the run, inflated offset inside it) of every
+        file's first line not taken -- and `fetched` = (bytes, row_off): the text the host needs (bv_engine_text_rows_fetch).
+        A damaged member raises RuntimeError with `.args[1] == BV_ERR_DATA`."""
+        fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
+        F, N = int(fs.size), int(fs.sum())
+        if len(runs) != F:
+            raise ValueError("lrt_bgzf: one run per batchfile")
+        members = [bytes(m) for run in runs for m in run]
+        data = np.frombuffer(b"".join(members), dtype=np.uint8)
+        moff = np.zeros(len(members) + 1, dtype=np.uint64)
+        moff[1:] = np.cumsum([len(m) for m in members])
+        fm = np.zeros(F + 1, dtype=np.uint32)
+        fm[1:] = np.cumsum([len(run) for run in runs])
+        sb = np.zeros(F, np.uint64) if skip_bytes is None else np.ascontiguousarray(skip_bytes, dtype=np.uint64)
+        sl = np.zeros(F, np.uint32) if skip_lines is None else np.ascontiguousarray(skip_lines, dtype=np.uint32)
+        cap = self.max_sites if max_positions is None else min(int(max_positions), self.max_sites)
+        br = _capi.BgzfRows(data.ctypes.data if data.size else None, moff.ctypes.data, int(data.size), fm.ctypes.data, fs.ctypes.data, sb.ctypes.data,
+                            sl.ctypes.data, F, self.max_sites if max_positions is None else int(max_positions), 1 if at_end else 0, 0)
+        gid = None if group_id is None else np.ascontiguousarray(group_id, dtype=np.uint8)
+        state = np.zeros((max(cap, 1), F), dtype=np.uint8)
+        n_pos = C.c_uint32(0)
+        cursors = np.zeros((F, 2), dtype=np.uint32)
+        rc = self._lib.bv_engine_text_parse_bgzf(self._h, C.byref(br), None if gid is None else gid.ctypes.data, int(n_groups), C.byref(n_pos),
+                                                 state.ctypes.data, cursors.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_parse_bgzf failed (%d): %s" % (rc, self._err()), rc)
+        P = int(n_pos.value)
+        state = np.ascontiguousarray(state.reshape(-1)[:P * F].reshape(P, F))
+        if P == 0:
+            batch = TextBatch(np.zeros(0, _capi.SITE_DTYPE), np.zeros((0, n_groups), _capi.GROUP_DTYPE) if n_groups else None, 0,
+                              np.zeros(0, np.uint32), state, np.zeros((0, N), np.uint8), np.zeros((0, N), np.uint8))
+            batch.cursors, batch.fetched = cursors, (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+            return batch
+        fetched = self.text_rows_fetch(P * F)
+        buf, roff = fetched
+        batch = self._text_submit("lrt_bgzf", state, P, F, N, n_groups, host_reader,
+                                  lambda p: [bytes(buf[int(roff[p * F + f]):int(roff[p * F + f + 1])]) for f in range(F)])
+        batch.cursors, batch.fetched = cursors, fetched
+        return batch
+
+    def text_rows_fetch(self, n_rows, capacity=None):
+        """(bytes uint8, row_off uint64 [n_rows + 1]) of bv_engine_text_rows_fetch after a parse of n_rows rows; with `capacity`
+        below what is needed: (None, bytes needed)"""
+        need = C.c_uint64(0)
+        roff = np.zeros(int(n_rows) + 1, dtype=np.uint64)
+        if capacity is None:
+            rc = self._lib.bv_engine_text_rows_fetch(self._h, None, 0, roff.ctypes.data, C.byref(need), None)
+            if rc != 0:
+                raise RuntimeError("bv_engine_text_rows_fetch failed (%d): %s" % (rc, self._err()))
+            capacity = int(need.value)
+        buf = np.zeros(max(int(capacity), 1), dtype=np.uint8)
+        rc = self._lib.bv_engine_text_rows_fetch(self._h, buf.ctypes.data, int(capacity), roff.ctypes.data, C.byref(need), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_rows_fetch failed (%d): %s" % (rc, self._err()))
+        if int(need.value) > int(capacity):
+            return None, int(need.value)
+        return buf[:int(need.value)], roff
+
+    # ---- BGZF members, inflated on the device
+    def bgzf_inflate(self, members_bytes, member_off, dst_ptr=0, dst_capacity=0):
+        """Whole BGZF members as they lie in a file in, their inflated bytes out (bv_engine_bgzf_inflate).
+
+        `members_bytes`: bytes / uint8 array; member k is members_bytes[member_off[k]:member_off[k + 1]].  Returns
+        (text, dst_off, status): the inflated bytes as one uint8 array with member k's at text[dst_off[k]:dst_off[k + 1]],
+        dst_off uint64 [n + 1] (the running sum of the ISIZE fields) and one BV_BGZF_* status per member; a member whose status is
+        not BV_BGZF_OK leaves its range unspecified.  With `dst_ptr` (a device pointer of `dst_capacity` bytes) the bytes are
+        written there instead and `text` is None."""
+        data = np.frombuffer(members_bytes, dtype=np.uint8) if isinstance(members_bytes, (bytes, bytearray)) else np.ascontiguousarray(members_bytes, np.uint8)
+        off = np.ascontiguousarray(member_off, dtype=np.uint64)
+        n = int(off.size) - 1
+        if n < 0:
+            raise ValueError("bgzf_inflate: member_off needs n + 1 entries")
+        mb = _capi.BgzfMembers(data.ctypes.data if data.size else None, off.ctypes.data, int(data.size), n, 0)
+        dst_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint8)
+        args = (dst_off.ctypes.data, status.ctypes.data if n else None, None)
+        if dst_ptr:
+            text = None
+            rc = self._lib.bv_engine_bgzf_inflate(self._h, C.byref(mb), int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, *args)
+        else:
+            # a call without room: the engine reads the ISIZE fields, writes dst_off and refuses; then the call with that room
+            text = np.zeros(0, dtype=np.uint8)
+            rc = self._lib.bv_engine_bgzf_inflate(self._h, C.byref(mb), None, 0, _capi.BV_MEM_HOST, *args)
+            if rc == _capi.BV_ERR_INVALID_ARG and int(dst_off[n]) > 0:
+                text = np.zeros(int(dst_off[n]), dtype=np.uint8)
+                rc = self._lib.bv_engine_bgzf_inflate(self._h, C.byref(mb), text.ctypes.data, int(text.size), _capi.BV_MEM_HOST, *args)
+        if rc != 0:
+            raise RuntimeError("bv_engine_bgzf_inflate failed (%d): %s" % (rc, self._err()))
+        return text, dst_off, status
 
 
 class TextBatch(BaseTypeBatch):

@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/basevar_amd.h"
+#include "../../include/basevar_amd_bgzf.h"
 #include "vcf_emit.hpp"  // SiteText
 
 namespace bvamd {
@@ -321,10 +321,61 @@ public:
             const uint64_t a = rows.row_off[p * F + f], b = rows.row_off[p * F + f + 1];
             return std::string(rows.text + a, (size_t)(b - a - 1));
         };
+        finish_text(tb, rows.n_positions, F, N, row_text, [&](size_t p, size_t f) { return rows.text + rows.row_off[p * F + f]; }, read_host, n_groups);
+        return tb;
+    }
+
+    // lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf, include/basevar_amd_bgzf.h), in two steps so
+    // that a reader can hand the cursors to the next batch as soon as the parse has returned: parse_bgzf() inflates, indexes
+    // and parses on the device (throws BgzfDataError for a damaged member); finish_bgzf() fetches the text the host still needs
+    // (bv_engine_text_rows_fetch), runs the host reader on the positions left to it and submits, exactly as lrt_text does.
+    struct BgzfDataError : std::runtime_error {
+        using std::runtime_error::runtime_error;
+    };
+    struct BgzfParse {
+        uint32_t n_positions = 0;
+        std::vector<uint8_t> row_state;
+        std::vector<bv_bgzf_cursor> cursor;
+    };
+    BgzfParse parse_bgzf(const bv_bgzf_rows &rows, uint32_t max_sites, const uint8_t *group_id = nullptr, uint32_t n_groups = 0) {
+        BgzfParse bp;
+        bp.row_state.resize((size_t)std::max<uint32_t>(1, std::min(rows.max_positions, max_sites)) * rows.n_files);
+        bp.cursor.resize(rows.n_files);
+        const int rc = bv_engine_text_parse_bgzf(e_, &rows, group_id, n_groups, &bp.n_positions, bp.row_state.data(), bp.cursor.data(), nullptr);
+        if (rc == BV_ERR_DATA) throw BgzfDataError(bv_last_error(e_));
+        if (rc != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        bp.row_state.resize((size_t)bp.n_positions * rows.n_files);
+        return bp;
+    }
+    template <class HostReader>
+    TextBatch finish_bgzf(BgzfParse &bp, const uint32_t *file_samples, size_t F, HostReader &&read_host, uint32_t n_groups = 0) {
+        TextBatch tb;
+        tb.row_state.swap(bp.row_state);
+        uint32_t N = 0;
+        for (size_t f = 0; f < F; ++f) N += file_samples[f];
+        const size_t R = (size_t)bp.n_positions * F;
+        std::vector<uint64_t> off(R + 1);
+        std::vector<uint8_t> buf;
+        uint64_t need = 0;
+        if (bv_engine_text_rows_fetch(e_, nullptr, 0, off.data(), &need, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        buf.resize((size_t)need + 1);
+        if (bv_engine_text_rows_fetch(e_, buf.data(), need, off.data(), &need, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        const char *text = reinterpret_cast<const char *>(buf.data());
+        finish_text(tb, bp.n_positions, F, N,
+                    [&](size_t p, size_t f) { return std::string(text + off[p * F + f], (size_t)(off[p * F + f + 1] - off[p * F + f])); },
+                    [&](size_t p, size_t f) { return text + off[p * F + f]; }, read_host, n_groups);
+        return tb;
+    }
+
+    // The host's part of a parsed batch and its submit (shared by lrt_text and lrt_bgzf): row_text(p, f) is a row without its
+    // line break (whole for the positions left to the host, through its fourth tab at least for file 0's row of any other),
+    // row_ptr(p, f) the first byte of a whole row flagged BV_TEXT_INDEL.
+    template <class RowText, class RowPtr, class HostReader>
+    void finish_text(TextBatch &tb, uint32_t P, size_t F, uint32_t N, RowText &&row_text, RowPtr &&row_ptr, HostReader &&read_host, uint32_t n_groups) {
         SlabBuilder host(N);
         std::vector<std::string> lines(F);
         uint32_t used = 0;
-        for (; used < rows.n_positions; ++used) {
+        for (; used < P; ++used) {
             uint8_t *rs = &tb.row_state[(size_t)used * F];
             if (rs[0] & BV_TEXT_SKIP) continue;
             SiteText st;
@@ -343,7 +394,7 @@ public:
                 st.ref_base = r0.substr(t2 + 1, t3 - t2 - 1);
                 for (size_t f = 0; f < F; ++f) {
                     if (!(rs[f] & BV_TEXT_INDEL)) continue;
-                    const char *p = rows.text + rows.row_off[used * F + f];
+                    const char *p = row_ptr(used, f);
                     for (int k = 0; k < 5; ++k) { while (*p != '\t') ++p; ++p; }  // to Readbases (a parsed row has its 8 tabs)
                     for (;;) {
                         const char *q = p;
@@ -369,7 +420,6 @@ public:
                                   n_groups ? tb.batch.groups.data() : nullptr, tb.cell.data(), tb.phred.data(), nullptr) != BV_OK)
             throw std::runtime_error(bv_last_error(e_));
         if (R && bv_engine_wait(e_) != BV_OK) throw std::runtime_error(bv_last_error(e_));
-        return tb;
     }
 
 private:

@@ -592,4 +592,104 @@ private:
     std::condition_variable cv_;
 };
 
+// ---- raw mode: BGZF batchfiles handed on as they lie in the files, for a consumer that inflates them itself
+// (bv_engine_text_parse_bgzf: the device inflates, finds the lines and parses).  No inflate, no line split, no packing: the
+// host's part is fread of compressed bytes.  A batch is, for every file, a run of whole members from the member that holds the
+// file's next row onward, worth about `per_file_text` inflated bytes by their ISIZE fields.  Where the next batch starts is
+// known only once the consumer has counted the lines (its cursors), so next() and advance() alternate; the member that holds a
+// partial last row, and the surplus rows of longer runs, are handed out again (members_handed counts every hand-out,
+// members_passed the members the cursors have moved beyond).  Not thread-safe: the callers serialise next() .. advance().
+struct BgzfRawRuns {
+    std::vector<unsigned char> data;       // all runs' members, file 0's first
+    std::vector<uint64_t> member_off;      // [members + 1]
+    std::vector<uint32_t> file_member;     // [files + 1]
+    std::vector<uint64_t> skip_bytes;      // [files] inflated bytes of the run before the file's next row
+    std::vector<uint32_t> skip_lines;      // [files] header lines still in front of it
+    std::vector<std::vector<uint64_t>> member_pos;  // per file: file offset of every member of the run, then of the byte behind it
+    bool at_end = false;                   // every run reaches the end of its file
+};
+class BgzfRawReader {
+public:
+    ~BgzfRawReader() { for (auto &f : files_) if (f.fp) std::fclose(f.fp); }
+    // false (and nothing kept open) unless every file starts with a BGZF member
+    bool open(const std::vector<std::string> &paths, const std::vector<size_t> &header_lines) {
+        for (size_t f = 0; f < paths.size(); ++f) {
+            File x;
+            x.fp = std::fopen(paths[f].c_str(), "rb");
+            unsigned char h[18];
+            const bool ok = x.fp && std::fread(h, 1, 18, x.fp) == 18 && bgzf_member_header(h) && h[10] == 6 && h[11] == 0;
+            x.skip_lines = f < header_lines.size() ? (uint32_t)header_lines[f] : 0u;
+            files_.push_back(x);
+            if (!ok) {
+                for (auto &g : files_) if (g.fp) std::fclose(g.fp);
+                files_.clear();
+                return false;
+            }
+        }
+        return !files_.empty();
+    }
+    size_t n_files() const { return files_.size(); }
+    uint64_t members_handed = 0, members_passed = 0;
+
+    void next(BgzfRawRuns &r, size_t per_file_text) {
+        const size_t F = files_.size();
+        r.data.clear(); r.member_off.assign(1, 0); r.file_member.assign(1, 0);
+        r.skip_bytes.resize(F); r.skip_lines.resize(F); r.member_pos.assign(F, {});
+        r.at_end = true;
+        for (size_t f = 0; f < F; ++f) {
+            File &x = files_[f];
+            if (std::fseek(x.fp, (long)x.pos, SEEK_SET) != 0) throw std::runtime_error("[ERROR] cannot seek in a batchfile");
+            uint64_t at = x.pos, text = 0;
+            bool end = false;
+            while (text < x.skip_bytes + per_file_text || r.member_pos[f].empty()) {
+                unsigned char h[18];
+                const size_t n = std::fread(h, 1, 18, x.fp);
+                if (n == 0) { end = true; break; }
+                if (n != 18 || !bgzf_member_header(h) || h[10] != 6 || h[11] != 0)
+                    throw std::runtime_error("[ERROR] not a BGZF member where one was expected (truncated or damaged batchfile)");
+                const size_t total = (size_t)(h[16] | (h[17] << 8)) + 1;
+                if (total < 26) throw std::runtime_error("[ERROR] damaged BGZF member");
+                const size_t o = r.data.size();
+                r.data.resize(o + total);
+                std::memcpy(&r.data[o], h, 18);
+                if (std::fread(&r.data[o + 18], 1, total - 18, x.fp) != total - 18) throw std::runtime_error("[ERROR] truncated BGZF member");
+                const unsigned char *t = &r.data[o + total - 4];
+                text += (uint64_t)t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24);
+                r.member_pos[f].push_back(at);
+                r.member_off.push_back(r.data.size());
+                at += total;
+            }
+            if (!end) {  // the run may still end exactly where the file does
+                const int c = std::fgetc(x.fp);
+                end = c == EOF;
+            }
+            r.member_pos[f].push_back(at);
+            r.file_member.push_back((uint32_t)(r.member_off.size() - 1));
+            r.skip_bytes[f] = x.skip_bytes;
+            r.skip_lines[f] = x.skip_lines;
+            r.at_end = r.at_end && end;
+            members_handed += r.member_pos[f].size() - 1;
+        }
+    }
+    // the consumer took positions from `r`: file f's next row starts `offset[f]` inflated bytes into member `member[f]` of its run
+    void advance(const BgzfRawRuns &r, const uint32_t *member, const uint32_t *offset) {
+        for (size_t f = 0; f < files_.size(); ++f) {
+            File &x = files_[f];
+            const size_t m = std::min<size_t>(member[f], r.member_pos[f].size() - 1);
+            x.pos = r.member_pos[f][m];
+            x.skip_bytes = offset[f];
+            x.skip_lines = 0;
+            members_passed += m;
+        }
+    }
+
+private:
+    struct File {
+        std::FILE *fp = nullptr;
+        uint64_t pos = 0, skip_bytes = 0;
+        uint32_t skip_lines = 0;
+    };
+    std::vector<File> files_;
+};
+
 }  // namespace bvamd

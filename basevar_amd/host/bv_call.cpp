@@ -13,7 +13,7 @@
 //
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
-//           [--timing FILE.json]
+//           [--timing FILE.json] [--inflate device|host]
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -133,7 +133,7 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 
 int main(int argc, char **argv) {
     std::vector<std::string> batchfiles, bams;
-    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file;
+    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host";
     int mapq_thd = 10, threads = 4, n_gpus = 1;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -149,6 +149,7 @@ int main(int argc, char **argv) {
         else if (a == "--min-af") user_min_af = std::stof(next());
         else if (a == "--batch-sites") batch_sites = (uint32_t)std::stoul(next());
         else if (a == "--timing") timing_file = next();
+        else if (a == "--inflate") inflate_arg = next();
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--gpus") n_gpus = std::stoi(next());
         else if (a == "--devices") devices_arg = next();
@@ -176,6 +177,7 @@ int main(int argc, char **argv) {
     }
     if (!(user_min_af > 0.f)) die("[ERROR] --min-af must be > 0");  // the reference refuses it too (caller.cpp:73)
     if (n_gpus < 1) die("[ERROR] --gpus must be >= 1");
+    if (inflate_arg != "host" && inflate_arg != "device") die("[ERROR] --inflate wants device or host");
     // one engine per entry: --devices a,b,... (an ordinal may repeat: several engines on one GPU), else device, device+1, ...
     std::vector<int> devices;
     if (!devices_arg.empty()) {
@@ -277,6 +279,22 @@ int main(int argc, char **argv) {
 
     // ---- the pipeline: producer (this thread) -> G engine workers -> emitter, results written in batch order
     const size_t G = devices.size();
+    // --inflate device: BGZF batchfiles go to the engine compressed (bv_engine_text_parse_bgzf inflates, finds the lines and
+    // parses).  There is no producer then: the engine workers take turns at the raw reader -- a worker reads the next runs from
+    // the cursors, parses them on its engine, hands the new cursors back and only then lets go of the reader, so its row fetch,
+    // host reader, submit and records overlap the next worker's parse.  Anything else keeps the host path.
+    bvamd::BgzfRawReader raw;
+    bool device_inflate = false;
+    if (inflate_arg == "device") {
+        if (from_bam) std::cerr << "[NOTE] --inflate device applies to BGZF batchfiles, not to BAM input: the host path is taken" << std::endl;
+        else if (G > 1) std::cerr << "[NOTE] --inflate device runs on one engine (--gpus 1): the host path is taken" << std::endl;
+        else if (!raw.open(batchfiles, header_lines)) std::cerr << "[NOTE] --inflate device needs BGZF batchfiles: the host path is taken" << std::endl;
+        else device_inflate = true;
+    }
+    std::mutex raw_mu;
+    bool raw_done = false;
+    uint64_t raw_seq = 0;
+    size_t raw_target = std::max<size_t>(text_block_bytes / std::max<size_t>(1, batchfiles.size()), 1);
     // batchfile input: three engine workers per GPU -- a text batch has host work on its worker (the rows into pinned staging,
     // the host reader for the positions the device leaves to it, the records and planes back), which the other two overlap
     const size_t W = from_bam ? G : 3 * G;
@@ -299,6 +317,73 @@ int main(int argc, char **argv) {
             try {
                 engine.reset(new bvamd::BaseTypeEngine(batch_sites, (uint32_t)n_sample, user_min_af, devices[g]));
             } catch (const std::exception &ex) { fail(ex.what()); }
+            auto host_reader = [](const std::vector<std::string> &r, size_t n, bvamd::SlabBuilder &sb, bvamd::SiteText &st) {
+                return bvamd::parse_site_rows_fast(r, n, sb, st);
+            };
+            while (device_inflate && engine) {
+                BatchPtr b;
+                bvamd::BaseTypeEngine::BgzfParse bp;
+                {
+                    std::lock_guard<std::mutex> lk(raw_mu);
+                    if (raw_done) break;
+                    {
+                        std::lock_guard<std::mutex> g2(err_mu);
+                        if (!first_error.empty()) { raw_done = true; break; }
+                    }
+                    std::string error;
+                    bvamd::BgzfRawRuns runs;
+                    try {
+                        const double t0 = StageClock::now();
+                        raw.next(runs, raw_target);
+                        const double t1 = StageClock::now();
+                        const bv_bgzf_rows rows{runs.data.data(), runs.member_off.data(), runs.data.size(), runs.file_member.data(), file_samples.data(),
+                                                runs.skip_bytes.data(), runs.skip_lines.data(), (uint32_t)file_samples.size(), batch_sites,
+                                                runs.at_end ? 1u : 0u, 0};
+                        bp = engine->parse_bgzf(rows, batch_sites, group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size());
+                        const double t2 = StageClock::now();
+                        std::lock_guard<std::mutex> g2(err_mu);
+                        clk.read += t1 - t0;
+                        clk.engine += t2 - t1;
+                    } catch (const bvamd::BaseTypeEngine::BgzfDataError &ex) {
+                        // the message the host reader has for such a file
+                        error = std::strstr(ex.what(), "bad header") ? "[ERROR] not a BGZF member where one was expected (truncated or damaged batchfile)"
+                                                                    : "[ERROR] a BGZF member does not inflate to its recorded size";
+                    } catch (const std::exception &ex) { error = ex.what(); }
+                    if (error.empty() && bp.n_positions == 0) {
+                        if (runs.at_end) { raw_done = true; break; }
+                        raw_target *= 2;  // not one complete row in every run: longer runs
+                        continue;
+                    }
+                    b.reset(new Batch((uint32_t)n_sample));
+                    b->from_text = true;
+                    b->seq = raw_seq++;
+                    if (!error.empty()) {
+                        b->error = error;
+                        raw_done = true;
+                    } else {
+                        std::vector<uint32_t> cm(bp.cursor.size()), co(bp.cursor.size());
+                        for (size_t f = 0; f < bp.cursor.size(); ++f) { cm[f] = bp.cursor[f].member; co[f] = bp.cursor[f].offset; }
+                        raw.advance(runs, cm.data(), co.data());
+                    }
+                }
+                if (b->error.empty()) {
+                    const double t0 = StageClock::now();
+                    try {
+                        auto tb = engine->finish_bgzf(bp, file_samples.data(), file_samples.size(), host_reader, (uint32_t)group_names.size());
+                        b->result = std::move(tb.batch);
+                        b->text = std::move(tb.text);
+                        b->cell = std::move(tb.cell);
+                        b->phred = std::move(tb.phred);
+                        if (tb.error) {
+                            try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b->error = ex.what(); }
+                        }
+                    } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); }
+                    const double dt = StageClock::now() - t0;
+                    std::lock_guard<std::mutex> lk(err_mu);
+                    clk.engine += dt;
+                }
+                to_emit.push(std::move(b));
+            }
             for (BatchPtr b; (b = to_gpu.pop());) {
                 if (engine) {
                     const double t0 = StageClock::now();
@@ -307,9 +392,7 @@ int main(int argc, char **argv) {
                         try {
                             const bv_text_rows rows{b->rows.data(), b->row_off.data(), file_samples.data(), b->rows.size(), b->n_positions,
                                                     (uint32_t)file_samples.size(), 0};
-                            auto tb = engine->lrt_text(rows, [](const std::vector<std::string> &r, size_t n, bvamd::SlabBuilder &sb,
-                                                                bvamd::SiteText &st) { return bvamd::parse_site_rows_fast(r, n, sb, st); },
-                                                       group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size());
+                            auto tb = engine->lrt_text(rows, host_reader, group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size());
                             b->result = std::move(tb.batch);
                             b->text = std::move(tb.text);
                             b->cell = std::move(tb.cell);
@@ -431,6 +514,8 @@ int main(int argc, char **argv) {
                 });
                 clk.parse += StageClock::now() - tp0;
             }
+        } else if (device_inflate) {
+            // (the engine workers read the files themselves: see `raw` above)
         } else {
             // ---- one row from every batchfile per position (caller.cpp:586-611), on `--thread` host threads: files read and
             // positions parsed in blocks by a pipeline of tasks (batch_producer.hpp), joined here in position order
@@ -480,7 +565,12 @@ int main(int argc, char **argv) {
            << ", \"batch_sites\": " << batch_sites << ", \"input\": \"" << (from_bam ? "bam" : "batchfile") << "\", \"parser\": \""
            << (from_bam ? "pileup" : "batchfile") << "\", \"total_s\": " << total << ", \"sites_per_s\": " << (total > 0 ? n_sites / total : 0.0)
            << ", \"read_s\": " << clk.read << ", \"parse_pack_s\": " << clk.parse << ", \"engine_s\": " << clk.engine
-           << ", \"emit_s\": " << clk.emit << "}\n";
+           << ", \"emit_s\": " << clk.emit;
+        // --inflate device: members handed to the device (those that hold a partial last row, and the surplus rows of longer
+        // runs, are inflated again with the next batch) against the members the files hold
+        if (device_inflate)
+            tf << ", \"inflate\": \"device\", \"members_inflated\": " << raw.members_handed << ", \"members_in_files\": " << raw.members_passed;
+        tf << "}\n";
     }
     return 0;
 }

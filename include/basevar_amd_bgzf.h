@@ -1,0 +1,108 @@
+/*
+ * basevar_amd_bgzf.h -- BGZF members inflated on the device.
+ *
+ * The reference reads its batchfiles through htslib's BGZF reader (src/basetype_caller.cpp:428 requires that format): a
+ * chain of independent gzip members of at most 64 KiB of text each, inflated one after the other by zlib on the host.  Here
+ * the members go to the device as they lie in the file and one wave inflates each of them (basevar_amd/csrc/bv_inflate.hip).
+ *
+ * Same conventions as basevar_amd.h: plain C, BV_OK or a negative status, bv_last_error() has the message.
+ */
+#ifndef BASEVAR_AMD_BGZF_H
+#define BASEVAR_AMD_BGZF_H
+
+#include "basevar_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* one more bv_status value: the input data, not the call, is wrong (a BGZF member that does not inflate to what it states) */
+#define BV_ERR_DATA (-6)
+
+/* what became of one member */
+typedef enum bv_bgzf_status {
+    BV_BGZF_OK = 0,
+    BV_BGZF_BAD_HEADER = 1,  /* not a gzip member with the 'BC' extra field, or its length there is not the packing's */
+    BV_BGZF_BAD_DEFLATE = 2, /* the DEFLATE stream is invalid (what zlib calls a data error)                          */
+    BV_BGZF_BAD_SIZE = 3,    /* the stream ends before ISIZE bytes, or holds more; ISIZE above 65,536                 */
+    BV_BGZF_BAD_CRC = 4      /* ISIZE bytes came out and their CRC32 is not the member's                              */
+} bv_bgzf_status;
+
+/* n_members whole BGZF members in host memory, as they lie in a file: member k is data[member_off[k] .. member_off[k + 1])
+ * (18-byte header with the 'BC' extra field, DEFLATE payload, CRC32, ISIZE).  They need not be neighbours in `data`. */
+typedef struct bv_bgzf_members {
+    const uint8_t *data;
+    const uint64_t *member_off; /* [n_members + 1], ascending */
+    uint64_t data_bytes;        /* size of `data`: every offset is <= it */
+    uint32_t n_members;
+    uint32_t reserved_;         /* must be 0 */
+} bv_bgzf_members;
+
+/* Inflate the members.  Member k's bytes land at dst + dst_off[k], where dst_off[0] = 0 and dst_off[k + 1] - dst_off[k] is
+ * member k's ISIZE field (0 for a member with a bad header or an ISIZE above 65,536, which no BGZF member has): dst_off
+ * [n_members + 1] is written for the caller.  dst is a host or a device buffer (mem_kind) of dst_capacity bytes;
+ * status[n_members] (host) receives a bv_bgzf_status per member.  A member whose status is not BV_BGZF_OK leaves its range of
+ * dst unspecified and touches nothing outside it.  Per member the device checks every read against the payload's length,
+ * every write against ISIZE, the inflated size against ISIZE and the CRC32 of the inflated bytes against the member's.
+ * Payload bytes behind the final DEFLATE block are ignored, as zlib's inflate() ignores them.
+ * Returns BV_OK when the call ran, whatever the statuses; BV_ERR_INVALID_ARG for NULL arguments, offsets out of order or
+ * beyond data_bytes, a member shorter than 26 bytes or longer than 65,536, mem_kind neither BV_MEM_HOST nor BV_MEM_DEVICE, or
+ * dst_capacity < dst_off[n_members] (dst_off is written even then, so the caller learns the size).  Any number of members:
+ * the engine stages the compressed bytes in chunks through pinned memory.  Blocks until dst and status are written.
+ * `stream`: a hipStream_t, or NULL for the engine's own. */
+int bv_engine_bgzf_inflate(bv_engine *e, const bv_bgzf_members *members, void *dst, uint64_t dst_capacity, int mem_kind,
+                           uint64_t *dst_off, uint8_t *status, void *stream);
+
+/* ---- batchfile rows that are still compressed: bv_engine_text_parse (basevar_amd.h) without the host's inflate, line split
+ * and row packing.  For each of n_files batchfiles a RUN of consecutive whole members: file f's run is members
+ * file_member[f] .. file_member[f + 1] - 1 of (data, member_off), packed as in bv_bgzf_members.  File f's first row starts
+ * skip_bytes[f] inflated bytes into its run and then skip_lines[f] further lines (the header lines of a file's first run: a
+ * reader knows their number, not their bytes). */
+typedef struct bv_bgzf_rows {
+    const uint8_t *data;
+    const uint64_t *member_off;   /* [file_member[n_files] + 1], ascending */
+    uint64_t data_bytes;
+    const uint32_t *file_member;  /* [n_files + 1], ascending, file_member[0] = 0 */
+    const uint32_t *file_samples; /* [n_files] samples per batchfile, each > 0 */
+    const uint64_t *skip_bytes;   /* [n_files], each <= the bytes the file's run inflates to */
+    const uint32_t *skip_lines;   /* [n_files] */
+    uint32_t n_files;
+    uint32_t max_positions;       /* > 0: take at most this many positions */
+    uint32_t at_end;              /* 1: every run reaches the end of its file, so a last line without '\n' is a line */
+    uint32_t reserved_;           /* must be 0 */
+} bv_bgzf_rows;
+
+/* where file f's next run starts: the first line not taken begins `offset` inflated bytes into member `member` of the run
+ * this call was given (member = the run's member count, offset = 0: everything was taken) */
+typedef struct bv_bgzf_cursor {
+    uint32_t member;
+    uint32_t offset;
+} bv_bgzf_cursor;
+
+/* Stateless.  The device inflates every run (file f's members back to back, so a row may span members), finds the line ends
+ * and takes *n_positions = min(max_positions, cfg.max_sites, min over f of file f's complete lines behind the skip).  Row
+ * (p, f) is file f's p-th line behind the skip.  The rows are then parsed exactly as bv_engine_text_parse parses them: the
+ * same strict form, the same row_state values (written for the first *n_positions * n_files rows; give room for
+ * min(max_positions, cfg.max_sites) * n_files), the same planes, and bv_engine_text_submit runs unchanged behind it (one
+ * submit per parse; this call counts as the parse).  cursor[n_files] is written for the caller.  *n_positions = 0 (some file
+ * has no complete line behind its skip): nothing is parsed and nothing is consumed -- cursor[f] is the place of skip_bytes[f]
+ * itself, and the skip_lines[f] lines behind it are still to be skipped: the caller comes back with longer runs and the same
+ * skip_lines (or, with at_end = 1, has reached the end of the files).
+ * Any member whose status is not BV_BGZF_OK: nothing is parsed, the call returns BV_ERR_DATA and bv_last_error() names the
+ * file index, the member's index inside its run and the status; the caller re-reads with its host reader.
+ * BV_ERR_INVALID_ARG as for bv_engine_text_parse and bv_engine_bgzf_inflate, and for a skip_bytes beyond its run. */
+int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
+                              uint8_t *row_state, bv_bgzf_cursor *cursor, void *stream);
+
+/* The text the host still needs after bv_engine_text_parse_bgzf (valid until the engine's next parse): one call gathers into
+ * buf, without line breaks, row (p, 0) through its fourth tab (CHROM, POS, REF, Depth) for every position not skipped, every
+ * row of a BV_TEXT_HOST position and every BV_TEXT_INDEL row whole, and nothing of any other row.  Row r = p * n_files + f is
+ * buf[row_off[r] .. row_off[r + 1]); row_off has n_positions * n_files + 1 entries.  *bytes_needed is always written; if
+ * capacity is smaller, nothing else is written, the call returns BV_OK and may be repeated with more room. */
+int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* BASEVAR_AMD_BGZF_H */
