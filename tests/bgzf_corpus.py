@@ -1,10 +1,13 @@
 """The corpus of BGZF members that the device DEFLATE decoder is held to (tests/test_bgzf_cpu.py through the CPU build of
 basevar_amd/csrc/bv_inflate_core.h, tests/test_gpu_bgzf.py on the GPU): valid members made at run time with zlib over every
-block type, level and strategy, and damaged variants, each made from a valid member or bit by bit.  zlib is the oracle."""
+block type, level and strategy, and damaged variants, each made from a valid member or bit by bit; and a foreign corpus
+(foreign_corpus(), foreign_damaged()) of members that zlib inflates and its compressor never writes, encoded by
+tests/deflate_writer.py.  zlib is the oracle."""
 import os
 import struct
 import subprocess
 import zlib
+from collections import Counter
 
 import numpy as np
 
@@ -263,3 +266,387 @@ def assert_block_coverage(names, members, verdicts):
     mixed = [n for n, v in zip(names, verdicts) if bin(v[2]).count("1") > 1]
     assert mixed, "no member with more than one block type"
     return mixed
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The foreign corpus: members that zlib's inflate accepts and zlib's deflate never writes, encoded by tests/deflate_writer.py.
+# zlib judges every one (zlib.decompress(payload, -15) gives the bytes); deflate_writer.trace says which features each holds.
+
+FOREIGN_SIZES = list(range(0, 50)) + [k * 1024 + d for k in (1, 2, 63) for d in (-1, 0, 1)] + [65535, 65536]
+
+
+def wrap_gzip(payload, data, subfields=(("BC", None),), flg=4, mtime=0, xfl=0, os_=255, fname=None, hcrc=False, crc=None, isize=None):
+    """a gzip member (RFC 1952) around the payload: subfields [(two-letter id, bytes)]; the bytes None stand for the BGZF length"""
+    extra_len = sum(4 + (2 if b is None else len(b)) for _, b in subfields)
+    tail = (fname + b"\0" if fname is not None else b"") + (b"\0\0" if hcrc else b"")
+    total = 12 + extra_len + len(tail) + len(payload) + 8
+    extra = b"".join(i.encode() + struct.pack("<H", 2 if b is None else len(b)) + (struct.pack("<H", (total - 1) & 0xFFFF) if b is None else b)
+                     for i, b in subfields)
+    head = b"\x1f\x8b\x08" + bytes([flg]) + struct.pack("<IBBH", mtime, xfl, os_, extra_len) + extra
+    if fname is not None:
+        head += fname + b"\0"
+    if hcrc:
+        head += struct.pack("<H", zlib.crc32(head) & 0xFFFF)
+    crc = (zlib.crc32(data) & 0xFFFFFFFF) if crc is None else crc
+    return head + bytes(payload) + struct.pack("<II", crc, len(data) if isize is None else isize)
+
+
+class _Tok:
+    """a token list under construction and the text it stands for"""
+
+    def __init__(self):
+        self.t, self.out, self.taken = [], bytearray(), 0
+
+    def lit(self, *bs):
+        for b in bs:
+            self.t.append(int(b))
+            self.out.append(int(b))
+        return self
+
+    def match(self, length, dist, alt=False):
+        assert 1 <= dist <= len(self.out) and 3 <= length <= 258
+        self.t.append((length, dist, True) if alt else (length, dist))
+        for _ in range(length):
+            self.out.append(self.out[-dist])
+        return self
+
+    def fill_to(self, n, dists):
+        """matches of 258 bytes at the distances in turn (where they reach), and a shorter one or two, up to byte n exactly"""
+        k = 0
+        while n - len(self.out) >= 3:
+            r = n - len(self.out)
+            length = 258 if r >= 261 else r if r <= 258 else r - 3
+            d = dists[k % len(dists)]
+            k += 1
+            self.match(length, d if d <= len(self.out) else 1)
+        while len(self.out) < n:
+            self.lit(0x21 + len(self.out) % 90)
+        assert len(self.out) == n
+        return self
+
+    def take(self):
+        """the tokens added since the last take()"""
+        part, self.taken = self.t[self.taken:], len(self.t)
+        return part
+
+
+def _random_tokens(rng, tok, size):
+    while len(tok.out) < size:
+        r = size - len(tok.out)
+        if r >= 3 and tok.out and rng.random() < 0.5:
+            far = min(len(tok.out), 32768)
+            dist = int(rng.integers(1, far + 1)) if rng.random() < 0.5 else int(rng.integers(1, min(far, 40) + 1))
+            tok.match(int(min(r, rng.integers(3, 259))), dist)
+        else:
+            tok.lit(int(rng.integers(0, 256)) if rng.random() < 0.3 else int(rng.integers(97, 105)))
+    return tok
+
+
+_FOREIGN = {}
+
+
+def _foreign():
+    """[(name, member, data, blocks)]; data is zlib's inflation of the payload"""
+    if "valid" in _FOREIGN:
+        return _FOREIGN["valid"]
+    import deflate_writer as dw
+    out = []
+
+    def add(name, blocks, gzip=None, **kw):
+        payload = dw.write_stream(blocks, **kw)
+        data = zlib.decompress(payload, -15)  # the judge
+        m = wrap(payload, data) if gzip is None else wrap_gzip(payload, data, **gzip)
+        assert len(m) <= 65536, (name, len(m))
+        out.append((name, m, data, blocks))
+
+    def dyn(tokens, **kw):
+        return dict({"type": "dynamic", "tokens": tokens}, **kw)
+
+    def fixed(tokens, **kw):
+        return dict({"type": "fixed", "tokens": tokens}, **kw)
+
+    def stored(data, **kw):
+        return dict({"type": "stored", "data": bytes(data)}, **kw)
+
+    rng = np.random.default_rng(101)
+    az = list(range(97, 111))  # 14 literals
+    lit16 = dw.assign(az + [257, 256], dw.skewed_lengths(16, 15), 286)
+    dist16 = dw.assign(list(range(16)), dw.skewed_lengths(16, 15), 30)
+
+    # every code length 1 .. 15 of both alphabets decoded: 16 symbols each, lengths 1, 2, ..., 15, 15, every symbol used
+    t = _Tok().lit(*[az[k % 14] for k in range(200)])
+    for s in range(16):
+        t.match(3, dw.DIST_BASE[s])
+    add("lengths_1_to_15", [dyn(t.take(), lit_lens=lit16, dist_lens=dist16)])
+    # ... and with the long codes on the other end of each alphabet
+    t = _Tok().lit(*[az[k % 14] for k in range(200)])
+    for s in range(16):
+        t.match(3, dw.DIST_BASE[s])
+    add("lengths_15_to_1", [dyn(t.take(), lit_lens=dw.assign([256, 257] + az[::-1], dw.skewed_lengths(16, 15), 286),
+                                dist_lens=dw.assign(list(range(15, -1, -1)), dw.skewed_lengths(16, 15), 30), spell="plain")])
+
+    # everything at once: 65 536 bytes, all 286 + 30 symbols coded, 15-bit codes in both alphabets, every length and distance
+    # symbol with its smallest and largest extra bits, distance 32 768 from the first byte it is legal at
+    lengths = [(dw.LEN_BASE[s] + e, s == 27 and e > 0) for s in range(28) for e in sorted({0, (1 << dw.LEN_EXTRA[s]) - 1})] + [(258, False)]
+    dists = [dw.DIST_BASE[s] + e for s in range(30) for e in sorted({0, (1 << dw.DIST_EXTRA[s]) - 1})]
+    near = [1, 2, 3, 7, 63, 64, 65, 257, 5, 1000, 31, 258]
+    t = _Tok().lit(*rng.permutation(256)).lit(*rng.integers(0, 256, 6000))
+    k = 0
+    for length, alt in lengths:
+        for _ in range(2):
+            d = [x for x in dists if x <= len(t.out)]
+            t.lit(int(rng.integers(0, 256))).match(length, d[k % len(d)], alt)
+            k += 1
+    for d in (3, 4, 16, 64, 100, 258):  # the source ends on the literal just written
+        t.lit(0x41 + d % 26).match(d, d)
+    t.fill_to(32768, near)
+    t.match(258, 32768)
+    for k, d in enumerate(dists + [32507, 32600, 32767, 32768]):
+        t.lit(int(rng.integers(0, 256))).match(*((lengths[k % len(lengths)][0], d) + ((True,) if lengths[k % len(lengths)][1] else ())))
+    t.fill_to(65536 - 258, near + [32768, 32767, 32507, 20000])
+    t.match(258, 32768, True)
+    assert len(t.out) == 65536
+    tokens = t.take()
+    lit_used, dist_used = dw._used(tokens)
+    lit_syms = [s for s, _ in sorted(lit_used.items(), key=lambda kv: (-kv[1], kv[0]))]
+    dist_syms = [s for s, _ in sorted(dist_used.items(), key=lambda kv: (-kv[1], kv[0]))]
+    assert len(lit_syms) == 286 and len(dist_syms) == 30
+    every = dict(lit_lens=dw.assign(lit_syms, dw.skewed_lengths(286, 15), 286), dist_lens=dw.assign(dist_syms, dw.skewed_lengths(30, 15), 30))
+    seq = every["lit_lens"] + every["dist_lens"]
+    cl_syms = [s for s, _ in Counter(o if isinstance(o, int) else int(o[0][1:]) for o in dw.spell_lengths(seq, "rle")).most_common()]
+    cl7 = dict(zip(cl_syms, dw.skewed_lengths(len(cl_syms), 7)))
+    add("everything_at_once", [dyn(tokens, cl_lens=cl7, hclen=19, **every)])
+    add("everything_in_blocks", [dyn(tokens[lo:lo + 500], spell="plain", **every) for lo in range(0, len(tokens), 500)])
+
+    # overlapping matches, the earliest legal source at distance 1, sources that end on the literal before the match
+    t = _Tok().lit(0x78).match(258, 1).lit(*rng.integers(0, 256, 300))
+    for d in (1, 2, 3, 7, 63, 64, 65):
+        t.match(258, d).lit(int(rng.integers(0, 256))).match(d + 1 if d >= 2 else 3, d).lit(int(rng.integers(0, 256)))
+    t.match(258, 257)
+    for d in (3, 4, 16, 64, 100, 258):
+        t.lit(0x41 + d % 26).match(d, d)
+    tokens = t.take()
+    add("overlaps/fixed", [fixed(tokens)])
+    add("overlaps/dynamic", [dyn(tokens)])
+    lit_used, dist_used = dw._used(tokens)
+    add("overlaps/skewed", [dyn(tokens, lit_lens=dw.assign(*dw.by_frequency(lit_used, lambda n: dw.skewed_lengths(n, 15)), 286),
+                                dist_lens=dw.assign(*dw.by_frequency(dist_used, lambda n: dw.skewed_lengths(n, min(15, n - 1))), 30))])
+
+    # headers.  HCLEN 4 gives lengths to the symbols 16, 17, 18 and 0 only: every code length is then 0 and no block is valid,
+    # so the smallest HCLEN of a valid block is 5 (symbol 8); HCLEN 4 is in foreign_damaged().
+    add("header/hlit257_hdist1_hclen5", [dyn([0, 7, 254, 256 - 2], lit_lens=[8] * 255 + [0, 8], dist_lens=[0], spell="plain")])
+    lens = [4] * 11 + [0] * 3 + [4] + [0] * 10 + [4] + [0] * 11 + [4] + [0] * 138 + [4] + [0] * 79 + [4]
+    add("header/repeat_counts", [dyn([0, 5, 14, 25, 37, 176], lit_lens=lens, dist_lens=[0],
+                                     spell=[4, ("r16", 3), 4, ("r16", 6), ("r17", 3), 4, ("r17", 10), 4, ("r18", 11), 4, ("r18", 138), 4, ("r18", 79), 4, 0])])
+    add("header/repeat_16_crosses", [dyn([254, 255, (3, 1), (3, 2), (3, 3), (3, 4)], lit_lens=[0] * 254 + [2] * 4, dist_lens=[2] * 4,
+                                         spell=[("r18", 138), ("r18", 116), 2, ("r16", 6), 2])])
+    two = [0] * 97 + [2, 2] + [0] * 157 + [2, 2]
+    add("header/repeat_17_crosses", [dyn([97, 98, 97, 98, (3, 4)], lit_lens=two, dist_lens=[0, 0, 0, 1], hlit=260,
+                                         spell=[("r18", 97), 2, 2, ("r18", 138), ("r18", 19), 2, 2, ("r17", 5), 1])])
+    add("header/repeat_18_crosses", [dyn([97, 98] * 30 + [(3, 33), (3, 48)], lit_lens=two, dist_lens=[0] * 10 + [1], hlit=270,
+                                         spell=[("r18", 97), 2, 2, ("r18", 138), ("r18", 19), 2, 2, ("r18", 22), 1])])
+    add("header/one_distance_code_used", [dyn([97, (3, 1), (3, 1)], lit_lens=dw.assign([257, 97, 256], [1, 2, 2], 286), dist_lens=[1])])
+    only_end = dyn([], lit_lens=[0] * 256 + [1], dist_lens=[0])
+    add("header/only_end_code_then_fixed", [only_end, fixed([104, 105])])
+    add("header/only_end_code_alone", [only_end])
+
+    # stored blocks
+    add("stored/len0_first_middle_final", [stored(b""), fixed([97, 98, (3, 2)]), stored(b"", pad=1), fixed([99]), stored(b"", pad=1)])
+    add("stored/len0_alone", [stored(b"")])
+    add("stored/65505", [stored(rng.integers(0, 256, 65505, dtype=np.uint8).tobytes())])
+    blocks = []
+    for k in range(16):  # k literals of 9 bits move the end of the block through every bit of a byte
+        blocks += [fixed([200] * k + [97, 98]), stored(rng.integers(0, 256, 2 * k + 1, dtype=np.uint8).tobytes(), pad=1)]
+    add("stored/after_huffman_every_padding", blocks + [fixed([122])])
+    add("stored/after_dynamic_every_padding", [b for k in range(8) for b in (dyn([200] * k + [97, 98, (4, 1)]), stored(bytes([65 + k]) * (k + 2), pad=1))]
+        + [dyn([122])])
+
+    # many blocks; code tables of very different depth one behind the other
+    dyn15 = dict(lit_lens=lit16, dist_lens=[1, 1])
+    dyn2 = dict(lit_lens=dw.assign([97, 98, 256, 257], [2] * 4, 286), dist_lens=[1, 1])
+    blocks = []
+    for k in range(334):
+        blocks += [stored(bytes([48 + k % 10] * (1 + k % 5)), pad=k & 1), fixed([97 + k % 14, 98, (3 + k % 20, 1 + k % 2)]),
+                   dyn([az[(k + j) % 14] for j in range(6)] + [(3, 2)], **dyn15) if k % 2 else dyn([97, 98, 98, (3, 1)], **dyn2)]
+    add("thousand_blocks", blocks)
+    add("deep_then_shallow_tables", [dyn(az + [(3, 1)], **dyn15), dyn([97, 98, (3, 2)], **dyn2), dyn(az[::-1] + [(3, 2)], **dyn15), fixed([97, (3, 1)]),
+                                     dyn([98, 97], **dyn2)])
+
+    # the end of the stream
+    add("trailing_bytes_behind_the_final_block", [fixed([97, 98, 99])], trailing=b"\xff\xff\x00\x01 not deflate")
+    add("final_block_ends_inside_a_byte/zeros", [fixed([97, 98, 99])], end_fill=0)
+
+    # text sizes: the write-out's head / lines / tail split and the edges of the CRC slices
+    for n in FOREIGN_SIZES:
+        r = np.random.default_rng(1000 + n)
+        t = _Tok()
+        if n % 3 == 2:
+            _random_tokens(r, t, n // 2)
+            first = [stored(bytes(t.out), pad=1)]
+            t.take()
+        else:
+            first = []
+        _random_tokens(r, t, n)
+        add("size/%d" % n, first + [fixed(t.take()) if n % 3 == 0 else dyn(t.take())])
+    add("size/0/dynamic", [dyn([])])
+
+    # the wrapper: what gzip allows around the BC subfield (judged by zlib.decompress(member, 31))
+    t = _random_tokens(np.random.default_rng(77), _Tok(), 1500)
+    blocks = [dyn(t.take())]
+    for name, gz in (("extra_before_bc", dict(subfields=(("XY", b"abc"), ("BC", None)))), ("extra_behind_bc", dict(subfields=(("BC", None), ("ZZ", b"")))),
+                     ("extra_on_both_sides", dict(subfields=(("AB", b"\0" * 9), ("BC", None), ("CB", b"BC\x02\x00")))),
+                     ("mtime_xfl_os", dict(mtime=0x5F3759DF, xfl=2, os_=3)), ("xlen_300", dict(subfields=(("BC", None), ("PD", b"\x07" * 290))))):
+        add("wrapper/" + name, blocks, gzip=gz)
+        assert zlib.decompress(out[-1][1], 31) == out[-1][2]
+    _FOREIGN["valid"] = out
+    return out
+
+
+def foreign_corpus():
+    """[(name, member bytes, inflated bytes)]: valid members that zlib's own compressor does not write"""
+    return [(n, m, d) for n, m, d, _ in _foreign()]
+
+
+def foreign_blocks():
+    """{name: the blocks the writer was given}"""
+    return {n: b for n, _, _, b in _foreign()}
+
+
+# gzip members that zlib reads and that are no BGZF members (SAM specification 4.1: FLG is FEXTRA alone, one BC subfield of 2 bytes)
+GZIP_NOT_BGZF = {"wrapper/fname": "FLG has FNAME", "wrapper/fhcrc": "FLG has FHCRC", "wrapper/no_bc": "no BC subfield",
+                 "wrapper/two_bc": "two BC subfields", "wrapper/bc_of_4_bytes": "a BC subfield of 4 bytes"}
+# what zlib, asked for exactly ISIZE bytes, makes of the damaged members whose fault is known by construction
+FOREIGN_DAMAGED_EXPECT = {}
+
+
+def foreign_damaged():
+    """[(name, member)]: damaged members made with the writer; zlib judges each (FOREIGN_DAMAGED_EXPECT: what it must find)"""
+    if "damaged" in _FOREIGN:
+        return _FOREIGN["damaged"]
+    import deflate_writer as dw
+    out = []
+    rng = np.random.default_rng(202)
+
+    def add(name, blocks, want, data=b"", isize=None, crc=None, cut=0, **kw):
+        payload = blocks if isinstance(blocks, bytes) else dw.write_stream(blocks, **kw)
+        out.append((name, wrap(payload[:len(payload) - cut], data, isize=isize, crc=crc)))
+        FOREIGN_DAMAGED_EXPECT[name] = want
+
+    def dyn(tokens, **kw):
+        return dict({"type": "dynamic", "tokens": tokens, "check": False}, **kw)
+
+    base = [int(x) for x in rng.integers(97, 123, 40)]
+    for form, tail in (("distance_ge_length", (30, 35)), ("distance_1", (30, 1)), ("overlapping", (30, 7))):
+        text = dw.expand(base + [tail])
+        add("match_past_isize/" + form, [{"type": "fixed", "tokens": base + [tail]}], BAD_SIZE, text[:-9])
+        add("match_past_isize/dynamic/" + form, [dyn(base + [tail], check=True)], BAD_SIZE, text[:-1])
+    add("control/match_ends_on_isize", [{"type": "fixed", "tokens": base + [(30, 7)]}], OK, dw.expand(base + [(30, 7)]))
+    add("distance_one_more_than_written", [{"type": "fixed", "tokens": base + [(5, 41), 97]}], BAD_DEFLATE, bytes(base) + b"aaaaaa")
+    one = dict(lit_lens=dw.assign([257, 97, 256], [1, 2, 2], 286), dist_lens=[1])
+    add("unassigned_code_of_a_one_code_distance_set", [dyn([97, ("sym", 257), ("bits", 1, 1), 97], **one)], BAD_DEFLATE, b"aaaaa")
+    add("length_symbol_without_any_distance_code", [dyn([97, ("sym", 257), ("bits", 0, 8), 97], lit_lens=one["lit_lens"], dist_lens=[0])], BAD_DEFLATE, b"aaaaa")
+    lens = [0] * 97 + [2, 2] + [0] * 157 + [2, 2]
+    add("symbol_16_first", [dyn([97], lit_lens=lens, dist_lens=[0], spell=[("r16", 3)] + lens[3:] + [0])], BAD_DEFLATE, b"a")
+    add("repeat_past_hlit_and_hdist_from_the_literal_part", [dyn([97], lit_lens=lens, dist_lens=[0], spell=[("r18", 97), 2, 2, ("r18", 138), ("r18", 138)])],
+        BAD_DEFLATE, b"a")
+    add("no_code_for_256_otherwise_complete", [dyn([97, 98, ("bits", 0, 16)], lit_lens=[0] * 97 + [1, 1], dist_lens=[0], hlit=257)], BAD_DEFLATE, b"ab")
+    lit16 = dw.assign(list(range(97, 111)) + [257, 256], dw.skewed_lengths(16, 15), 286)
+    dist16 = dw.assign(list(range(16)), dw.skewed_lengths(16, 15), 30)
+    less = lambda lens: [0 if (l == 15 and k == max(i for i, x in enumerate(lens) if x == 15)) else l for k, l in enumerate(lens)]  # noqa: E731
+    more = lambda lens, at: lens[:at] + [15] + lens[at + 1:]  # noqa: E731
+    toks = [97, 98, 99, (3, 1)]
+    add("incomplete_at_15_bits/literals", [dyn(toks[:3], lit_lens=less(lit16), dist_lens=dist16)], BAD_DEFLATE, b"abc")
+    add("incomplete_at_15_bits/distances", [dyn(toks, lit_lens=lit16, dist_lens=less(dist16))], BAD_DEFLATE, b"abccc")
+    add("oversubscribed_at_15_bits/literals", [dyn(toks, lit_lens=more(lit16, 5), dist_lens=dist16)], BAD_DEFLATE, b"abccc")
+    add("oversubscribed_at_15_bits/distances", [dyn(toks, lit_lens=lit16, dist_lens=more(dist16, 20))], BAD_DEFLATE, b"abccc")
+    add("hclen_4", [dyn([], lit_lens=[0] * 257, dist_lens=[0], cl_lens={0: 1, 18: 1}, spell=[("r18", 138), ("r18", 120)])], BAD_DEFLATE)
+    add("stored_len_past_the_payload", [{"type": "stored", "data": b"abcdef", "len": 10}], BAD_SIZE, b"abcdefghij")
+    add("stored_len_past_isize", [{"type": "stored", "data": b"abcdefghij"}], BAD_SIZE, b"abcdef")
+    # a payload whose last token is a match with a 15-bit distance code and 13 extra bits: cut short, zlib runs out of input
+    head = rng.integers(0, 256, 30000, dtype=np.uint8).tobytes()
+    far = [{"type": "stored", "data": head}, dyn([97, (3, 24577 + 5000)], check=True, lit_lens=one["lit_lens"],
+                                                 dist_lens=dw.assign(list(range(15)) + [29], dw.skewed_lengths(16, 15), 30))]
+    text = dw.block_text(far)
+    assert zlib.decompress(dw.write_stream(far), -15) == text
+    for cut in range(1, 7):
+        add("cut_%d_inside_a_15_bit_code_with_13_extra_bits" % cut, far, BAD_SIZE, text, cut=cut)
+    valid = {n: (m, d) for n, m, d, _ in _foreign()}
+    m, d = valid["everything_at_once"]
+    add("everything_at_once/isize-1", payload_of(m), BAD_SIZE, d, isize=len(d) - 1)
+    add("everything_at_once/crc", payload_of(m), BAD_CRC, d, crc=zlib.crc32(d) ^ 0x80000000)
+    m, d = valid["size/33"]
+    add("size/33/isize+1", payload_of(m), BAD_SIZE, d, isize=34)
+    add("size/33/crc", payload_of(m), BAD_CRC, d, crc=zlib.crc32(d) ^ 1)
+    # gzip members that are no BGZF members
+    p = payload_of(m)
+    for name, gz in (("fname", dict(flg=12, fname=b"rows.txt")), ("fhcrc", dict(flg=6, hcrc=True)), ("no_bc", dict(subfields=(("XY", b"\x01\x02"),))),
+                     ("two_bc", dict(subfields=(("BC", None), ("BC", None)))), ("bc_of_4_bytes", dict(subfields=(("BC", b"\0\0\0\0"),)))):
+        g = wrap_gzip(p, d, **gz)
+        assert zlib.decompress(g, 31) == d and "wrapper/" + name in GZIP_NOT_BGZF
+        out.append(("wrapper/" + name, g))
+        FOREIGN_DAMAGED_EXPECT["wrapper/" + name] = BAD_HEADER
+    _FOREIGN["damaged"] = out
+    return out
+
+
+def foreign_features(members):
+    """the tracer over valid members [(name, member, data)]: its text must be zlib's; returns (Counter of the features of
+    deflate_writer.trace summed over the members, plus what only a whole member shows; {name: the member's own Counter})"""
+    import deflate_writer as dw
+    total, per = Counter(), {}
+    for name, m, data in members:
+        xlen = struct.unpack_from("<H", m, 10)[0]
+        payload = m[12 + xlen:-8]
+        tr = dw.trace(payload)
+        assert tr.text == zlib.decompress(payload, -15) == data, name
+        f = tr.features
+        kinds = [b[0] for b in tr.blocks]
+        if len(kinds) >= 1000 and all(kinds[k] == (0, 1, 2)[k % 3] for k in range(len(kinds))):
+            f["member_1000_blocks_cycling"] += 1
+        if len(data) == 65536 and f["hlit:286"] and f["hdist:30"] and f["lit_bits:15"] and f["dist_bits:15"] and f["dist_32768"] and \
+                all(f["len_sym:%d:min" % s] for s in range(257, 286)) and all(f["dist_sym:%d:max" % s] for s in range(30)):
+            f["everything_at_once"] += 1
+        subfields, at = [], 12
+        while at < 12 + xlen:
+            subfields.append(m[at:at + 2])
+            at += 4 + struct.unpack_from("<H", m, at + 2)[0]
+        if subfields.index(b"BC") > 0:
+            f["wrapper_extra_before_bc"] += 1
+        if subfields.index(b"BC") < len(subfields) - 1:
+            f["wrapper_extra_behind_bc"] += 1
+        if 0 < subfields.index(b"BC") < len(subfields) - 1:
+            f["wrapper_extra_on_both_sides"] += 1
+        if xlen > 6:
+            f["wrapper_xlen_above_6"] += 1
+        if m[4:8] != b"\0\0\0\0" and m[8] and m[9] != 255:
+            f["wrapper_mtime_xfl_os"] += 1
+        per[name] = f
+        total.update(f)
+    return total, per
+
+
+def required_features():
+    req = ["lit_bits:%d" % l for l in range(1, 16)] + ["dist_bits:%d" % l for l in range(1, 16)]
+    req += ["len_sym:%d:%s" % (s, e) for s in range(257, 286) for e in ("min", "max")] + ["dist_sym:%d:%s" % (s, e) for s in range(30) for e in ("min", "max")]
+    req += ["len258_as_285", "len258_as_284", "dist_32768", "dist_32507_32767", "dist_eq_written:32768", "dist_eq_written:1", "match_ends_at_65536_of_65536"]
+    req += ["overlap:%d" % d for d in (1, 2, 3, 7, 63, 64, 65)] + ["overlap_257_len258", "src_ends_on_prev_literal"]
+    # (HCLEN 4 cannot occur in a valid block -- see _foreign() -- so the smallest that can, 5, stands for it here)
+    req += ["hlit:257", "hlit:286", "hdist:1", "hdist:30", "hclen:5", "hclen:19", "hclen19_slot18_nonzero", "cl_len7", "cl_bits:7"]
+    req += ["rep16:3", "rep16:6", "rep17:3", "rep17:10", "rep18:11", "rep18:138", "rep16_cross", "rep17_cross", "rep18_cross"]
+    req += ["dist_one_code_used", "lit_only_end_code", "hdist1_len0_no_match"]
+    req += ["stored_len0_first", "stored_len0_middle", "stored_len0_final", "stored_len:65505", "stored_after_huffman_pad:0"]
+    req += ["stored_after_huffman_pad:%d_ones" % k for k in range(1, 8)] + ["after_stored_pos_mod4:%d" % r for r in range(4)]
+    req += ["member_1000_blocks_cycling", "dyn15_then_dyn2", "dyn2_then_dyn15", "fixed_after_dynamic", "final_ends_inside_byte_rest_ones", "trailing_bytes"]
+    req += ["text_size:%d" % n for n in FOREIGN_SIZES] + ["everything_at_once"]
+    req += ["wrapper_extra_before_bc", "wrapper_extra_behind_bc", "wrapper_extra_on_both_sides", "wrapper_xlen_above_6", "wrapper_mtime_xfl_os"]
+    return req
+
+
+# what the issue's table found absent from valid_corpus() (zlib's compressor does not write it)
+ABSENT_FROM_ZLIB = ["dist_32768", "dist_32507_32767", "lit_bits:15", "len258_as_284", "hclen19_slot18_nonzero", "rep16_cross", "rep17_cross", "rep18_cross",
+                    "dist_one_code_used"] + ["dist_bits:%d" % l for l in range(12, 16)]
+
+
+def assert_features_hit(counter):
+    missing = [k for k in required_features() if not counter[k]]
+    assert not missing, "the foreign corpus misses: %s" % missing

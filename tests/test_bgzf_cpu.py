@@ -1,6 +1,7 @@
 """CPU tests (no GPU) of the device BGZF path: the new public header against the ctypes layer and the library, the CPU build of
 the DEFLATE decoder's core (basevar_amd/csrc/bv_inflate_core.h, the code the kernel compiles) against zlib over the whole
-valid and damaged corpus of tests/bgzf_corpus.py, plain and under ASan + UBSan, and the inflate kernel's resources."""
+valid and damaged corpus of tests/bgzf_corpus.py and over its foreign corpus (streams zlib's compressor never writes; the tracer
+of tests/deflate_writer.py says what each holds), plain and under ASan + UBSan, and the inflate kernel's resources."""
 import ctypes as C
 import os
 import re
@@ -113,6 +114,102 @@ def test_inflate_core_under_asan_and_ubsan(corpus, tmp_path):
     """the same run with the `sanitize` build of basevar_amd/csrc/Makefile: no report over either corpus"""
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "basevar_amd", "csrc"), "../lib/san/inflate_core_check.asan"])
     _check(os.path.join(ROOT, "basevar_amd", "lib", "san", "inflate_core_check.asan"), corpus, tmp_path)
+
+
+@pytest.fixture(scope="module")
+def foreign():
+    valid = bc.foreign_corpus()
+    damaged = bc.foreign_damaged()
+    assert len(valid) > 80 and len(damaged) > 30
+    assert len({n for n, _, _ in valid}) == len(valid) and len({n for n, _ in damaged}) == len(damaged)
+    return valid, damaged
+
+
+def test_tracer_gives_zlibs_bytes_and_the_foreign_corpus_holds_every_feature(foreign):
+    """tests/deflate_writer.py's tracer inflates every valid foreign member to zlib's bytes (raw inflate of the payload, and gzip
+    inflate of the whole member: the wrapper's judge), and the features it counts there are all of bc.required_features();
+    one member is everything at once."""
+    import zlib
+    valid, _ = foreign
+    total, per = bc.foreign_features(valid)  # (asserts the tracer's text against zlib's, member by member)
+    for name, m, d in valid:  # (gzip expects CRC32 and ISIZE right behind the final block; BGZF finds them by the BC length)
+        assert per[name]["trailing_bytes"] or zlib.decompress(m, 31) == d, name
+    assert sum(1 for n in per if per[n]["trailing_bytes"]) == 1
+    bc.assert_features_hit(total)
+    assert per["everything_at_once"]["everything_at_once"] == 1 and per["everything_at_once"]["cl_len7"]
+    assert len(bc.payload_of(dict((n, m) for n, m, _ in valid)["everything_at_once"])) < 40000
+
+
+def test_zlibs_own_streams_lack_what_the_foreign_corpus_adds(corpus):
+    """The tracer over all of valid_corpus() (every member; zlib's bytes again): none of the features of bc.ABSENT_FROM_ZLIB
+    occurs there, the text sizes mod 16 are 0, 1, 8 and 12 and below 16 bytes 0 and 1.  (If a zlib build does write one of
+    them, the assertion names it; it may then be dropped from that list alone.)"""
+    valid, _ = corpus
+    total, _ = bc.foreign_features(valid)
+    assert not [k for k in bc.ABSENT_FROM_ZLIB if total[k]]
+    assert not [k for k in total if k.startswith("dist_bits:") and int(k[10:]) > 11] and not total["hclen:19"]
+    assert {len(d) % 16 for _, _, d in valid} == {0, 1, 8, 12} and {len(d) for _, _, d in valid if len(d) < 16} == {0, 1}
+    added = [k for k in bc.required_features() if not total[k]]
+    assert len(added) > 100, len(added)
+
+
+def test_writer_against_itself(foreign):
+    """expand() of the tokens the writer was given is what zlib inflates from what it wrote, for every valid foreign member;
+    transcode() keeps the text and writes the codes it was asked for"""
+    import zlib
+    import deflate_writer as dw
+    valid, _ = foreign
+    blocks = bc.foreign_blocks()
+    for name, _, d in valid:
+        assert dw.block_text(blocks[name]) == d, name
+    for n in (16, 30, 286):
+        lens = dw.skewed_lengths(n, 15)
+        assert len(lens) == n and dw.kraft(lens) == 1 << 15 and set(lens) == set(range(lens[0], 16)), n
+    assert dw.skewed_lengths(16, 15) == list(range(1, 16)) + [15]
+    text = valid[0][2] * 3 + bytes(range(256)) * 40
+    payload, out = dw.transcode(bc.deflate(text, 6), cut=40, stored_every=3)
+    assert out == text and zlib.decompress(payload, -15) == text
+    f = dw.trace(payload).features
+    assert f["hclen:19"] and f["hclen19_slot18_nonzero"] and f["hlit:286"] and f["hdist:30"] and f["blocks:0"] and f["blocks:2"] > 2
+
+
+def _check_foreign(exe, foreign, tmp_path):
+    import zlib
+    valid, damaged = foreign
+    p, rows = bc.core_verdicts(exe, [m for _, m, _ in valid], tmp_path)
+    report = [l for l in p.stderr.splitlines() if "Sanitizer" in l or "runtime error:" in l]
+    assert not report and p.returncode == 0, p.stderr[-3000:]
+    assert len(rows) == len(valid)
+    wrong = [(n, r) for (n, _, d), r in zip(valid, rows) if r[0] != bc.OK or r[1] != bc.OK or r[3] != len(d)]
+    assert not wrong, wrong[:10]
+    p, rows = bc.core_verdicts(exe, [m for _, m in damaged], tmp_path)
+    print(p.stderr[-2000:])
+    report = [l for l in p.stderr.splitlines() if "Sanitizer" in l or "runtime error:" in l]
+    assert not report and p.returncode == 0, p.stderr[-3000:]
+    assert len(rows) == len(damaged)
+    assert {r[0] for r in rows} == {bc.OK, bc.BAD_HEADER, bc.BAD_DEFLATE, bc.BAD_SIZE, bc.BAD_CRC}
+    assert set(bc.FOREIGN_DAMAGED_EXPECT) == {n for n, _ in damaged}
+    for (n, m), r in zip(damaged, rows):
+        want = bc.FOREIGN_DAMAGED_EXPECT[n]
+        if n in bc.GZIP_NOT_BGZF:  # gzip reads it, BGZF does not allow it
+            assert zlib.decompress(m, 31) and want == bc.BAD_HEADER and r[0] == bc.BAD_HEADER, (n, bc.GZIP_NOT_BGZF[n], r)
+        else:  # the core's status, and zlib's own verdict, are what the construction says
+            assert (r[0], r[1]) == (want, want), (n, r, want)
+    assert set(bc.GZIP_NOT_BGZF) <= {n for n, _ in damaged}
+    # HCLEN 4 (header bits 13 .. 16 are 0) can only spell lengths of zero: no valid block has it, zlib refuses this one
+    head = int.from_bytes(bc.payload_of(dict(damaged)["hclen_4"])[:3], "little")
+    assert (head >> 1) & 3 == 2 and (head >> 13) & 15 == 0 and bc.FOREIGN_DAMAGED_EXPECT["hclen_4"] == bc.BAD_DEFLATE
+
+
+def test_inflate_core_against_zlib_on_the_foreign_corpus(foreign, tmp_path):
+    """the CPU build of the core over members that zlib's compressor never writes: OK with zlib's bytes on every valid one,
+    zlib's verdict and category on every damaged one, all five statuses seen"""
+    _check_foreign(bc.build_core_check(tmp_path), foreign, tmp_path)
+
+
+def test_inflate_core_under_asan_and_ubsan_on_the_foreign_corpus(foreign, tmp_path):
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "basevar_amd", "csrc"), "../lib/san/inflate_core_check.asan"])
+    _check_foreign(os.path.join(ROOT, "basevar_amd", "lib", "san", "inflate_core_check.asan"), foreign, tmp_path)
 
 
 def test_new_sources_hold_no_scalar_store_mnemonics():

@@ -46,7 +46,7 @@ def same_batch(got, exp, groups):
     assert got.cell.tobytes() == exp.cell.tobytes() and got.phred.tobytes() == exp.phred.tobytes()
 
 
-def compare(slab, fs, n_groups=0, depth_zero=(), member=0xff00, level=1, headers=None, last_newline=True):
+def compare(slab, fs, n_groups=0, depth_zero=(), member=0xff00, level=1, headers=None, last_newline=True, members_of=members_of):
     from basevar_amd import _capi
     P, N, F = slab["base_strand"].shape[0], int(slab["n_samples"]), len(fs)
     text, row_off = slab_rows(slab, fs, depth_zero)
@@ -280,3 +280,100 @@ def test_argument_errors():
         assert len(eng.lrt_bgzf(runs, fs).sites) > 0
     finally:
         eng.close()
+
+
+# ---- members written by zlib and written again by tests/deflate_writer.py under codes zlib's compressor never chooses
+
+
+def transcoded_members(data, member, level=1, cut=150, stored_every=5):
+    """members_of(), every member's tokens written again: dynamic blocks of `cut` tokens under skewed codes of up to 15 bits over
+    all 286 + 30 symbols (every other block with its data in the longest codes), HCLEN 19, every stored_every-th block stored; zlib inflates each to the same text"""
+    import zlib
+    import deflate_writer as dw
+    out = []
+    for at in range(0, len(data), member):
+        part = data[at:at + member]
+        payload, text = dw.transcode(bc.deflate(part, level), cut=cut, stored_every=stored_every)
+        assert text == part and zlib.decompress(payload, -15) == part
+        out.append(bc.wrap(payload, part))
+        assert len(out[-1]) <= 65536
+    return out + [bc.member(b"")]
+
+
+def tokens_at_distance(before, text, dist):
+    """text as tokens behind `before`: matches at exactly `dist` wherever at least three bytes repeat there, else literals"""
+    assert len(before) >= dist
+    whole, tokens, i = before + text, [], 0
+    base = len(before)
+    while i < len(text):
+        n = 0
+        while n < 258 and i + n < len(text) and whole[base + i + n] == whole[base + i + n - dist]:
+            n += 1
+        if n >= 3:
+            tokens.append((n, dist))
+            i += n
+        else:
+            tokens.append(text[i])
+            i += 1
+    return tokens
+
+
+def test_rows_from_transcoded_members():
+    import deflate_writer as dw
+    slab = make_slab(40, 3 * 200 + 37, seed=312, coverage=0.1, indel_frac=0.02, n_groups=2)
+    compare(slab, [200] * 3 + [37], n_groups=2, member=0x6000, members_of=transcoded_members)
+    f = dw.trace(bc.payload_of(transcoded_members(bc.rows_text(0x6000, seed=9), 0x6000)[0])).features
+    assert f["hclen19_slot18_nonzero"] and f["hlit:286"] and f["hdist:30"] and f["blocks:0"] and f["blocks:2"] > 5
+    assert f["lit_bits:15"] and f["dist_bits:15"]
+
+
+def repeated_block_file(P_tail=25, N=60, seed=313):
+    """(rows [[bytes]] per position, members): one file whose first 2 * 32 768 bytes are a block of rows and the same rows again
+    at the next positions (CHROM padded so that the block is 32 768 bytes), the second block written as matches at distance
+    32 768 with literals where POS differs; everything under transcoded codes"""
+    import zlib
+    import deflate_writer as dw
+    slab = make_slab(200, N, seed=seed, coverage=0.3, indel_frac=0.02)
+    text, off = slab_rows(slab, [N])
+    P_block = int(np.searchsorted(off, 32768, side="right")) - 1  # the rows that fit 32 768 bytes
+    assert 20 < P_block and 2 * P_block + P_tail <= 200
+    slab["base_strand"][P_block:2 * P_block] = slab["base_strand"][:P_block]
+    for k in ("qual", "mapq", "rpr", "ref_base"):
+        slab[k][P_block:2 * P_block] = slab[k][:P_block]
+    text, off = slab_rows(slab, [N])
+    rows = [bytes(text[int(off[p]):int(off[p + 1]) - 1]) for p in range(2 * P_block + P_tail)]
+    short = 32768 - sum(len(r) + 1 for r in rows[:P_block])
+    assert 0 <= short < 25 * P_block, short
+    for p in range(2 * P_block):  # a longer CHROM: short // P_block letters, one more on the first short % P_block rows
+        j = p % P_block
+        rows[p] = b"chr9" + b"x" * (short // P_block + (j < short % P_block)) + rows[p][4:]
+    first, second = (b"".join(r + b"\n" for r in rows[a:a + P_block]) for a in (0, P_block))
+    assert len(first) == len(second) == 32768 and first != second
+    extra = tokens_at_distance(first, second, 32768)
+    payload, both = dw.transcode(bc.deflate(first, 6), cut=400, stored_every=7, extra_tokens=extra)
+    assert both == first + second and zlib.decompress(payload, -15) == both
+    f = dw.trace(payload).features
+    assert f["dist_32768"] > 100 and f["dist_32768"] > len(extra) // 2 and f["hclen19_slot18_nonzero"]
+    head = bc.wrap(payload, both)
+    assert len(head) <= 65536
+    tail = b"".join(r + b"\n" for r in rows[2 * P_block:])
+    return rows, [head] + transcoded_members(tail, 0x3000, 6)
+
+
+def test_rows_repeated_at_distance_32768():
+    from basevar_amd import _capi
+    N = 60
+    rows, members = repeated_block_file(N=N)
+    P = len(rows)
+    flat = np.frombuffer(b"".join(r + b"\n" for r in rows), np.uint8)
+    row_off = np.concatenate([[0], np.cumsum([len(r) + 1 for r in rows])]).astype(np.uint64)
+    eng = engine(P, N)
+    try:
+        exp = eng.lrt_text([[r] for r in rows], [N])
+        got = eng.lrt_bgzf([members], [N])
+    finally:
+        eng.close()
+    assert got.row_state.shape == (P, 1) and not (got.row_state & _capi.BV_TEXT_HOST).any()
+    same_batch(got, exp, 0)
+    assert got.n_variant > 0
+    check_fetched(got, flat, row_off, P, 1)
