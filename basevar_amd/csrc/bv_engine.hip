@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "bv_kernels.h"
+#include "bv_engine_impl.h"
 
 void bv_launch_synth(const bv_synth_params &p, uint32_t n_sites, uint32_t n_samples, uint64_t pitch, uint8_t *bs,
                      uint8_t *q, uint8_t *mapq, uint16_t *rpr, uint8_t *ref_base, hipStream_t stream);
@@ -164,122 +164,7 @@ bool load_host_log_table_once(double *dst) {
 }
 }  // namespace
 
-struct bv_engine {
-    bv_engine_config cfg;
-    hipStream_t stream = nullptr;      // engine-owned stream
-    hipStream_t last_stream = nullptr; // stream of the last submit
-    std::vector<hipStream_t> used_streams;  // every stream that carried work since the last bv_engine_wait
-    hipEvent_t ev_host = nullptr;      // BV_FLAG_HOST_ORDERED: what the copy stream waits for before it reads host planes
-    hipEvent_t ev_done = nullptr;      // end of the last submit: a submit on ANOTHER stream waits for it (shared scratch)
-    bool ev_done_set = false;
-    bool done_pending = false;         // the last submit's end is not recorded in ev_done yet (flush_done)
-    hipStream_t done_stream = nullptr;
-    uint32_t n_cu = 256;               // hipDeviceProp_t::multiProcessorCount
-    int host_log_exact = 0;            // 1: the device replays shallow sites with the host libm's log(), verified bit-exact
-    uint8_t *d_gid = nullptr;          // engine-owned copy of group_id, padded to 16 bytes with BV_NO_GROUP
-    size_t d_gid_bytes = 0;
-    BvTables *d_tables = nullptr;
-    double *d_lnfact = nullptr;
-    uint32_t *d_var_list = nullptr;
-    // Counter blocks (BV_CTR_* words each, bv_kernels.h): a launch that is cut into chunks (short rows, launch_passes)
-    // gives every chunk a block of its own; everything else uses block 0.
-    static constexpr uint32_t kCtrBlocks = 8;
-    uint32_t *d_counters = nullptr;    // [kCtrBlocks][BV_CTR_WORDS]
-    uint32_t *h_counters = nullptr;    // pinned host mirror
-    uint32_t last_blocks = 1;          // blocks the last launch used (their VARIANTS words add up to its variant count)
-    uint32_t last_ctr_base = 0;        // ... starting at this block
-    // Submits take the counter blocks in turn (launch i: block i % kCtrBlocks): all blocks' per-launch lines are zeroed by ONE
-    // 2-D fill every kCtrBlocks launches, and the host mirror is filled by bv_engine_wait, not by a copy behind every submit.
-    // (Measured: the 23 KB device-to-host copy behind each submit kept the next submit's first kernel waiting ~10 us --
-    // 100 k sites x 10 k samples 157.7 -> 160.4 M sites/s without it, 8,192-site batches 51.9 -> 55.7 M.)
-    uint32_t ctr_rot = 0;
-    bool ctr_mirror_stale = false;     // the device counters are ahead of h_counters
-    static constexpr int kRing = 256;
-    hipEvent_t ring[kRing][4] = {};    // per-submit events: start, end of pass 1, end of pass 2, [3] end of the streaming kernel of pass 1
-    bool ring_one_kernel[kRing] = {};  // pass 1 was ONE kernel (long rows): [3] was not recorded, its time is [0] -> [1]
-    int ring_head = 0, ring_count = 0; // pending (not yet accumulated) triplets
-    int last_slot = -1;
-    uint32_t n_launches = 0;           // launches since creation (BV_FLAG_SPARSE_TIMING times every eighth)
-    uint32_t last_form = 0;            // BV_FORM_* bits of the last launch (bv_engine_last_launch_form)
-    double acc1_ms = 0., acc2_ms = 0., acc_stream_ms = 0.;
-    // short rows (bv_pass1_short.hip): HBM scratch between the streaming kernel and the solve kernel
-    BvSiteSummary *d_summ = nullptr;
-    uint32_t *d_bins = nullptr, *d_cand_list = nullptr, *d_easy_list = nullptr, *d_easy3_list = nullptr, *d_ovf = nullptr;
-    uint32_t short_sites = 0;          // sites the short-row scratch holds
-    uint32_t *d_gitems = nullptr;      // pop-group calls handed from the pass-2 tally kernels to bv_p2g_solve16_kernel
-    uint32_t gitem_cap = 0;            // items (of BV_P2G_ITEM_WORDS words) d_gitems holds
-    uint8_t *d_gidp = nullptr;         // group ids prepared for bv_p2g_stream_kernel (bv_launch_gid_prepare)
-    // more than BV_GROUPS_PER_ROUND pop-groups: pass 2 runs once per round of groups, on the round's own view of the group plane
-    // (groups of other rounds read as "no group") and into records of its own, which are then moved to their columns of `gout`
-    uint8_t *d_gid_round = nullptr;
-    size_t d_gid_round_bytes = 0;
-    bv_group_result *d_gout_round = nullptr;
-    size_t d_gout_round_bytes = 0;
-    BvChain *d_chain = nullptr;        // segment tables of chained launches (bv_engine_submit_many)
-    uint8_t *d_ref_cat = nullptr;      // chained short-row launches: reference bases / records of all segments, contiguous
-    bv_site_result *d_out_cat = nullptr;
-    unsigned chain_next = 0;
-    size_t d_gidp_bytes = 0;
-    uint32_t acc_n = 0;
-    bool submitted = false;
-    // Host buffers (BV_MEM_HOST slabs, tiles, record buffers) go through a ring of device staging buffers filled by a
-    // copy stream of their own: the PCIe copy of submit / tile k+1 runs under the kernels of k, and a buffer is reused
-    // only after the work that read it has finished (events).
-    static constexpr int kStage = 4;
-    struct StageSlot {
-        void *buf = nullptr;
-        size_t bytes = 0;
-        hipEvent_t copied = nullptr, freed = nullptr;
-        hipStream_t cs = nullptr;  // the copy stream that fills this slot
-        bool used = false;
-    };
-    StageSlot sring[kStage];
-    unsigned sring_next = 0;
-    bv_site_result *stage_out = nullptr;
-    bv_group_result *stage_gout = nullptr;
-    bv_site_result *host_out = nullptr;
-    bv_group_result *host_gout = nullptr;
-    size_t host_out_bytes = 0, host_gout_bytes = 0;
-    // sample-axis tile mode
-    uint32_t *tile_state = nullptr;
-    uint32_t *tile_maxr = nullptr;
-    size_t tile_state_bytes = 0, tile_maxr_bytes = 0;
-    uint32_t tile_sites = 0, tile_groups = 0, tile_stride = 0, tile_samples_total = 0, tile_samples_seen = 0;
-    uint32_t tile_rank_win = 1024, tile_hg_off = 0, tile_ord_off = 0;
-    uint32_t *tile_ovf = nullptr;      // pool of read-position ranks beyond the window (bv_tiles.hip), kOvfCap entries
-    static constexpr uint32_t kOvfCap = 1u << 22;
-    bool tile_ranks = false, tile_open = false;
-    uint32_t tile_layout = 0;          // bv_slab.layout of the job's tiles (every tile of a job has the first one's)
-    bool tile_layout_set = false;
-    bool j_filled = false;             // joined rows: the columns not yet delivered hold "uncovered" (a packed tile scatters into them)
-    hipStream_t copy_stream[2] = {nullptr, nullptr};  // alternate: the set-up of one copy hides under the transfer of the other
-    // joined-rows realisation of the tile mode: resident planes [tile_sites][j_pitch]
-    bool tile_join = false;
-    uint8_t *j_buf = nullptr;
-    size_t j_bytes = 0, j_pitch = 0, j_o_q = 0, j_o_mq = 0, j_o_rp = 0, j_o_gid = 0;
-    // BV_FLAG_LANES: device-resident submits alternate between two child engines (streams and scratch of their own), so that
-    // the solve kernels of one submit run under the streaming kernels of the next; the parent runs no kernels then
-    static constexpr int kMaxLanes = 4;
-    bv_engine *lane[kMaxLanes] = {nullptr, nullptr, nullptr, nullptr};
-    int n_lanes = 2;                   // (BASEVAR_AMD_LANES: tuning runs)
-    unsigned lane_next = 0;
-    int last_lane = -1;
-    bool is_lane = false;
-    hipEvent_t ev_entry = nullptr;     // what a lane waits for: the caller's stream at the time of the submit
-    // bv_engine_tiles_add_many: descriptor tables, a ring of pinned host + device buffers
-    static constexpr int kDescRing = 4;
-    BvTileScatterPlane *h_desc[kDescRing] = {}, *d_desc[kDescRing] = {};
-    hipEvent_t ev_desc[kDescRing] = {};
-    bool desc_used[kDescRing] = {};
-    unsigned desc_next = 0;
-    BvTextState *text = nullptr;       // bv_engine_text_parse / _submit (bv_text.hip)
-    BvBgzfState *bgzf = nullptr;       // bv_engine_bgzf_inflate (bv_inflate.hip)
-    mutable std::mutex mu;
-    std::string err;
-};
-
-namespace {
-int fail(bv_engine *e, int code, const std::string &msg) {
+int bv_impl::fail(bv_engine *e, int code, const std::string &msg) {
     if (e) {
         std::lock_guard<std::mutex> lk(e->mu);
         e->err = msg;
@@ -288,13 +173,7 @@ int fail(bv_engine *e, int code, const std::string &msg) {
     }
     return code;
 }
-#define BV_HIP(e, call)                                                                         \
-    do {                                                                                        \
-        hipError_t _s = (call);                                                                 \
-        if (_s != hipSuccess)                                                                   \
-            return fail((e), BV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s));    \
-    } while (0)
-}  // namespace
+using namespace bv_impl;
 
 namespace {
 // fold every completed pending triplet into the accumulators; `block` waits for them
@@ -335,6 +214,9 @@ int flush_done(bv_engine *e) {
     }
     return BV_OK;
 }
+}  // namespace
+
+namespace bv_impl {
 int use_stream(bv_engine *e, hipStream_t st) {
     bool seen = false;
     for (hipStream_t u : e->used_streams) seen |= (u == st);
@@ -359,35 +241,28 @@ int mark_done(bv_engine *e, hipStream_t st) {
 // group ids as the kernels read them: 16-byte chunks up to round_up(n_samples, 16) -- the ABI promises only
 // [n_samples] bytes of any alignment, so the engine keeps its own padded copy (n_samples bytes per submit)
 int stage_group_ids(bv_engine *e, const uint8_t *gid, uint32_t n_samples, bool host, hipStream_t st, const uint8_t **out) {
-    const size_t need = (((size_t)n_samples + 255) & ~(size_t)255) + 256;
-    if (need > e->d_gid_bytes) {
-        if (e->d_gid) BV_HIP(e, hipFree(e->d_gid));
-        e->d_gid = nullptr; e->d_gid_bytes = 0;
-        BV_HIP(e, hipMalloc(&e->d_gid, need));
-        e->d_gid_bytes = need;
-    }
+    const size_t need = up256(n_samples) + 256;
+    const int rc = grow_device(e, &e->d_gid, &e->d_gid_bytes, need);
+    if (rc != BV_OK) return rc;
     BV_HIP(e, hipMemsetAsync(e->d_gid, 0xFF, need, st));
     BV_HIP(e, hipMemcpyAsync(e->d_gid, gid, n_samples, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
     *out = e->d_gid;
     return BV_OK;
 }
 // ---- staging ring
-int stage_acquire(bv_engine *e, size_t bytes, bv_engine::StageSlot **out) {
+int stage_acquire(bv_engine *e, size_t bytes, StageSlot **out) {
     for (auto &cs : e->copy_stream)
         if (!cs) BV_HIP(e, hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
     const unsigned k = e->sring_next++;
-    bv_engine::StageSlot &sl = e->sring[k % bv_engine::kStage];
+    StageSlot &sl = e->sring[k % bv_engine::kStage];
     sl.cs = e->copy_stream[k & 1u];
     if (!sl.copied) {
         BV_HIP(e, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
         BV_HIP(e, hipEventCreateWithFlags(&sl.freed, hipEventDisableTiming));
     }
-    if (bytes > sl.bytes) {
-        if (sl.buf) BV_HIP(e, hipFree(sl.buf));  // synchronises with work that still uses it
-        sl.buf = nullptr; sl.bytes = 0; sl.used = false;
-        BV_HIP(e, hipMalloc(&sl.buf, bytes));
-        sl.bytes = bytes;
-    }
+    if (bytes > sl.bytes) sl.used = false;  // a new buffer: nothing reads it yet
+    const int rc = grow_device(e, &sl.buf, &sl.bytes, bytes);
+    if (rc != BV_OK) return rc;
     // the buffer is free again once the work that read it last has run
     if (sl.used) BV_HIP(e, hipStreamWaitEvent(sl.cs, sl.freed, 0));
     *out = &sl;
@@ -396,78 +271,56 @@ int stage_acquire(bv_engine *e, size_t bytes, bv_engine::StageSlot **out) {
 // BV_FLAG_HOST_ORDERED: the copies of host planes wait for everything queued on the caller's stream so far (a caller that
 // fills its pinned planes with asynchronous work on that stream).  Default: host planes are complete when the call is made
 // (include/basevar_amd.h) and the copy runs ahead, under the kernels of earlier submits.
-int stage_order(bv_engine *e, bv_engine::StageSlot *sl, hipStream_t st) {
+int stage_order(bv_engine *e, StageSlot *sl, hipStream_t st) {
     if (!(e->cfg.flags & BV_FLAG_HOST_ORDERED)) return BV_OK;
     if (!e->ev_host) BV_HIP(e, hipEventCreateWithFlags(&e->ev_host, hipEventDisableTiming));
     BV_HIP(e, hipEventRecord(e->ev_host, st));
     BV_HIP(e, hipStreamWaitEvent(sl->cs, e->ev_host, 0));
     return BV_OK;
 }
-int stage_publish(bv_engine *e, bv_engine::StageSlot *sl, hipStream_t st) {  // the copies are queued: `st` may read after them
+int stage_publish(bv_engine *e, StageSlot *sl, hipStream_t st) {  // the copies are queued: `st` may read after them
     BV_HIP(e, hipEventRecord(sl->copied, sl->cs));
     BV_HIP(e, hipStreamWaitEvent(st, sl->copied, 0));
     return BV_OK;
 }
-int stage_release(bv_engine *e, bv_engine::StageSlot *sl, hipStream_t st) {  // everything queued on `st` so far is the last reader
+int stage_release(bv_engine *e, StageSlot *sl, hipStream_t st) {  // everything queued on `st` so far is the last reader
     BV_HIP(e, hipEventRecord(sl->freed, st));
     sl->used = true;
     return BV_OK;
 }
 // Host planes that lie in ONE allocation, one after the other (a packed tile, see bv_tile_packed_layout), go over the
 // link as one copy: the per-copy cost of five 2-3 MB copies per tile was a quarter of the tile's transfer time.
-struct HostSpan {
-    const uint8_t *lo = nullptr, *hi = nullptr;
-    void add(const void *p, size_t n) {
-        if (!p || !n) return;
-        const uint8_t *a = static_cast<const uint8_t *>(p);
-        if (!lo || a < lo) lo = a;
-        if (!hi || a + n > hi) hi = a + n;
-    }
-    size_t bytes() const { return (size_t)(hi - lo); }
-};
-struct HostPlane {
-    const void *src;     // host pointer (may be NULL: plane absent)
-    size_t bytes;
-    const uint8_t *dev;  // out: where the plane lives in the staging buffer
-};
-// Where `n` host planes go in a staging buffer: the bytes they take there, and whether they cross as ONE copy (`sp`).
-struct HostPlanes {
-    HostSpan sp;
-    bool one_copy = false;
-    size_t bytes = 0;
-};
 HostPlanes plan_host_planes(const HostPlane *pl, int n) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     HostPlanes h;
     size_t sum = 0;
     for (int i = 0; i < n; ++i) {
         if (!pl[i].src || !pl[i].bytes) continue;
-        h.sp.add(pl[i].src, pl[i].bytes);
-        sum += up(pl[i].bytes);
+        const uint8_t *a = static_cast<const uint8_t *>(pl[i].src);
+        if (!h.lo || a < h.lo) h.lo = a;
+        if (!h.hi || a + pl[i].bytes > h.hi) h.hi = a + pl[i].bytes;
+        sum += up256(pl[i].bytes);
     }
     // ONE copy only for the exact layout of bv_tile_packed_layout: the planes in order, each at the 256-aligned end of the one
     // before it, in one allocation -- then every byte of [lo, hi) is the caller's.  (Planes that merely lie close together
     // are copied one by one: the bytes between them are not ours to read.)
-    bool one_copy = h.sp.lo != nullptr && (reinterpret_cast<uintptr_t>(h.sp.lo) & 15u) == 0;
+    bool one_copy = h.lo != nullptr && (reinterpret_cast<uintptr_t>(h.lo) & 15u) == 0;
     {
         size_t at = 0;
         for (int i = 0; i < n && one_copy; ++i) {
             if (!pl[i].src || !pl[i].bytes) continue;
-            one_copy = static_cast<const uint8_t *>(pl[i].src) == h.sp.lo + at;
-            at += up(pl[i].bytes);
+            one_copy = static_cast<const uint8_t *>(pl[i].src) == h.lo + at;
+            at += up256(pl[i].bytes);
         }
     }
     h.one_copy = one_copy;
-    h.bytes = one_copy ? up(h.sp.bytes()) : sum;
+    h.bytes = one_copy ? up256((size_t)(h.hi - h.lo)) : sum;
     return h;
 }
-// Queue the copies of planes planned by plan_host_planes to `base` (device) on the copy stream `cs`; pl[i].dev = where plane i lands.
 int copy_host_planes(bv_engine *e, HostPlane *pl, int n, const HostPlanes &h, uint8_t *base, hipStream_t cs) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (h.one_copy) {
-        BV_HIP(e, hipMemcpyAsync(base, h.sp.lo, h.sp.bytes(), hipMemcpyHostToDevice, cs));
+        BV_HIP(e, hipMemcpyAsync(base, h.lo, (size_t)(h.hi - h.lo), hipMemcpyHostToDevice, cs));
         for (int i = 0; i < n; ++i)
-            pl[i].dev = (pl[i].src && pl[i].bytes) ? base + (static_cast<const uint8_t *>(pl[i].src) - h.sp.lo) : nullptr;
+            pl[i].dev = (pl[i].src && pl[i].bytes) ? base + (static_cast<const uint8_t *>(pl[i].src) - h.lo) : nullptr;
     } else {
         size_t off = 0;
         for (int i = 0; i < n; ++i) {
@@ -475,17 +328,15 @@ int copy_host_planes(bv_engine *e, HostPlane *pl, int n, const HostPlanes &h, ui
             if (!pl[i].src || !pl[i].bytes) continue;
             BV_HIP(e, hipMemcpyAsync(base + off, pl[i].src, pl[i].bytes, hipMemcpyHostToDevice, cs));
             pl[i].dev = base + off;
-            off += up(pl[i].bytes);
+            off += up256(pl[i].bytes);
         }
     }
     return BV_OK;
 }
-// Queue the host->device copies of `n` planes into a fresh staging slot (+ `extra` bytes of device scratch behind them).
-int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engine::StageSlot **slot_out, uint8_t **extra_dev, hipStream_t st) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, StageSlot **slot_out, uint8_t **extra_dev, hipStream_t st) {
     const HostPlanes h = plan_host_planes(pl, n);
-    bv_engine::StageSlot *sl = nullptr;
-    int rc = stage_acquire(e, h.bytes + up(extra), &sl);
+    StageSlot *sl = nullptr;
+    int rc = stage_acquire(e, h.bytes + up256(extra), &sl);
     if (rc != BV_OK) return rc;
     rc = stage_order(e, sl, st);
     if (rc != BV_OK) return rc;
@@ -496,12 +347,30 @@ int stage_host_planes(bv_engine *e, HostPlane *pl, int n, size_t extra, bv_engin
     if (extra_dev) *extra_dev = base + h.bytes;
     return BV_OK;
 }
-}  // namespace
-
-BvEngineView bv_engine_view(bv_engine *e) {
-    return BvEngineView{e->cfg.device, e->cfg.max_sites, e->cfg.max_samples, e->stream, &e->text, &e->bgzf};
+int stage_records(bv_engine *e, HostPlane *pl, int n, size_t S, size_t G, bv_site_result *out, bv_group_result *gout, StageSlot **slot,
+                  bv_site_result **dout, bv_group_result **dgout, hipStream_t st) {
+    const size_t out_b = up256(S * sizeof(bv_site_result)), gout_b = up256(S * G * sizeof(bv_group_result));
+    uint8_t *extra = nullptr;
+    int rc = stage_host_planes(e, pl, n, out_b + gout_b, slot, &extra, st);
+    if (rc != BV_OK) return rc;
+    rc = stage_publish(e, *slot, st);
+    if (rc != BV_OK) return rc;
+    *dout = reinterpret_cast<bv_site_result *>(extra);
+    *dgout = G ? reinterpret_cast<bv_group_result *>(extra + out_b) : nullptr;
+    e->stage_out = *dout; e->stage_gout = *dgout;
+    e->host_out = out; e->host_gout = gout;
+    e->host_out_bytes = S * sizeof(bv_site_result);
+    e->host_gout_bytes = S * G * sizeof(bv_group_result);
+    return BV_OK;
 }
-int bv_engine_fail(bv_engine *e, int code, const std::string &msg) { return fail(e, code, msg); }
+int copy_records_back(bv_engine *e, hipStream_t st) {
+    if (!e->host_out) return BV_OK;
+    BV_HIP(e, hipMemcpyAsync(e->host_out, e->stage_out, e->host_out_bytes, hipMemcpyDeviceToHost, st));
+    if (e->host_gout && e->host_gout_bytes)
+        BV_HIP(e, hipMemcpyAsync(e->host_gout, e->stage_gout, e->host_gout_bytes, hipMemcpyDeviceToHost, st));
+    return BV_OK;
+}
+}  // namespace bv_impl
 
 extern "C" {
 
@@ -665,17 +534,9 @@ int bv_engine_destroy(bv_engine *e) {
         if (sl.copied) (void)hipEventDestroy(sl.copied);
         if (sl.freed) (void)hipEventDestroy(sl.freed);
     }
-    for (int i = 0; i < bv_engine::kDescRing; ++i) {
-        if (e->h_desc[i]) (void)hipHostFree(e->h_desc[i]);
-        if (e->d_desc[i]) (void)hipFree(e->d_desc[i]);
-        if (e->ev_desc[i]) (void)hipEventDestroy(e->ev_desc[i]);
-    }
+    tile_job_free(e->tile);
     if (e->d_gid_round) (void)hipFree(e->d_gid_round);
     if (e->d_gout_round) (void)hipFree(e->d_gout_round);
-    if (e->tile_state) (void)hipFree(e->tile_state);
-    if (e->tile_maxr) (void)hipFree(e->tile_maxr);
-    if (e->tile_ovf) (void)hipFree(e->tile_ovf);
-    if (e->j_buf) (void)hipFree(e->j_buf);
     for (hipStream_t cs : e->copy_stream)
         if (cs) (void)hipStreamSynchronize(cs);
     for (hipStream_t cs : e->copy_stream)
@@ -685,15 +546,16 @@ int bv_engine_destroy(bv_engine *e) {
     return BV_OK;
 }
 
+}  // extern "C"
+
 // The two passes over device-resident planes + the copies back (records to a host caller, counters).
 //
 // (Round 3 also ran short-row batches as a software pipeline of chunks over two streams -- the solve kernels of chunk c under the
 // streaming kernel of chunk c + 1.  Measured a loss at every size (beside a streaming kernel the solve kernels get one
 // workgroup per CU and run 3 x longer, the streaming kernel slows by 50-70 %): removed; docs/history/DESIGN_round3.md 4.2b.)
-static int launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, const uint8_t *mq, const uint16_t *rp,
-                         const uint8_t *refb, const uint8_t *gid, size_t P, uint32_t n_sites, uint32_t n_samples, uint32_t n_groups,
-                         bv_site_result *dout, bv_group_result *dgout, hipStream_t st, const BvChain *chain = nullptr /* device */,
-                         bool chain_cat = false /* chained short rows: refb / dout are contiguous copies */, uint32_t layout = 0 /* BV_SLAB_* */) {
+int bv_impl::launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, const uint8_t *mq, const uint16_t *rp, const uint8_t *refb,
+                           const uint8_t *gid, size_t P, uint32_t n_sites, uint32_t n_samples, uint32_t n_groups, bv_site_result *dout,
+                           bv_group_result *dgout, hipStream_t st, const BvChain *chain, bool chain_cat, uint32_t layout) {
     const uint32_t rpr_tag = (layout & BV_SLAB_RPR_TAGGED) && rp != nullptr ? 1u : 0u;
     const size_t S = n_sites, G = n_groups;
     // The group kernels hold one (base, phred) histogram per group in LDS and are built for at most BV_GROUPS_PER_ROUND of them;
@@ -704,19 +566,9 @@ static int launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, cons
     if (n_rounds > 1 && chain != nullptr) return fail(e, BV_ERR_INVALID_ARG, "launch_passes: more than 32 pop-groups do not chain");
     if (G && chain == nullptr) BV_HIP(e, hipMemsetAsync(dgout, 0, S * G * sizeof(bv_group_result), st));  // (chained: per segment, by the caller)
     if (n_rounds > 1) {
-        const size_t gb = (((size_t)n_samples + 255) & ~(size_t)255) + 256, ob = S * Gr * sizeof(bv_group_result);
-        if (gb > e->d_gid_round_bytes) {
-            if (e->d_gid_round) BV_HIP(e, hipFree(e->d_gid_round));
-            e->d_gid_round = nullptr; e->d_gid_round_bytes = 0;
-            BV_HIP(e, hipMalloc(&e->d_gid_round, gb));
-            e->d_gid_round_bytes = gb;
-        }
-        if (ob > e->d_gout_round_bytes) {
-            if (e->d_gout_round) BV_HIP(e, hipFree(e->d_gout_round));
-            e->d_gout_round = nullptr; e->d_gout_round_bytes = 0;
-            BV_HIP(e, hipMalloc(&e->d_gout_round, ob));
-            e->d_gout_round_bytes = ob;
-        }
+        int rc = grow_device(e, &e->d_gid_round, &e->d_gid_round_bytes, up256(n_samples) + 256);
+        if (rc == BV_OK) rc = grow_device(e, &e->d_gout_round, &e->d_gout_round_bytes, S * Gr * sizeof(bv_group_result));
+        if (rc != BV_OK) return rc;
     }
 
     // Per-pass timing: four event records per launch (start, end of the streaming kernel, end of pass 1, end of pass 2).  They are
@@ -774,12 +626,8 @@ static int launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, cons
         a2.gitems = e->d_gitems; a2.gitem_cap = e->gitem_cap;
         // short rows: the group plane as the streaming group tally wants it
         const size_t n16 = ((size_t)n_samples + 15) & ~(size_t)15;
-        if (n16 > e->d_gidp_bytes) {
-            if (e->d_gidp) BV_HIP(e, hipFree(e->d_gidp));
-            e->d_gidp = nullptr; e->d_gidp_bytes = 0;
-            BV_HIP(e, hipMalloc(&e->d_gidp, n16 + 256));
-            e->d_gidp_bytes = n16;
-        }
+        const int rc = grow_device(e, &e->d_gidp, &e->d_gidp_bytes, n16 + 256);
+        if (rc != BV_OK) return rc;
         a2.gidp = e->d_gidp;
         // the group plane as the perm-form tallies read it (short rows: bv_p2g_stream_kernel; long rows: bv_p2_fast_sweep)
         // (several rounds of groups: prepared per round, below)
@@ -906,14 +754,13 @@ static int launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, cons
 
     if (rotate) e->ctr_mirror_stale = true;  // mirrored by bv_engine_wait
     else BV_HIP(e, hipMemcpyAsync(e->h_counters, e->d_counters, sizeof(uint32_t) * BV_CTR_WORDS * bv_engine::kCtrBlocks, hipMemcpyDeviceToHost, st));
-    if (e->host_out) {
-        BV_HIP(e, hipMemcpyAsync(e->host_out, e->stage_out, e->host_out_bytes, hipMemcpyDeviceToHost, st));
-        if (e->host_gout && e->host_gout_bytes)
-            BV_HIP(e, hipMemcpyAsync(e->host_gout, e->stage_gout, e->host_gout_bytes, hipMemcpyDeviceToHost, st));
-    }
+    const int rc = copy_records_back(e, st);
+    if (rc != BV_OK) return rc;
     e->submitted = true;
     return mark_done(e, st);
 }
+
+extern "C" {
 
 int bv_engine_submit(bv_engine *e, const bv_slab *slab, bv_site_result *out, bv_group_result *gout, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_submit: null engine");
@@ -983,27 +830,16 @@ int bv_engine_submit(bv_engine *e, const bv_slab *slab, bv_site_result *out, bv_
     bv_site_result *dout = out;
     bv_group_result *dgout = gout;
     const size_t S = slab->n_sites, P = slab->pitch, G = slab->n_groups;
-    bv_engine::StageSlot *slot = nullptr;
+    StageSlot *slot = nullptr;
     if (slab->mem_kind == BV_MEM_HOST) {
         // host planes -> a staging slot, copied by the copy stream (under the kernels of the previous submit)
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
         HostPlane pl[5] = {{bs, S * P, nullptr}, {q, S * P, nullptr}, {mq, mq ? S * P : 0, nullptr},
                            {rp, rp ? S * P * 2 : 0, nullptr}, {refb, S, nullptr}};
-        const size_t out_b = up(S * sizeof(bv_site_result)), gout_b = up(S * G * sizeof(bv_group_result));
-        uint8_t *extra = nullptr;
-        int rc = stage_host_planes(e, pl, 5, out_b + gout_b, &slot, &extra, st);
-        if (rc != BV_OK) return rc;
-        rc = stage_publish(e, slot, st);
+        const int rc = stage_records(e, pl, 5, S, G, out, gout, &slot, &dout, &dgout, st);
         if (rc != BV_OK) return rc;
         bs = pl[0].dev; q = pl[1].dev; mq = pl[2].dev;
         rp = reinterpret_cast<const uint16_t *>(pl[3].dev);
         refb = pl[4].dev;
-        dout = reinterpret_cast<bv_site_result *>(extra);
-        dgout = G ? reinterpret_cast<bv_group_result *>(extra + out_b) : nullptr;
-        e->stage_out = dout; e->stage_gout = dgout;
-        e->host_out = out; e->host_gout = gout;
-        e->host_out_bytes = S * sizeof(bv_site_result);
-        e->host_gout_bytes = S * G * sizeof(bv_group_result);
     } else {
         e->host_out = nullptr; e->host_gout = nullptr;
     }
@@ -1136,636 +972,6 @@ int bv_engine_submit_many_g(bv_engine *e, uint32_t n_slabs, const bv_slab *slabs
     return BV_OK;
 }
 
-// ---------------------------------------------------------------- sample-axis tile mode
-int bv_engine_tiles_begin(bv_engine *e, uint32_t n_sites, uint32_t n_samples_total, uint32_t n_groups, int with_ranks) {
-    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_tiles_begin: null engine");
-    if (n_sites == 0 || n_samples_total == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_begin: empty job");
-    if (n_sites > e->cfg.max_sites) return fail(e, BV_ERR_TOO_LARGE, "bv_engine_tiles_begin: n_sites exceeds cfg.max_sites");
-    if (n_groups > BV_MAX_GROUPS) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_begin: n_groups exceeds BV_MAX_GROUPS");
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    // The job's state is cleared ON THE ENGINE'S STREAM, ordered like a submit (use_stream / mark_done): a tile added on another
-    // stream waits for it.  (Until round 6 these were hipMemset calls on the null stream, which nothing orders against the engine's
-    // non-blocking stream: a tally kernel could meet the state of a fresh allocation -- once in the round-6 campaigns, 8,037
-    // mismatching fields in one 4,096-site job, gone on the re-run.)
-    hipStream_t st0 = e->stream;
-    {
-        int rc = use_stream(e, st0);
-        if (rc != BV_OK) return rc;
-    }
-    e->tile_join = false;
-    e->tile_layout = 0; e->tile_layout_set = false; e->j_filled = false;
-    if (!(e->cfg.flags & BV_FLAG_TILE_STATE)) {
-        // joined rows: [n_sites][pitch] planes resident in HBM, if they fit next to what is already there
-        const size_t pitch = ((size_t)n_samples_total + 255) & ~(size_t)255, plane = (size_t)n_sites * pitch;
-        const size_t o_q = plane, o_mq = 2 * plane, o_rp = o_mq + (with_ranks ? plane : 0), o_gid = o_rp + (with_ranks ? 2 * plane : 0),
-                     need = o_gid + pitch;
-        bool ok = need <= e->j_bytes;
-        if (!ok) {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= (free_b + e->j_bytes) / 10 * 9) {
-                if (e->j_buf) BV_HIP(e, hipFree(e->j_buf));
-                e->j_buf = nullptr;
-                e->j_bytes = 0;
-                if (hipMalloc(&e->j_buf, need) == hipSuccess) {
-                    e->j_bytes = need;
-                    ok = true;
-                } else {
-                    (void)hipGetLastError();
-                    e->j_buf = nullptr;
-                }
-            }
-        }
-        if (ok) {
-            e->j_pitch = pitch; e->j_o_q = o_q; e->j_o_mq = o_mq; e->j_o_rp = o_rp; e->j_o_gid = o_gid;
-            // (tiles fill the columns from the left in the order they are added; what a job leaves unfilled is set to 'N' at
-            // finish -- not the whole plane here: 8.6 GB of memset for 8 Ki sites x 1 M samples)
-            BV_HIP(e, hipMemsetAsync(e->j_buf + o_gid, 0xFF, pitch, st0));   // no pop-group
-            e->tile_sites = n_sites; e->tile_groups = n_groups; e->tile_stride = 0;
-            e->tile_samples_total = n_samples_total; e->tile_samples_seen = 0;
-            e->tile_ranks = with_ranks != 0;
-            e->tile_join = true;
-            e->tile_open = true;
-            return mark_done(e, st0);
-        }
-    }
-    if (n_groups > BV_GROUPS_PER_ROUND)
-        return fail(e, BV_ERR_TOO_LARGE, "bv_engine_tiles_begin: more than 32 pop-groups need the joined-rows realisation (2 KiB of "
-                                         "per-site state per group otherwise), and the joined planes of this job do not fit the device");
-    // H1 2048 + Hm 1024 + Hr 4 x W + Hg 512/group (bv_tiles.hip); W = 1024 ranks, or what the caller announced
-    const uint32_t rank_win = with_ranks > 1 ? (uint32_t)((with_ranks + 1023) / 1024 * 1024) : 1024u;
-    const uint32_t hg_off = 3072u + 4u * rank_win, ord_off = hg_off + n_groups * 512u, stride = ord_off + (1u + n_groups) * BV_TS_ORD_WORDS;
-    e->tile_rank_win = rank_win; e->tile_hg_off = hg_off; e->tile_ord_off = ord_off;
-    if (!e->tile_ovf) BV_HIP(e, hipMalloc(&e->tile_ovf, sizeof(uint32_t) * (2u + 2u * (size_t)bv_engine::kOvfCap)));
-    BV_HIP(e, hipMemsetAsync(e->tile_ovf, 0, 2 * sizeof(uint32_t), st0));
-    const size_t bytes = (size_t)n_sites * stride * sizeof(uint32_t), mbytes = (size_t)n_sites * sizeof(uint32_t);
-    if (bytes > e->tile_state_bytes) {
-        if (e->tile_state) BV_HIP(e, hipFree(e->tile_state));
-        e->tile_state = nullptr;
-        e->tile_state_bytes = 0;
-        BV_HIP(e, hipMalloc(&e->tile_state, bytes));
-        e->tile_state_bytes = bytes;
-    }
-    if (mbytes > e->tile_maxr_bytes) {
-        if (e->tile_maxr) BV_HIP(e, hipFree(e->tile_maxr));
-        e->tile_maxr = nullptr;
-        e->tile_maxr_bytes = 0;
-        BV_HIP(e, hipMalloc(&e->tile_maxr, mbytes));
-        e->tile_maxr_bytes = mbytes;
-    }
-    BV_HIP(e, hipMemsetAsync(e->tile_state, 0, bytes, st0));
-    BV_HIP(e, hipMemsetAsync(e->tile_maxr, 0, mbytes, st0));
-    e->tile_sites = n_sites; e->tile_groups = n_groups; e->tile_stride = stride;
-    e->tile_samples_total = n_samples_total; e->tile_samples_seen = 0;
-    e->tile_ranks = with_ranks != 0;
-    e->tile_open = true;
-    return mark_done(e, st0);
-}
-
-int bv_tile_packed_layout(uint32_t n_sites, uint32_t width, int with_ranks, int with_groups, uint64_t *pitch,
-                          uint64_t offsets[5], uint64_t *total_bytes) {
-    if (!n_sites || !width || !pitch || !offsets || !total_bytes)
-        return fail(nullptr, BV_ERR_INVALID_ARG, "bv_tile_packed_layout: bad argument");
-    auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t P = ((uint64_t)width + 15) / 16 * 16, plane = up((uint64_t)n_sites * P);
-    uint64_t at = 0;
-    offsets[0] = at; at += plane;
-    offsets[1] = at; at += plane;
-    offsets[2] = with_ranks ? at : 0; at += with_ranks ? plane : 0;
-    offsets[3] = with_ranks ? at : 0; at += with_ranks ? up((uint64_t)n_sites * P * 2) : 0;
-    offsets[4] = with_groups ? at : 0; at += with_groups ? up(P) : 0;
-    *pitch = P;
-    *total_bytes = at;
-    return BV_OK;
-}
-
-int bv_engine_tiles_add(bv_engine *e, const bv_slab *t, void *stream_) {
-    if (!e || !t) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: null argument");
-    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: call bv_engine_tiles_begin first");
-    if (t->n_sites != e->tile_sites) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: tile n_sites differs from the job's");
-    if (t->n_samples == 0 || t->pitch < t->n_samples || (t->pitch & 15ull) || !t->base_strand || !t->qual)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: bad tile geometry or missing planes");
-    if (e->tile_ranks && (!t->mapq || !t->rpr)) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: job was opened with rank planes");
-    if (e->tile_groups && !t->group_id) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: job has groups, tile has no group_id");
-    if ((uint64_t)e->tile_samples_seen + t->n_samples > e->tile_samples_total)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: more samples than announced");
-    if ((t->layout & ~BV_SLAB_RPR_TAGGED) || t->reserved_ || (e->tile_layout_set && t->layout != e->tile_layout))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add: every tile of a job must have the same bv_slab.layout (known bits only)");
-    e->tile_layout = t->layout; e->tile_layout_set = true;
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    const uint8_t *bs = t->base_strand, *q = t->qual, *mq = e->tile_ranks ? t->mapq : nullptr, *gid = e->tile_groups ? t->group_id : nullptr;
-    const uint16_t *rp = e->tile_ranks ? t->rpr : nullptr;
-    const size_t S = t->n_sites, P = t->pitch;
-    bv_engine::StageSlot *slot = nullptr;
-    if (t->mem_kind == BV_MEM_HOST) {
-        HostPlane pl[5] = {{bs, S * P, nullptr}, {q, S * P, nullptr}, {mq, mq ? S * P : 0, nullptr},
-                           {rp, rp ? S * P * 2 : 0, nullptr}, {gid, gid ? (size_t)t->n_samples : 0, nullptr}};
-        int rc = stage_host_planes(e, pl, 5, 0, &slot, nullptr, st);
-        if (rc != BV_OK) return rc;
-        rc = stage_publish(e, slot, st);
-        if (rc != BV_OK) return rc;
-        bs = pl[0].dev; q = pl[1].dev; mq = pl[2].dev;
-        rp = reinterpret_cast<const uint16_t *>(pl[3].dev);
-        gid = pl[4].dev;
-    }
-    if (e->tile_join) {
-        const uint64_t lo = e->tile_samples_seen, JP = e->j_pitch;
-        const uint32_t w = t->n_samples, rows = t->n_sites;
-        BvTileScatterArgs sc;
-        sc.max_rows = rows;
-        sc.n_planes = 0;
-        auto plane = [&](uint8_t *dst, const uint8_t *src, uint64_t scale, uint32_t n_rows) {
-            BvTileScatterPlane &p = sc.plane[sc.n_planes++];
-            p.dst = dst; p.src = src; p.dst_pitch = scale * JP; p.src_pitch = scale * P; p.col_off = scale * lo;
-            p.width_bytes = (uint32_t)(scale * w); p.n_rows = n_rows;
-        };
-        plane(e->j_buf, bs, 1, rows);
-        plane(e->j_buf + e->j_o_q, q, 1, rows);
-        if (mq) plane(e->j_buf + e->j_o_mq, mq, 1, rows);
-        if (rp) plane(e->j_buf + e->j_o_rp, reinterpret_cast<const uint8_t *>(rp), 2, rows);
-        if (gid) plane(e->j_buf + e->j_o_gid, gid, 1, 1);  // one row: the tile's group ids, in the same launch
-        bv_launch_tile_scatter(sc, st);
-        BV_HIP(e, hipGetLastError());
-        if (slot) {
-            int rc = stage_release(e, slot, st);
-            if (rc != BV_OK) return rc;
-        }
-        e->tile_samples_seen += t->n_samples;
-        return mark_done(e, st);
-    }
-    BvTileArgs a;
-    a.bs = bs; a.q = q; a.mapq = mq; a.rpr = rp; a.group_id = gid; a.pitch = P; a.n_sites = t->n_sites;
-    a.width = t->n_samples; a.n_groups = e->tile_groups; a.stride = e->tile_stride; a.state = e->tile_state;
-    a.rank_win = e->tile_rank_win; a.hg_off = e->tile_hg_off;
-    a.maxr = e->tile_maxr;
-    a.ord_off = e->tile_ord_off; a.col0 = e->tile_samples_seen; a.ovf = e->tile_ovf; a.ovf_cap = bv_engine::kOvfCap;
-    a.rpr_tag = (e->tile_layout & BV_SLAB_RPR_TAGGED) ? 1u : 0u;
-    bv_launch_tile_tally(a, st);
-    BV_HIP(e, hipGetLastError());
-    if (slot) {
-        int rc = stage_release(e, slot, st);
-        if (rc != BV_OK) return rc;
-    }
-    e->tile_samples_seen += t->n_samples;
-    return mark_done(e, st);
-}
-
-// A tile as its covered cells only (include/basevar_amd.h): scattered into the joined planes, which hold "uncovered" wherever no
-// tile has delivered yet (filled once, when the job's first packed tile arrives), or added to the per-site tallies entry by entry.
-int bv_sparse_tile_packed_layout(uint32_t n_sites, uint32_t n_entries, uint32_t width, int with_ranks, int with_groups,
-                                 uint64_t offsets[7], uint64_t *total_bytes) {
-    if (!n_sites || !width || !offsets || !total_bytes) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_sparse_tile_packed_layout: bad argument");
-    auto up = [](uint64_t x) { return (x + 255) & ~(uint64_t)255; };
-    const uint64_t E = n_entries ? n_entries : 1u;
-    uint64_t at = 0;
-    offsets[0] = at; at += up(4ull * ((uint64_t)n_sites + 1));
-    offsets[1] = at; at += up(2 * E);
-    offsets[2] = at; at += up(E);
-    offsets[3] = at; at += up(E);
-    offsets[4] = with_ranks ? at : 0; at += with_ranks ? up(E) : 0;
-    offsets[5] = with_ranks ? at : 0; at += with_ranks ? up(2 * E) : 0;
-    offsets[6] = with_groups ? at : 0; at += with_groups ? up(width) : 0;
-    *total_bytes = at;
-    return BV_OK;
-}
-
-int bv_engine_tiles_add_sparse(bv_engine *e, const bv_sparse_tile *t, void *stream_) {
-    if (!e || !t) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: null argument");
-    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: call bv_engine_tiles_begin first");
-    if (t->n_sites != e->tile_sites) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: tile n_sites differs from the job's");
-    if (t->n_samples == 0 || t->n_samples > 65536u || !t->row_start || (t->n_entries && (!t->sample || !t->base_strand || !t->qual)))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: bad tile geometry (at most 65,536 samples per tile) or missing arrays");
-    if (e->tile_ranks && t->n_entries && (!t->mapq || !t->rpr)) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: job was opened with rank planes");
-    if (e->tile_groups && !t->group_id) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: job has groups, tile has no group_id");
-    if ((uint64_t)e->tile_samples_seen + t->n_samples > e->tile_samples_total)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: more samples than announced");
-    if ((t->layout & ~BV_SLAB_RPR_TAGGED) || (e->tile_layout_set && t->layout != e->tile_layout))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse: every tile of a job must have the same layout (known bits only)");
-    e->tile_layout = t->layout; e->tile_layout_set = true;
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    const size_t S = t->n_sites, E = t->n_entries;
-    const bool ranks = e->tile_ranks;
-    const uint32_t *row_start = t->row_start;
-    const uint16_t *smp = t->sample, *rp = ranks ? t->rpr : nullptr;
-    const uint8_t *bs = t->base_strand, *q = t->qual, *mq = ranks ? t->mapq : nullptr, *gid = e->tile_groups ? t->group_id : nullptr;
-    bv_engine::StageSlot *slot = nullptr;
-    if (t->mem_kind == BV_MEM_HOST) {
-        HostPlane pl[7] = {{row_start, 4 * (S + 1), nullptr}, {smp, 2 * E, nullptr}, {bs, E, nullptr}, {q, E, nullptr}, {mq, mq ? E : 0, nullptr},
-                           {rp, rp ? 2 * E : 0, nullptr}, {gid, gid ? (size_t)t->n_samples : 0, nullptr}};
-        int rc = stage_host_planes(e, pl, 7, 0, &slot, nullptr, st);
-        if (rc != BV_OK) return rc;
-        rc = stage_publish(e, slot, st);
-        if (rc != BV_OK) return rc;
-        row_start = reinterpret_cast<const uint32_t *>(pl[0].dev); smp = reinterpret_cast<const uint16_t *>(pl[1].dev);
-        bs = pl[2].dev; q = pl[3].dev; mq = pl[4].dev; rp = reinterpret_cast<const uint16_t *>(pl[5].dev); gid = pl[6].dev;
-    }
-    BvSparseTileArgs a{};
-    a.row_start = row_start; a.sample = smp; a.call = bs; a.phred = q; a.mapq = E ? mq : nullptr; a.rank = rp;
-    a.n_sites = t->n_sites; a.width = t->n_samples; a.n_entries = t->n_entries;
-    a.rpr_tag = (e->tile_layout & BV_SLAB_RPR_TAGGED) ? 1u : 0u;
-    a.col0 = e->tile_samples_seen;
-    if (e->tile_join) {
-        uint8_t *jb = e->j_buf, *jq = e->j_buf + e->j_o_q, *jm = ranks ? e->j_buf + e->j_o_mq : nullptr;
-        uint16_t *jr = ranks ? reinterpret_cast<uint16_t *>(e->j_buf + e->j_o_rp) : nullptr;
-        if (!e->j_filled) {
-            // every column that has not been delivered yet: "nobody covered" (once per job; dense tiles that follow overwrite theirs)
-            if (e->tile_samples_seen == 0) {
-                bv_launch_tile_fill_uncovered(jb, jq, jm, jr, (uint64_t)e->tile_sites * e->j_pitch, a.rpr_tag, st);
-                BV_HIP(e, hipGetLastError());
-            } else {
-                const size_t lo = e->tile_samples_seen, w = e->tile_samples_total - lo;
-                BV_HIP(e, hipMemset2DAsync(jb + lo, e->j_pitch, 0x08, w, S, st));
-                BV_HIP(e, hipMemset2DAsync(jq + lo, e->j_pitch, 0, w, S, st));
-                if (ranks) {
-                    BV_HIP(e, hipMemset2DAsync(jm + lo, e->j_pitch, 0, w, S, st));
-                    BV_HIP(e, hipMemset2DAsync(reinterpret_cast<uint8_t *>(jr) + 2 * lo, 2 * e->j_pitch, a.rpr_tag ? 0x80 : 0, 2 * w, S, st));
-                }
-            }
-            e->j_filled = true;
-        }
-        a.bs = jb; a.q = jq; a.mq = jm; a.rp = jr; a.pitch = e->j_pitch;
-        if (E) {
-            bv_launch_tile_sparse_scatter(a, st);
-            BV_HIP(e, hipGetLastError());
-        }
-        if (gid) BV_HIP(e, hipMemcpyAsync(e->j_buf + e->j_o_gid + e->tile_samples_seen, gid, t->n_samples, hipMemcpyDeviceToDevice, st));
-    } else {
-        a.group_id = gid; a.n_groups = e->tile_groups; a.stride = e->tile_stride; a.rank_win = e->tile_rank_win; a.hg_off = e->tile_hg_off;
-        a.ord_off = e->tile_ord_off; a.ovf_cap = bv_engine::kOvfCap; a.state = e->tile_state; a.maxr = e->tile_maxr; a.ovf = e->tile_ovf;
-        if (E) {
-            bv_launch_tile_sparse_tally(a, st);
-            BV_HIP(e, hipGetLastError());
-        }
-    }
-    if (slot) {
-        int rc = stage_release(e, slot, st);
-        if (rc != BV_OK) return rc;
-    }
-    e->tile_samples_seen += t->n_samples;
-    return mark_done(e, st);
-}
-
-// Many packed tiles per call (include/basevar_amd.h): the records of n_tiles calls of bv_engine_tiles_add_sparse, but the tiles go
-// in GROUPS -- at most BV_TILE_MANY_MAX tiles and kSparseManyStage bytes of host tiles -- and a group costs one staging slot (one
-// copy per host tile into it), one descriptor table and ONE launch, where a tile cost a slot, two events, two waits and a launch of
-// its own (~48 us per 200-sample tile of a 16,384-site job, round 6).  64 MiB: ~33 such tiles (1.9 MB each) per group, so the
-// copies of the next group still run under the kernel of this one, and the four slots of the staging ring hold at most 256 MiB.
-static constexpr size_t kSparseManyStage = (size_t)64 << 20;
-int bv_engine_tiles_add_sparse_many(bv_engine *e, uint32_t n_tiles, const bv_sparse_tile *tiles, void *stream_) {
-    if (!e || !tiles || n_tiles == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: null / empty argument");
-    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: call bv_engine_tiles_begin first");
-    // every check of bv_engine_tiles_add_sparse, for every tile, before anything changes: a refused call leaves the job as it was
-    uint64_t seen = e->tile_samples_seen;
-    for (uint32_t k = 0; k < n_tiles; ++k) {
-        const bv_sparse_tile &t = tiles[k];
-        auto bad = [&](const char *why) {
-            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_sparse_many: tile " + std::to_string(k) + ": " + why);
-        };
-        if (t.n_sites != e->tile_sites) return bad("n_sites differs from the job's");
-        if (t.n_samples == 0 || t.n_samples > 65536u || !t.row_start || (t.n_entries && (!t.sample || !t.base_strand || !t.qual)))
-            return bad("bad tile geometry (at most 65,536 samples per tile) or missing arrays");
-        if (e->tile_ranks && t.n_entries && (!t.mapq || !t.rpr)) return bad("job was opened with rank planes");
-        if (e->tile_groups && !t.group_id) return bad("job has groups, tile has no group_id");
-        seen += t.n_samples;
-        if (seen > e->tile_samples_total) return bad("more samples than announced");
-        if ((t.layout & ~BV_SLAB_RPR_TAGGED) || t.layout != tiles[0].layout || (e->tile_layout_set && t.layout != e->tile_layout))
-            return bad("every tile of a job must have the same layout (known bits only)");
-        if (t.mem_kind == BV_MEM_HOST) {  // the kernels trust row_start: on the host it costs a pass over n_sites + 1 words
-            const uint32_t *rs = t.row_start;
-            bool ok = rs[0] == 0 && rs[t.n_sites] == t.n_entries;
-            for (uint32_t s = 0; s < t.n_sites && ok; ++s) ok = rs[s] <= rs[s + 1];
-            if (!ok) return bad("row_start must start at 0, never decrease and end at n_entries");
-        }
-    }
-    e->tile_layout = tiles[0].layout; e->tile_layout_set = true;
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    const size_t S = e->tile_sites;
-    const bool ranks = e->tile_ranks, groups = e->tile_groups != 0;
-    BvSparseTileArgs a{};
-    a.n_sites = e->tile_sites;
-    a.rpr_tag = (e->tile_layout & BV_SLAB_RPR_TAGGED) ? 1u : 0u;
-    if (e->tile_join) {
-        uint8_t *jb = e->j_buf, *jq = e->j_buf + e->j_o_q, *jm = ranks ? e->j_buf + e->j_o_mq : nullptr;
-        uint16_t *jr = ranks ? reinterpret_cast<uint16_t *>(e->j_buf + e->j_o_rp) : nullptr;
-        if (!e->j_filled) {  // as bv_engine_tiles_add_sparse: the columns not delivered yet say "nobody covered", once per job
-            if (e->tile_samples_seen == 0) {
-                bv_launch_tile_fill_uncovered(jb, jq, jm, jr, (uint64_t)e->tile_sites * e->j_pitch, a.rpr_tag, st);
-                BV_HIP(e, hipGetLastError());
-            } else {
-                const size_t lo = e->tile_samples_seen, w = e->tile_samples_total - lo;
-                BV_HIP(e, hipMemset2DAsync(jb + lo, e->j_pitch, 0x08, w, S, st));
-                BV_HIP(e, hipMemset2DAsync(jq + lo, e->j_pitch, 0, w, S, st));
-                if (ranks) {
-                    BV_HIP(e, hipMemset2DAsync(jm + lo, e->j_pitch, 0, w, S, st));
-                    BV_HIP(e, hipMemset2DAsync(reinterpret_cast<uint8_t *>(jr) + 2 * lo, 2 * e->j_pitch, a.rpr_tag ? 0x80 : 0, 2 * w, S, st));
-                }
-            }
-            e->j_filled = true;
-        }
-        a.bs = jb; a.q = jq; a.mq = jm; a.rp = jr; a.pitch = e->j_pitch;
-    } else {
-        a.n_groups = e->tile_groups; a.stride = e->tile_stride; a.rank_win = e->tile_rank_win; a.hg_off = e->tile_hg_off;
-        a.ord_off = e->tile_ord_off; a.ovf_cap = bv_engine::kOvfCap; a.state = e->tile_state; a.maxr = e->tile_maxr; a.ovf = e->tile_ovf;
-    }
-    uint8_t *jgid = e->tile_join && groups ? e->j_buf + e->j_o_gid : nullptr;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    struct Staged {
-        HostPlane pl[7];
-        HostPlanes h;
-    };
-    std::vector<Staged> plan(n_tiles < (uint32_t)BV_TILE_MANY_MAX ? n_tiles : (uint32_t)BV_TILE_MANY_MAX);
-    constexpr size_t kDescBytes = sizeof(BvTileScatterPlane) * 5 * BV_TILE_MANY_MAX;  // the ring's tables (bv_engine_tiles_add_many)
-    static_assert(sizeof(BvSparseTileDesc) * BV_TILE_MANY_MAX <= kDescBytes, "a group's descriptors must fit one table of the ring");
-    for (uint32_t k0 = 0, k1 = 0; k0 < n_tiles; k0 = k1) {
-        // the group [k0, k1): its host tiles' staging bytes
-        size_t bytes = 0;
-        for (k1 = k0; k1 < n_tiles && k1 - k0 < (uint32_t)BV_TILE_MANY_MAX; ++k1) {
-            const bv_sparse_tile &t = tiles[k1];
-            Staged &p = plan[k1 - k0];
-            p.h = HostPlanes{};
-            if (t.mem_kind == BV_MEM_HOST) {
-                const size_t E = t.n_entries;
-                const uint16_t *rp = ranks ? t.rpr : nullptr;
-                const uint8_t *mq = ranks ? t.mapq : nullptr, *gid = groups ? t.group_id : nullptr;
-                HostPlane pl[7] = {{t.row_start, 4 * (S + 1), nullptr}, {t.sample, 2 * E, nullptr}, {t.base_strand, E, nullptr}, {t.qual, E, nullptr},
-                                   {mq, mq ? E : 0, nullptr}, {rp, rp ? 2 * E : 0, nullptr}, {gid, gid ? (size_t)t.n_samples : 0, nullptr}};
-                std::copy(pl, pl + 7, p.pl);
-                p.h = plan_host_planes(p.pl, 7);
-            }
-            if (k1 > k0 && bytes + p.h.bytes > kSparseManyStage) break;  // (a group holds at least one tile, however large)
-            bytes += p.h.bytes;
-        }
-        const uint32_t nk = k1 - k0;
-        bv_engine::StageSlot *slot = nullptr;
-        if (bytes) {
-            int rc = stage_acquire(e, bytes, &slot);
-            if (rc != BV_OK) return rc;
-            rc = stage_order(e, slot, st);
-            if (rc != BV_OK) return rc;
-            uint8_t *base = static_cast<uint8_t *>(slot->buf);
-            size_t off = 0;
-            for (uint32_t i = 0; i < nk; ++i) {
-                Staged &p = plan[i];
-                if (!p.h.bytes) continue;
-                rc = copy_host_planes(e, p.pl, 7, p.h, base + off, slot->cs);
-                if (rc != BV_OK) return rc;
-                off += up(p.h.bytes);
-            }
-        }
-        // the descriptor table: pinned, then one copy on `st` (ahead of the wait for the staging copies)
-        const int ds = (int)(e->desc_next++ % bv_engine::kDescRing);
-        if (!e->h_desc[ds]) {
-            BV_HIP(e, hipHostMalloc(&e->h_desc[ds], kDescBytes));
-            BV_HIP(e, hipMalloc(&e->d_desc[ds], kDescBytes));
-            BV_HIP(e, hipEventCreateWithFlags(&e->ev_desc[ds], hipEventDisableTiming));
-        }
-        if (e->desc_used[ds]) BV_HIP(e, hipEventSynchronize(e->ev_desc[ds]));  // the copy that last read this pinned table
-        BvSparseTileDesc *tab = reinterpret_cast<BvSparseTileDesc *>(e->h_desc[ds]);
-        uint64_t col = e->tile_samples_seen;
-        for (uint32_t i = 0; i < nk; ++i) {
-            const bv_sparse_tile &t = tiles[k0 + i];
-            BvSparseTileDesc &d = tab[i];
-            if (plan[i].h.bytes) {
-                const HostPlane *pl = plan[i].pl;
-                d.row_start = reinterpret_cast<const uint32_t *>(pl[0].dev); d.sample = reinterpret_cast<const uint16_t *>(pl[1].dev);
-                d.call = pl[2].dev; d.phred = pl[3].dev; d.mapq = pl[4].dev; d.rank = reinterpret_cast<const uint16_t *>(pl[5].dev);
-                d.group_id = pl[6].dev;
-            } else {
-                d.row_start = t.row_start; d.sample = t.sample; d.call = t.base_strand; d.phred = t.qual;
-                d.mapq = ranks ? t.mapq : nullptr; d.rank = ranks ? t.rpr : nullptr; d.group_id = groups ? t.group_id : nullptr;
-            }
-            if (!t.n_entries) d.mapq = nullptr;  // (as bv_engine_tiles_add_sparse: an empty tile reads no arrays but row_start)
-            d.col0 = col; d.width = t.n_samples; d.n_entries = t.n_entries;
-            col += t.n_samples;
-        }
-        BV_HIP(e, hipMemcpyAsync(e->d_desc[ds], tab, sizeof(BvSparseTileDesc) * nk, hipMemcpyHostToDevice, st));
-        BV_HIP(e, hipEventRecord(e->ev_desc[ds], st));
-        e->desc_used[ds] = true;
-        if (slot) {
-            int rc = stage_publish(e, slot, st);
-            if (rc != BV_OK) return rc;
-        }
-        const BvSparseTileDesc *dtab = reinterpret_cast<const BvSparseTileDesc *>(e->d_desc[ds]);
-        if (e->tile_join) bv_launch_tile_sparse_scatter_many(a, dtab, nk, jgid, st);
-        else bv_launch_tile_sparse_tally_many(a, dtab, nk, st);
-        BV_HIP(e, hipGetLastError());
-        if (slot) {
-            int rc = stage_release(e, slot, st);
-            if (rc != BV_OK) return rc;
-        }
-        e->tile_samples_seen = (uint32_t)col;
-    }
-    return mark_done(e, st);
-}
-
-// Several tiles at once.  Device-resident tiles of a joined-rows job go to their columns in ONE launch per <= 256 tiles
-// (descriptor table in device memory); anything else -- host tiles, the per-site-tally realisation -- is added tile by tile.
-int bv_engine_tiles_add_many(bv_engine *e, uint32_t n_tiles, const bv_slab *tiles, void *stream_) {
-    if (!e || !tiles || n_tiles == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: null / empty argument");
-    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: call bv_engine_tiles_begin first");
-    bool one_launch = e->tile_join;
-    uint64_t seen = e->tile_samples_seen;
-    for (uint32_t k = 0; k < n_tiles; ++k) {  // the checks of bv_engine_tiles_add, for every tile before anything is queued
-        const bv_slab &t = tiles[k];
-        if (t.n_sites != e->tile_sites) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: tile n_sites differs from the job's");
-        if (t.n_samples == 0 || t.pitch < t.n_samples || (t.pitch & 15ull) || !t.base_strand || !t.qual)
-            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: bad tile geometry or missing planes");
-        if (e->tile_ranks && (!t.mapq || !t.rpr)) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: job was opened with rank planes");
-        if (e->tile_groups && !t.group_id) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: job has groups, tile has no group_id");
-        seen += t.n_samples;
-        if (seen > e->tile_samples_total) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: more samples than announced");
-        if ((t.layout & ~BV_SLAB_RPR_TAGGED) || t.reserved_ || t.layout != tiles[0].layout || (e->tile_layout_set && t.layout != e->tile_layout))
-            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_add_many: every tile of a job must have the same bv_slab.layout (known bits only)");
-        one_launch = one_launch && t.mem_kind != BV_MEM_HOST;
-    }
-    if (!one_launch) {
-        for (uint32_t k = 0; k < n_tiles; ++k) {
-            int rc = bv_engine_tiles_add(e, &tiles[k], stream_);
-            if (rc != BV_OK) return rc;
-        }
-        return BV_OK;
-    }
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    e->tile_layout = tiles[0].layout; e->tile_layout_set = true;
-    const uint64_t JP = e->j_pitch;
-    for (uint32_t k0 = 0; k0 < n_tiles; k0 += BV_TILE_MANY_MAX) {
-        const uint32_t nk = n_tiles - k0 < (uint32_t)BV_TILE_MANY_MAX ? n_tiles - k0 : (uint32_t)BV_TILE_MANY_MAX;
-        const int slot = (int)(e->desc_next++ % bv_engine::kDescRing);
-        constexpr size_t kBytes = sizeof(BvTileScatterPlane) * 5 * BV_TILE_MANY_MAX;
-        if (!e->h_desc[slot]) {
-            BV_HIP(e, hipHostMalloc(&e->h_desc[slot], kBytes));
-            BV_HIP(e, hipMalloc(&e->d_desc[slot], kBytes));
-            BV_HIP(e, hipEventCreateWithFlags(&e->ev_desc[slot], hipEventDisableTiming));
-        }
-        if (e->desc_used[slot]) BV_HIP(e, hipEventSynchronize(e->ev_desc[slot]));  // the copy that last read this pinned table
-        // the usual job -- tiles of one width and pitch, every byte quantity a multiple of 8: whole destination rows are
-        // gathered across the tiles (bv_tile_join_rows_kernel); anything else: one descriptor per tile and plane
-        const bv_slab &t0 = tiles[k0];
-        bool uniform = !((t0.n_samples | t0.pitch | e->tile_samples_seen | JP) & 7u);
-        for (uint32_t i = 0; i < nk && uniform; ++i) {
-            const bv_slab &t = tiles[k0 + i];
-            uniform = t.n_samples == t0.n_samples && t.pitch == t0.pitch &&
-                      !(((uintptr_t)t.base_strand | (uintptr_t)t.qual | (uintptr_t)t.mapq | (uintptr_t)t.rpr | (uintptr_t)t.group_id) & 7u);
-        }
-        if (uniform) {
-            const uint8_t **tab = reinterpret_cast<const uint8_t **>(e->h_desc[slot]);  // [5][nk] pointers
-            for (uint32_t i = 0; i < nk; ++i) {
-                const bv_slab &t = tiles[k0 + i];
-                tab[0 * nk + i] = t.base_strand; tab[1 * nk + i] = t.qual; tab[2 * nk + i] = t.mapq;
-                tab[3 * nk + i] = reinterpret_cast<const uint8_t *>(t.rpr); tab[4 * nk + i] = t.group_id;
-            }
-            BV_HIP(e, hipMemcpyAsync(e->d_desc[slot], tab, sizeof(void *) * 5 * nk, hipMemcpyHostToDevice, st));
-            BV_HIP(e, hipEventRecord(e->ev_desc[slot], st));
-            e->desc_used[slot] = true;
-            const uint8_t *const *dtab = reinterpret_cast<const uint8_t *const *>(e->d_desc[slot]);
-            const uint64_t lo = e->tile_samples_seen;
-            auto join = [&](uint8_t *dst, int k, uint64_t scale, uint32_t n_rows) {
-                BvTileJoinArgs ja;
-                ja.dst = dst; ja.srcs = dtab + (size_t)k * nk; ja.dst_pitch = scale * JP; ja.src_pitch = scale * t0.pitch; ja.col_off = scale * lo;
-                ja.width_bytes = (uint32_t)(scale * t0.n_samples); ja.n_tiles = nk; ja.n_rows = n_rows;
-                bv_launch_tile_join_rows(ja, st);
-            };
-            join(e->j_buf, 0, 1, t0.n_sites);
-            join(e->j_buf + e->j_o_q, 1, 1, t0.n_sites);
-            if (e->tile_ranks) {
-                join(e->j_buf + e->j_o_mq, 2, 1, t0.n_sites);
-                join(e->j_buf + e->j_o_rp, 3, 2, t0.n_sites);
-            }
-            if (e->tile_groups) join(e->j_buf + e->j_o_gid, 4, 1, 1);
-            BV_HIP(e, hipGetLastError());
-            e->tile_samples_seen += (uint64_t)nk * t0.n_samples;
-            continue;
-        }
-        BvTileScatterPlane wide[5 * BV_TILE_MANY_MAX], narrow[5 * BV_TILE_MANY_MAX];
-        uint32_t nw = 0, nn = 0;
-        uint64_t uw = 0, un = 0;
-        for (uint32_t i = 0; i < nk; ++i) {
-            const bv_slab &t = tiles[k0 + i];
-            const uint64_t lo = e->tile_samples_seen, P = t.pitch;
-            auto plane = [&](uint8_t *dst, const void *src, uint64_t scale, uint32_t n_rows) {
-                BvTileScatterPlane p;
-                p.dst = dst; p.src = static_cast<const uint8_t *>(src); p.dst_pitch = scale * JP; p.src_pitch = scale * P; p.col_off = scale * lo;
-                p.width_bytes = (uint32_t)(scale * t.n_samples); p.n_rows = n_rows;
-                const bool w8 = !((p.dst_pitch | p.col_off | p.src_pitch | p.width_bytes | (uint64_t)(uintptr_t)p.dst | (uint64_t)(uintptr_t)p.src) & 7u);
-                if (w8) { wide[nw++] = p; const uint64_t u = (uint64_t)(p.width_bytes / 8u) * n_rows; if (u > uw) uw = u; }
-                else { narrow[nn++] = p; const uint64_t u = (uint64_t)p.width_bytes * n_rows; if (u > un) un = u; }
-            };
-            plane(e->j_buf, t.base_strand, 1, t.n_sites);
-            plane(e->j_buf + e->j_o_q, t.qual, 1, t.n_sites);
-            if (e->tile_ranks) {
-                plane(e->j_buf + e->j_o_mq, t.mapq, 1, t.n_sites);
-                plane(e->j_buf + e->j_o_rp, t.rpr, 2, t.n_sites);
-            }
-            if (e->tile_groups) plane(e->j_buf + e->j_o_gid, t.group_id, 1, 1);
-            e->tile_samples_seen += t.n_samples;
-        }
-        std::memcpy(e->h_desc[slot], wide, sizeof(BvTileScatterPlane) * nw);
-        std::memcpy(e->h_desc[slot] + nw, narrow, sizeof(BvTileScatterPlane) * nn);
-        BV_HIP(e, hipMemcpyAsync(e->d_desc[slot], e->h_desc[slot], sizeof(BvTileScatterPlane) * (nw + nn), hipMemcpyHostToDevice, st));
-        BV_HIP(e, hipEventRecord(e->ev_desc[slot], st));
-        e->desc_used[slot] = true;
-        bv_launch_tile_scatter_many(e->d_desc[slot], nw, nn, uw, un, st);
-        BV_HIP(e, hipGetLastError());
-    }
-    return mark_done(e, st);
-}
-
-int bv_engine_tiles_finish(bv_engine *e, const uint8_t *ref_base, bv_site_result *out, bv_group_result *gout,
-                           uint32_t mem_kind, void *stream_) {
-    if (!e || !ref_base || !out) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_finish: null argument");
-    if (!e->tile_open) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_finish: no open tile job");
-    if (e->tile_groups && !gout) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_tiles_finish: job has groups, gout is NULL");
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    const size_t S = e->tile_sites, G = e->tile_groups;
-    const uint8_t *dref = ref_base;
-    bv_site_result *dout = out;
-    bv_group_result *dgout = gout;
-    e->host_out = nullptr; e->host_gout = nullptr;
-    bv_engine::StageSlot *slot = nullptr;
-    if (mem_kind == BV_MEM_HOST) {
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        HostPlane pl[1] = {{ref_base, S, nullptr}};
-        const size_t out_b = up(S * sizeof(bv_site_result)), gout_b = up(S * G * sizeof(bv_group_result));
-        uint8_t *extra = nullptr;
-        int rc = stage_host_planes(e, pl, 1, out_b + gout_b, &slot, &extra, st);
-        if (rc != BV_OK) return rc;
-        rc = stage_publish(e, slot, st);
-        if (rc != BV_OK) return rc;
-        dref = pl[0].dev;
-        dout = reinterpret_cast<bv_site_result *>(extra);
-        dgout = G ? reinterpret_cast<bv_group_result *>(extra + out_b) : nullptr;
-        e->stage_out = dout; e->stage_gout = dgout;
-        e->host_out = out; e->host_gout = gout;
-        e->host_out_bytes = S * sizeof(bv_site_result);
-        e->host_gout_bytes = S * G * sizeof(bv_group_result);
-    }
-    if (e->tile_join) {
-        e->tile_open = false;
-        if (e->tile_samples_seen < e->tile_samples_total && !e->j_filled)  // samples announced but never delivered: uncovered cells
-        {
-            BV_HIP(e, hipMemset2DAsync(e->j_buf + e->tile_samples_seen, e->j_pitch, 0x08, e->tile_samples_total - e->tile_samples_seen, S, st));
-            // (tagged ranks: the same cells' rank words must say "no call" too -- 0x8080: the tag's bit 15, rank 128)
-            if (e->tile_ranks && (e->tile_layout & BV_SLAB_RPR_TAGGED))
-                BV_HIP(e, hipMemset2DAsync(e->j_buf + e->j_o_rp + 2 * (size_t)e->tile_samples_seen, 2 * e->j_pitch, 0x80,
-                                           2 * (size_t)(e->tile_samples_total - e->tile_samples_seen), S, st));
-        }
-        int rc = launch_passes(e, e->j_buf, e->j_buf + e->j_o_q, e->tile_ranks ? e->j_buf + e->j_o_mq : nullptr,
-                               e->tile_ranks ? reinterpret_cast<const uint16_t *>(e->j_buf + e->j_o_rp) : nullptr, dref,
-                               G ? e->j_buf + e->j_o_gid : nullptr, e->j_pitch, e->tile_sites, e->tile_samples_total, e->tile_groups,
-                               dout, dgout, st, nullptr, false, e->tile_layout);
-        if (rc == BV_OK && slot) rc = stage_release(e, slot, st);
-        return rc;
-    }
-    BV_HIP(e, hipMemsetAsync(e->d_counters, 0, sizeof(uint32_t) * BV_CTR_PER_LAUNCH * BV_CTR_STRIDE, st));
-    if (G) BV_HIP(e, hipMemsetAsync(dgout, 0, S * G * sizeof(bv_group_result), st));
-    BvTileFinishArgs f;
-    f.state = e->tile_state; f.maxr = e->tile_maxr; f.ref_base = dref; f.n_sites = e->tile_sites; f.n_groups = e->tile_groups;
-    f.stride = e->tile_stride; f.have_ranks = e->tile_ranks ? 1u : 0u; f.min_af = e->cfg.min_af; f.tables = e->d_tables;
-    f.rank_win = e->tile_rank_win; f.hg_off = e->tile_hg_off;
-    f.ord_off = e->tile_ord_off; f.ovf = e->tile_ovf; f.ovf_cap = bv_engine::kOvfCap;
-    f.out = dout; f.gout = dgout; f.var_list = e->d_var_list; f.counters = e->d_counters;
-    bv_launch_tile_finish(f, st);
-    BV_HIP(e, hipGetLastError());
-    e->last_blocks = 1; e->last_ctr_base = 0; e->ctr_rot = 0;
-    BV_HIP(e, hipMemcpyAsync(e->h_counters, e->d_counters, sizeof(uint32_t) * BV_CTR_WORDS * bv_engine::kCtrBlocks, hipMemcpyDeviceToHost, st));
-    if (e->host_out) {
-        BV_HIP(e, hipMemcpyAsync(e->host_out, e->stage_out, e->host_out_bytes, hipMemcpyDeviceToHost, st));
-        if (e->host_gout && e->host_gout_bytes)
-            BV_HIP(e, hipMemcpyAsync(e->host_gout, e->stage_gout, e->host_gout_bytes, hipMemcpyDeviceToHost, st));
-    }
-    e->tile_open = false;
-    e->submitted = true;
-    e->last_slot = -1;  // no pass-1/pass-2 event triplet for this realisation: bv_engine_kernel_ms has nothing to report
-    if (slot) {
-        int rc = stage_release(e, slot, st);
-        if (rc != BV_OK) return rc;
-    }
-    return mark_done(e, st);
-}
 
 void *bv_engine_stream(bv_engine *e) { return e ? (void *)e->stream : nullptr; }
 

@@ -20,7 +20,9 @@
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "bv_inflate_core.h"
-#include "bv_kernels.h"
+#include "bv_engine_impl.h"
+
+using namespace bv_impl;
 
 static_assert(BV_INF_OK == BV_BGZF_OK && BV_INF_BAD_HEADER == BV_BGZF_BAD_HEADER && BV_INF_BAD_DEFLATE == BV_BGZF_BAD_DEFLATE &&
                   BV_INF_BAD_SIZE == BV_BGZF_BAD_SIZE && BV_INF_BAD_CRC == BV_BGZF_BAD_CRC,
@@ -80,13 +82,6 @@ constexpr size_t kInChunkBytes = (size_t)32 << 20;  // compressed bytes per stag
 constexpr size_t kOutPerIn = 4;                     // inflated bytes a chunk may hold, per compressed byte of its capacity
 constexpr uint32_t kChunkMembers = 16384;
 
-#define BV_INF_HIP(e, call)                                                                        \
-    do {                                                                                           \
-        hipError_t _s = (call);                                                                    \
-        if (_s != hipSuccess)                                                                      \
-            return bv_engine_fail((e), BV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
-    } while (0)
-
 }  // namespace
 
 // Per-engine staging of bv_engine_bgzf_inflate: two pinned host + two device chunks of compressed bytes and member tables, and
@@ -129,50 +124,44 @@ int ensure_staging(bv_engine *e, BvBgzfState *t, size_t in_bytes, size_t out_byt
     if (!t->ready) {
         // the kernel's LDS (window + tables) is more than the 64 KiB every launch may have: ask once whether this device takes it
         hipFuncAttributes fa;
-        BV_INF_HIP(e, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(bv_bgzf_inflate_kernel)));
+        BV_HIP(e, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(bv_bgzf_inflate_kernel)));
         int lds_max = 0;
-        BV_INF_HIP(e, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
+        BV_HIP(e, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
         if (fa.sharedSizeBytes > (size_t)lds_max)
-            return bv_engine_fail(e, BV_ERR_NO_DEVICE, "bv_engine_bgzf_inflate: the inflate kernel needs " + std::to_string(fa.sharedSizeBytes) +
+            return fail(e, BV_ERR_NO_DEVICE, "bv_engine_bgzf_inflate: the inflate kernel needs " + std::to_string(fa.sharedSizeBytes) +
                                                            " bytes of LDS per workgroup, the device offers " + std::to_string(lds_max));
-        if (!t->cs) BV_INF_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
+        if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) {  // (each object if it is missing: a call that failed half-way is taken up where it stopped)
-            if (!t->ev_copied[k]) BV_INF_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
-            if (!t->ev_done[k]) BV_INF_HIP(e, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
-            if (!t->h_meta[k]) BV_INF_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_meta[k]), sizeof(BvInfMember) * kChunkMembers));
-            if (!t->d_meta[k]) BV_INF_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_meta[k]), sizeof(BvInfMember) * kChunkMembers));
+            if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
+            if (!t->ev_done[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
+            if (!t->h_meta[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_meta[k]), sizeof(BvInfMember) * kChunkMembers));
+            if (!t->d_meta[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_meta[k]), sizeof(BvInfMember) * kChunkMembers));
         }
         t->ready = true;
     }
     if (in_bytes > t->in_cap) {
         for (int k = 0; k < 2; ++k) {
-            if (t->h_in[k]) BV_INF_HIP(e, hipHostFree(t->h_in[k]));
-            if (t->d_in[k]) BV_INF_HIP(e, hipFree(t->d_in[k]));
+            if (t->h_in[k]) BV_HIP(e, hipHostFree(t->h_in[k]));
+            if (t->d_in[k]) BV_HIP(e, hipFree(t->d_in[k]));
             t->h_in[k] = t->d_in[k] = nullptr;
         }
         t->in_cap = 0;
         for (int k = 0; k < 2; ++k) {
-            BV_INF_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_in[k]), in_bytes));
-            BV_INF_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_in[k]), in_bytes));
+            BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_in[k]), in_bytes));
+            BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_in[k]), in_bytes));
         }
         t->in_cap = in_bytes;
     }
     if (out_bytes > t->out_cap) {
         for (int k = 0; k < 2; ++k) {
-            if (t->d_out[k]) BV_INF_HIP(e, hipFree(t->d_out[k]));
+            if (t->d_out[k]) BV_HIP(e, hipFree(t->d_out[k]));
             t->d_out[k] = nullptr;
         }
         t->out_cap = 0;
-        for (int k = 0; k < 2; ++k) BV_INF_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_out[k]), out_bytes));
+        for (int k = 0; k < 2; ++k) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_out[k]), out_bytes));
         t->out_cap = out_bytes;
     }
-    if (n_members > t->status_cap) {
-        if (t->d_status) BV_INF_HIP(e, hipFree(t->d_status));
-        t->d_status = nullptr; t->status_cap = 0;
-        BV_INF_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_status), n_members));
-        t->status_cap = n_members;
-    }
-    return BV_OK;
+    return grow_device(e, &t->d_status, &t->status_cap, n_members);
 }
 
 struct Chunk {
@@ -183,10 +172,10 @@ struct Chunk {
 int bgzf_inflate(bv_engine *e, BvBgzfState *t, const bv_bgzf_members *mb, const std::vector<BvBgzfMember> &hd, const std::vector<uint8_t> &pre,
                  uint8_t *dst, bool host_dst, const uint64_t *out_pos, uint8_t *status, hipStream_t st) {
     const uint32_t n = mb->n_members;
-    BV_INF_HIP(e, hipSetDevice(t->device));
+    BV_HIP(e, hipSetDevice(t->device));
     // a call that failed part-way may have left work queued: the staging is free only once it is through
-    if (t->cs) BV_INF_HIP(e, hipStreamSynchronize(t->cs));
-    BV_INF_HIP(e, hipStreamSynchronize(st));
+    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
+    BV_HIP(e, hipStreamSynchronize(st));
     // (BASEVAR_AMD_TEXT_CHUNK_BYTES: a smaller chunk, for tests of the staging's reuse; never above the default)
     size_t in_cap = kInChunkBytes;
     if (const char *v = std::getenv("BASEVAR_AMD_TEXT_CHUNK_BYTES")) {
@@ -213,7 +202,7 @@ int bgzf_inflate(bv_engine *e, BvBgzfState *t, const bv_bgzf_members *mb, const 
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
         const Chunk &c = chunks[ci];
         const unsigned s = ci & 1u;
-        if (ci >= 2) BV_INF_HIP(e, hipEventSynchronize(t->ev_done[s]));  // the slot's kernel (and its copy back) is through
+        if (ci >= 2) BV_HIP(e, hipEventSynchronize(t->ev_done[s]));  // the slot's kernel (and its copy back) is through
         size_t at = 0;
         for (uint32_t j = 0; j < c.count; ++j) {
             const uint32_t k = c.first + j;
@@ -225,29 +214,28 @@ int bgzf_inflate(bv_engine *e, BvBgzfState *t, const bv_bgzf_members *mb, const 
             m.isize = hd[k].isize; m.crc = hd[k].crc; m.pre = pre[k]; m.reserved_ = 0;
             at += len;
         }
-        BV_INF_HIP(e, hipMemcpyAsync(t->d_in[s], t->h_in[s], c.in_bytes, hipMemcpyHostToDevice, t->cs));
-        BV_INF_HIP(e, hipMemcpyAsync(t->d_meta[s], t->h_meta[s], sizeof(BvInfMember) * c.count, hipMemcpyHostToDevice, t->cs));
-        BV_INF_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
-        BV_INF_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
+        BV_HIP(e, hipMemcpyAsync(t->d_in[s], t->h_in[s], c.in_bytes, hipMemcpyHostToDevice, t->cs));
+        BV_HIP(e, hipMemcpyAsync(t->d_meta[s], t->h_meta[s], sizeof(BvInfMember) * c.count, hipMemcpyHostToDevice, t->cs));
+        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
+        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
         hipLaunchKernelGGL(bv_bgzf_inflate_kernel, dim3(c.count), dim3(64), 0, st, (const uint8_t *)t->d_in[s], (const BvInfMember *)t->d_meta[s],
                            c.count, host_dst ? t->d_out[s] : dst, t->d_status + c.first);
-        BV_INF_HIP(e, hipGetLastError());
+        BV_HIP(e, hipGetLastError());
         if (host_dst && c.out_bytes)
-            BV_INF_HIP(e, hipMemcpyAsync(dst + out_pos[c.first], t->d_out[s], c.out_bytes, hipMemcpyDeviceToHost, st));
-        BV_INF_HIP(e, hipEventRecord(t->ev_done[s], st));
+            BV_HIP(e, hipMemcpyAsync(dst + out_pos[c.first], t->d_out[s], c.out_bytes, hipMemcpyDeviceToHost, st));
+        BV_HIP(e, hipEventRecord(t->ev_done[s], st));
     }
-    BV_INF_HIP(e, hipMemcpyAsync(status, t->d_status, n, hipMemcpyDeviceToHost, st));
-    BV_INF_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipMemcpyAsync(status, t->d_status, n, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
 }
 
-BvBgzfState *state_of(const BvEngineView &v) {
-    BvBgzfState *&t = *v.bgzf;
-    if (!t) {
-        t = new BvBgzfState();
-        t->device = v.device;
+BvBgzfState *state_of(bv_engine *e) {
+    if (!e->bgzf) {
+        e->bgzf = new BvBgzfState();
+        e->bgzf->device = e->cfg.device;
     }
-    return t;
+    return e->bgzf;
 }
 
 }  // namespace
@@ -259,9 +247,9 @@ int bv_bgzf_headers(bv_engine *e, const char *who, const bv_bgzf_members *mb, st
     for (uint32_t k = 0; k < n; ++k) {
         const uint64_t a = mb->member_off[k], b = mb->member_off[k + 1];
         if (b < a || b > mb->data_bytes)
-            return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": member " + std::to_string(k) + ": member_off out of order or beyond data_bytes");
+            return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": member " + std::to_string(k) + ": member_off out of order or beyond data_bytes");
         if (b - a < BV_INF_MIN_MEMBER || b - a > 65536u)
-            return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": member " + std::to_string(k) + " is " + std::to_string(b - a) +
+            return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": member " + std::to_string(k) + " is " + std::to_string(b - a) +
                                                              " bytes: a BGZF member has 26 to 65536");
     }
     hd.resize(n);
@@ -278,20 +266,20 @@ int bv_bgzf_headers(bv_engine *e, const char *who, const bv_bgzf_members *mb, st
 // Member k's text to d_dst + out_pos[k] (device memory of the engine's device); status[n_members] on the host.  Blocks.
 int bv_bgzf_inflate_placed(bv_engine *e, const bv_bgzf_members *mb, const std::vector<BvBgzfMember> &hd, const std::vector<uint8_t> &pre,
                            const uint64_t *out_pos, uint8_t *d_dst, uint8_t *status, hipStream_t st) {
-    return bgzf_inflate(e, state_of(bv_engine_view(e)), mb, hd, pre, d_dst, false, out_pos, status, st);
+    return bgzf_inflate(e, state_of(e), mb, hd, pre, d_dst, false, out_pos, status, st);
 }
 
 extern "C" {
 
 int bv_engine_bgzf_inflate(bv_engine *e, const bv_bgzf_members *mb, void *dst, uint64_t dst_capacity, int mem_kind, uint64_t *dst_off,
                            uint8_t *status, void *stream_) {
-    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null engine");
-    if (!mb || !dst_off) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null members/dst_off");
-    if (mb->reserved_) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: reserved_ must be zero");
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null engine");
+    if (!mb || !dst_off) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null members/dst_off");
+    if (mb->reserved_) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: reserved_ must be zero");
     if (mem_kind != BV_MEM_HOST && mem_kind != BV_MEM_DEVICE)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
     const uint32_t n = mb->n_members;
-    if (n && (!mb->data || !mb->member_off || !status)) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null data/member_off/status");
+    if (n && (!mb->data || !mb->member_off || !status)) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null data/member_off/status");
     dst_off[0] = 0;
     if (n == 0) return BV_OK;
     std::vector<BvBgzfMember> hd;
@@ -300,11 +288,10 @@ int bv_engine_bgzf_inflate(bv_engine *e, const bv_bgzf_members *mb, void *dst, u
     if (rc != BV_OK) return rc;
     for (uint32_t k = 0; k < n; ++k) dst_off[k + 1] = dst_off[k] + hd[k].isize;
     if (dst_capacity < dst_off[n])
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: dst_capacity " + std::to_string(dst_capacity) + " < the " +
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: dst_capacity " + std::to_string(dst_capacity) + " < the " +
                                                          std::to_string(dst_off[n]) + " bytes the members inflate to");
-    if (!dst && dst_off[n]) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null dst");
-    const BvEngineView v = bv_engine_view(e);
-    return bgzf_inflate(e, state_of(v), mb, hd, pre, static_cast<uint8_t *>(dst), mem_kind == BV_MEM_HOST, dst_off, status, stream_ ? (hipStream_t)stream_ : v.stream);
+    if (!dst && dst_off[n]) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null dst");
+    return bgzf_inflate(e, state_of(e), mb, hd, pre, static_cast<uint8_t *>(dst), mem_kind == BV_MEM_HOST, dst_off, status, stream_ ? (hipStream_t)stream_ : e->stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // bv_kernels.h -- launch-argument blocks shared by the kernels (bv_pass1.hip, bv_pass2.hip)
-// and the engine (bv_engine.hip).
+// and the engine (bv_engine.hip, bv_engine_tiles.hip; its own view of itself is bv_engine_impl.h).
 #pragma once
 
 #include "bv_device.h"
@@ -167,7 +167,7 @@ void bv_launch_chain_scatter_out(const BvChain *ch, uint32_t n_sites, const bv_s
 void bv_launch_p1s_stream(const BvP1ShortArgs &a, hipStream_t stream);
 void bv_launch_p1s_solve(const BvP1ShortArgs &a, hipStream_t stream, bool beside_stream = false);
 
-// sample-axis tile mode (bv_tiles.hip)
+// sample-axis tile mode (kernels: bv_tiles.hip; the job protocol that fills these blocks: bv_engine_tiles.hip)
 struct BvTileArgs {
     const uint8_t *bs;        // [n_sites][pitch] tile planes (device)
     const uint8_t *q;
@@ -294,22 +294,6 @@ size_t bv_pass2_lds_bytes(uint32_t n_groups);
 // planes in a.mapq / a.rpr, the variant sites' pass-2 rows -- as ONE persistent kernel (bv_pass1_fused.hip)
 bool bv_p1s_fused_takes(const BvP1ShortArgs &a);
 void bv_launch_p1s_fused(const BvP1ShortArgs &a, hipStream_t stream);
-
-// batchfile text rows (bv_text.hip): what the text entry points need from the engine (bv_engine.hip)
-#include <string>
-struct BvTextState;
-void bv_text_state_free(BvTextState *t);
-struct BvBgzfState;
-void bv_bgzf_state_free(BvBgzfState *t);
-struct BvEngineView {
-    int device;
-    uint32_t max_sites, max_samples;
-    hipStream_t stream;   // the engine's own stream
-    BvTextState **text;   // the engine's text state (created by the first bv_engine_text_parse)
-    BvBgzfState **bgzf;   // the engine's BGZF staging (created by the first bv_engine_bgzf_inflate; bv_inflate.hip)
-};
-BvEngineView bv_engine_view(bv_engine *e);
-int bv_engine_fail(bv_engine *e, int code, const std::string &msg);  // sets bv_last_error(e) (or the global one), returns code
 
 // BGZF members (bv_inflate.hip) for the text path (bv_text.hip): their wrappers read on the host, then inflated to chosen places
 #include <vector>

@@ -24,7 +24,9 @@
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "bv_inflate_core.h"
-#include "bv_kernels.h"
+#include "bv_engine_impl.h"
+
+using namespace bv_impl;
 
 namespace {
 
@@ -439,42 +441,24 @@ void bv_text_state_free(BvTextState *t) {
 }
 
 namespace {
-#define BV_TXT_HIP(e, call)                                                                        \
-    do {                                                                                           \
-        hipError_t _s = (call);                                                                    \
-        if (_s != hipSuccess)                                                                      \
-            return bv_engine_fail((e), BV_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(_s)); \
-    } while (0)
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int grow(bv_engine *e, uint8_t **buf, size_t *have, size_t need) {
-    if (need <= *have) return BV_OK;
-    if (*buf) BV_TXT_HIP(e, hipFree(*buf));
-    *buf = nullptr; *have = 0;
-    BV_TXT_HIP(e, hipMalloc(buf, need));
-    *have = need;
-    return BV_OK;
-}
-
 // The staging of text chunks: two pinned host buffers and two device buffers of `bytes` each.
 int ensure_chunks(bv_engine *e, BvTextState *t, size_t bytes) {
-    if (!t->cs) BV_TXT_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
+    if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
-        if (!t->ev_copied[k]) BV_TXT_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
-        if (!t->ev_parsed[k]) BV_TXT_HIP(e, hipEventCreateWithFlags(&t->ev_parsed[k], hipEventDisableTiming));
+        if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
+        if (!t->ev_parsed[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_parsed[k], hipEventDisableTiming));
     }
     if (bytes <= t->chunk_cap) return BV_OK;
-    BV_TXT_HIP(e, hipStreamSynchronize(t->cs));
+    BV_HIP(e, hipStreamSynchronize(t->cs));
     for (int k = 0; k < 2; ++k) {
-        if (t->h_text[k]) BV_TXT_HIP(e, hipHostFree(t->h_text[k]));
-        if (t->d_text[k]) BV_TXT_HIP(e, hipFree(t->d_text[k]));
+        if (t->h_text[k]) BV_HIP(e, hipHostFree(t->h_text[k]));
+        if (t->d_text[k]) BV_HIP(e, hipFree(t->d_text[k]));
         t->h_text[k] = t->d_text[k] = nullptr;
     }
     t->chunk_cap = 0;
     for (int k = 0; k < 2; ++k) {
-        BV_TXT_HIP(e, hipHostMalloc(&t->h_text[k], bytes));
-        BV_TXT_HIP(e, hipMalloc(&t->d_text[k], bytes));
+        BV_HIP(e, hipHostMalloc(&t->h_text[k], bytes));
+        BV_HIP(e, hipMalloc(&t->d_text[k], bytes));
     }
     t->chunk_cap = bytes;
     return BV_OK;
@@ -496,16 +480,16 @@ int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint
     const uint64_t pitch = (n_samples + 255ull) & ~255ull;
     t->parsed = false;
     t->bgzf_rows = false;
-    BV_TXT_HIP(e, hipSetDevice(t->device));
+    BV_HIP(e, hipSetDevice(t->device));
     // a parse that failed part-way may have left chunk copies queued: the staging is free only once they are through
-    if (t->cs) BV_TXT_HIP(e, hipStreamSynchronize(t->cs));
+    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
     // device buffers: planes, then the small per-position / per-row arrays
     const size_t cells = (size_t)P * pitch;
-    int rc = grow(e, &t->d_planes, &t->planes_bytes, 6 * cells + up256(P));
+    int rc = grow_device(e, &t->d_planes, &t->planes_bytes, 6 * cells + up256(P));
     if (rc != BV_OK) return rc;
     const size_t o_pstate = up256(4ull * P), o_pmax = 2 * o_pstate, o_flag = 3 * o_pstate, o_off = o_flag + up256(R),
                  o_foff = o_off + up256(16 * (R + 1)), o_fs = o_foff + up256(4ull * F), aux = o_fs + up256(4ull * F);
-    rc = grow(e, &t->d_aux, &t->aux_bytes, aux);
+    rc = grow_device(e, &t->d_aux, &t->aux_bytes, aux);
     if (rc != BV_OK) return rc;
     b->pitch = pitch;
     b->bs = t->d_planes; b->q = b->bs + cells; b->mq = b->q + cells; b->stp = b->mq + cells;
@@ -518,12 +502,12 @@ int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint
     b->d_off = reinterpret_cast<uint64_t *>(t->d_aux + o_off);
     t->h_foff.resize(F);
     for (uint32_t f = 0, s = 0; f < F; s += file_samples[f], ++f) t->h_foff[f] = s;
-    BV_TXT_HIP(e, hipMemsetAsync(b->bs, BV_CELL_N, cells, st));
-    BV_TXT_HIP(e, hipMemsetAsync(b->q, 0, 3 * cells, st));  // q, mq, strand
-    BV_TXT_HIP(e, hipMemsetAsync(b->rp, 0, 2 * cells, st));
-    BV_TXT_HIP(e, hipMemsetAsync(t->d_aux, 0, o_off, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(b->foff, t->h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(b->fsamp, file_samples, 4ull * F, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemsetAsync(b->bs, BV_CELL_N, cells, st));
+    BV_HIP(e, hipMemsetAsync(b->q, 0, 3 * cells, st));  // q, mq, strand
+    BV_HIP(e, hipMemsetAsync(b->rp, 0, 2 * cells, st));
+    BV_HIP(e, hipMemsetAsync(t->d_aux, 0, o_off, st));
+    BV_HIP(e, hipMemcpyAsync(b->foff, t->h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(b->fsamp, file_samples, 4ull * F, hipMemcpyHostToDevice, st));
     return BV_OK;
 }
 
@@ -542,7 +526,7 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
     uint16_t *rp = pb.rp;
     uint32_t *depth = pb.depth, *pstate = pb.pstate, *pmax = pb.pmax, *foff = pb.foff, *fsamp = pb.fsamp;
     uint64_t *d_off = pb.d_off;
-    BV_TXT_HIP(e, hipMemcpyAsync(d_off, rows->row_off, 8 * (R + 1), hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(d_off, rows->row_off, 8 * (R + 1), hipMemcpyHostToDevice, st));
     // the chunks: whole positions, at most kChunkBytes (or one position, if it is longer)
     size_t need = 0;
     for (uint32_t p = 0; p < P; ++p) need = std::max<size_t>(need, rows->row_off[(size_t)(p + 1) * F] - rows->row_off[(size_t)p * F]);
@@ -555,7 +539,7 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
     }
     rc = ensure_chunks(e, t, std::max(up256(need), std::min(chunk_bytes, up256(total))));
     if (rc != BV_OK) return rc;
-    BV_TXT_HIP(e, hipStreamSynchronize(st));  // (the pageable uploads above are complete; the chunk buffers may be reused)
+    BV_HIP(e, hipStreamSynchronize(st));  // (the pageable uploads above are complete; the chunk buffers may be reused)
     unsigned k = 0;
     for (uint32_t p0 = 0; p0 < P; ++k) {
         const uint64_t base = rows->row_off[(size_t)p0 * F];
@@ -563,20 +547,20 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
         while (p1 < P && rows->row_off[(size_t)(p1 + 1) * F] - base <= t->chunk_cap) ++p1;
         const size_t bytes = rows->row_off[(size_t)p1 * F] - base;
         const unsigned s = k & 1u;
-        if (k >= 2) BV_TXT_HIP(e, hipEventSynchronize(t->ev_copied[s]));  // the pinned buffer has crossed the link
+        if (k >= 2) BV_HIP(e, hipEventSynchronize(t->ev_copied[s]));  // the pinned buffer has crossed the link
         std::memcpy(t->h_text[s], rows->text + base, bytes);
-        if (k >= 2) BV_TXT_HIP(e, hipStreamWaitEvent(t->cs, t->ev_parsed[s], 0));  // the device buffer has been parsed
-        BV_TXT_HIP(e, hipMemcpyAsync(t->d_text[s], t->h_text[s], bytes, hipMemcpyHostToDevice, t->cs));
-        BV_TXT_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
-        BV_TXT_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
+        if (k >= 2) BV_HIP(e, hipStreamWaitEvent(t->cs, t->ev_parsed[s], 0));  // the device buffer has been parsed
+        BV_HIP(e, hipMemcpyAsync(t->d_text[s], t->h_text[s], bytes, hipMemcpyHostToDevice, t->cs));
+        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
+        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
         TextParseArgs a;
         a.text = t->d_text[s]; a.row_beg = d_off; a.row_end = d_off + 1; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
         a.row_first = p0 * F; a.n_rows_chunk = (p1 - p0) * F; a.n_files = F; a.pitch = pitch;
         a.bs = bs; a.q = q; a.mq = mq; a.st = stp; a.ref = ref; a.rowflag = rowflag; a.rp = rp;
         a.depth = depth; a.pstate = pstate; a.pmax = pmax;
         hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
-        BV_TXT_HIP(e, hipGetLastError());
-        BV_TXT_HIP(e, hipEventRecord(t->ev_parsed[s], st));
+        BV_HIP(e, hipGetLastError());
+        BV_HIP(e, hipEventRecord(t->ev_parsed[s], st));
         p0 = p1;
     }
     return parse_finish(e, t, P, F, n_samples, group_id, n_groups, row_state, st, pb);
@@ -588,13 +572,13 @@ int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t 
     const size_t R = (size_t)P * F;
     hipLaunchKernelGGL(bv_text_strand_kernel, dim3(P), dim3(256), 0, st, b.bs, (const uint8_t *)b.stp, (const uint32_t *)b.depth, b.pstate, b.pitch,
                        n_samples);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     std::vector<uint32_t> h(3ull * P);
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data(), b.depth, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + P, b.pstate, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(h.data() + 2ull * P, b.pmax, 4ull * P, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(row_state, b.rowflag, R, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipMemcpyAsync(h.data(), b.depth, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(h.data() + P, b.pstate, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(h.data() + 2ull * P, b.pmax, 4ull * P, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(row_state, b.rowflag, R, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     // the position's state, in the host reader's order: field count / coordinates / Depth first, then Depth 0, then the tokens
     t->pos_state.assign(P, 0);
     t->pos_max_rank.assign(h.begin() + 2ull * P, h.end());
@@ -620,50 +604,48 @@ extern "C" {
 
 int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
                          void *stream_) {
-    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null engine");
-    if (!rows || !row_state) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null rows/row_state");
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null engine");
+    if (!rows || !row_state) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null rows/row_state");
     if (!rows->text || !rows->row_off || !rows->file_samples)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null text/row_off/file_samples");
-    if (rows->reserved_) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: reserved_ must be zero");
-    const BvEngineView v = bv_engine_view(e);
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null text/row_off/file_samples");
+    if (rows->reserved_) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: reserved_ must be zero");
     if (rows->n_positions == 0 || rows->n_files == 0)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions and n_files must be > 0");
-    if (rows->n_positions > v.max_sites)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions exceeds cfg.max_sites");
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions and n_files must be > 0");
+    if (rows->n_positions > e->cfg.max_sites)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions exceeds cfg.max_sites");
     uint64_t n_samples = 0;
     for (uint32_t f = 0; f < rows->n_files; ++f) {
-        if (rows->file_samples[f] == 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: file_samples[f] == 0");
+        if (rows->file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: file_samples[f] == 0");
         n_samples += rows->file_samples[f];
     }
-    if (n_samples > v.max_samples)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: the files hold more samples than cfg.max_samples");
+    if (n_samples > e->cfg.max_samples)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: the files hold more samples than cfg.max_samples");
     if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
     const size_t R = (size_t)rows->n_positions * rows->n_files;
     for (size_t r = 0; r < R; ++r) {  // rows in order, inside the text, each ending in '\n'
         const uint64_t a = rows->row_off[r], b = rows->row_off[r + 1];
         if (b <= a || b > rows->text_bytes || rows->text[b - 1] != '\n')
-            return bv_engine_fail(e, BV_ERR_INVALID_ARG,
+            return fail(e, BV_ERR_INVALID_ARG,
                                   "bv_engine_text_parse: row " + std::to_string(r) + ": row_off outside text_bytes, out of order, or no final '\\n'");
-        if (b - a > 0xFFFFFFFFull) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: a row is longer than 4 GiB");
+        if (b - a > 0xFFFFFFFFull) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: a row is longer than 4 GiB");
     }
-    BvTextState *&t = *v.text;
+    BvTextState *&t = e->text;
     if (!t) {
         t = new BvTextState();
-        t->device = v.device;
+        t->device = e->cfg.device;
     }
-    const int rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : v.stream, (uint32_t)n_samples);
+    const int rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : e->stream, (uint32_t)n_samples);
     if (rc != BV_OK) t->parsed = false;
     return rc;
 }
 
 int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab *host_rows, uint32_t n_used, bv_site_result *out,
                           bv_group_result *gout, uint8_t *cell, uint8_t *phred, void *stream_) {
-    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null engine");
-    const BvEngineView v = bv_engine_view(e);
-    BvTextState *t = *v.text;
-    if (!t || !t->parsed) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: no bv_engine_text_parse before it");
-    if (n_used > t->n_pos) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_positions_used exceeds the parsed batch");
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null engine");
+    BvTextState *t = e->text;
+    if (!t || !t->parsed) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: no bv_engine_text_parse before it");
+    if (n_used > t->n_pos) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_positions_used exceeds the parsed batch");
     // row_state (may be NULL: as the parse left it): the host reader may have skipped a "host" position (its Depth fields, read
     // its way, sum to 0); nothing else may change
     std::vector<uint8_t> state(t->pos_state.begin(), t->pos_state.begin() + n_used);
@@ -671,7 +653,7 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
         for (uint32_t p = 0; p < n_used; ++p) {
             const uint8_t s = (uint8_t)(row_state[(size_t)p * t->n_files] & (BV_TEXT_SKIP | BV_TEXT_HOST));
             if (s != state[p] && !(state[p] == BV_TEXT_HOST && s == BV_TEXT_SKIP))
-                return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: row_state of position " + std::to_string(p) +
+                return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: row_state of position " + std::to_string(p) +
                                                                  " differs from the parse (only HOST -> SKIP is allowed)");
             state[p] = s;
         }
@@ -689,19 +671,19 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
         if (!host_rows || host_rows->n_sites != n_host || host_rows->n_samples != N || host_rows->pitch < N ||
             (host_rows->pitch & 15u) || host_rows->mem_kind != BV_MEM_HOST || host_rows->layout || host_rows->reserved_ || !host_rows->base_strand ||
             !host_rows->qual || !host_rows->mapq || !host_rows->rpr || !host_rows->ref_base)
-            return bv_engine_fail(e, BV_ERR_INVALID_ARG,
+            return fail(e, BV_ERR_INVALID_ARG,
                                   "bv_engine_text_submit: host_rows must hold the " + std::to_string(n_host) +
                                       " host positions as a plain BV_MEM_HOST slab of n_samples = " + std::to_string(N) +
                                       " with all five planes");
     } else if (host_rows && host_rows->n_sites) {
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: host_rows given, but no position is marked host");
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: host_rows given, but no position is marked host");
     }
-    if (n_out && !out) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null out");
-    if (n_out && t->n_groups && !gout) return bv_engine_fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_groups > 0 needs gout");
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
+    if (n_out && !out) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: null out");
+    if (n_out && t->n_groups && !gout) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_groups > 0 needs gout");
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     t->parsed = false;  // one submit per parse, whatever happens below
     if (n_out == 0) return BV_OK;
-    BV_TXT_HIP(e, hipSetDevice(t->device));
+    BV_HIP(e, hipSetDevice(t->device));
     const uint64_t HP = n_host ? host_rows->pitch : 0;
     for (uint32_t h = 0; h < n_host; ++h) {  // the tagged layout needs every rank <= BV_RPR_TAG_MAX_RANK, host rows' too
         const uint16_t *r = host_rows->rpr + (size_t)h * HP;
@@ -709,11 +691,11 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     }
     const uint64_t P = t->pitch;
     const size_t cells = (size_t)n_out * P, hcells = (size_t)n_host * HP, G = t->n_groups;
-    int rc = grow(e, &t->d_sub, &t->sub_bytes, 5 * cells + up256(n_out));
+    int rc = grow_device(e, &t->d_sub, &t->sub_bytes, 5 * cells + up256(n_out));
     if (rc != BV_OK) return rc;
     const size_t o_host = up256(4ull * n_out), o_out = o_host + up256(5 * hcells + n_host), o_gout = o_out + up256(sizeof(bv_site_result) * n_out),
                  misc = o_gout + up256(sizeof(bv_group_result) * n_out * G);
-    rc = grow(e, &t->d_misc, &t->misc_bytes, misc);
+    rc = grow_device(e, &t->d_misc, &t->misc_bytes, misc);
     if (rc != BV_OK) return rc;
     std::vector<int32_t> src(n_out);
     for (uint32_t p = 0, j = 0, h = 0; p < n_used; ++p) {
@@ -722,18 +704,18 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
         else if (s == BV_TEXT_HOST) src[j++] = -(int32_t)(h++) - 1;
     }
     uint8_t *hb = t->d_misc + o_host;
-    BV_TXT_HIP(e, hipMemcpyAsync(t->d_misc, src.data(), 4ull * n_out, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(t->d_misc, src.data(), 4ull * n_out, hipMemcpyHostToDevice, st));
     if (n_host) {
-        BV_TXT_HIP(e, hipMemcpyAsync(hb, host_rows->base_strand, hcells, hipMemcpyHostToDevice, st));
-        BV_TXT_HIP(e, hipMemcpyAsync(hb + hcells, host_rows->qual, hcells, hipMemcpyHostToDevice, st));
-        BV_TXT_HIP(e, hipMemcpyAsync(hb + 2 * hcells, host_rows->mapq, hcells, hipMemcpyHostToDevice, st));
-        BV_TXT_HIP(e, hipMemcpyAsync(hb + 3 * hcells, host_rows->rpr, 2 * hcells, hipMemcpyHostToDevice, st));
-        BV_TXT_HIP(e, hipMemcpyAsync(hb + 5 * hcells, host_rows->ref_base, n_host, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(hb, host_rows->base_strand, hcells, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(hb + hcells, host_rows->qual, hcells, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(hb + 2 * hcells, host_rows->mapq, hcells, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(hb + 3 * hcells, host_rows->rpr, 2 * hcells, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(hb + 5 * hcells, host_rows->ref_base, n_host, hipMemcpyHostToDevice, st));
     }
     if (t->has_gid) {
-        rc = grow(e, &t->d_gid, &t->gid_bytes, up256(N));
+        rc = grow_device(e, &t->d_gid, &t->gid_bytes, up256(N));
         if (rc != BV_OK) return rc;
-        BV_TXT_HIP(e, hipMemcpyAsync(t->d_gid, t->group_id.data(), N, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(t->d_gid, t->group_id.data(), N, hipMemcpyHostToDevice, st));
     }
     const size_t pcells = (size_t)t->n_pos * P;
     const uint32_t tagged = max_rank <= BV_RPR_TAG_MAX_RANK ? 1u : 0u;
@@ -746,7 +728,7 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     a.bs = t->d_sub; a.q = a.bs + cells; a.mq = a.q + cells; a.rp = reinterpret_cast<uint16_t *>(a.mq + cells);
     a.ref = t->d_sub + 5 * cells; a.pitch = P; a.n_samples = N; a.tagged = tagged;
     hipLaunchKernelGGL(bv_text_gather_kernel, dim3(n_out), dim3(256), 0, st, a);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     bv_slab s{};
     s.n_sites = n_out; s.n_samples = N; s.pitch = P;
     s.base_strand = a.bs; s.qual = a.q; s.mapq = a.mq; s.rpr = a.rp; s.ref_base = a.ref;
@@ -758,52 +740,51 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     if (rc != BV_OK) return rc;
     rc = bv_engine_join(e, st);
     if (rc != BV_OK) return rc;
-    BV_TXT_HIP(e, hipMemcpyAsync(out, d_out, sizeof(bv_site_result) * n_out, hipMemcpyDeviceToHost, st));
-    if (G) BV_TXT_HIP(e, hipMemcpyAsync(gout, d_gout, sizeof(bv_group_result) * n_out * G, hipMemcpyDeviceToHost, st));
-    if (cell) BV_TXT_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
-    if (phred) BV_TXT_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipMemcpyAsync(out, d_out, sizeof(bv_site_result) * n_out, hipMemcpyDeviceToHost, st));
+    if (G) BV_HIP(e, hipMemcpyAsync(gout, d_gout, sizeof(bv_group_result) * n_out * G, hipMemcpyDeviceToHost, st));
+    if (cell) BV_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
+    if (phred) BV_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
 }
 
 int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
                               uint8_t *row_state, bv_bgzf_cursor *cursor, void *stream_) {
     const char *who = "bv_engine_text_parse_bgzf";
-    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
-    if (!rows || !row_state || !n_positions || !cursor) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!rows || !row_state || !n_positions || !cursor) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
     if (!rows->member_off || !rows->file_member || !rows->file_samples || !rows->skip_bytes || !rows->skip_lines)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null member_off/file_member/file_samples/skip_bytes/skip_lines");
-    if (rows->reserved_ || rows->at_end > 1u) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": reserved_ must be zero, at_end 0 or 1");
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null member_off/file_member/file_samples/skip_bytes/skip_lines");
+    if (rows->reserved_ || rows->at_end > 1u) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": reserved_ must be zero, at_end 0 or 1");
     if (rows->n_files == 0 || rows->max_positions == 0)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": n_files and max_positions must be > 0");
-    const BvEngineView v = bv_engine_view(e);
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": n_files and max_positions must be > 0");
     const uint32_t F = rows->n_files;
     uint64_t n_samples = 0;
-    if (rows->file_member[0] != 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member[0] must be 0");
+    if (rows->file_member[0] != 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member[0] must be 0");
     for (uint32_t f = 0; f < F; ++f) {
-        if (rows->file_samples[f] == 0) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
-        if (rows->file_member[f + 1] < rows->file_member[f]) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member out of order");
+        if (rows->file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
+        if (rows->file_member[f + 1] < rows->file_member[f]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member out of order");
         n_samples += rows->file_samples[f];
     }
-    if (!rows->data && rows->file_member[F]) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null data");
-    if (n_samples > v.max_samples)
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the files hold more samples than cfg.max_samples");
+    if (!rows->data && rows->file_member[F]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null data");
+    if (n_samples > e->cfg.max_samples)
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the files hold more samples than cfg.max_samples");
     if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
-        return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
     *n_positions = 0;
     bv_bgzf_members mb{rows->data, rows->member_off, rows->data_bytes, rows->file_member[F], 0};
     std::vector<BvBgzfMember> hd;
     std::vector<uint8_t> pre;
     int rc = bv_bgzf_headers(e, who, &mb, hd, pre);
     if (rc != BV_OK) return rc;
-    BvTextState *&t = *v.text;
+    BvTextState *&t = e->text;
     if (!t) {
         t = new BvTextState();
-        t->device = v.device;
+        t->device = e->cfg.device;
     }
     t->parsed = false;
     t->bgzf_rows = false;
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     // where every member's text goes: file f's members back to back, one spare byte behind each run (16-byte aligned runs)
     const uint32_t M = mb.n_members;
     std::vector<uint64_t> out_pos(M + 1, 0);
@@ -820,15 +801,15 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
         L.len = at - L.base;
         L.skip = rows->skip_bytes[f]; L.skip_lines = rows->skip_lines[f]; L.reserved_ = 0;
         if (L.skip > L.len)
-            return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": skip_bytes of file " + std::to_string(f) + " is beyond its run");
+            return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": skip_bytes of file " + std::to_string(f) + " is beyond its run");
         L.tile_first = tiles;
         L.n_tiles = L.len > L.skip ? (uint32_t)((L.len + rows->at_end - L.skip + kLineTile - 1) / kLineTile) : 0u;
         tiles += L.n_tiles;
         at = (at + 1 + 15) & ~(uint64_t)15;
     }
     out_pos[M] = at;
-    BV_TXT_HIP(e, hipSetDevice(t->device));
-    rc = grow(e, &t->d_btext, &t->btext_bytes, up256(at + 16));
+    BV_HIP(e, hipSetDevice(t->device));
+    rc = grow_device(e, &t->d_btext, &t->btext_bytes, up256(at + 16));
     if (rc != BV_OK) return rc;
     std::vector<uint8_t> status(M ? M : 1);
     if (M) {
@@ -838,7 +819,7 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     for (uint32_t f = 0; f < F; ++f)
         for (uint32_t k = rows->file_member[f]; k < rows->file_member[f + 1]; ++k)
             if (status[k] != BV_BGZF_OK)
-                return bv_engine_fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(f) + ", member " + std::to_string(k - rows->file_member[f]) +
+                return fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(f) + ", member " + std::to_string(k - rows->file_member[f]) +
                                                           " of its run: BGZF status " + std::to_string(status[k]) +
                                                           (status[k] == BV_BGZF_BAD_HEADER ? " (bad header)" : status[k] == BV_BGZF_BAD_DEFLATE ? " (invalid DEFLATE stream)"
                                                            : status[k] == BV_BGZF_BAD_SIZE ? " (inflated size is not ISIZE)" : " (CRC32 mismatch)"));
@@ -851,24 +832,24 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
         cursor[f].offset = k < k1 ? (uint32_t)(x - base) : 0u;
     };
     for (uint32_t f = 0; f < F; ++f) start_cursor(f, fl[f].skip);
-    const uint32_t Pmax = std::min(rows->max_positions, v.max_sites);
+    const uint32_t Pmax = std::min(rows->max_positions, e->cfg.max_sites);
     if (tiles == 0) return BV_OK;  // no text behind the skips: no position
     // the line index
     const size_t o_cnt = up256(sizeof(LineFile) * F), o_npos = o_cnt + up256(4ull * tiles);
-    rc = grow(e, &t->d_lines, &t->lines_bytes, o_npos + 256);
+    rc = grow_device(e, &t->d_lines, &t->lines_bytes, o_npos + 256);
     if (rc != BV_OK) return rc;
     LineFile *d_fl = reinterpret_cast<LineFile *>(t->d_lines);
     uint32_t *d_cnt = reinterpret_cast<uint32_t *>(t->d_lines + o_cnt), *d_npos = reinterpret_cast<uint32_t *>(t->d_lines + o_npos);
     const char *text = reinterpret_cast<const char *>(t->d_btext);
-    BV_TXT_HIP(e, hipMemcpyAsync(d_fl, fl.data(), sizeof(LineFile) * F, hipMemcpyHostToDevice, st));
-    BV_TXT_HIP(e, hipMemcpyAsync(d_npos, &Pmax, 4, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(d_fl, fl.data(), sizeof(LineFile) * F, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(d_npos, &Pmax, 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bv_text_line_pad_kernel, dim3((F + 63u) / 64u), dim3(64), 0, st, (char *)t->d_btext, (const LineFile *)d_fl, F);
     hipLaunchKernelGGL(bv_text_line_count_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, d_cnt);
     hipLaunchKernelGGL(bv_text_line_scan_kernel, dim3(1), dim3(256), 0, st, (const LineFile *)d_fl, F, d_cnt, d_npos);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     uint32_t P = 0;
-    BV_TXT_HIP(e, hipMemcpyAsync(&P, d_npos, 4, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipMemcpyAsync(&P, d_npos, 4, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     if (P == 0) return BV_OK;
     ParseBufs pb;
     rc = parse_begin(e, t, P, F, rows->file_samples, (uint32_t)n_samples, st, &pb);
@@ -877,16 +858,16 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     uint64_t *row_beg = pb.d_off, *row_end = pb.d_off + R;
     hipLaunchKernelGGL(bv_text_line_scatter_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, (const uint32_t *)d_cnt, P,
                        row_beg, row_end);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     TextParseArgs a;
     a.text = text; a.row_beg = row_beg; a.row_end = row_end; a.foff = pb.foff; a.fsamp = pb.fsamp; a.chunk_base = 0;
     a.row_first = 0; a.n_rows_chunk = (uint32_t)R; a.n_files = F; a.pitch = pb.pitch;
     a.bs = pb.bs; a.q = pb.q; a.mq = pb.mq; a.st = pb.stp; a.ref = pb.ref; a.rowflag = pb.rowflag; a.rp = pb.rp;
     a.depth = pb.depth; a.pstate = pb.pstate; a.pmax = pb.pmax;
     hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     std::vector<uint64_t> last(F);
-    BV_TXT_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
     rc = parse_finish(e, t, P, F, (uint32_t)n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
     if (rc != BV_OK) {
         t->parsed = false;
@@ -901,51 +882,50 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
 
 int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream_) {
     const char *who = "bv_engine_text_rows_fetch";
-    if (!e) return bv_engine_fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
-    if (!bytes_needed) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null bytes_needed");
-    const BvEngineView v = bv_engine_view(e);
-    BvTextState *t = *v.text;
-    if (!t || !t->bgzf_rows) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": no bv_engine_text_parse_bgzf before it");
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : v.stream;
-    BV_TXT_HIP(e, hipSetDevice(t->device));
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!bytes_needed) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null bytes_needed");
+    BvTextState *t = e->text;
+    if (!t || !t->bgzf_rows) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": no bv_engine_text_parse_bgzf before it");
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    BV_HIP(e, hipSetDevice(t->device));
     const uint32_t P = t->n_pos, F = t->n_files;
     const size_t R = (size_t)P * F;
     const uint64_t *row_beg = t->bz_row_beg, *row_end = t->bz_row_end;
     const uint8_t *rowflag = t->bz_rowflag;
     const char *text = reinterpret_cast<const char *>(t->d_btext);
     const size_t o_len = up256(P), o_roff = o_len + up256(4 * R), o_bytes = o_roff + up256(8 * (R + 1));
-    int rc = grow(e, &t->d_fetch, &t->fetch_bytes, o_bytes);
+    int rc = grow_device(e, &t->d_fetch, &t->fetch_bytes, o_bytes);
     if (rc != BV_OK) return rc;
     uint32_t *d_len = reinterpret_cast<uint32_t *>(t->d_fetch + o_len);
-    BV_TXT_HIP(e, hipMemcpyAsync(t->d_fetch, t->pos_state.data(), P, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(t->d_fetch, t->pos_state.data(), P, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bv_text_fetch_len_kernel, dim3((uint32_t)((R + 255) / 256)), dim3(256), 0, st, text, row_beg, row_end, (const uint8_t *)t->d_fetch, rowflag,
                        (uint32_t)R, F, d_len);
-    BV_TXT_HIP(e, hipGetLastError());
+    BV_HIP(e, hipGetLastError());
     std::vector<uint32_t> len(R);
-    BV_TXT_HIP(e, hipMemcpyAsync(len.data(), d_len, 4 * R, hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipMemcpyAsync(len.data(), d_len, 4 * R, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     std::vector<uint64_t> off(R + 1, 0);
     for (size_t r = 0; r < R; ++r) off[r + 1] = off[r] + len[r];
     *bytes_needed = off[R];
     if (capacity < off[R]) return BV_OK;
-    if (!row_off || (!buf && off[R])) return bv_engine_fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null buf/row_off");
+    if (!row_off || (!buf && off[R])) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null buf/row_off");
     std::memcpy(row_off, off.data(), 8 * (R + 1));
     if (off[R] == 0) return BV_OK;
     // the gathered bytes live behind the offsets; the buffer may move when it grows, so the lengths are copied again after it
     const size_t need = o_bytes + up256(off[R]);
     if (need > t->fetch_bytes) {
-        rc = grow(e, &t->d_fetch, &t->fetch_bytes, need);
+        rc = grow_device(e, &t->d_fetch, &t->fetch_bytes, need);
         if (rc != BV_OK) return rc;
         d_len = reinterpret_cast<uint32_t *>(t->d_fetch + o_len);
-        BV_TXT_HIP(e, hipMemcpyAsync(d_len, len.data(), 4 * R, hipMemcpyHostToDevice, st));
+        BV_HIP(e, hipMemcpyAsync(d_len, len.data(), 4 * R, hipMemcpyHostToDevice, st));
     }
     uint64_t *d_roff = reinterpret_cast<uint64_t *>(t->d_fetch + o_roff);
-    BV_TXT_HIP(e, hipMemcpyAsync(d_roff, off.data(), 8 * (R + 1), hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(d_roff, off.data(), 8 * (R + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bv_text_fetch_copy_kernel, dim3((uint32_t)((R + 3) / 4)), dim3(256), 0, st, text, row_beg, (const uint32_t *)d_len, (const uint64_t *)d_roff,
                        (uint32_t)R, t->d_fetch + o_bytes);
-    BV_TXT_HIP(e, hipGetLastError());
-    BV_TXT_HIP(e, hipMemcpyAsync(buf, t->d_fetch + o_bytes, off[R], hipMemcpyDeviceToHost, st));
-    BV_TXT_HIP(e, hipStreamSynchronize(st));
+    BV_HIP(e, hipGetLastError());
+    BV_HIP(e, hipMemcpyAsync(buf, t->d_fetch + o_bytes, off[R], hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
 }
 

@@ -249,7 +249,7 @@ int bv_engine_tiles_finish(bv_engine *e, const uint8_t *ref_base, bv_site_result
 typedef struct bv_sparse_tile {
     uint32_t n_sites, n_samples;  /* sites of the job; samples (columns) of this tile, <= 65,536 */
     uint32_t n_entries, n_groups; /* covered cells of the tile (= row_start[n_sites]); the job's group count */
-    const uint32_t *row_start;    /* [n_sites + 1] */
+    const uint32_t *row_start;    /* [n_sites + 1]: starts at 0, never decreases, ends at n_entries (a host tile's is checked) */
     const uint16_t *sample;       /* [n_entries] column inside the tile */
     const uint8_t *base_strand, *qual, *mapq;  /* [n_entries]; mapq and rpr NULL for a job without rank planes */
     const uint16_t *rpr;          /* [n_entries] */
@@ -258,7 +258,7 @@ typedef struct bv_sparse_tile {
 } bv_sparse_tile;
 int bv_engine_tiles_add_sparse(bv_engine *e, const bv_sparse_tile *tile, void *stream);
 /* = n_tiles calls of bv_engine_tiles_add_sparse (byte-identical records; widths, mem_kind may differ; empty tiles allowed), as one
- * staging copy set and one launch per group of tiles.  All or nothing: every tile is checked first (host tiles: row_start too). */
+ * staging copy set and one launch per group of tiles.  All or nothing: every tile is checked first, as the single call checks its one. */
 int bv_engine_tiles_add_sparse_many(bv_engine *e, uint32_t n_tiles, const bv_sparse_tile *tiles, void *stream);
 int bv_sparse_tile_packed_layout(uint32_t n_sites, uint32_t n_entries, uint32_t width, int with_ranks, int with_groups,
                                  uint64_t offsets[7], uint64_t *total_bytes);

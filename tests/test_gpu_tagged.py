@@ -355,7 +355,29 @@ def test_packed_tile_api_errors_and_an_empty_tile(bv):
     assert eng._lib.bv_engine_tiles_add_sparse(eng._h, C.byref(t), None) == _capi.BV_ERR_INVALID_ARG
     assert eng._lib.bv_engine_tiles_begin(eng._h, S, 100000, 0, 1) == 0
     assert eng._lib.bv_engine_tiles_add_sparse(eng._h, C.byref(t), None) == _capi.BV_ERR_INVALID_ARG
-    eng.close()
+    # a host tile's row_start is walked before a kernel trusts it (as bv_engine_tiles_add_sparse_many does): it starts at 0,
+    # never decreases and ends at n_entries -- one entry per site here, then each of the three ways to break that
+    E = S
+    smp, bs, q, mq = (np.zeros(E, dtype=d) for d in (np.uint16, np.uint8, np.uint8, np.uint8))
+    rp = np.ones(E, dtype=np.uint16)
+
+    def one_per_site(rs):
+        return _capi.SparseTile(S, w, E, 0, rs.ctypes.data, smp.ctypes.data, bs.ctypes.data, q.ctypes.data, mq.ctypes.data, rp.ctypes.data,
+                                None, _capi.BV_MEM_HOST, 0)
+    for how in ("start", "decrease", "end"):
+        rs = np.arange(S + 1, dtype=np.uint32)
+        if how == "start":
+            rs[0] = 1
+        elif how == "decrease":
+            rs[5], rs[6] = rs[6] + 1, rs[6]
+        else:
+            rs[S] = rs[S] + 1
+        assert eng._lib.bv_engine_tiles_add_sparse(eng._h, C.byref(one_per_site(rs)), None) == _capi.BV_ERR_INVALID_ARG, how
+        assert eng._err() == "bv_engine_tiles_add_sparse: row_start must start at 0, never decrease and end at n_entries", how
+    # ... and the refusals left the job as it was: it still takes the same tile with its row_start intact
+    rs = np.arange(S + 1, dtype=np.uint32)
+    assert eng._lib.bv_engine_tiles_add_sparse(eng._h, C.byref(one_per_site(rs)), None) == 0, eng._err()
+    eng.close()   # (waits for the copy of the tile's arrays)
 
 
 @pytest.mark.parametrize("n,G,cov,ranks", [(10000, 32, 0.08, True), (10000, 64, 0.08, True), (6000, 12, 0.05, False), (20000, 40, 0.1, True), (3000, 9, 0.3, True)],
