@@ -104,7 +104,7 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_engine_text_parse", "bv_engine_text_submit"]
 
 # every symbol include/basevar_amd_bgzf.h declares
-BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch"]
+BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch", "bv_engine_bgzf_deflate"]
 
 _lib = None
 
@@ -205,5 +205,7 @@ def load():
     L.bv_engine_text_parse_bgzf.argtypes = [C.c_void_p, C.POINTER(BgzfRows), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]
     L.bv_engine_text_rows_fetch.restype = C.c_int
     L.bv_engine_text_rows_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+    L.bv_engine_bgzf_deflate.restype = C.c_int
+    L.bv_engine_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     _lib = L
     return L

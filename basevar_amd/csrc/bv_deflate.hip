@@ -1,0 +1,322 @@
+// bv_deflate.hip -- text deflated into BGZF members on the device (bv_engine_bgzf_deflate, include/basevar_amd_bgzf.h; the
+// contract is INTEGRATION.md section 2g).  The mirror of bv_inflate.hip.
+//
+// The host writer (host/bgzf_tabix.hpp) compresses every 0xff00-byte block of a `*.vcf.gz` / `*.cvg.gz` with one zlib
+// deflate() on the one thread that keeps the output in order.  Here every block is one single-wave workgroup.  The encoder is
+// bv_deflate_core.h, shared with a CPU harness: the block's text and the match table stay in LDS (63.8 KiB + 8 KiB of table +
+// 0.7 KiB of chunk state + 4 KiB of CRC tables: two workgroups per CU), the lanes share the hashing, the match measuring, the
+// table update and the CRC32, and walk the parse together.  What a block becomes depends on its text alone, so the device's
+// members are the CPU build's, byte for byte.
+//
+// A member is first written to a slot of its own (its size is not known before), then the slots of a chunk are compacted on
+// the device -- a prefix sum over the member sizes and a gather -- so that one contiguous run of members is copied back.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/basevar_amd_bgzf.h"
+#include "bv_deflate_core.h"
+#include "bv_engine_impl.h"
+
+using namespace bv_impl;
+
+namespace {
+
+constexpr uint32_t kSlotStride = 0x10020;  // bytes between two members' slots: 16-byte aligned, > 0xff00 + 31 + the 8 a word-wise reader may touch
+constexpr uint32_t kChunkBlocks = 1024;    // blocks per staged chunk (two chunks in flight)
+constexpr uint32_t kScanThreads = 256;
+static_assert(BV_DEF_MAX_BLOCK + BV_DEF_MEMBER_EXTRA + 8u <= kSlotStride && kSlotStride % 16u == 0, "a member and a reader's last word fit a slot");
+
+// one block of a staged chunk
+struct BvDefBlock {
+    uint64_t text_off;  // from the kernel's `text`
+    uint32_t n;         // 1 .. BV_DEF_MAX_BLOCK
+    uint32_t reserved_;
+};
+
+// the two aligned words around bytes [at, at + 4) of `base` (4-byte aligned), as one little-endian word
+__device__ inline uint32_t word_at(const uint32_t *base, uint32_t at, bool second) {
+    const uint32_t sh = 8u * (at & 3u);
+    const uint32_t w0 = base[at >> 2];
+    if (sh == 0) return w0;
+    const uint32_t w1 = second ? base[(at >> 2) + 1u] : 0u;
+    return (w0 >> sh) | (w1 << (32u - sh));
+}
+
+__global__ __launch_bounds__(64) void bv_bgzf_deflate_kernel(const uint8_t *__restrict__ text, const BvDefBlock *__restrict__ meta, uint32_t nblk,
+                                                             uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[BV_DEF_MAX_BLOCK + BV_DEF_TEXT_PAD];
+    __shared__ BvDefState S;
+    __shared__ uint32_t crc_tab[1024];
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= nblk) return;
+    const BvDefBlock m = meta[k];
+    if (m.n < 1u || m.n > BV_DEF_MAX_BLOCK) {  // (the host has refused such a block; nothing is read or written for it)
+        if (lane == 0) sizes[k] = 0;
+        return;
+    }
+    bv_inf_crc_tables(crc_tab, lane, 64);
+    // The text to LDS, a word per lane and step.  Its place in memory has any alignment: a word of the window is cut from the
+    // two aligned words of global memory around it; the second is read only where it holds a byte of the block (an aligned
+    // word with one byte inside the buffer lies inside the buffer's pages).
+    {
+        const uint8_t *g = text + m.text_off;
+        const uint32_t mis = (uint32_t)((uintptr_t)g & 3u);
+        const uint32_t *ga = reinterpret_cast<const uint32_t *>(g - mis);
+        uint32_t *w = reinterpret_cast<uint32_t *>(win);
+        const uint32_t words = (m.n + 3u) / 4u;
+        for (uint32_t j = lane; j < words; j += 64u) w[j] = word_at(ga, mis + 4u * j, 4u * j + 4u - mis < m.n);
+        // (what lies behind the text in the window is read by bv_def_load4 and never used: cleared, so that no run differs)
+        for (uint32_t j = words + lane; j < words + BV_DEF_TEXT_PAD / 4u && j < sizeof(win) / 4u; j += 64u) w[j] = 0;
+    }
+    __syncthreads();
+    const uint32_t total = bv_def_member(win, m.n, slots + (size_t)k * kSlotStride, &S, crc_tab, lane, 64, [](uint32_t c) {
+        for (int d = 32; d > 0; d >>= 1) c ^= __shfl_xor(c, d, 64);
+        return c;
+    });
+    if (lane == 0) sizes[k] = total;
+}
+
+// off[0] = 0, off[k + 1] = off[k] + sizes[k]: one workgroup, every thread a contiguous share
+__global__ __launch_bounds__(kScanThreads) void bv_bgzf_deflate_scan_kernel(const uint32_t *__restrict__ sizes, uint32_t nblk, uint32_t *__restrict__ off) {
+    __shared__ uint32_t part[kScanThreads];
+    const uint32_t t = threadIdx.x, per = (nblk + kScanThreads - 1u) / kScanThreads;
+    const uint32_t lo = t * per < nblk ? t * per : nblk, hi = lo + per < nblk ? lo + per : nblk;
+    uint32_t sum = 0;
+    for (uint32_t k = lo; k < hi; ++k) sum += sizes[k];
+    part[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (uint32_t i = 0; i < kScanThreads; ++i) { const uint32_t v = part[i]; part[i] = run; run += v; }
+        off[0] = 0;
+    }
+    __syncthreads();
+    uint32_t run = part[t];
+    for (uint32_t k = lo; k < hi; ++k) { run += sizes[k]; off[k + 1u] = run; }
+}
+
+// member k from its slot to packed + off[k]: bytes up to the first aligned word of the destination, whole words (cut from the
+// slot's aligned words; a slot has room behind the longest member for the last of them), bytes behind them
+__global__ __launch_bounds__(256) void bv_bgzf_deflate_gather_kernel(const uint8_t *__restrict__ slots, const uint32_t *__restrict__ off, uint32_t nblk,
+                                                                    uint8_t *__restrict__ packed) {
+    const uint32_t k = blockIdx.x, t = threadIdx.x;
+    if (k >= nblk) return;
+    const uint32_t size = off[k + 1u] - off[k];
+    const uint8_t *src = slots + (size_t)k * kSlotStride;
+    uint8_t *dst = packed + off[k];
+    const uint32_t align = (uint32_t)(-(uintptr_t)dst & 3u), head = align < size ? align : size;
+    const uint32_t words = (size - head) / 4u, tail = head + words * 4u;
+    if (t < head) dst[t] = src[t];
+    const uint32_t *sa = reinterpret_cast<const uint32_t *>(src);
+    uint32_t *da = reinterpret_cast<uint32_t *>(dst + head);
+    for (uint32_t j = t; j < words; j += 256u) da[j] = word_at(sa, head + 4u * j, true);
+    if (tail + t < size) dst[tail + t] = src[tail + t];
+}
+
+}  // namespace
+
+// Per-engine staging of bv_engine_bgzf_deflate: two pinned host + two device chunks of text (host text only), two chunks of
+// member slots, of packed members and of block tables, the member sizes and their running sums.
+struct BvDeflateState {
+    int device = 0;
+    hipStream_t cs = nullptr;  // copy stream of the text chunks
+    hipEvent_t ev_copied[2] = {}, ev_done[2] = {};
+    uint8_t *h_in[2] = {}, *d_in[2] = {};
+    size_t in_cap = 0;
+    BvDefBlock *h_meta[2] = {}, *d_meta[2] = {};
+    uint32_t *h_off[2] = {}, *d_off[2] = {}, *d_sizes[2] = {};
+    uint8_t *d_slots[2] = {}, *d_packed[2] = {};
+    size_t slots_cap = 0, packed_cap = 0;
+    bool ready = false;  // the kernel's LDS was accepted and the stream, events and block tables exist
+};
+
+void bv_deflate_state_free(BvDeflateState *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    if (t->cs) (void)hipStreamSynchronize(t->cs);
+    for (int k = 0; k < 2; ++k) {
+        if (t->h_in[k]) (void)hipHostFree(t->h_in[k]);
+        if (t->d_in[k]) (void)hipFree(t->d_in[k]);
+        if (t->h_meta[k]) (void)hipHostFree(t->h_meta[k]);
+        if (t->d_meta[k]) (void)hipFree(t->d_meta[k]);
+        if (t->h_off[k]) (void)hipHostFree(t->h_off[k]);
+        if (t->d_off[k]) (void)hipFree(t->d_off[k]);
+        if (t->d_sizes[k]) (void)hipFree(t->d_sizes[k]);
+        if (t->d_slots[k]) (void)hipFree(t->d_slots[k]);
+        if (t->d_packed[k]) (void)hipFree(t->d_packed[k]);
+        if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
+        if (t->ev_done[k]) (void)hipEventDestroy(t->ev_done[k]);
+    }
+    if (t->cs) (void)hipStreamDestroy(t->cs);
+    delete t;
+}
+
+namespace {
+
+int ensure_staging(bv_engine *e, BvDeflateState *t, size_t in_bytes, size_t blocks, size_t packed_bytes) {
+    if (!t->ready) {
+        // the kernel's LDS (window + tables) is more than the 64 KiB every launch may have: ask once whether this device takes it
+        hipFuncAttributes fa;
+        BV_HIP(e, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(bv_bgzf_deflate_kernel)));
+        int lds_max = 0;
+        BV_HIP(e, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
+        if (fa.sharedSizeBytes > (size_t)lds_max)
+            return fail(e, BV_ERR_NO_DEVICE, "bv_engine_bgzf_deflate: the deflate kernel needs " + std::to_string(fa.sharedSizeBytes) +
+                                                           " bytes of LDS per workgroup, the device offers " + std::to_string(lds_max));
+        if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {  // (each object if it is missing: a call that failed half-way is taken up where it stopped)
+            if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
+            if (!t->ev_done[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
+            if (!t->h_meta[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_meta[k]), sizeof(BvDefBlock) * kChunkBlocks));
+            if (!t->d_meta[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_meta[k]), sizeof(BvDefBlock) * kChunkBlocks));
+            if (!t->h_off[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_off[k]), sizeof(uint32_t) * (kChunkBlocks + 1)));
+            if (!t->d_off[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_off[k]), sizeof(uint32_t) * (kChunkBlocks + 1)));
+            if (!t->d_sizes[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_sizes[k]), sizeof(uint32_t) * kChunkBlocks));
+        }
+        t->ready = true;
+    }
+    if (in_bytes > t->in_cap) {
+        for (int k = 0; k < 2; ++k) {
+            if (t->h_in[k]) BV_HIP(e, hipHostFree(t->h_in[k]));
+            if (t->d_in[k]) BV_HIP(e, hipFree(t->d_in[k]));
+            t->h_in[k] = t->d_in[k] = nullptr;
+        }
+        t->in_cap = 0;
+        for (int k = 0; k < 2; ++k) {
+            BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_in[k]), in_bytes));
+            BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_in[k]), in_bytes));
+        }
+        t->in_cap = in_bytes;
+    }
+    for (int k = 0; k < 2; ++k) {
+        size_t have = t->slots_cap;
+        const int rc = grow_device(e, &t->d_slots[k], &have, blocks * kSlotStride);
+        if (rc != BV_OK) { t->slots_cap = 0; return rc; }
+        if (k == 1) t->slots_cap = have;
+    }
+    for (int k = 0; k < 2; ++k) {
+        size_t have = t->packed_cap;
+        const int rc = grow_device(e, &t->d_packed[k], &have, packed_bytes);
+        if (rc != BV_OK) { t->packed_cap = 0; return rc; }
+        if (k == 1) t->packed_cap = have;
+    }
+    return BV_OK;
+}
+
+struct Chunk {
+    uint32_t first, count;
+    uint64_t text_lo, text_bytes;  // the text its blocks span (block_off[first] .. block_off[first + count])
+};
+
+int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host_text, const uint64_t *block_off, uint32_t n, uint8_t *dst,
+                 uint64_t *member_off, hipStream_t st) {
+    BV_HIP(e, hipSetDevice(t->device));
+    // a call that failed part-way may have left work queued: the staging is free only once it is through
+    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
+    BV_HIP(e, hipStreamSynchronize(st));
+    // (BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS: a smaller chunk, for tests of the staging's reuse; never above the default)
+    uint32_t per = kChunkBlocks;
+    if (const char *v = std::getenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS")) {
+        const unsigned long long x = std::strtoull(v, nullptr, 10);
+        if (x > 0 && x < kChunkBlocks) per = (uint32_t)x;
+    }
+    std::vector<Chunk> chunks;
+    size_t in_max = 0;
+    for (uint32_t k = 0; k < n; k += per) {
+        const uint32_t count = std::min(per, n - k);
+        chunks.push_back(Chunk{k, count, block_off[k], block_off[k + count] - block_off[k]});
+        in_max = std::max<size_t>(in_max, chunks.back().text_bytes);
+    }
+    const size_t blocks_max = std::min<size_t>(per, n);
+    int rc = ensure_staging(e, t, host_text ? in_max + 4 : 0, blocks_max, in_max + (size_t)BV_DEF_MEMBER_EXTRA * blocks_max);
+    if (rc != BV_OK) return rc;
+    // a chunk's packed members are copied back while the next chunk is being coded: `finish` is one chunk behind `issue`
+    auto finish = [&](size_t ci) -> int {
+        const Chunk &c = chunks[ci];
+        const unsigned s = ci & 1u;
+        BV_HIP(e, hipEventSynchronize(t->ev_done[s]));  // the slot's kernels and the copy of its running sums are through
+        const uint32_t *off = t->h_off[s];
+        for (uint32_t j = 0; j < c.count; ++j) {
+            const uint32_t size = off[j + 1] - off[j];
+            if (size < BV_INF_MIN_MEMBER || size > block_off[c.first + j + 1] - block_off[c.first + j] + BV_DEF_MEMBER_EXTRA)
+                return fail(e, BV_ERR_HIP, "bv_engine_bgzf_deflate: block " + std::to_string(c.first + j) + " came back as a member of " +
+                                               std::to_string(size) + " bytes");
+            member_off[c.first + j + 1] = member_off[c.first + j] + size;
+        }
+        BV_HIP(e, hipMemcpyAsync(dst + member_off[c.first], t->d_packed[s], off[c.count], hipMemcpyDeviceToHost, st));
+        return BV_OK;
+    };
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const Chunk &c = chunks[ci];
+        const unsigned s = ci & 1u;
+        // (slot s is free: finish(ci - 2) has waited for its kernels, and its copy back was queued on `st` before what follows)
+        for (uint32_t j = 0; j < c.count; ++j) {
+            BvDefBlock &m = t->h_meta[s][j];
+            const uint64_t a = block_off[c.first + j];
+            m.text_off = host_text ? a - c.text_lo : a;
+            m.n = (uint32_t)(block_off[c.first + j + 1] - a);
+            m.reserved_ = 0;
+        }
+        if (host_text) {
+            std::memcpy(t->h_in[s], text + c.text_lo, c.text_bytes);
+            BV_HIP(e, hipMemcpyAsync(t->d_in[s], t->h_in[s], c.text_bytes, hipMemcpyHostToDevice, t->cs));
+        }
+        BV_HIP(e, hipMemcpyAsync(t->d_meta[s], t->h_meta[s], sizeof(BvDefBlock) * c.count, hipMemcpyHostToDevice, t->cs));
+        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
+        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
+        hipLaunchKernelGGL(bv_bgzf_deflate_kernel, dim3(c.count), dim3(64), 0, st, host_text ? (const uint8_t *)t->d_in[s] : text,
+                           (const BvDefBlock *)t->d_meta[s], c.count, t->d_slots[s], t->d_sizes[s]);
+        BV_HIP(e, hipGetLastError());
+        hipLaunchKernelGGL(bv_bgzf_deflate_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)t->d_sizes[s], c.count, t->d_off[s]);
+        BV_HIP(e, hipGetLastError());
+        hipLaunchKernelGGL(bv_bgzf_deflate_gather_kernel, dim3(c.count), dim3(256), 0, st, (const uint8_t *)t->d_slots[s], (const uint32_t *)t->d_off[s],
+                           c.count, t->d_packed[s]);
+        BV_HIP(e, hipGetLastError());
+        BV_HIP(e, hipMemcpyAsync(t->h_off[s], t->d_off[s], sizeof(uint32_t) * (c.count + 1), hipMemcpyDeviceToHost, st));
+        BV_HIP(e, hipEventRecord(t->ev_done[s], st));
+        if (ci >= 1 && (rc = finish(ci - 1)) != BV_OK) return rc;
+    }
+    if ((rc = finish(chunks.size() - 1)) != BV_OK) return rc;
+    BV_HIP(e, hipStreamSynchronize(st));
+    return BV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off, uint32_t n_blocks,
+                           uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream_) {
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: null engine");
+    if (!member_off) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: null member_off");
+    if (text_mem_kind != BV_MEM_HOST && text_mem_kind != BV_MEM_DEVICE)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: text_mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
+    member_off[0] = 0;
+    if (n_blocks == 0) return BV_OK;
+    if (!text || !block_off || !dst) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: null text/block_off/dst");
+    for (uint32_t k = 0; k < n_blocks; ++k) {
+        const uint64_t a = block_off[k], b = block_off[k + 1];
+        if (b < a || b > text_bytes)
+            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: block " + std::to_string(k) + ": block_off out of order or beyond text_bytes");
+        if (b - a < 1 || b - a > BV_DEF_MAX_BLOCK)
+            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: block " + std::to_string(k) + " is " + std::to_string(b - a) +
+                                                             " bytes: a BGZF block has 1 to 65280");
+    }
+    const uint64_t need = text_bytes + (uint64_t)BV_DEF_MEMBER_EXTRA * n_blocks;
+    if (dst_capacity < need)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: dst_capacity " + std::to_string(dst_capacity) + " < text_bytes + 31 * n_blocks = " +
+                                                         std::to_string(need));
+    if (!e->deflate) {
+        e->deflate = new BvDeflateState();
+        e->deflate->device = e->cfg.device;
+    }
+    return bgzf_deflate(e, e->deflate, static_cast<const uint8_t *>(text), text_mem_kind == BV_MEM_HOST, block_off, n_blocks, dst, member_off,
+                        stream_ ? (hipStream_t)stream_ : e->stream);
+}
+
+}  // extern "C"

@@ -15,6 +15,8 @@ struct BvTextState;   // bv_engine_text_parse / _submit (bv_text.hip)
 void bv_text_state_free(BvTextState *t);
 struct BvBgzfState;   // bv_engine_bgzf_inflate (bv_inflate.hip)
 void bv_bgzf_state_free(BvBgzfState *t);
+struct BvDeflateState;  // bv_engine_bgzf_deflate (bv_deflate.hip)
+void bv_deflate_state_free(BvDeflateState *t);
 
 struct bv_engine {
     bv_engine_config cfg;
@@ -133,6 +135,7 @@ struct bv_engine {
     hipEvent_t ev_entry = nullptr;     // what a lane waits for: the caller's stream at the time of the submit
     BvTextState *text = nullptr;       // created by the first bv_engine_text_parse
     BvBgzfState *bgzf = nullptr;       // created by the first bv_engine_bgzf_inflate
+    BvDeflateState *deflate = nullptr;  // created by the first bv_engine_bgzf_deflate
     mutable std::mutex mu;
     std::string err;
 };

@@ -538,6 +538,41 @@ class BaseTypeEngine:
             raise RuntimeError("bv_engine_bgzf_inflate failed (%d): %s" % (rc, self._err()))
         return text, dst_off, status
 
+    # ---- text, deflated into BGZF members on the device
+    def bgzf_deflate(self, text, block_bytes=0xff00, block_off=None):
+        """Text in, whole BGZF members out (bv_engine_bgzf_deflate): one member per block of `block_bytes` bytes (1 .. 0xff00;
+        the last block takes what is left), or per block text[block_off[k]:block_off[k + 1]] where `block_off` is given.
+
+        `text`: bytes / uint8 array, or a uint8 torch tensor on the engine's device, which is read where it lies (the caller has
+        synchronised what wrote it).  Returns (members, member_off): the members back to back as one uint8 array, member k at
+        members[member_off[k]:member_off[k + 1]], member_off uint64 [n + 1].  No end-of-file marker is appended."""
+        keep = text
+        if hasattr(text, "data_ptr"):  # a torch tensor
+            if text.dtype.itemsize != 1 or not text.is_contiguous():
+                raise ValueError("bgzf_deflate: a contiguous tensor of bytes")
+            kind = _capi.BV_MEM_DEVICE if text.is_cuda else _capi.BV_MEM_HOST
+            ptr, size = int(text.data_ptr()), int(text.numel())
+        else:
+            keep = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+            kind, ptr, size = _capi.BV_MEM_HOST, (keep.ctypes.data if keep.size else None), int(keep.size)
+        if block_off is None:
+            if not 1 <= int(block_bytes) <= 0xff00:
+                raise ValueError("bgzf_deflate: block_bytes is 1 to 0xff00")
+            off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
+        else:
+            off = np.ascontiguousarray(block_off, dtype=np.uint64)
+        n = int(off.size) - 1
+        if n < 0:
+            raise ValueError("bgzf_deflate: block_off needs n + 1 entries")
+        members = np.zeros(size + 31 * n, dtype=np.uint8)
+        member_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_bgzf_deflate(self._h, ptr, size, kind, off.ctypes.data, n, members.ctypes.data if members.size else None,
+                                              int(members.size), member_off.ctypes.data, None)
+        del keep
+        if rc != 0:
+            raise RuntimeError("bv_engine_bgzf_deflate failed (%d): %s" % (rc, self._err()), rc)
+        return members[:int(member_off[n])], member_off
+
 
 class TextBatch(BaseTypeBatch):
     """Records of BaseTypeEngine.lrt_text, plus the positions they belong to, the row states and the returned planes."""

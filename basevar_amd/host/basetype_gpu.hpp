@@ -325,6 +325,14 @@ public:
         return tb;
     }
 
+    // Text deflated into BGZF members on the device (bv_engine_bgzf_deflate, include/basevar_amd_bgzf.h): block k is
+    // text[block_off[k] .. block_off[k + 1]) of host memory, 1 to 0xff00 bytes; member k lands at dst + member_off[k].  `dst`
+    // has room for text_bytes + 31 * n_blocks bytes, `member_off` for n_blocks + 1 entries.  Blocks until dst is written.
+    void bgzf_deflate(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off) {
+        if (bv_engine_bgzf_deflate(e_, text, text_bytes, BV_MEM_HOST, block_off, n_blocks, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+    }
+
     // lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf, include/basevar_amd_bgzf.h), in two steps so
     // that a reader can hand the cursors to the next batch as soon as the parse has returned: parse_bgzf() inflates, indexes
     // and parses on the device (throws BgzfDataError for a damaged member); finish_bgzf() fetches the text the host still needs

@@ -9,6 +9,8 @@
 //                 (so that a reader can seek to a block), raw deflate inside, CRC32 + ISIZE behind; the 28-byte empty block as
 //                 end-of-file marker.  tell() is the VIRTUAL offset of the next byte: (file offset of its block) << 16 | (offset
 //                 inside the block's payload).
+//                 write_blocks() is a second way in: the same cut, the whole blocks of a batch compressed by one call of a
+//                 BlockDeflater (bv_call --deflate device: bv_engine_bgzf_deflate).
 //   TabixIndex    one call per data line (sequence name, 1-based position, virtual offsets before and after the line):
 //                 the binning index (UCSC bins over 2^29 bases, 16 kb leaves: runs of consecutive lines in one bin become a chunk),
 //                 the linear index (per 16 kb window the smallest offset of a line in it; empty windows take the next one's), the
@@ -26,12 +28,19 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 namespace bvamd {
+
+// Compresses whole blocks in one call: block k is text[block_off[k] .. block_off[k + 1]); member k -- a whole BGZF member --
+// goes to dst + member_off[k], member_off[0] = 0; dst has room for text_bytes + 31 * n_blocks bytes, member_off for
+// n_blocks + 1 entries.  (basetype_gpu.hpp's BaseTypeEngine::bgzf_deflate is one.)
+typedef std::function<void(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off)>
+    BlockDeflater;
 
 class BgzfWriter {
 public:
@@ -58,6 +67,36 @@ public:
         }
     }
     void write(const std::string &s) { write(s.data(), s.size()); }
+    // write(p, n) with the blocks that it completes compressed by one call of `deflate`: the cut is the same -- what is
+    // pending, then p, in blocks of kBlock bytes, the partial last block kept for the next call -- so the file inflates to the
+    // same bytes and every byte has the same place in its block.  block_file_off[j] is the file offset of the j-th block of
+    // (pending bytes, then p); its last entry is that of the block that is pending afterwards.
+    void write_blocks(const char *p, size_t n, const BlockDeflater &deflate, std::vector<uint64_t> &block_file_off) {
+        const size_t carry = buf_.size(), full = (carry + n) / kBlock;
+        block_file_off.assign(full + 1, block_off_);
+        if (full == 0) { buf_.insert(buf_.end(), p, p + n); return; }
+        const size_t bytes = full * kBlock;
+        const char *text = p;
+        if (carry) {  // (the blocks must lie in one piece: what was pending goes in front of them)
+            buf_.insert(buf_.end(), p, p + (bytes - carry));
+            text = buf_.data();
+        }
+        std::vector<uint64_t> off(full + 1), moff(full + 1, 0);
+        for (size_t k = 0; k <= full; ++k) off[k] = k * kBlock;
+        members_.resize(bytes + 31 * full);
+        deflate(text, bytes, off.data(), (uint32_t)full, members_.data(), moff.data());
+        for (size_t k = 0; k < full; ++k) {  // what came back is written as it is: hold it to the format first
+            const uint64_t a = moff[k], b = moff[k + 1];
+            if (b < a + 26 || b - a > 0x10000 || b > members_.size() || members_[a] != 0x1f || members_[a + 1] != 0x8b ||
+                (uint64_t)(members_[a + 16] | (members_[a + 17] << 8)) + 1 != b - a)
+                throw std::runtime_error("[ERROR] the block deflater returned something that is not a BGZF member");
+        }
+        if (std::fwrite(members_.data(), 1, moff[full], f_) != moff[full]) throw std::runtime_error("[ERROR] write failure on " + path_);
+        for (size_t k = 0; k <= full; ++k) block_file_off[k] = block_off_ + moff[k];
+        block_off_ += moff[full];
+        buf_.assign(p + (bytes - carry), p + n);
+    }
+    size_t pending() const { return buf_.size(); }
     // end the current block here (a reader can then start at tell() without inflating what came before)
     void flush() { if (!buf_.empty()) flush_block(); }
     void close() {
@@ -99,6 +138,7 @@ private:
     std::string path_;
     int level_ = Z_DEFAULT_COMPRESSION;
     std::vector<char> buf_;
+    std::vector<uint8_t> members_;  // write_blocks: what the deflater returned
     uint64_t block_off_ = 0;
 };
 
@@ -240,6 +280,27 @@ public:
                 const size_t t1 = s.find('\t', p), t2 = t1 == std::string::npos ? t1 : s.find('\t', t1 + 1);
                 if (t2 == std::string::npos || t2 >= e) throw std::runtime_error("[ERROR] a data line without two columns cannot be indexed");
                 idx_.add_line(s.substr(p, t1 - p), std::stoll(s.substr(t1 + 1, t2 - t1 - 1)), o0, bg_.tell());
+            }
+            p = e;
+        }
+    }
+    // The second way to write whole lines: as write_lines(), with the whole blocks that the batch completes compressed by one
+    // call of `deflate` (BgzfWriter::write_blocks).  Every line's place -- block of the batch, offset in the block -- is known
+    // from the cut alone; the index takes the lines once the blocks' file offsets are.  A plain output takes write_lines().
+    void write_lines(const std::string &s, const BlockDeflater &deflate) {
+        if (!gz_) { put(s.data(), s.size()); return; }
+        const size_t carry = bg_.pending();
+        std::vector<uint64_t> file_off;
+        bg_.write_blocks(s.data(), s.size(), deflate, file_off);
+        auto voff = [&](size_t at) { return (file_off[(carry + at) / BgzfWriter::kBlock] << 16) | (uint64_t)((carry + at) % BgzfWriter::kBlock); };
+        size_t p = 0;
+        while (p < s.size()) {
+            size_t e = s.find('\n', p);
+            e = (e == std::string::npos) ? s.size() : e + 1;
+            if (s[p] != '#') {
+                const size_t t1 = s.find('\t', p), t2 = t1 == std::string::npos ? t1 : s.find('\t', t1 + 1);
+                if (t2 == std::string::npos || t2 >= e) throw std::runtime_error("[ERROR] a data line without two columns cannot be indexed");
+                idx_.add_line(s.substr(p, t1 - p), std::stoll(s.substr(t1 + 1, t2 - t1 - 1)), voff(p), voff(e));
             }
             p = e;
         }

@@ -13,7 +13,7 @@
 //
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
-//           [--timing FILE.json] [--inflate device|host]
+//           [--timing FILE.json] [--inflate device|host] [--deflate device|host]
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -133,7 +133,7 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 
 int main(int argc, char **argv) {
     std::vector<std::string> batchfiles, bams;
-    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host";
+    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host", deflate_arg = "host";
     int mapq_thd = 10, threads = 4, n_gpus = 1;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -150,6 +150,7 @@ int main(int argc, char **argv) {
         else if (a == "--batch-sites") batch_sites = (uint32_t)std::stoul(next());
         else if (a == "--timing") timing_file = next();
         else if (a == "--inflate") inflate_arg = next();
+        else if (a == "--deflate") deflate_arg = next();
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--gpus") n_gpus = std::stoi(next());
         else if (a == "--devices") devices_arg = next();
@@ -178,6 +179,7 @@ int main(int argc, char **argv) {
     if (!(user_min_af > 0.f)) die("[ERROR] --min-af must be > 0");  // the reference refuses it too (caller.cpp:73)
     if (n_gpus < 1) die("[ERROR] --gpus must be >= 1");
     if (inflate_arg != "host" && inflate_arg != "device") die("[ERROR] --inflate wants device or host");
+    if (deflate_arg != "host" && deflate_arg != "device") die("[ERROR] --deflate wants device or host");
     // one engine per entry: --devices a,b,... (an ordinal may repeat: several engines on one GPU), else device, device+1, ...
     std::vector<int> devices;
     if (!devices_arg.empty()) {
@@ -255,6 +257,20 @@ int main(int argc, char **argv) {
     std::string hc = bvamd::cvg_header() + "\n";
     VCF.write_header(hv);
     CVG.write_header(hc);
+    // --deflate device: the whole 0xff00-byte blocks of every batch of lines are compressed by one bv_engine_bgzf_deflate call
+    // instead of one zlib deflate() each on the emitter thread (bgzf_tabix.hpp: TextOut::write_lines with a BlockDeflater; the
+    // headers and the last partial block of a file stay with zlib).  An engine is not re-entrant and the workers' engines are
+    // busy: the emitter thread makes a small one of its own on the first engine's device when its first batch arrives.
+    const auto ends_in_gz = [](const std::string &s) { return s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0; };
+    bool device_deflate = false;
+    if (deflate_arg == "device") {
+        device_deflate = ends_in_gz(out_vcf) || ends_in_gz(out_cvg);
+        if (!ends_in_gz(out_vcf) || !ends_in_gz(out_cvg))
+            std::cerr << "[NOTE] --deflate device applies to *.gz outputs: " << (device_deflate ? (ends_in_gz(out_vcf) ? out_cvg : out_vcf) : "both outputs")
+                      << " take" << (device_deflate ? "s" : "") << " the host path" << std::endl;
+    }
+    uint64_t members_deflated = 0;
+    double deflate_s = 0;
 
     // ---- batches are bounded by cells (2^28 cells = 5 x 256 MiB of planes per batch in flight), not by a site count that
     // ignores the row length: a launch carries ~0.1 ms of fill and drain whatever its size, so small batches run the engine
@@ -418,6 +434,15 @@ int main(int argc, char **argv) {
     size_t n_sites = 0, n_variants = 0;
     std::thread emitter([&]() {
         std::map<uint64_t, BatchPtr> waiting;  // finished out of order
+        std::unique_ptr<bvamd::BaseTypeEngine> deflate_engine;
+        const bvamd::BlockDeflater deflate = [&](const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst,
+                                                 uint64_t *member_off) {
+            const double t0 = StageClock::now();
+            if (!deflate_engine) deflate_engine.reset(new bvamd::BaseTypeEngine(1, 1, user_min_af, devices[0]));
+            deflate_engine->bgzf_deflate(text, text_bytes, block_off, n_blocks, dst, member_off);
+            members_deflated += n_blocks;
+            deflate_s += StageClock::now() - t0;
+        };
         uint64_t next_seq = 0;
         bool stopped = false;  // a batch failed: nothing behind it is written
         for (BatchPtr b; (b = to_emit.pop());) {
@@ -447,9 +472,20 @@ int main(int argc, char **argv) {
                         }
                     });
                     try {
+                        if (device_deflate) {
+                            // one call a file and batch: a call takes as long as its slowest block, however few blocks it has
+                            for (size_t t = 1; t < nt; ++t) {
+                                cvg_txt[0] += cvg_txt[t]; std::string().swap(cvg_txt[t]);
+                                vcf_txt[0] += vcf_txt[t]; std::string().swap(vcf_txt[t]);
+                            }
+                            CVG.write_lines(cvg_txt[0], deflate);
+                            VCF.write_lines(vcf_txt[0], deflate);
+                        }
                         for (size_t t = 0; t < nt; ++t) {
-                            CVG.write_lines(cvg_txt[t]);
-                            VCF.write_lines(vcf_txt[t]);
+                            if (!device_deflate) {
+                                CVG.write_lines(cvg_txt[t]);
+                                VCF.write_lines(vcf_txt[t]);
+                            }
                             n_variants += nv[t];
                         }
                     } catch (const std::exception &ex) { fail(ex.what()); }
@@ -570,6 +606,8 @@ int main(int argc, char **argv) {
         // runs, are inflated again with the next batch) against the members the files hold
         if (device_inflate)
             tf << ", \"inflate\": \"device\", \"members_inflated\": " << raw.members_handed << ", \"members_in_files\": " << raw.members_passed;
+        // --deflate device: whole output blocks compressed by the device, and the emitter's seconds inside those calls (part of emit_s)
+        if (device_deflate) tf << ", \"deflate\": \"device\", \"members_deflated\": " << members_deflated << ", \"deflate_s\": " << deflate_s;
         tf << "}\n";
     }
     return 0;

@@ -1,5 +1,5 @@
 /*
- * basevar_amd_bgzf.h -- BGZF members inflated on the device.
+ * basevar_amd_bgzf.h -- BGZF members inflated and written (section 2g) on the device.
  *
  * The reference reads its batchfiles through htslib's BGZF reader (src/basetype_caller.cpp:428 requires that format): a
  * chain of independent gzip members of at most 64 KiB of text each, inflated one after the other by zlib on the host.  Here
@@ -100,6 +100,21 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
  * buf[row_off[r] .. row_off[r + 1]); row_off has n_positions * n_files + 1 entries.  *bytes_needed is always written; if
  * capacity is smaller, nothing else is written, the call returns BV_OK and may be repeated with more room. */
 int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream);
+
+/* ---- the way back: text deflated into BGZF members on the device (basevar_amd/csrc/bv_deflate.hip).
+ * Block k is text[block_off[k] .. block_off[k + 1]), of 1 to 65,280 (0xff00) bytes; `text` is a host or a device buffer
+ * (text_mem_kind) of text_bytes bytes.  Every block becomes one whole BGZF member -- the 18-byte header with the 'BC' field,
+ * one raw DEFLATE stream (LZ77 with a 32 KiB window and the fixed Huffman codes, or a stored block where that is not smaller),
+ * CRC32, ISIZE -- of at most the block's bytes + 31.  The bytes of a member depend on the block's text and on nothing else.
+ * Member k lands at dst + member_off[k] (host memory), member_off[0] = 0; member_off[n_blocks + 1] is written for the caller.
+ * No end-of-file marker is written: that stays with the writer.
+ * Returns BV_ERR_INVALID_ARG for NULL arguments, a block of 0 bytes or of more than 65,280, offsets out of order or beyond
+ * text_bytes, text_mem_kind neither BV_MEM_HOST nor BV_MEM_DEVICE, or dst_capacity < text_bytes + 31 * n_blocks (the worst
+ * case, known before the call).  n_blocks = 0: BV_OK, member_off[0] alone is written.  Any number of blocks: the engine stages
+ * them in chunks.  Blocks until dst is written.  `stream`: a hipStream_t, or NULL for the engine's own; text in device memory
+ * must be complete on it. */
+int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off,
+                           uint32_t n_blocks, uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream);
 
 #ifdef __cplusplus
 }
