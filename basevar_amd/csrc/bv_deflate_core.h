@@ -12,7 +12,8 @@
 //   len(p)   = the common prefix of text[p ..) and text[cand(p) ..), at most min(258, n - p); a match if it is >= 4 and
 //              p - cand(p) <= 32768
 //   the parse is greedy from p = 0: a match at p is taken whole, else text[p] is a literal.
-// A serial coder with a head-of-chain hash table computes exactly this.  Here the positions are handled BV_DEF_CHUNK at a
+// A serial coder with a head-of-chain hash table computes exactly this (tests/deflate_model.py is one, written from these lines;
+// the tests hold this file's members to its bytes).  Here the positions are handled BV_DEF_CHUNK at a
 // time, in steps that are separated by BV_DEF_WAVE_SYNC and are data-parallel inside:
 //   1  every position of the chunk reads the table as the chunks before left it and posts its hash;
 //   2  ... takes the nearest earlier position of its own chunk with the same hash in its place, if there is one (so a match at
@@ -171,7 +172,7 @@ BV_DEF_FN uint32_t bv_def_fixed(const uint8_t *text, uint32_t n, uint8_t *out, u
             }
             S->last[i] = (uint8_t)last;
             S->len[i] = (uint16_t)len;
-            S->dist[i] = (uint16_t)(len ? p - (c - 1u) - 1u : 0u);  // distance - 1: 32768 does not fit 16 bits
+            S->dist[i] = (uint16_t)(len ? p - (c - 1u) - 1u : 0u);  // distance - 1: 0 .. 32767
         }
         BV_DEF_WAVE_SYNC();
         for (uint32_t i = lane; i < BV_DEF_CHUNK; i += nlanes)

@@ -1,7 +1,10 @@
 """CPU tests (no GPU) of the device DEFLATE encoder: the core the kernel compiles (basevar_amd/csrc/bv_deflate_core.h), built
 with g++ under ASan + UBSan (tests/cpp/deflate_core_check.cpp), over the corpus of tests/deflate_corpus.py.  zlib, the CPU build
 of the device decoder (tests/cpp/inflate_core_check.cpp) and the bit-by-bit tracer of tests/deflate_writer.py judge what it
-writes; the size of what it writes is held to 2.5 times zlib's level 6 on VCF records."""
+writes; the size of what it writes is held to 2.5 times zlib's level 6 on VCF records.  Which bytes it writes is held to
+tests/deflate_model.py, a serial restatement of the header's definition that shares no code with the encoder: over the edge
+corpus (deflate_corpus.edge_corpus(): the window's bound, every length and distance code, the stored-or-fixed tie, the
+64-position schedule, collisions, block ends) and over the corpus above, member for member, byte for byte."""
 import os
 import re
 import subprocess
@@ -13,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bgzf_corpus as bc  # noqa: E402
 import deflate_corpus as dc  # noqa: E402
+import deflate_model as dm  # noqa: E402
 import deflate_writer as dw  # noqa: E402
 
 
@@ -121,3 +125,119 @@ def test_the_writers_second_way_cuts_where_the_first_does(tmp_path):
         # every whole block but the header's went through the deflater; what it wrote is not what zlib wrote
         assert blocks == sum(1 for _, _, p in blocks_batch if len(p) == dc.MAX_BLOCK)
         assert open(host, "rb").read() != open(batch, "rb").read()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The encoder against the model.  What these tests add, by one-line changes to bv_deflate_core.h that were each run through
+# this file on the CPU build (`before`: the tests above; `model`: the two byte-for-byte tests below):
+#   window `<` for `<=`                              before: all pass                      model: fails (edge corpus)
+#   dist stored without `- 1`                        before: 4 of 6 fail                   model: fails
+#   ... and read back without `+ 1` as well          no byte changes: 32768 fits the uint16_t, the `- 1` is a convention
+#   `len == 258` case removed (284 + 31 is written)  before: the one_byte size bound fails model: fails; zlib accepts the stream
+#   0x190 -> 0x191                                   before: zlib refuses the members      model: fails
+#   the in-chunk candidate not taken                 before: the two size tests fail       model: fails
+#   `last` always 1                                  no byte changes on one lane: the writes of step 3 run in ascending order and
+#                                                    the last one stays.  On the device they are one store of 64 lanes to one
+#                                                    address; there the GPU test against the model is the check
+#   `measure` always true, `p >= cur` dropped        no byte changes: positions the parse has passed are measured and never read
+#   the tie turned to fixed (`>` for `>=`)           before: random_sizes_1_64 fails       model: fails, edge corpus and corpus()
+
+
+@pytest.fixture(scope="module")
+def edge(tmp_path_factory):
+    """the edge corpus: ([(name, [blocks])], every block, the sanitized CPU build's members, the model's members)"""
+    d = tmp_path_factory.mktemp("deflate_edge")
+    core = dc.cxx("deflate_core_check", d, sanitize=True)
+    entries = dc.edge_corpus()
+    text, sizes = dc.edge_text(entries)
+    members = dc.split_members(dc.cpu_members(core, text, sizes, d))
+    assert len(members) == len(sizes)
+    blocks = list(dc.blocks_of(text, sizes))
+    return entries, blocks, members, [dm.member(b) for b in blocks]
+
+
+def first_difference(got, want):
+    """where two members of one text part, in the tracer's tokens"""
+    try:
+        a, b = dc.traced(got).tokens, dc.traced(want).tokens
+    except Exception as e:  # (not a stream at all)
+        return "the tracer: %r" % (e,)
+    at = 0
+    for k, (x, y) in enumerate(zip(a, b)):
+        if x != y:
+            return "token %d, at byte %d of the text: the encoder wrote %r, the model %r" % (k, at, x, y)
+        at += 1 if isinstance(x, int) else x[0]
+    if len(a) != len(b):
+        return "%d tokens against the model's %d" % (len(a), len(b))
+    return "the same tokens; member bytes %d against %d, first difference at byte %d" % (
+        len(got), len(want), next((i for i, (x, y) in enumerate(zip(got, want)) if x != y), min(len(got), len(want))))
+
+
+def assert_members_are_the_models(names, members, expected):
+    bad = [(name, first_difference(m, e)) for name, m, e in zip(names, members, expected) if m != e]
+    assert not bad, "%d of %d members differ from the model's; the first: %s: %s" % (len(bad), len(members), bad[0][0], bad[0][1])
+
+
+def test_the_edge_corpus_goes_where_it_is_meant_to_in_the_models_members(edge):
+    """the conditions on the corpus, on what the model writes: they hold whatever the encoder does"""
+    entries, blocks, _, model = edge
+    for m, block in zip(model, blocks):
+        dc.check_member(m, block)
+    rep = dc.edge_report(model, blocks)
+    dc.assert_edge_conditions(rep)
+    # what single entries are for, read from the model's tokens
+    at = {}
+    k = 0
+    for name, bs in entries:
+        at[name] = [dc.traced(m) for m in model[k:k + len(bs)]]
+        k += len(bs)
+    window = [[t for t in tr.tokens if not isinstance(t, int) and t[1] > 30000] for tr in at["window"]]
+    # (32767 and 32768 coded for both x and both tails; 32769 refused at every byte of x: literals)
+    assert [[t[1] for t in w] for w in window] == [[32767]] * 3 + [[32768]] * 3 + [[]] * 3
+    assert [w[0][0] for w in window[:6]] == [4, 4, 12] * 2 and at["window"][8].tokens[-14:] == list(b"klmnopqrstuv!?")
+    # a shadowed repeat is literals, the same repeat without the collision a match
+    coll = at["collisions"]
+    n_lit = [sum(1 for t in tr.tokens if isinstance(t, int)) for tr in coll]  # (eight blocks a pair: four shadowed, four not)
+    assert len(coll) % 8 == 0 and all(n_lit[k + j] > n_lit[k + 4 + j] for k in range(0, len(coll), 8) for j in range(4)), n_lit
+    # the schedule's tail codes to the same tokens behind every lead (the lead's bytes are literals: they occur once)
+    tails = [tr.tokens[lead:] for lead, tr in zip(list(range(64)) + [62, 63, 64, 65, 66, 126, 127, 128, 129, 130], at["schedule"])]
+    assert len(tails) == 74 and all(t == tails[0] for t in tails)
+    assert (258, 302) in tails[0] and (40, 158) in tails[0] and (4, 7) in tails[0] and (4, 9) in tails[0] and (4, 10) in tails[0]
+    # every stored-or-fixed size of n different bytes >= 144: the first tie and the first larger one are where the bit count says
+    small = at["stored_or_fixed"][:40]
+    kinds = ["fixed" if tr.blocks[0][0] == 1 else "stored" for tr in small]
+    first_stored = kinds.index("stored") + 1
+    assert kinds == ["fixed"] * (first_stored - 1) + ["stored"] * (41 - first_stored)
+    assert (10 + 9 * (first_stored - 1) + 7) // 8 < 5 + first_stored - 1 and (10 + 9 * first_stored + 7) // 8 == 5 + first_stored
+    # the largest blocks: fixed at the last bit that fits, stored from the first bit of the tie
+    assert ["fixed" if tr.blocks[0][0] == 1 else "stored" for tr in at["stored_or_fixed"][-6:]] == ["fixed", "stored", "stored", "stored", "fixed", "stored"]
+    print("edge corpus: %d blocks, %d bytes; %d stored, %d of them ties; %d literals >= 144 beside matches; %d distances" % (
+        len(blocks), sum(len(b) for b in blocks), rep["stored"], rep["ties"], rep["high_literals_beside_matches"], len(rep["distances"])))
+
+
+def test_edge_members_are_the_models_byte_for_byte(edge):
+    entries, blocks, members, model = edge
+    names = ["%s[%d]" % (name, k) for name, bs in entries for k in range(len(bs))]
+    assert_members_are_the_models(names, members, model)
+    dc.assert_edge_conditions(dc.edge_report(members, blocks))
+
+
+def test_edge_members_inflate_with_zlib_and_with_the_device_decoders_core(edge, tmp_path):
+    _, blocks, members, _ = edge
+    for m, block in zip(members, blocks):
+        dc.check_member(m, block)
+    exe = bc.build_core_check(tmp_path, sanitize=False)
+    p, rows = bc.core_verdicts(exe, members, tmp_path)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert len(rows) == len(members) and all(r[0] == bc.OK and r[1] == bc.OK for r in rows)
+
+
+def test_members_of_the_corpus_are_the_models_byte_for_byte(coded):
+    """Every block of every entry of corpus(): none is left out (the model takes about a second for a megabyte of text).  For
+    random_sizes_1_64 this is the exact stored-or-fixed decision where the test above asks for `stored, or smaller`."""
+    n = 0
+    for name, (text, sizes, members) in coded.items():
+        blocks = list(dc.blocks_of(text, sizes))
+        assert_members_are_the_models(["%s[%d]" % (name, k) for k in range(len(blocks))], members, [dm.member(b) for b in blocks])
+        n += len(blocks)
+    assert n > 380

@@ -1,6 +1,8 @@
 """GPU tests of bv_engine_bgzf_deflate (include/basevar_amd_bgzf.h): the corpus of tests/deflate_corpus.py deflated on the
 device.  The oracle is the CPU build of the same encoder core (tests/test_deflate_cpu.py holds it to zlib, to the device
-decoder's core and to the size condition under ASan + UBSan): the device's members are its members, byte for byte."""
+decoder's core and to the size condition under ASan + UBSan): the device's members are its members, byte for byte.  Over the
+edge corpus (deflate_corpus.edge_corpus()) the oracle is tests/deflate_model.py, a serial restatement of the encoder's definition
+that shares no code with the kernel, and the CPU build beside it."""
 import ctypes as C
 import gzip
 import os
@@ -14,6 +16,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import deflate_corpus as dc  # noqa: E402
+import deflate_model as dm  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -171,3 +174,96 @@ def test_no_blocks(eng):
     assert moff[0] == 0 and moff[1] == 0xEEEE
     members, off = eng.bgzf_deflate(b"")
     assert members.size == 0 and off.tolist() == [0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the device against the model (tests/deflate_model.py) over the edge corpus
+
+_model = {}
+
+
+def model_member(block):
+    if block not in _model:
+        _model[block] = dm.member(block)
+    return _model[block]
+
+
+@pytest.fixture(scope="module")
+def edge(tmp_path_factory):
+    """([(name, [blocks])], text, sizes, the model's members back to back, the CPU core's)"""
+    d = tmp_path_factory.mktemp("deflate_edge_gpu")
+    core = dc.cxx("deflate_core_check", d)
+    entries = dc.edge_corpus()
+    text, sizes = dc.edge_text(entries)
+    model = b"".join(model_member(b) for b in dc.blocks_of(text, sizes))
+    return entries, text, sizes, model, dc.cpu_members(core, text, sizes, d)
+
+
+def assert_members(got, want, sizes, what):
+    """the members back to back against the expected ones; on a difference, the first block that differs"""
+    if got == want:
+        return
+    a, b = dc.split_members(got), dc.split_members(want)
+    k = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+    raise AssertionError("%s: %d members against %d; the first difference is block %d of %d bytes (%d bytes against %d)" % (
+        what, len(a), len(b), k, sizes[k] if k < len(sizes) else -1, len(a[k]) if k < len(a) else -1, len(b[k]) if k < len(b) else -1))
+
+
+def test_edge_members_are_the_models_bytes_and_the_cpu_cores(eng, edge):
+    _, text, sizes, model, cpu = edge
+    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    assert_members(members.tobytes(), model, sizes, "the device against the model")
+    assert_members(members.tobytes(), cpu, sizes, "the device against the CPU build")
+    assert off.tolist() == offsets([len(m) for m in dc.split_members(model)]).tolist()
+
+
+def test_edge_text_as_a_device_pointer_at_every_misalignment(eng, edge):
+    """The slices [0:], [1:], [2:], [3:] of one allocation of len(text) + 3 bytes, each filled to its end: the text, and a last
+    block of the 3, 2, 1 or 0 bytes that are left, so that the last block ends with the slice whatever its base."""
+    import torch
+    _, text, sizes, model, _ = edge
+    assert {s % 4 for s in sizes} == {0, 1, 2, 3}
+    buf = torch.zeros(len(text) + 3, dtype=torch.uint8, device="cuda:0")
+    assert buf.data_ptr() % 4 == 0
+    for k in range(4):
+        rest = text[:3 - k]
+        fill, ss = text + rest, sizes + ([len(rest)] if rest else [])
+        buf[k:] = torch.frombuffer(bytearray(fill), dtype=torch.uint8).to("cuda:0")
+        torch.cuda.synchronize()
+        view = buf[k:]
+        assert view.data_ptr() % 4 == k and view.numel() == sum(ss)
+        members, off = eng.bgzf_deflate(view, block_off=offsets(ss))
+        assert_members(members.tobytes(), model + (model_member(rest) if rest else b""), ss, "a text %d bytes behind an aligned word" % k)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1023, 1024, 1025, 2500])
+def test_member_off_is_the_running_sum_of_the_models_sizes(eng, edge, monkeypatch, n):
+    """n small blocks in one call with the staging as it is: the 256 threads of the scan have no block, one, or several, and
+    calls of more than 1024 blocks cross staging chunks by themselves"""
+    monkeypatch.delenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", raising=False)
+    entries = dict(edge[0])
+    pool = [b for b in entries["ends"] + entries["collisions"] + entries["stored_or_fixed"] if len(b) < 200]
+    assert len(pool) > 150 and {len(b) for b in pool} >= set(range(1, 8))
+    blocks = [pool[(k * 37 + k // len(pool)) % len(pool)] for k in range(n)]
+    expect = [model_member(b) for b in blocks]
+    assert n < 200 or len({len(m) for m in expect}) > 40
+    members, off = eng.bgzf_deflate(b"".join(blocks), block_off=offsets([len(b) for b in blocks]))
+    assert off.dtype == np.uint64 and off.tolist() == offsets([len(m) for m in expect]).tolist()
+    assert_members(members.tobytes(), b"".join(expect), [len(b) for b in blocks], "%d small blocks" % n)
+
+
+def test_edge_members_do_not_depend_on_the_staging_chunk(eng, edge, monkeypatch):
+    _, text, sizes, model, _ = edge
+    monkeypatch.setenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", "3")
+    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    assert_members(members.tobytes(), model, sizes, "three blocks a staging chunk")
+    assert int(off[-1]) == len(model)
+
+
+def test_the_device_inflate_reads_the_edge_members_back(eng, edge):
+    from basevar_amd import _capi
+    _, text, sizes, model, _ = edge
+    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    back, dst_off, status = eng.bgzf_inflate(members, off)
+    assert (status == _capi.BV_BGZF_OK).all() and back.tobytes() == text
+    assert [int(b - a) for a, b in zip(dst_off[:-1], dst_off[1:])] == sizes
