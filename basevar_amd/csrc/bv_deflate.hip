@@ -1,5 +1,5 @@
 // bv_deflate.hip -- text deflated into BGZF members on the device (bv_engine_bgzf_deflate, include/basevar_amd_bgzf.h; the
-// contract is INTEGRATION.md section 2g).  The mirror of bv_inflate.hip.
+// contract is INTEGRATION.md section 2g).  The text goes to the device as bv_inflate.hip's members do: bv_chunk_stage.h.
 //
 // The host writer (host/bgzf_tabix.hpp) compresses every 0xff00-byte block of a `*.vcf.gz` / `*.cvg.gz` with one zlib
 // deflate() on the one thread that keeps the output in order.  Here every block is one single-wave workgroup.  The encoder is
@@ -13,14 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "bv_deflate_core.h"
-#include "bv_engine_impl.h"
+#include "bv_chunk_stage.h"
 
 using namespace bv_impl;
 
@@ -120,93 +119,33 @@ __global__ __launch_bounds__(256) void bv_bgzf_deflate_gather_kernel(const uint8
 
 }  // namespace
 
-// Per-engine staging of bv_engine_bgzf_deflate: two pinned host + two device chunks of text (host text only), two chunks of
-// member slots, of packed members and of block tables, the member sizes and their running sums.
+// Per-engine staging of bv_engine_bgzf_deflate: the chunks of text (host text only), each with its block table behind it, and
+// the running sums that come back (bv_chunk_stage.h has the rule of their reuse); per slot the member slots, the packed
+// members, the member sizes and their running sums on the device.
 struct BvDeflateState {
     int device = 0;
-    hipStream_t cs = nullptr;  // copy stream of the text chunks
-    hipEvent_t ev_copied[2] = {}, ev_done[2] = {};
-    uint8_t *h_in[2] = {}, *d_in[2] = {};
-    size_t in_cap = 0;
-    BvDefBlock *h_meta[2] = {}, *d_meta[2] = {};
-    uint32_t *h_off[2] = {}, *d_off[2] = {}, *d_sizes[2] = {};
-    uint8_t *d_slots[2] = {}, *d_packed[2] = {};
-    size_t slots_cap = 0, packed_cap = 0;
-    bool ready = false;  // the kernel's LDS was accepted and the stream, events and block tables exist
+    ChunkStage in;
+    // Touched on the call's stream alone, by the slot's kernels and the copies behind them.  The copy back of `d_packed` is
+    // queued by finish(), which bgzf_deflate calls for chunk k before it issues chunk k + 2: stream order keeps them apart.
+    struct Slot {
+        uint8_t *d_slots = nullptr, *d_packed = nullptr;
+        uint32_t *d_sums = nullptr;  // sizes [kChunkBlocks], then off [kChunkBlocks + 1]
+        size_t slots_cap = 0, packed_cap = 0, sums_cap = 0;
+    } slot[2];
+    bool lds_ok = false;  // the kernel's LDS was accepted
 };
 
 void bv_deflate_state_free(BvDeflateState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    if (t->cs) (void)hipStreamSynchronize(t->cs);
-    for (int k = 0; k < 2; ++k) {
-        if (t->h_in[k]) (void)hipHostFree(t->h_in[k]);
-        if (t->d_in[k]) (void)hipFree(t->d_in[k]);
-        if (t->h_meta[k]) (void)hipHostFree(t->h_meta[k]);
-        if (t->d_meta[k]) (void)hipFree(t->d_meta[k]);
-        if (t->h_off[k]) (void)hipHostFree(t->h_off[k]);
-        if (t->d_off[k]) (void)hipFree(t->d_off[k]);
-        if (t->d_sizes[k]) (void)hipFree(t->d_sizes[k]);
-        if (t->d_slots[k]) (void)hipFree(t->d_slots[k]);
-        if (t->d_packed[k]) (void)hipFree(t->d_packed[k]);
-        if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
-        if (t->ev_done[k]) (void)hipEventDestroy(t->ev_done[k]);
-    }
-    if (t->cs) (void)hipStreamDestroy(t->cs);
+    chunk_stage_free(t->in);
+    for (BvDeflateState::Slot &sl : t->slot)
+        for (void *b : {(void *)sl.d_slots, (void *)sl.d_packed, (void *)sl.d_sums})
+            if (b) (void)hipFree(b);
     delete t;
 }
 
 namespace {
-
-int ensure_staging(bv_engine *e, BvDeflateState *t, size_t in_bytes, size_t blocks, size_t packed_bytes) {
-    if (!t->ready) {
-        // the kernel's LDS (window + tables) is more than the 64 KiB every launch may have: ask once whether this device takes it
-        hipFuncAttributes fa;
-        BV_HIP(e, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(bv_bgzf_deflate_kernel)));
-        int lds_max = 0;
-        BV_HIP(e, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
-        if (fa.sharedSizeBytes > (size_t)lds_max)
-            return fail(e, BV_ERR_NO_DEVICE, "bv_engine_bgzf_deflate: the deflate kernel needs " + std::to_string(fa.sharedSizeBytes) +
-                                                           " bytes of LDS per workgroup, the device offers " + std::to_string(lds_max));
-        if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {  // (each object if it is missing: a call that failed half-way is taken up where it stopped)
-            if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
-            if (!t->ev_done[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
-            if (!t->h_meta[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_meta[k]), sizeof(BvDefBlock) * kChunkBlocks));
-            if (!t->d_meta[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_meta[k]), sizeof(BvDefBlock) * kChunkBlocks));
-            if (!t->h_off[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_off[k]), sizeof(uint32_t) * (kChunkBlocks + 1)));
-            if (!t->d_off[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_off[k]), sizeof(uint32_t) * (kChunkBlocks + 1)));
-            if (!t->d_sizes[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_sizes[k]), sizeof(uint32_t) * kChunkBlocks));
-        }
-        t->ready = true;
-    }
-    if (in_bytes > t->in_cap) {
-        for (int k = 0; k < 2; ++k) {
-            if (t->h_in[k]) BV_HIP(e, hipHostFree(t->h_in[k]));
-            if (t->d_in[k]) BV_HIP(e, hipFree(t->d_in[k]));
-            t->h_in[k] = t->d_in[k] = nullptr;
-        }
-        t->in_cap = 0;
-        for (int k = 0; k < 2; ++k) {
-            BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_in[k]), in_bytes));
-            BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_in[k]), in_bytes));
-        }
-        t->in_cap = in_bytes;
-    }
-    for (int k = 0; k < 2; ++k) {
-        size_t have = t->slots_cap;
-        const int rc = grow_device(e, &t->d_slots[k], &have, blocks * kSlotStride);
-        if (rc != BV_OK) { t->slots_cap = 0; return rc; }
-        if (k == 1) t->slots_cap = have;
-    }
-    for (int k = 0; k < 2; ++k) {
-        size_t have = t->packed_cap;
-        const int rc = grow_device(e, &t->d_packed[k], &have, packed_bytes);
-        if (rc != BV_OK) { t->packed_cap = 0; return rc; }
-        if (k == 1) t->packed_cap = have;
-    }
-    return BV_OK;
-}
 
 struct Chunk {
     uint32_t first, count;
@@ -216,15 +155,11 @@ struct Chunk {
 int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host_text, const uint64_t *block_off, uint32_t n, uint8_t *dst,
                  uint64_t *member_off, hipStream_t st) {
     BV_HIP(e, hipSetDevice(t->device));
-    // a call that failed part-way may have left work queued: the staging is free only once it is through
-    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
-    BV_HIP(e, hipStreamSynchronize(st));
-    // (BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS: a smaller chunk, for tests of the staging's reuse; never above the default)
-    uint32_t per = kChunkBlocks;
-    if (const char *v = std::getenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS")) {
-        const unsigned long long x = std::strtoull(v, nullptr, 10);
-        if (x > 0 && x < kChunkBlocks) per = (uint32_t)x;
-    }
+    int rc = chunk_stage_begin(e, t->in, st);
+    if (rc == BV_OK)
+        rc = kernel_lds_fits(e, "bv_engine_bgzf_deflate: the deflate kernel", reinterpret_cast<const void *>(bv_bgzf_deflate_kernel), t->device, &t->lds_ok);
+    if (rc != BV_OK) return rc;
+    const uint32_t per = (uint32_t)chunk_limit_from_env("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", kChunkBlocks);
     std::vector<Chunk> chunks;
     size_t in_max = 0;
     for (uint32_t k = 0; k < n; k += per) {
@@ -233,14 +168,21 @@ int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host
         in_max = std::max<size_t>(in_max, chunks.back().text_bytes);
     }
     const size_t blocks_max = std::min<size_t>(per, n);
-    int rc = ensure_staging(e, t, host_text ? in_max + 4 : 0, blocks_max, in_max + (size_t)BV_DEF_MEMBER_EXTRA * blocks_max);
+    // a staged chunk: the text (host text only; the kernel reads whole words around it), then the block table
+    rc = chunk_stage_reserve(e, t->in, (host_text ? up16(in_max + 4) : 0) + sizeof(BvDefBlock) * blocks_max, sizeof(uint32_t) * (kChunkBlocks + 1));
     if (rc != BV_OK) return rc;
+    for (BvDeflateState::Slot &sl : t->slot) {
+        if ((rc = grow_device(e, &sl.d_slots, &sl.slots_cap, blocks_max * kSlotStride)) != BV_OK) return rc;
+        if ((rc = grow_device(e, &sl.d_packed, &sl.packed_cap, in_max + (size_t)BV_DEF_MEMBER_EXTRA * blocks_max)) != BV_OK) return rc;
+        if ((rc = grow_device(e, &sl.d_sums, &sl.sums_cap, sizeof(uint32_t) * (2 * kChunkBlocks + 1))) != BV_OK) return rc;
+    }
     // a chunk's packed members are copied back while the next chunk is being coded: `finish` is one chunk behind `issue`
     auto finish = [&](size_t ci) -> int {
         const Chunk &c = chunks[ci];
         const unsigned s = ci & 1u;
-        BV_HIP(e, hipEventSynchronize(t->ev_done[s]));  // the slot's kernels and the copy of its running sums are through
-        const uint32_t *off = t->h_off[s];
+        const int rw = chunk_stage_wait_done(e, t->in, s);  // the slot's kernels and the copy of its running sums are through
+        if (rw != BV_OK) return rw;
+        const uint32_t *off = reinterpret_cast<const uint32_t *>(t->in.slot[s].back);
         for (uint32_t j = 0; j < c.count; ++j) {
             const uint32_t size = off[j + 1] - off[j];
             if (size < BV_INF_MIN_MEMBER || size > block_off[c.first + j + 1] - block_off[c.first + j] + BV_DEF_MEMBER_EXTRA)
@@ -248,37 +190,39 @@ int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host
                                                std::to_string(size) + " bytes");
             member_off[c.first + j + 1] = member_off[c.first + j] + size;
         }
-        BV_HIP(e, hipMemcpyAsync(dst + member_off[c.first], t->d_packed[s], off[c.count], hipMemcpyDeviceToHost, st));
+        BV_HIP(e, hipMemcpyAsync(dst + member_off[c.first], t->slot[s].d_packed, off[c.count], hipMemcpyDeviceToHost, st));
         return BV_OK;
     };
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
         const Chunk &c = chunks[ci];
         const unsigned s = ci & 1u;
-        // (slot s is free: finish(ci - 2) has waited for its kernels, and its copy back was queued on `st` before what follows)
+        // (finish(ci - 2) has waited for the slot's kernels on the host: the stricter wait, kept because it reads the sums)
+        if ((rc = chunk_stage_fill(e, t->in, s)) != BV_OK) return rc;
+        uint8_t *h_in = t->in.slot[s].h;
+        const size_t meta_at = host_text ? up16(c.text_bytes + 4) : 0;
+        if (host_text) std::memcpy(h_in, text + c.text_lo, c.text_bytes);
+        BvDefBlock *h_meta = reinterpret_cast<BvDefBlock *>(h_in + meta_at);
         for (uint32_t j = 0; j < c.count; ++j) {
-            BvDefBlock &m = t->h_meta[s][j];
+            BvDefBlock &m = h_meta[j];
             const uint64_t a = block_off[c.first + j];
             m.text_off = host_text ? a - c.text_lo : a;
             m.n = (uint32_t)(block_off[c.first + j + 1] - a);
             m.reserved_ = 0;
         }
-        if (host_text) {
-            std::memcpy(t->h_in[s], text + c.text_lo, c.text_bytes);
-            BV_HIP(e, hipMemcpyAsync(t->d_in[s], t->h_in[s], c.text_bytes, hipMemcpyHostToDevice, t->cs));
-        }
-        BV_HIP(e, hipMemcpyAsync(t->d_meta[s], t->h_meta[s], sizeof(BvDefBlock) * c.count, hipMemcpyHostToDevice, t->cs));
-        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
-        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
-        hipLaunchKernelGGL(bv_bgzf_deflate_kernel, dim3(c.count), dim3(64), 0, st, host_text ? (const uint8_t *)t->d_in[s] : text,
-                           (const BvDefBlock *)t->d_meta[s], c.count, t->d_slots[s], t->d_sizes[s]);
+        if ((rc = chunk_stage_upload(e, t->in, s, meta_at + sizeof(BvDefBlock) * c.count, st)) != BV_OK) return rc;
+        const uint8_t *d_in = t->in.slot[s].d;
+        const BvDeflateState::Slot &sl = t->slot[s];
+        uint32_t *d_sizes = sl.d_sums, *d_off = sl.d_sums + kChunkBlocks;
+        hipLaunchKernelGGL(bv_bgzf_deflate_kernel, dim3(c.count), dim3(64), 0, st, host_text ? d_in : text,
+                           reinterpret_cast<const BvDefBlock *>(d_in + meta_at), c.count, sl.d_slots, d_sizes);
         BV_HIP(e, hipGetLastError());
-        hipLaunchKernelGGL(bv_bgzf_deflate_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)t->d_sizes[s], c.count, t->d_off[s]);
+        hipLaunchKernelGGL(bv_bgzf_deflate_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)d_sizes, c.count, d_off);
         BV_HIP(e, hipGetLastError());
-        hipLaunchKernelGGL(bv_bgzf_deflate_gather_kernel, dim3(c.count), dim3(256), 0, st, (const uint8_t *)t->d_slots[s], (const uint32_t *)t->d_off[s],
-                           c.count, t->d_packed[s]);
+        hipLaunchKernelGGL(bv_bgzf_deflate_gather_kernel, dim3(c.count), dim3(256), 0, st, (const uint8_t *)sl.d_slots, (const uint32_t *)d_off, c.count,
+                           sl.d_packed);
         BV_HIP(e, hipGetLastError());
-        BV_HIP(e, hipMemcpyAsync(t->h_off[s], t->d_off[s], sizeof(uint32_t) * (c.count + 1), hipMemcpyDeviceToHost, st));
-        BV_HIP(e, hipEventRecord(t->ev_done[s], st));
+        BV_HIP(e, hipMemcpyAsync(t->in.slot[s].back, d_off, sizeof(uint32_t) * (c.count + 1), hipMemcpyDeviceToHost, st));
+        if ((rc = chunk_stage_done(e, t->in, s, st)) != BV_OK) return rc;
         if (ci >= 1 && (rc = finish(ci - 1)) != BV_OK) return rc;
     }
     if ((rc = finish(chunks.size() - 1)) != BV_OK) return rc;
@@ -311,11 +255,7 @@ int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, 
     if (dst_capacity < need)
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: dst_capacity " + std::to_string(dst_capacity) + " < text_bytes + 31 * n_blocks = " +
                                                          std::to_string(need));
-    if (!e->deflate) {
-        e->deflate = new BvDeflateState();
-        e->deflate->device = e->cfg.device;
-    }
-    return bgzf_deflate(e, e->deflate, static_cast<const uint8_t *>(text), text_mem_kind == BV_MEM_HOST, block_off, n_blocks, dst, member_off,
+    return bgzf_deflate(e, engine_state(e, e->deflate), static_cast<const uint8_t *>(text), text_mem_kind == BV_MEM_HOST, block_off, n_blocks, dst, member_off,
                         stream_ ? (hipStream_t)stream_ : e->stream);
 }
 

@@ -1,6 +1,6 @@
 // bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_tiles.hip, bv_text.hip,
-// bv_inflate.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the files that hold
-// the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
+// bv_inflate.hip, bv_deflate.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
+// files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -153,6 +153,16 @@ int fail(bv_engine *e, int code, const std::string &msg);
     } while (0)
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// e->text, e->bgzf, e->deflate: each is created by the first call that needs it, on the engine's device
+template <class S>
+S *engine_state(bv_engine *e, S *&state) {
+    if (!state) {
+        state = new S();
+        state->device = e->cfg.device;
+    }
+    return state;
+}
 
 // A device buffer that only grows: at least `need` bytes behind *buf afterwards (hipFree synchronises with work that still uses it)
 template <class T>

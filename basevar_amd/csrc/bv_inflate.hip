@@ -13,14 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "bv_inflate_core.h"
-#include "bv_engine_impl.h"
+#include "bv_chunk_stage.h"
 
 using namespace bv_impl;
 
@@ -84,85 +83,31 @@ constexpr uint32_t kChunkMembers = 16384;
 
 }  // namespace
 
-// Per-engine staging of bv_engine_bgzf_inflate: two pinned host + two device chunks of compressed bytes and member tables, and
-// (for a host destination) two device chunks of inflated text.
+// Per-engine staging of bv_engine_bgzf_inflate: the compressed chunks, each with its member table behind it (bv_chunk_stage.h
+// has the rule of their reuse), and per slot a device chunk of inflated text for a host destination.
 struct BvBgzfState {
     int device = 0;
-    hipStream_t cs = nullptr;  // copy stream of the compressed chunks
-    hipEvent_t ev_copied[2] = {}, ev_done[2] = {};
-    uint8_t *h_in[2] = {}, *d_in[2] = {};
-    size_t in_cap = 0;
-    BvInfMember *h_meta[2] = {}, *d_meta[2] = {};
-    uint8_t *d_out[2] = {};
-    size_t out_cap = 0;
+    ChunkStage in;
+    struct Slot {
+        uint8_t *d_out = nullptr;  // written by the slot's kernel and copied back on the same stream: stream order keeps the next
+        size_t out_cap = 0;        // chunk of the slot behind both, no event is needed
+    } slot[2];
     uint8_t *d_status = nullptr;
     size_t status_cap = 0;
-    bool ready = false;  // the kernel's LDS was accepted and the stream, events and member tables exist
+    bool lds_ok = false;  // the kernel's LDS was accepted
 };
 
 void bv_bgzf_state_free(BvBgzfState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    if (t->cs) (void)hipStreamSynchronize(t->cs);
-    for (int k = 0; k < 2; ++k) {
-        if (t->h_in[k]) (void)hipHostFree(t->h_in[k]);
-        if (t->d_in[k]) (void)hipFree(t->d_in[k]);
-        if (t->h_meta[k]) (void)hipHostFree(t->h_meta[k]);
-        if (t->d_meta[k]) (void)hipFree(t->d_meta[k]);
-        if (t->d_out[k]) (void)hipFree(t->d_out[k]);
-        if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
-        if (t->ev_done[k]) (void)hipEventDestroy(t->ev_done[k]);
-    }
+    chunk_stage_free(t->in);
+    for (BvBgzfState::Slot &sl : t->slot)
+        if (sl.d_out) (void)hipFree(sl.d_out);
     if (t->d_status) (void)hipFree(t->d_status);
-    if (t->cs) (void)hipStreamDestroy(t->cs);
     delete t;
 }
 
 namespace {
-
-int ensure_staging(bv_engine *e, BvBgzfState *t, size_t in_bytes, size_t out_bytes, size_t n_members) {
-    if (!t->ready) {
-        // the kernel's LDS (window + tables) is more than the 64 KiB every launch may have: ask once whether this device takes it
-        hipFuncAttributes fa;
-        BV_HIP(e, hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(bv_bgzf_inflate_kernel)));
-        int lds_max = 0;
-        BV_HIP(e, hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, t->device));
-        if (fa.sharedSizeBytes > (size_t)lds_max)
-            return fail(e, BV_ERR_NO_DEVICE, "bv_engine_bgzf_inflate: the inflate kernel needs " + std::to_string(fa.sharedSizeBytes) +
-                                                           " bytes of LDS per workgroup, the device offers " + std::to_string(lds_max));
-        if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {  // (each object if it is missing: a call that failed half-way is taken up where it stopped)
-            if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
-            if (!t->ev_done[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_done[k], hipEventDisableTiming));
-            if (!t->h_meta[k]) BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_meta[k]), sizeof(BvInfMember) * kChunkMembers));
-            if (!t->d_meta[k]) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_meta[k]), sizeof(BvInfMember) * kChunkMembers));
-        }
-        t->ready = true;
-    }
-    if (in_bytes > t->in_cap) {
-        for (int k = 0; k < 2; ++k) {
-            if (t->h_in[k]) BV_HIP(e, hipHostFree(t->h_in[k]));
-            if (t->d_in[k]) BV_HIP(e, hipFree(t->d_in[k]));
-            t->h_in[k] = t->d_in[k] = nullptr;
-        }
-        t->in_cap = 0;
-        for (int k = 0; k < 2; ++k) {
-            BV_HIP(e, hipHostMalloc(reinterpret_cast<void **>(&t->h_in[k]), in_bytes));
-            BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_in[k]), in_bytes));
-        }
-        t->in_cap = in_bytes;
-    }
-    if (out_bytes > t->out_cap) {
-        for (int k = 0; k < 2; ++k) {
-            if (t->d_out[k]) BV_HIP(e, hipFree(t->d_out[k]));
-            t->d_out[k] = nullptr;
-        }
-        t->out_cap = 0;
-        for (int k = 0; k < 2; ++k) BV_HIP(e, hipMalloc(reinterpret_cast<void **>(&t->d_out[k]), out_bytes));
-        t->out_cap = out_bytes;
-    }
-    return grow_device(e, &t->d_status, &t->status_cap, n_members);
-}
 
 struct Chunk {
     uint32_t first, count;
@@ -173,19 +118,14 @@ int bgzf_inflate(bv_engine *e, BvBgzfState *t, const bv_bgzf_members *mb, const 
                  uint8_t *dst, bool host_dst, const uint64_t *out_pos, uint8_t *status, hipStream_t st) {
     const uint32_t n = mb->n_members;
     BV_HIP(e, hipSetDevice(t->device));
-    // a call that failed part-way may have left work queued: the staging is free only once it is through
-    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
-    BV_HIP(e, hipStreamSynchronize(st));
-    // (BASEVAR_AMD_TEXT_CHUNK_BYTES: a smaller chunk, for tests of the staging's reuse; never above the default)
-    size_t in_cap = kInChunkBytes;
-    if (const char *v = std::getenv("BASEVAR_AMD_TEXT_CHUNK_BYTES")) {
-        const unsigned long long x = std::strtoull(v, nullptr, 10);
-        if (x > 0 && x < kInChunkBytes) in_cap = (size_t)x;
-    }
-    in_cap = std::max<size_t>(in_cap, 65536);  // one member always fits
+    int rc = chunk_stage_begin(e, t->in, st);
+    if (rc == BV_OK)
+        rc = kernel_lds_fits(e, "bv_engine_bgzf_inflate: the inflate kernel", reinterpret_cast<const void *>(bv_bgzf_inflate_kernel), t->device, &t->lds_ok);
+    if (rc != BV_OK) return rc;
+    const size_t in_cap = std::max<size_t>(chunk_limit_from_env("BASEVAR_AMD_TEXT_CHUNK_BYTES", kInChunkBytes), 65536);  // one member always fits
     const size_t out_cap = in_cap * kOutPerIn;
     std::vector<Chunk> chunks;
-    size_t in_max = 0, out_max = 0;
+    size_t stage_max = 0, out_max = 0;
     for (uint32_t k = 0; k < n;) {
         Chunk c{k, 0, 0, 0};
         while (k < n && c.count < kChunkMembers) {
@@ -194,48 +134,45 @@ int bgzf_inflate(bv_engine *e, BvBgzfState *t, const bv_bgzf_members *mb, const 
             c.in_bytes += len; c.out_bytes += text;
             ++c.count; ++k;
         }
-        in_max = std::max(in_max, c.in_bytes); out_max = std::max(out_max, c.out_bytes);
+        stage_max = std::max(stage_max, up16(c.in_bytes) + sizeof(BvInfMember) * c.count); out_max = std::max(out_max, c.out_bytes);
         chunks.push_back(c);
     }
-    int rc = ensure_staging(e, t, in_max, host_dst ? std::max<size_t>(out_max, 16) : 0, n);
-    if (rc != BV_OK) return rc;
+    if ((rc = chunk_stage_reserve(e, t->in, stage_max)) != BV_OK) return rc;
+    for (BvBgzfState::Slot &sl : t->slot)
+        if ((rc = grow_device(e, &sl.d_out, &sl.out_cap, host_dst ? std::max<size_t>(out_max, 16) : 0)) != BV_OK) return rc;
+    if ((rc = grow_device(e, &t->d_status, &t->status_cap, n)) != BV_OK) return rc;
     for (size_t ci = 0; ci < chunks.size(); ++ci) {
         const Chunk &c = chunks[ci];
         const unsigned s = ci & 1u;
-        if (ci >= 2) BV_HIP(e, hipEventSynchronize(t->ev_done[s]));  // the slot's kernel (and its copy back) is through
+        if ((rc = chunk_stage_fill(e, t->in, s)) != BV_OK) return rc;
+        // the members as they lie in the file, then their table
+        uint8_t *h_in = t->in.slot[s].h;
+        const size_t meta_at = up16(c.in_bytes);
+        BvInfMember *h_meta = reinterpret_cast<BvInfMember *>(h_in + meta_at);
         size_t at = 0;
         for (uint32_t j = 0; j < c.count; ++j) {
             const uint32_t k = c.first + j;
             const size_t len = mb->member_off[k + 1] - mb->member_off[k];
-            std::memcpy(t->h_in[s] + at, mb->data + mb->member_off[k], len);
-            BvInfMember &m = t->h_meta[s][j];
+            std::memcpy(h_in + at, mb->data + mb->member_off[k], len);
+            BvInfMember &m = h_meta[j];
             m.out_off = host_dst ? out_pos[k] - out_pos[c.first] : out_pos[k];
             m.in_off = (uint32_t)(at + hd[k].payload_off); m.in_len = hd[k].payload_len;
             m.isize = hd[k].isize; m.crc = hd[k].crc; m.pre = pre[k]; m.reserved_ = 0;
             at += len;
         }
-        BV_HIP(e, hipMemcpyAsync(t->d_in[s], t->h_in[s], c.in_bytes, hipMemcpyHostToDevice, t->cs));
-        BV_HIP(e, hipMemcpyAsync(t->d_meta[s], t->h_meta[s], sizeof(BvInfMember) * c.count, hipMemcpyHostToDevice, t->cs));
-        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
-        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
-        hipLaunchKernelGGL(bv_bgzf_inflate_kernel, dim3(c.count), dim3(64), 0, st, (const uint8_t *)t->d_in[s], (const BvInfMember *)t->d_meta[s],
-                           c.count, host_dst ? t->d_out[s] : dst, t->d_status + c.first);
+        if ((rc = chunk_stage_upload(e, t->in, s, meta_at + sizeof(BvInfMember) * c.count, st)) != BV_OK) return rc;
+        const uint8_t *d_in = t->in.slot[s].d;
+        uint8_t *d_out = t->slot[s].d_out;
+        hipLaunchKernelGGL(bv_bgzf_inflate_kernel, dim3(c.count), dim3(64), 0, st, d_in, reinterpret_cast<const BvInfMember *>(d_in + meta_at), c.count,
+                           host_dst ? d_out : dst, t->d_status + c.first);
         BV_HIP(e, hipGetLastError());
         if (host_dst && c.out_bytes)
-            BV_HIP(e, hipMemcpyAsync(dst + out_pos[c.first], t->d_out[s], c.out_bytes, hipMemcpyDeviceToHost, st));
-        BV_HIP(e, hipEventRecord(t->ev_done[s], st));
+            BV_HIP(e, hipMemcpyAsync(dst + out_pos[c.first], d_out, c.out_bytes, hipMemcpyDeviceToHost, st));
+        if ((rc = chunk_stage_done(e, t->in, s, st)) != BV_OK) return rc;
     }
     BV_HIP(e, hipMemcpyAsync(status, t->d_status, n, hipMemcpyDeviceToHost, st));
     BV_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
-}
-
-BvBgzfState *state_of(bv_engine *e) {
-    if (!e->bgzf) {
-        e->bgzf = new BvBgzfState();
-        e->bgzf->device = e->cfg.device;
-    }
-    return e->bgzf;
 }
 
 }  // namespace
@@ -266,7 +203,7 @@ int bv_bgzf_headers(bv_engine *e, const char *who, const bv_bgzf_members *mb, st
 // Member k's text to d_dst + out_pos[k] (device memory of the engine's device); status[n_members] on the host.  Blocks.
 int bv_bgzf_inflate_placed(bv_engine *e, const bv_bgzf_members *mb, const std::vector<BvBgzfMember> &hd, const std::vector<uint8_t> &pre,
                            const uint64_t *out_pos, uint8_t *d_dst, uint8_t *status, hipStream_t st) {
-    return bgzf_inflate(e, state_of(e), mb, hd, pre, d_dst, false, out_pos, status, st);
+    return bgzf_inflate(e, engine_state(e, e->bgzf), mb, hd, pre, d_dst, false, out_pos, status, st);
 }
 
 extern "C" {
@@ -291,7 +228,7 @@ int bv_engine_bgzf_inflate(bv_engine *e, const bv_bgzf_members *mb, void *dst, u
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: dst_capacity " + std::to_string(dst_capacity) + " < the " +
                                                          std::to_string(dst_off[n]) + " bytes the members inflate to");
     if (!dst && dst_off[n]) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_inflate: null dst");
-    return bgzf_inflate(e, state_of(e), mb, hd, pre, static_cast<uint8_t *>(dst), mem_kind == BV_MEM_HOST, dst_off, status, stream_ ? (hipStream_t)stream_ : e->stream);
+    return bgzf_inflate(e, engine_state(e, e->bgzf), mb, hd, pre, static_cast<uint8_t *>(dst), mem_kind == BV_MEM_HOST, dst_off, status, stream_ ? (hipStream_t)stream_ : e->stream);
 }
 
 }  // extern "C"

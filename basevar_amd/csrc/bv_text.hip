@@ -17,14 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "bv_inflate_core.h"
-#include "bv_engine_impl.h"
+#include "bv_chunk_stage.h"
 
 using namespace bv_impl;
 
@@ -386,13 +385,10 @@ __global__ __launch_bounds__(256) void bv_text_fetch_copy_kernel(const char *tex
 }  // namespace
 
 // Per-engine state of the text path: the parsed planes of the last bv_engine_text_parse, the slab handed to the calling kernels,
-// the text staging (two pinned host + two device chunks) and what the host learnt from the parse.
+// the staging of the text chunks (bv_chunk_stage.h) and what the host learnt from the parse.
 struct BvTextState {
     int device = 0;
-    hipStream_t cs = nullptr;               // copy stream of the text chunks
-    hipEvent_t ev_copied[2] = {}, ev_parsed[2] = {};
-    char *h_text[2] = {}, *d_text[2] = {};
-    size_t chunk_cap = 0;
+    ChunkStage chunks;
     uint8_t *d_planes = nullptr;            // parsed rows: bs, q, mq, st [cap][pitch], rp [cap][pitch] u16, ref [cap]
     size_t planes_bytes = 0;
     uint8_t *d_sub = nullptr;               // the submitted slab: bs, q, mq [cap][pitch], rp [cap][pitch] u16, ref [cap]
@@ -427,43 +423,13 @@ struct BvTextState {
 void bv_text_state_free(BvTextState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
-    if (t->cs) (void)hipStreamSynchronize(t->cs);
-    for (int k = 0; k < 2; ++k) {
-        if (t->h_text[k]) (void)hipHostFree(t->h_text[k]);
-        if (t->d_text[k]) (void)hipFree(t->d_text[k]);
-        if (t->ev_copied[k]) (void)hipEventDestroy(t->ev_copied[k]);
-        if (t->ev_parsed[k]) (void)hipEventDestroy(t->ev_parsed[k]);
-    }
+    chunk_stage_free(t->chunks);
     for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch})
         if (b) (void)hipFree(b);
-    if (t->cs) (void)hipStreamDestroy(t->cs);
     delete t;
 }
 
 namespace {
-// The staging of text chunks: two pinned host buffers and two device buffers of `bytes` each.
-int ensure_chunks(bv_engine *e, BvTextState *t, size_t bytes) {
-    if (!t->cs) BV_HIP(e, hipStreamCreateWithFlags(&t->cs, hipStreamNonBlocking));
-    for (int k = 0; k < 2; ++k) {
-        if (!t->ev_copied[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_copied[k], hipEventDisableTiming));
-        if (!t->ev_parsed[k]) BV_HIP(e, hipEventCreateWithFlags(&t->ev_parsed[k], hipEventDisableTiming));
-    }
-    if (bytes <= t->chunk_cap) return BV_OK;
-    BV_HIP(e, hipStreamSynchronize(t->cs));
-    for (int k = 0; k < 2; ++k) {
-        if (t->h_text[k]) BV_HIP(e, hipHostFree(t->h_text[k]));
-        if (t->d_text[k]) BV_HIP(e, hipFree(t->d_text[k]));
-        t->h_text[k] = t->d_text[k] = nullptr;
-    }
-    t->chunk_cap = 0;
-    for (int k = 0; k < 2; ++k) {
-        BV_HIP(e, hipHostMalloc(&t->h_text[k], bytes));
-        BV_HIP(e, hipMalloc(&t->d_text[k], bytes));
-    }
-    t->chunk_cap = bytes;
-    return BV_OK;
-}
-
 // The device arrays of one parse of P positions x F files.
 struct ParseBufs {
     uint8_t *bs, *q, *mq, *stp, *ref, *rowflag;
@@ -481,8 +447,6 @@ int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint
     t->parsed = false;
     t->bgzf_rows = false;
     BV_HIP(e, hipSetDevice(t->device));
-    // a parse that failed part-way may have left chunk copies queued: the staging is free only once they are through
-    if (t->cs) BV_HIP(e, hipStreamSynchronize(t->cs));
     // device buffers: planes, then the small per-position / per-row arrays
     const size_t cells = (size_t)P * pitch;
     int rc = grow_device(e, &t->d_planes, &t->planes_bytes, 6 * cells + up256(P));
@@ -531,39 +495,47 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
     size_t need = 0;
     for (uint32_t p = 0; p < P; ++p) need = std::max<size_t>(need, rows->row_off[(size_t)(p + 1) * F] - rows->row_off[(size_t)p * F]);
     const size_t total = rows->row_off[R] - rows->row_off[0];
-    // (BASEVAR_AMD_TEXT_CHUNK_BYTES: a smaller chunk, for tests of the staging's reuse; never above the default)
-    size_t chunk_bytes = kChunkBytes;
-    if (const char *v = std::getenv("BASEVAR_AMD_TEXT_CHUNK_BYTES")) {
-        const unsigned long long x = std::strtoull(v, nullptr, 10);
-        if (x > 0 && x < kChunkBytes) chunk_bytes = (size_t)x;
-    }
-    rc = ensure_chunks(e, t, std::max(up256(need), std::min(chunk_bytes, up256(total))));
+    const size_t chunk_bytes = chunk_limit_from_env("BASEVAR_AMD_TEXT_CHUNK_BYTES", kChunkBytes);
+    ChunkStage &cst = t->chunks;
+    rc = chunk_stage_begin(e, cst, st);  // (with it, the pageable uploads above are complete)
+    if (rc == BV_OK) rc = chunk_stage_reserve(e, cst, std::max(up256(need), std::min(chunk_bytes, up256(total))));
     if (rc != BV_OK) return rc;
-    BV_HIP(e, hipStreamSynchronize(st));  // (the pageable uploads above are complete; the chunk buffers may be reused)
     unsigned k = 0;
     for (uint32_t p0 = 0; p0 < P; ++k) {
         const uint64_t base = rows->row_off[(size_t)p0 * F];
         uint32_t p1 = p0 + 1;
-        while (p1 < P && rows->row_off[(size_t)(p1 + 1) * F] - base <= t->chunk_cap) ++p1;
+        while (p1 < P && rows->row_off[(size_t)(p1 + 1) * F] - base <= cst.cap) ++p1;
         const size_t bytes = rows->row_off[(size_t)p1 * F] - base;
         const unsigned s = k & 1u;
-        if (k >= 2) BV_HIP(e, hipEventSynchronize(t->ev_copied[s]));  // the pinned buffer has crossed the link
-        std::memcpy(t->h_text[s], rows->text + base, bytes);
-        if (k >= 2) BV_HIP(e, hipStreamWaitEvent(t->cs, t->ev_parsed[s], 0));  // the device buffer has been parsed
-        BV_HIP(e, hipMemcpyAsync(t->d_text[s], t->h_text[s], bytes, hipMemcpyHostToDevice, t->cs));
-        BV_HIP(e, hipEventRecord(t->ev_copied[s], t->cs));
-        BV_HIP(e, hipStreamWaitEvent(st, t->ev_copied[s], 0));
+        if ((rc = chunk_stage_fill(e, cst, s)) != BV_OK) return rc;
+        std::memcpy(cst.slot[s].h, rows->text + base, bytes);
+        if ((rc = chunk_stage_upload(e, cst, s, bytes, st)) != BV_OK) return rc;
         TextParseArgs a;
-        a.text = t->d_text[s]; a.row_beg = d_off; a.row_end = d_off + 1; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
+        a.text = reinterpret_cast<const char *>(cst.slot[s].d); a.row_beg = d_off; a.row_end = d_off + 1; a.foff = foff; a.fsamp = fsamp; a.chunk_base = base;
         a.row_first = p0 * F; a.n_rows_chunk = (p1 - p0) * F; a.n_files = F; a.pitch = pitch;
         a.bs = bs; a.q = q; a.mq = mq; a.st = stp; a.ref = ref; a.rowflag = rowflag; a.rp = rp;
         a.depth = depth; a.pstate = pstate; a.pmax = pmax;
         hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
         BV_HIP(e, hipGetLastError());
-        BV_HIP(e, hipEventRecord(t->ev_parsed[s], st));
+        if ((rc = chunk_stage_done(e, cst, s, st)) != BV_OK) return rc;
         p0 = p1;
     }
     return parse_finish(e, t, P, F, n_samples, group_id, n_groups, row_state, st, pb);
+}
+
+// What both parse entry points ask of file_samples and group_id / n_groups; *n_samples = the samples of all files.
+int check_samples_groups(bv_engine *e, const char *who, const uint32_t *file_samples, uint32_t F, const uint8_t *group_id, uint32_t n_groups,
+                         uint64_t *n_samples) {
+    *n_samples = 0;
+    for (uint32_t f = 0; f < F; ++f) {
+        if (file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
+        *n_samples += file_samples[f];
+    }
+    if (*n_samples > e->cfg.max_samples)
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the files hold more samples than cfg.max_samples");
+    if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+    return BV_OK;
 }
 
 // The strands into the cells, then what the host needs to know of every position.
@@ -614,14 +586,8 @@ int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *
     if (rows->n_positions > e->cfg.max_sites)
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions exceeds cfg.max_sites");
     uint64_t n_samples = 0;
-    for (uint32_t f = 0; f < rows->n_files; ++f) {
-        if (rows->file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: file_samples[f] == 0");
-        n_samples += rows->file_samples[f];
-    }
-    if (n_samples > e->cfg.max_samples)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: the files hold more samples than cfg.max_samples");
-    if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+    int rc = check_samples_groups(e, "bv_engine_text_parse", rows->file_samples, rows->n_files, group_id, n_groups, &n_samples);
+    if (rc != BV_OK) return rc;
     const size_t R = (size_t)rows->n_positions * rows->n_files;
     for (size_t r = 0; r < R; ++r) {  // rows in order, inside the text, each ending in '\n'
         const uint64_t a = rows->row_off[r], b = rows->row_off[r + 1];
@@ -630,12 +596,8 @@ int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *
                                   "bv_engine_text_parse: row " + std::to_string(r) + ": row_off outside text_bytes, out of order, or no final '\\n'");
         if (b - a > 0xFFFFFFFFull) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: a row is longer than 4 GiB");
     }
-    BvTextState *&t = e->text;
-    if (!t) {
-        t = new BvTextState();
-        t->device = e->cfg.device;
-    }
-    const int rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : e->stream, (uint32_t)n_samples);
+    BvTextState *t = engine_state(e, e->text);
+    rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : e->stream, (uint32_t)n_samples);
     if (rc != BV_OK) t->parsed = false;
     return rc;
 }
@@ -761,27 +723,18 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     const uint32_t F = rows->n_files;
     uint64_t n_samples = 0;
     if (rows->file_member[0] != 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member[0] must be 0");
-    for (uint32_t f = 0; f < F; ++f) {
-        if (rows->file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
+    for (uint32_t f = 0; f < F; ++f)
         if (rows->file_member[f + 1] < rows->file_member[f]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member out of order");
-        n_samples += rows->file_samples[f];
-    }
     if (!rows->data && rows->file_member[F]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null data");
-    if (n_samples > e->cfg.max_samples)
-        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the files hold more samples than cfg.max_samples");
-    if (n_groups > BV_MAX_GROUPS || (n_groups > 0) != (group_id != nullptr))
-        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": group_id must be given with 0 < n_groups <= BV_MAX_GROUPS");
+    int rc = check_samples_groups(e, who, rows->file_samples, F, group_id, n_groups, &n_samples);
+    if (rc != BV_OK) return rc;
     *n_positions = 0;
     bv_bgzf_members mb{rows->data, rows->member_off, rows->data_bytes, rows->file_member[F], 0};
     std::vector<BvBgzfMember> hd;
     std::vector<uint8_t> pre;
-    int rc = bv_bgzf_headers(e, who, &mb, hd, pre);
+    rc = bv_bgzf_headers(e, who, &mb, hd, pre);
     if (rc != BV_OK) return rc;
-    BvTextState *&t = e->text;
-    if (!t) {
-        t = new BvTextState();
-        t->device = e->cfg.device;
-    }
+    BvTextState *t = engine_state(e, e->text);
     t->parsed = false;
     t->bgzf_rows = false;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
