@@ -14,6 +14,7 @@
 #include "../../basevar_amd/host/vcf_emit.hpp"
 #include "../../basevar_amd/host/batchfile_fast.hpp"
 #include "../../oracle/literal_reader.hpp"  // the literal restatement of the reference's reader: the checker (test infrastructure)
+#include "row_lane_cases.hpp"               // the positional corpus of the device row parser (tests/cpp/text_rows_check.cpp runs it on the GPU)
 
 using namespace bvamd;
 
@@ -186,9 +187,9 @@ int main(int argc, char **argv) {
         // every case also goes to argv[4] with the FAST reader's outcome: the Python test runs the reference's own
         // _basevar_caller (oracle/_ref/libbvcaller.so) on the same rows and compares outcome kind and exception text
         FILE *dump = argc > 4 ? std::fopen(argv[4], "w") : nullptr;
-        auto compare = [&](const std::vector<std::string> &rows, size_t n, const char *tag) {
+        auto compare = [&](const std::vector<std::string> &rows, size_t n, const char *tag, bool lines = true) {
             const Outcome a = literal(rows, n), b = fast(rows, n);
-            if (dump) {
+            if (dump && lines) {  // (a row with a line break inside cannot go into a file of lines)
                 std::string w = b.what;
                 for (char &ch : w) if (ch == '\n') ch = '\x01';
                 std::fprintf(dump, "CASE %zu %zu %d %s\n", rows.size(), n, b.kind, w.c_str());
@@ -261,6 +262,26 @@ int main(int argc, char **argv) {
         compare({"chr1\t5\tA\t1\t6e1\tA\tI\t3.7\t+"}, 1, "numbers the int reader stops inside");
         compare({"chr1\t5\tA\t2\t60 60\t+A -A\tI I\t3 4\t. ."}, 2, "indels only, no strands");
         compare({"chr1\t5\tA\t2\t60 60\tA N\tI !\t3 0\t+ x"}, 2, "a strange strand on an N call is never looked at");
+        // the positional corpus of the device row parser (row_lane_cases.hpp): valid rows with every token start, tab and line
+        // break on every lane of the kernel's 64-byte steps, and damage placed on the lanes at the step boundaries.  The host
+        // reader is the device's oracle on these rows (text_rows_check.cpp), so it is held to the literal reader -- and, through
+        // the dump, to the reference's caller -- on exactly these.  The tracer's coverage is asserted here, without a GPU.
+        {
+            const std::vector<rowlane::Case> lane_cases = rowlane::corpus();
+            const size_t bad = rowlane::check_corpus(lane_cases, std::cout);
+            CHECK(bad == 0, "the positional corpus does not reach " << bad << " of the lanes / defects it must (LANE_COVERAGE lines)");
+            size_t lane_outcome[3] = {0, 0, 0};
+            for (const rowlane::Case &c : lane_cases) {
+                size_t n = 0;
+                for (uint32_t v : c.fs) n += v;
+                const size_t before[3] = {n_valid, n_skipped, n_threw};
+                compare(c.rows, n, c.kind.c_str(), !c.inner_newline);
+                lane_outcome[n_valid > before[0] ? 0 : n_skipped > before[1] ? 1 : 2]++;
+                if (c.valid) CHECK(n_valid > before[0], "a row of the valid sweep was not taken: " << c.kind);
+            }
+            std::cout << "LANE_READER_CASES valid " << lane_outcome[0] << " skipped " << lane_outcome[1] << " threw " << lane_outcome[2] << std::endl;
+            CHECK(lane_outcome[0] > 100 && lane_outcome[2] > 50, "the positional corpus exercises both outcomes");
+        }
         if (dump) std::fclose(dump);
         std::cout << "FAST_READER_CASES valid " << n_valid << " skipped " << n_skipped << " threw " << n_threw << std::endl;
         CHECK(n_valid > 100 && n_threw > 100, "the damaged rows exercise both outcomes");

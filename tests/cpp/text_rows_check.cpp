@@ -6,13 +6,24 @@
 // the batch as a whole must give the records, skips and error (message and position) of the host reader run position by
 // position.  Cases: the row cases of host_formats_check.cpp's FAST_READER_CASES (restated here), and a seeded corpus of damaged
 // valid rows.  Usage: text_rows_check [n_sites]; prints "TEXT_ROWS device <n> host <n> skipped <n> threw <n>" and "FAILS <n>".
+//
+// text_rows_check <n> lanes runs the positional corpus of row_lane_cases.hpp instead -- valid rows with every token start, tab and
+// line break on every lane of the kernel's 64-byte steps, damage placed on the lanes at the step boundaries -- through the same
+// comparison, many positions to a batch: a case the host reader does not throw on stands between clean positions, a case it
+// throws on ends its batch.  Every row of the valid sweep and every clean position must be parsed on the device.
+// text_rows_check <n> lanes-dump <file> writes the corpus's cases that can stand in a file of lines and that the host reader does
+// not throw on ("CASE <valid> <samples per file, comma separated> <kind>", then one row per file), for the BGZF route
+// (tests/test_gpu_bgzf_rows.py); it does not touch the GPU.
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
+#include <map>
 #include <random>
 
 #include "../../basevar_amd/host/basetype_gpu.hpp"
 #include "../../basevar_amd/host/batchfile_fast.hpp"
+#include "row_lane_cases.hpp"
 
 using namespace bvamd;
 
@@ -30,8 +41,15 @@ struct HostRun {  // the host reader, position by position, as BatchfileProducer
 
 static size_t n_device = 0, n_host = 0, n_skip = 0, n_threw = 0;
 
+// what a position of a batch is: a clean row, a case, or a row of the valid sweep (a case that must be parsed on the device)
+enum { CLEAN = 0, CASE = 1, VALID = 2 };
+
+// `what` / `tags`: per position (default: clean, the case, clean -- all under `tag`)
 static void run_case(BaseTypeEngine &eng, const std::vector<std::vector<std::string>> &batch, const std::vector<uint32_t> &fs,
-                     const char *tag) {
+                     const char *tag0, const std::vector<int> &what = {CLEAN, CASE, CLEAN}, const std::vector<std::string> *tags = nullptr) {
+    const std::string all_tags = tags ? (*tags)[0] + " .. " + tags->back() : std::string(tag0);
+    const char *tag = all_tags.c_str();
+    auto tag_of = [&](size_t p) { return tags ? (*tags)[p] : std::string(tag0); };
     uint32_t N = 0;
     for (uint32_t v : fs) N += v;
     const size_t F = fs.size();
@@ -62,8 +80,11 @@ static void run_case(BaseTypeEngine &eng, const std::vector<std::vector<std::str
     if (tb.error) {
         try { std::rethrow_exception(tb.error); } catch (const std::exception &e) { dev_error = e.what(); }
     }
-    const uint8_t st1 = tb.row_state[1 * F];
-    (st1 & BV_TEXT_HOST ? n_host : st1 & BV_TEXT_SKIP ? n_skip : n_device)++;
+    for (uint32_t p = 0; p < batch.size(); ++p) {
+        if (what[p] == CLEAN) continue;
+        const uint8_t st1 = tb.row_state[p * F];
+        (st1 & BV_TEXT_HOST ? n_host : st1 & BV_TEXT_SKIP ? n_skip : n_device)++;
+    }
     if (!h.error.empty()) ++n_threw;
     CHECK(dev_error == h.error, tag << ": error [" << dev_error << "] vs host [" << h.error << "]");
     CHECK(tb.n_positions_used == h.n_used, tag << ": positions used " << tb.n_positions_used << " vs host " << h.n_used);
@@ -71,11 +92,14 @@ static void run_case(BaseTypeEngine &eng, const std::vector<std::vector<std::str
     if (tb.position != h.position) return;
     // the clean positions are always the device's; the case is the device's only if the host reader wrote those same bytes
     for (uint32_t p = 0; p < batch.size(); ++p)
-        if (p != 1) CHECK(tb.row_state[p * F] == 0 || (tb.row_state[p * F] & BV_TEXT_INDEL), tag << ": clean position " << p << " not parsed on the device");
+        if (what[p] != CASE)
+            CHECK(!(tb.row_state[p * F] & (BV_TEXT_HOST | BV_TEXT_SKIP)), tag_of(p) << ": " << (what[p] == VALID ? "valid" : "clean") << " position " << p << " not parsed on the device");
     BaseTypeBatch ref;
     if (h.sb.n_sites()) ref = eng.lrt(h.sb);
     CHECK(ref.sites.size() == tb.batch.sites.size(), tag << ": record count");
     for (size_t i = 0; i < h.position.size() && i < tb.batch.sites.size(); ++i) {
+        const std::string tag_i = tag_of(h.position[i]);
+        const char *tag = tag_i.c_str();
         CHECK(std::memcmp(&ref.sites[i], &tb.batch.sites[i], sizeof(bv_site_result)) == 0, tag << ": record " << i << " differs");
         CHECK(std::memcmp(h.sb.cell_row(i), &tb.cell[i * N], N) == 0, tag << ": cell plane of record " << i);
         CHECK(std::memcmp(h.sb.phred_row(i), &tb.phred[i * N], N) == 0, tag << ": phred plane of record " << i);
@@ -105,8 +129,74 @@ static std::string clean_row(uint32_t pos, uint32_t n, uint32_t salt, bool ref_a
            q + "\t" + rk + "\t" + sd;
 }
 
+// the positional corpus (row_lane_cases.hpp); `dump`: only write the cases for the BGZF route
+static int run_lanes(const char *dump) {
+    const std::vector<rowlane::Case> cases = rowlane::corpus();
+    CHECK(rowlane::check_corpus(cases, std::cout) == 0, "the positional corpus does not reach the lanes / defects it must");
+    // the host reader first: a case it throws on ends a batch
+    std::vector<char> throws(cases.size(), 0);
+    std::map<std::vector<uint32_t>, std::vector<size_t>> by_files;
+    for (size_t i = 0; i < cases.size(); ++i) {
+        uint32_t N = 0;
+        for (uint32_t v : cases[i].fs) N += v;
+        SlabBuilder sb(N);
+        SiteText st;
+        try { parse_site_rows_fast(cases[i].rows, N, sb, st); } catch (const std::exception &) { throws[i] = 1; }
+        by_files[cases[i].fs].push_back(i);
+    }
+    if (dump) {
+        std::ofstream out(dump, std::ios::binary);
+        for (size_t i = 0; i < cases.size(); ++i) {
+            if (throws[i] || cases[i].inner_newline) continue;
+            out << "CASE " << (cases[i].valid ? 1 : 0) << " ";
+            for (size_t f = 0; f < cases[i].fs.size(); ++f) out << (f ? "," : "") << cases[i].fs[f];
+            out << " " << cases[i].kind << "\n";
+            for (const std::string &r : cases[i].rows) out << r << "\n";
+        }
+        return fails ? 1 : 0;
+    }
+    const uint32_t kBatch = 64;  // positions per batch, and the engine's max_sites
+    size_t n_batches = 0;
+    for (const auto &group : by_files) {
+        const std::vector<uint32_t> &fs = group.first;
+        uint32_t N = 0;
+        for (uint32_t v : fs) N += v;
+        BaseTypeEngine eng(kBatch, N);
+        std::vector<std::vector<std::string>> batch;
+        std::vector<int> what;
+        std::vector<std::string> tags;
+        uint32_t clean_pos = 1;
+        auto add_clean = [&]() {
+            std::vector<std::string> rows;
+            for (size_t f = 0; f < fs.size(); ++f) rows.push_back(rowlane::clean(clean_pos, fs[f], (uint32_t)f + 3).str());
+            ++clean_pos;
+            batch.push_back(rows); what.push_back(CLEAN); tags.push_back("clean");
+        };
+        auto flush = [&]() {
+            if (batch.empty()) return;
+            run_case(eng, batch, fs, "lanes", what, &tags);
+            ++n_batches;
+            batch.clear(); what.clear(); tags.clear();
+        };
+        for (size_t i : group.second) {
+            const rowlane::Case &c = cases[i];
+            if (!c.valid) add_clean();
+            batch.push_back(c.rows); what.push_back(c.valid ? VALID : CASE); tags.push_back(c.kind);
+            if (throws[i]) flush();  // the reader stops here: nothing behind it would be looked at
+            else if (batch.size() + 3 > kBatch) { add_clean(); flush(); }
+        }
+        if (!batch.empty()) { add_clean(); flush(); }
+    }
+    std::cout << "TEXT_ROWS_LANES batches " << n_batches << " device " << n_device << " host " << n_host << " skipped " << n_skip << " threw " << n_threw << std::endl;
+    CHECK(n_device > 0 && n_host > 0 && n_skip > 0 && n_threw > 0, "the positional corpus exercises every outcome");
+    std::cout << "FAILS " << fails << std::endl;
+    return fails ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
     const int n_sites = argc > 1 ? std::atoi(argv[1]) : 40;
+    if (argc > 2 && std::string(argv[2]) == "lanes") return run_lanes(nullptr);
+    if (argc > 3 && std::string(argv[2]) == "lanes-dump") return run_lanes(argv[3]);
     BaseTypeEngine eng(8, 64);
     auto with_clean = [&](const std::vector<std::string> &rows, const std::vector<uint32_t> &fs, const char *tag) {
         std::vector<std::vector<std::string>> batch(3);

@@ -377,3 +377,327 @@ def test_rows_repeated_at_distance_32768():
     same_batch(got, exp, 0)
     assert got.n_variant > 0
     check_fetched(got, flat, row_off, P, 1)
+
+
+# ---- the positional corpus of the row parser (tests/cpp/row_lane_cases.hpp) through the line index
+def tolerant_reader(N, seen=None):
+    """_py_host_reader for rows it may not be able to take: those are skipped (in both paths alike); `seen` collects the lines of
+    every position it was asked for"""
+    def reader(lines):
+        if seen is not None:
+            seen.add(tuple(lines))
+        try:
+            got = _py_host_reader(N)([l.rstrip(b"\r") for l in lines])
+        except (ValueError, IndexError, OverflowError):
+            return None
+        return got if got is not None and all(len(a) == N for a in got[:4]) else None
+    return reader
+
+
+def lane_corpus(tmp_path):
+    """{samples per file: [(valid, kind, [row per file])]}: the cases of the corpus that can stand in a file of lines and that the
+    C++ host reader does not throw on (text_rows_check <n> lanes-dump)"""
+    import subprocess
+    from test_gpu_text_rows import build_text_rows_check
+    path = tmp_path / "lane_cases.txt"
+    subprocess.check_call([build_text_rows_check(tmp_path), "0", "lanes-dump", str(path)], stdout=subprocess.DEVNULL)
+    lines = open(path, "rb").read().split(b"\n")
+    groups, i = {}, 0
+    while i < len(lines) and lines[i].startswith(b"CASE "):
+        _, valid, fs, kind = lines[i].split(b" ", 3)
+        fs = tuple(int(x) for x in fs.split(b","))
+        groups.setdefault(fs, []).append((valid == b"1", kind.decode("latin-1"), lines[i + 1:i + 1 + len(fs)]))
+        i += 1 + len(fs)
+    assert i == len(lines) - 1 and lines[-1] == b""
+    return groups
+
+
+def test_positional_corpus_through_the_line_index(tmp_path):
+    """the valid sweep and the damaged rows the host reader does not throw on, written as BGZF files: the kernel gets row_beg /
+    row_end from the line index instead of contiguous offsets, the host reader gets rows fetched from the device; row_state and
+    records are lrt_text's on the same rows uncompressed"""
+    from basevar_amd import _capi
+    groups = lane_corpus(tmp_path)
+    assert sum(len(c) for c in groups.values()) > 250 and len(groups) >= 2
+    for fs, cases in groups.items():
+        P, N, F = len(cases), sum(fs), len(fs)
+        rows = [c[2] for c in cases]
+        valid = np.array([c[0] for c in cases])
+        flat = b"".join(r + b"\n" for pos in rows for r in pos)
+        flat_off = np.concatenate([[0], np.cumsum([len(r) + 1 for pos in rows for r in pos])]).astype(np.uint64)
+        seen = set()
+        eng = engine(P, N)
+        try:
+            exp = eng.lrt_text(rows, list(fs), host_reader=tolerant_reader(N, seen))
+            runs = [members_of(b"".join(rows[p][f] + b"\n" for p in range(P)), 0x1300) for f in range(F)]
+            got = eng.lrt_bgzf(runs, list(fs), host_reader=tolerant_reader(N))
+        finally:
+            eng.close()
+        assert got.row_state.shape == (P, F)
+        assert not (exp.row_state[valid] & (_capi.BV_TEXT_HOST | _capi.BV_TEXT_SKIP)).any(), "a row of the valid sweep was not parsed on the device"
+        same_batch(got, exp, 0)
+        host = [p for p in range(P) if tuple(rows[p]) in seen]
+        if len(fs) == 3:
+            on_device = ((exp.row_state[:, 0] & (_capi.BV_TEXT_HOST | _capi.BV_TEXT_SKIP)) == 0).sum()
+            assert len(host) > 50 and on_device >= valid.sum() > 100 and (exp.row_state & _capi.BV_TEXT_INDEL).any()
+        check_fetched(got, np.frombuffer(flat, np.uint8), flat_off, P, F, host_positions=host)
+
+
+# ---- the line index at the edges of its 16 KiB tiles (bv_text_line_count / _scan / _scatter_kernel): rows built as bytes, an
+# insertion token in sample 0 pads a row to an exact length (such a row is parsed on the device and fetched whole)
+TILE = 16384
+
+
+def pad_row(pos, n, salt, length=None):
+    """one row of n samples with its line break; with `length`, exactly that many bytes (None if that is too short)"""
+    cols = [[], [], [], [], []]
+    cov = 0
+    for i in range(n):
+        k = (i * 7 + salt * 3 + pos) % 11
+        if length is not None and i == 0:
+            tok = (b"60", b"+A", b"I", b"9", b"+")
+        elif k < 4:
+            tok = (b"%d" % (20 + (i * 13 + salt) % 41), b"ACGT"[k:k + 1], bytes([38 + (i * 5 + salt) % 36]), b"%d" % (1 + (i * 11 + salt) % 150),
+                   b"-" if (i + salt) % 2 else b"+")
+        else:
+            tok = (b"0", b"N", b"!", b"0", b".")
+        cov += tok[1] != b"N"
+        for c in range(5):
+            cols[c].append(tok[c])
+    if cov == 0:
+        cols[0][-1], cols[1][-1], cols[2][-1], cols[3][-1], cols[4][-1] = b"33", b"C", b"F", b"12", b"-"
+        cov = 1
+    row = b"chr7\t%d\tA\t%d\t" % (pos, cov) + b"\t".join(b" ".join(c) for c in cols) + b"\n"
+    if length is None:
+        return row
+    if length < len(row):
+        return None
+    cols[1][0] = b"+A" + b"C" * (length - len(row))
+    return b"chr7\t%d\tA\t%d\t" % (pos, cov) + b"\t".join(b" ".join(c) for c in cols) + b"\n"
+
+
+def plain_rows(n_rows, n, salt, first=1):
+    return [pad_row(first + p, n, salt) for p in range(n_rows)]
+
+
+def fit_newline(rows, n, salt, at, first=1):
+    """the rows with one of them padded so that its line break is byte `at` of their concatenation; (rows, its index)"""
+    ends = np.cumsum([len(r) for r in rows])  # ends[j] - 1: row j's line break
+    j = int(np.searchsorted(ends - 1, at, side="right")) - 1
+    while j >= 0:
+        row = pad_row(first + j, n, salt, len(rows[j]) + at - int(ends[j] - 1))
+        if row is not None:
+            out = rows[:j] + [row] + rows[j + 1:]
+            assert b"".join(out)[at:at + 1] == b"\n" and b"".join(out[:j + 1]).endswith(b"\n") and len(b"".join(out[:j + 1])) == at + 1
+            return out, j
+        j -= 1
+    raise AssertionError("no row in front of byte %d" % at)
+
+
+def lines_behind(text, skip_b, skip_l, at_end):
+    """(begin, end, offset of the first byte behind) of every line the index must take from a run: the complete lines behind
+    skip_b bytes and skip_l further lines, and with at_end an unterminated last one"""
+    out, at = [], skip_b
+    while True:
+        nl = text.find(b"\n", at)
+        if nl < 0:
+            if at_end and at < len(text):
+                out.append((at, len(text), len(text)))
+            break
+        out.append((at, nl, nl + 1))
+        at = nl + 1
+    return out[skip_l:]
+
+
+def cursor_of(members_text, x):
+    """(member, offset) of inflated byte x of a run whose members hold members_text bytes each: the first member that reaches
+    beyond x; (number of members, 0) behind the last"""
+    k = base = 0
+    while k < len(members_text) and base + members_text[k] <= x:
+        base += members_text[k]
+        k += 1
+    return [k, x - base if k < len(members_text) else 0]
+
+
+def index_check(eng, texts, fs, skip_bytes=None, skip_lines=None, at_end=True, max_positions=None, member=0x5000, want_positions=None):
+    """lrt_bgzf on the files' texts against what their bytes say: the number of positions, the cursors, the fetched text and --
+    through lrt_text on the same rows uncompressed -- row_state and records.  Returns (got, expected first bytes not taken)."""
+    F = len(fs)
+    sb = list(skip_bytes) if skip_bytes is not None else [0] * F
+    sl = list(skip_lines) if skip_lines is not None else [0] * F
+    lines = [lines_behind(texts[f], sb[f], sl[f], at_end) for f in range(F)]
+    P = min([len(l) for l in lines] + [eng.max_sites] + ([max_positions] if max_positions is not None else []))
+    if want_positions is not None:
+        assert P == want_positions, (P, want_positions)
+    rows = [[texts[f][lines[f][p][0]:lines[f][p][1]] for f in range(F)] for p in range(P)]
+    x = [lines[f][P - 1][2] if P else sb[f] for f in range(F)]
+    sizes = [[min(member, len(t) - at) for at in range(0, len(t), member)] + [0] for t in texts]
+    got = eng.lrt_bgzf([members_of(t, member) for t in texts], fs, skip_bytes=sb, skip_lines=sl, at_end=at_end, max_positions=max_positions)
+    assert got.row_state.shape == (P, F), (got.row_state.shape, P)
+    assert got.cursors.tolist() == [cursor_of(sizes[f], x[f]) for f in range(F)], (got.cursors.tolist(), x)
+    if P:
+        exp = eng.lrt_text(rows, fs)  # (raises if a position is not in the strict form)
+        same_batch(got, exp, 0)
+        flat = np.frombuffer(b"".join(r + b"\n" for pos in rows for r in pos), np.uint8)
+        off = np.concatenate([[0], np.cumsum([len(r) + 1 for pos in rows for r in pos])]).astype(np.uint64)
+        check_fetched(got, flat, off, P, F)
+    else:
+        assert len(got.sites) == 0 and got.fetched[0].size == 0
+    return got, x
+
+
+FS3 = [36, 40, 44]  # rows of about 400, 440 and 480 bytes: 90 rows are three tiles in every file
+HEAD = [b"#" + b"h" * 35 + b"\n", b"#" + b"h" * 19 + b"\n", b"#" + b"h" * 51 + b"\n"]  # 37, 21 and 53 bytes: no multiple of 16
+
+
+@pytest.mark.parametrize("headers", [False, True])
+def test_line_breaks_on_the_last_and_first_byte_of_a_tile(headers):
+    """a row's line break on bytes 16383, 16384, 32767 and 32768 behind skip_bytes, in file 0 and in the last file"""
+    from basevar_amd import _capi
+    P, F = 90, 3
+    skip = [len(h) if headers else 0 for h in HEAD]
+    eng = engine(128, sum(FS3))
+    try:
+        for at in (TILE - 1, TILE, 2 * TILE - 1, 2 * TILE):
+            texts, hit = [], []
+            for f in range(F):
+                rows = plain_rows(P, FS3[f], f)
+                if f != 1:
+                    rows, j = fit_newline(rows, FS3[f], f, at)
+                    hit.append(j)
+                texts.append((HEAD[f] if headers else b"") + b"".join(rows))
+                if f != 1:
+                    assert texts[f][skip[f] + at] == 10 and 2 * TILE < len(texts[f]) - skip[f] <= 4 * TILE
+            got, _ = index_check(eng, texts, FS3, skip_bytes=skip, want_positions=P)
+            assert (got.row_state[hit[0], 0] & _capi.BV_TEXT_INDEL) and (got.row_state[hit[1], 2] & _capi.BV_TEXT_INDEL)
+    finally:
+        eng.close()
+
+
+def test_a_line_break_on_every_lane_of_the_scatter_kernel():
+    """the scatter kernel finds line ends with 64-byte ballots: rows of 64 consecutive pad lengths, twice, so that -- read back
+    from the built bytes -- a line break falls on each of the 64 lanes, behind a skip that is no multiple of 64"""
+    P, n = 128, 40
+    rows = [pad_row(1 + p, n, 0, 450 + p % 64) for p in range(P)]
+    text0 = HEAD[0] + b"".join(rows)
+    lanes = {(i - len(HEAD[0])) % 64 for i in range(len(HEAD[0]), len(text0)) if text0[i] == 10}
+    assert lanes == set(range(64))
+    assert {len(r) for r in rows} == set(range(450, 514))
+    eng = engine(P, n + 20)
+    try:
+        index_check(eng, [text0, b"".join(plain_rows(P, 20, 1))], [n, 20], skip_bytes=[len(HEAD[0]), 0], want_positions=P)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("size", [TILE - 1, TILE, TILE + 1, 2 * TILE - 1, 2 * TILE, 2 * TILE + 1])
+def test_runs_that_end_on_a_tile_boundary(size):
+    """file 0's bytes behind its skip are exactly `size`: with the last line terminated; unterminated at the end of the file (the
+    spare line break then lies at byte `size`, for 16384 and 32768 in a tile of its own -- the row is counted, parsed and fetched);
+    unterminated with at_end = 0 (the partial line is no position and the cursor points at its first byte)"""
+    n, m = 40, 24
+    eng = engine(128, n + m)
+    try:
+        for skip0 in (0, len(HEAD[0])):
+            head = HEAD[0] if skip0 else b""
+            rows, j = fit_newline(plain_rows(100, n, 0), n, 0, size - 1)
+            whole = head + b"".join(rows[:j + 1])                       # terminated: `size` bytes behind the skip
+            rows_u, ju = fit_newline(plain_rows(100, n, 0), n, 0, size)
+            cut = head + b"".join(rows_u[:ju + 1])[:-1]                 # unterminated: `size` bytes, the line break would be byte `size`
+            assert len(whole) - skip0 == size and len(cut) - skip0 == size and whole.endswith(b"\n") and not cut.endswith(b"\n")
+            other = b"".join(plain_rows(max(j, ju) + 6, m, 1))
+            for at_end in (True, False):
+                index_check(eng, [whole, other], [n, m], skip_bytes=[skip0, 0], at_end=at_end, want_positions=j + 1)
+            got, x = index_check(eng, [cut, other], [n, m], skip_bytes=[skip0, 0], at_end=True, want_positions=ju + 1)
+            assert x[0] == len(cut)
+            got, x = index_check(eng, [cut, other], [n, m], skip_bytes=[skip0, 0], at_end=False, want_positions=ju)
+            assert x[0] == len(head) + len(b"".join(rows_u[:ju])) and cut[x[0] - 1:x[0]] == b"\n"
+            # ... and the same in the last file
+            index_check(eng, [other, cut], [m, n], skip_bytes=[0, skip0], at_end=True, want_positions=ju + 1)
+            index_check(eng, [other, cut], [m, n], skip_bytes=[0, skip0], at_end=False, want_positions=ju)
+    finally:
+        eng.close()
+
+
+def test_more_header_lines_than_the_first_tile_holds():
+    """skip_lines beyond the lines of the first tile: 700 header lines, more than 16 KiB of them"""
+    heads = [b"".join(b"##header of file %d line %d\n" % (f, k) for k in range(nk)) for f, nk in ((0, 700), (1, 3), (2, 0))]
+    assert len(heads[0]) > TILE + 1000 and heads[0][:TILE].count(b"\n") < 700
+    texts = [heads[f] + b"".join(plain_rows(60, FS3[f], f)) for f in range(3)]
+    eng = engine(64, sum(FS3))
+    try:
+        index_check(eng, texts, FS3, skip_lines=[700, 3, 0], want_positions=60)
+        index_check(eng, texts, FS3, skip_lines=[700, 3, 0], want_positions=59, at_end=False, skip_bytes=None, max_positions=59)
+        index_check(eng, [t[:-1] for t in texts], FS3, skip_lines=[700, 3, 0], want_positions=59, at_end=False)
+    finally:
+        eng.close()
+
+
+def test_one_tile_beside_three():
+    """files of very different length: the minimum over the files decides, the long files' cursors stop inside their runs"""
+    texts = [b"".join(plain_rows(110, FS3[0], 0)), b"".join(plain_rows(30, FS3[1], 1)), b"".join(plain_rows(95, FS3[2], 2))]
+    assert len(texts[1]) < TILE and 2 * TILE < len(texts[0]) <= 3 * TILE and 2 * TILE < len(texts[2]) <= 3 * TILE
+    eng = engine(128, sum(FS3))
+    try:
+        got, x = index_check(eng, texts, FS3, want_positions=30)
+        assert x[1] == len(texts[1]) and x[0] < TILE and x[2] < TILE
+        index_check(eng, [texts[1], texts[0], texts[2]], [FS3[1], FS3[0], FS3[2]], want_positions=30)
+        index_check(eng, [texts[0], texts[2], texts[1][:-1]], [FS3[0], FS3[2], FS3[1]], want_positions=29, at_end=False)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("where", [0, 1, 2])
+def test_a_file_with_nothing_behind_its_skip(where):
+    """len == skip_bytes in one file (first, in the middle, last) beside files that have text: no position, no error, and the
+    cursors stay where they started"""
+    eng = engine(64, sum(FS3))
+    try:
+        for empty, skip in ((HEAD[0], len(HEAD[0])), (b"", 0)):
+            texts = [HEAD[f] + b"".join(plain_rows(50, FS3[f], f)) for f in range(3)]
+            sb = [len(h) for h in HEAD]
+            texts[where], sb[where] = empty, skip
+            for at_end in (True, False):
+                got, x = index_check(eng, texts, FS3, skip_bytes=sb, at_end=at_end, want_positions=0)
+                assert x == sb
+        texts[where] = HEAD[where] + b"".join(plain_rows(50, FS3[where], where))  # ... and the engine goes on
+        index_check(eng, texts, FS3, skip_bytes=[len(h) for h in HEAD], want_positions=50)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("at", [TILE - 1, TILE])
+def test_max_positions_cuts_at_a_tile_boundary(at):
+    """max_positions ends the window with a row whose line break is the last byte of a tile (16383) or the first byte of the next
+    (16384), in file 0 and in the last file; the next window, started from the cursors, goes on exactly there and the two
+    together are the one-call result"""
+    P, F, member = 90, 3, 0x2800
+    texts, hit = [], []
+    for f in range(F):
+        rows = plain_rows(P, FS3[f], f)
+        if f != 1:
+            rows, j = fit_newline(rows, FS3[f], f, at)
+            hit.append(j)
+        texts.append(b"".join(rows))
+    eng = engine(128, sum(FS3))
+    try:
+        whole, _ = index_check(eng, texts, FS3, member=member, want_positions=P)
+        for cut in sorted({hit[0] + 1, hit[1] + 1}):
+            first, x = index_check(eng, texts, FS3, member=member, max_positions=cut, want_positions=cut)
+            assert all(texts[f][x[f] - 1] == 10 for f in range(F)) and (x[0] == at + 1 or x[2] == at + 1)
+            # the next window: from the member each cursor names, skip_bytes = its offset
+            files = [members_of(t, member) for t in texts]
+            runs = [files[f][int(first.cursors[f, 0]):] for f in range(F)]
+            rest = eng.lrt_bgzf(runs, FS3, skip_bytes=[int(c) for c in first.cursors[:, 1]])
+            assert rest.row_state.shape[0] == P - cut
+            assert np.array_equal(np.concatenate([first.row_state, rest.row_state]), whole.row_state)
+            assert np.array_equal(np.concatenate([first.positions, rest.positions + cut]), whole.positions)
+            assert first.sites.tobytes() + rest.sites.tobytes() == whole.sites.tobytes()
+            assert first.cell.tobytes() + rest.cell.tobytes() == whole.cell.tobytes() and first.phred.tobytes() + rest.phred.tobytes() == whole.phred.tobytes()
+            tail = [t[x[f]:] for f, t in enumerate(texts)]
+            rows = [[l for l in tail[f].split(b"\n")[:-1]] for f in range(F)]
+            flat = np.frombuffer(b"".join(rows[f][p] + b"\n" for p in range(P - cut) for f in range(F)), np.uint8)
+            off = np.concatenate([[0], np.cumsum([len(rows[f][p]) + 1 for p in range(P - cut) for f in range(F)])]).astype(np.uint64)
+            check_fetched(rest, flat, off, P - cut, F)
+    finally:
+        eng.close()

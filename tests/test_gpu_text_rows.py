@@ -148,13 +148,37 @@ def test_depth_zero_positions_give_no_record():
     assert (got.row_state[[3, 9, 17, 25]] == _capi.BV_TEXT_SKIP).all()
 
 
-def test_device_parser_against_the_host_reader(tmp_path):
+def build_text_rows_check(tmp_path):
     exe = tmp_path / "text_rows_check"
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", "text_rows_check.cpp"), "-L", os.path.join(ROOT, "basevar_amd", "lib"),
                            "-lbasevar_amd", "-Wl,-rpath," + os.path.join(ROOT, "basevar_amd", "lib"), "-o", str(exe)])
-    p = subprocess.run([str(exe), "40"], capture_output=True, text=True, timeout=600)
+    return str(exe)
+
+
+def test_device_parser_against_the_host_reader(tmp_path):
+    exe = build_text_rows_check(tmp_path)
+    p = subprocess.run([exe, "40"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "FAILS 0" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+
+
+def test_device_parser_on_the_positional_corpus(tmp_path):
+    """tests/cpp/row_lane_cases.hpp through the device parser: valid rows of 3 to 10 of the kernel's 64-byte steps with every
+    token start, tab and line break on every lane, and damaged rows whose defect sits on lanes 0, 1, 62, 63 and 31 of a step
+    behind the first (the tracer's LANE_COVERAGE line says what was reached; anything missing is a failure).  Many positions to a
+    batch: records, cell / phred planes, SiteText, positions kept and used and the error text are the host reader's, every valid
+    and every clean row is parsed on the device, and all four outcomes occur.
+    Measured on an MI355X in one run, compiling the harness included: test_device_parser_against_the_host_reader (as in the parent
+    commit; the library is the parent's) 3.74 s, this test 3.30 s (194 batches); test_gpu_bgzf_rows.py's corpus test 5.07 s as
+    the first test of its process, its line-index tests 0.01 to 0.04 s each."""
+    import re
+    exe = build_text_rows_check(tmp_path)
+    p = subprocess.run([exe, "0", "lanes"], capture_output=True, text=True, timeout=600)
+    print(p.stdout[-2000:])
+    assert p.returncode == 0 and "FAILS 0" in p.stdout, p.stdout[-3000:] + p.stderr[-3000:]
+    assert re.search(r"LANE_COVERAGE rows \d+ .* missing 0\n", p.stdout) and re.search(r"LANE_CASES .* bad 0\n", p.stdout), p.stdout[-3000:]
+    m = re.search(r"TEXT_ROWS_LANES batches (\d+) device (\d+) host (\d+) skipped (\d+) threw (\d+)", p.stdout)
+    assert m and all(int(g) > 0 for g in m.groups()), p.stdout[-3000:]
 
 
 def test_text_staging_reused_over_many_chunks(monkeypatch):

@@ -185,6 +185,12 @@ def test_host_formats_harness(tmp_path, restatement):
     assert out.returncode == 0, out.stderr[-3000:]
     assert "PRIMITIVES_CHECKED 1" in out.stdout and "FAILS 0" in out.stdout
     assert "FAST_READER_CASES" in out.stdout  # the byte-level batchfile reader against the literal one
+    # ... and on the positional corpus of the device row parser (tests/cpp/row_lane_cases.hpp), whose tracer shows here, without a
+    # GPU, that every token start, tab and line break falls on every lane and every placed defect on the lane it was meant for
+    cov = [l for l in out.stdout.split("\n") if l.startswith(("LANE_COVERAGE", "LANE_CASES", "LANE_READER_CASES"))]
+    print("\n".join(cov))
+    assert any(l.startswith("LANE_COVERAGE rows") and l.endswith(" missing 0") for l in cov), cov
+    assert any(l.startswith("LANE_CASES") and l.endswith(" bad 0") for l in cov) and any(l.startswith("LANE_READER_CASES") for l in cov), cov
     lines = out.stdout.split("\n")
     # headers
     cvg_h = lines[lines.index("CVG_HEADER_BEGIN") + 1:lines.index("CVG_HEADER_END")]
