@@ -1,4 +1,6 @@
-// bv_engine.hip -- host side of the C ABI declared in include/basevar_amd.h.
+// bv_engine.hip -- host side of the C ABI declared in include/basevar_amd.h: the engine's life cycle, stream ordering, the
+// staging ring of host buffers, wait / timing / join, the host-log probe, NUMA placement and the synth entry point.  (Row
+// submits: bv_engine_rows.hip; the tile mode: bv_engine_tiles.hip.)
 //
 // One engine = one HIP stream + the small device scratch the two passes share (phred
 // tables, variant-site list, counters) + HIP events that time each pass on the stream it
@@ -19,6 +21,9 @@
 #include <vector>
 
 #include "bv_engine_impl.h"
+#ifdef BV_TEAM_DEBUG
+#include "bv_engine_debug.h"
+#endif
 
 void bv_launch_synth(const bv_synth_params &p, uint32_t n_sites, uint32_t n_samples, uint64_t pitch, uint8_t *bs,
                      uint8_t *q, uint8_t *mapq, uint16_t *rpr, uint8_t *ref_base, hipStream_t stream);
@@ -175,9 +180,8 @@ int bv_impl::fail(bv_engine *e, int code, const std::string &msg) {
 }
 using namespace bv_impl;
 
-namespace {
 // fold every completed pending triplet into the accumulators; `block` waits for them
-int drain_timings(bv_engine *e, bool block) {
+int bv_impl::drain_timings(bv_engine *e, bool block) {
     while (e->ring_count > 0) {
         int slot = (e->ring_head - e->ring_count + bv_engine::kRing * 2) % bv_engine::kRing;
         hipEvent_t *t = e->ring[slot];
@@ -199,8 +203,6 @@ int drain_timings(bv_engine *e, bool block) {
     }
     return BV_OK;
 }
-}  // namespace
-
 
 namespace {
 // The engine's scratch (variant list, counters, staging) is shared by its submits, so work of one engine is
@@ -516,17 +518,7 @@ int bv_engine_destroy(bv_engine *e) {
     if (e->d_var_list) (void)hipFree(e->d_var_list);
     if (e->d_counters) (void)hipFree(e->d_counters);
     if (e->d_gid) (void)hipFree(e->d_gid);
-    if (e->d_summ) (void)hipFree(e->d_summ);
-    if (e->d_bins) (void)hipFree(e->d_bins);
-    if (e->d_cand_list) (void)hipFree(e->d_cand_list);
-    if (e->d_easy_list) (void)hipFree(e->d_easy_list);
-    if (e->d_easy3_list) (void)hipFree(e->d_easy3_list);
-    if (e->d_ovf) (void)hipFree(e->d_ovf);
-    if (e->d_gitems) (void)hipFree(e->d_gitems);
-    if (e->d_gidp) (void)hipFree(e->d_gidp);
-    if (e->d_chain) (void)hipFree(e->d_chain);
-    if (e->d_ref_cat) (void)hipFree(e->d_ref_cat);
-    if (e->d_out_cat) (void)hipFree(e->d_out_cat);
+    row_scratch_free(e);
     if (e->ev_done) (void)hipEventDestroy(e->ev_done);
     if (e->ev_host) (void)hipEventDestroy(e->ev_host);
     if (e->h_counters) (void)hipHostFree(e->h_counters);
@@ -536,8 +528,6 @@ int bv_engine_destroy(bv_engine *e) {
         if (sl.freed) (void)hipEventDestroy(sl.freed);
     }
     tile_job_free(e->tile);
-    if (e->d_gid_round) (void)hipFree(e->d_gid_round);
-    if (e->d_gout_round) (void)hipFree(e->d_gout_round);
     for (hipStream_t cs : e->copy_stream)
         if (cs) (void)hipStreamSynchronize(cs);
     for (hipStream_t cs : e->copy_stream)
@@ -547,564 +537,7 @@ int bv_engine_destroy(bv_engine *e) {
     return BV_OK;
 }
 
-}  // extern "C"
-
-// The two passes over device-resident planes + the copies back (records to a host caller, counters).
-//
-// (Round 3 also ran short-row batches as a software pipeline of chunks over two streams -- the solve kernels of chunk c under the
-// streaming kernel of chunk c + 1.  Measured a loss at every size (beside a streaming kernel the solve kernels get one
-// workgroup per CU and run 3 x longer, the streaming kernel slows by 50-70 %): removed; docs/history/DESIGN_round3.md 4.2b.)
-int bv_impl::launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, const uint8_t *mq, const uint16_t *rp, const uint8_t *refb,
-                           const uint8_t *gid, size_t P, uint32_t n_sites, uint32_t n_samples, uint32_t n_groups, bv_site_result *dout,
-                           bv_group_result *dgout, hipStream_t st, const BvChain *chain, bool chain_cat, uint32_t layout) {
-    const uint32_t rpr_tag = (layout & BV_SLAB_RPR_TAGGED) && rp != nullptr ? 1u : 0u;
-    const size_t S = n_sites, G = n_groups;
-    // The group kernels hold one (base, phred) histogram per group in LDS and are built for at most BV_GROUPS_PER_ROUND of them;
-    // the reference takes any number of groups (a std::map, basetype_caller.cpp:372-410).  More groups run as ROUNDS of pass 2:
-    // round r sees groups [r x 32, r x 32 + 32) only (bv_launch_gid_round) and writes [S][32] records of its own, which one 2-D
-    // copy moves to their columns of the caller's [S][G] array.  Only round 0 forms the rank sums.
-    const size_t Gr = G < BV_GROUPS_PER_ROUND ? G : (size_t)BV_GROUPS_PER_ROUND, n_rounds = G ? (G + Gr - 1) / Gr : 1;
-    if (n_rounds > 1 && chain != nullptr) return fail(e, BV_ERR_INVALID_ARG, "launch_passes: more than 32 pop-groups do not chain");
-    if (G && chain == nullptr) BV_HIP(e, hipMemsetAsync(dgout, 0, S * G * sizeof(bv_group_result), st));  // (chained: per segment, by the caller)
-    if (n_rounds > 1) {
-        int rc = grow_device(e, &e->d_gid_round, &e->d_gid_round_bytes, up256(n_samples) + 256);
-        if (rc == BV_OK) rc = grow_device(e, &e->d_gout_round, &e->d_gout_round_bytes, S * Gr * sizeof(bv_group_result));
-        if (rc != BV_OK) return rc;
-    }
-
-    // Per-pass timing: four event records per launch (start, end of the streaming kernel, end of pass 1, end of pass 2).  They are
-    // not free -- each is a packet the next kernel queues behind: ~15 us per launch together (measured: 100 k sites x 10 k samples
-    // 158.4 -> 162.4 M sites/s without them, 8,192-site batches 56.7 -> 63.0 M) -- so BV_FLAG_SPARSE_TIMING records them for one
-    // launch in eight; the averages of bv_engine_timing_get then rest on those launches.
-    const bool timed = !(e->cfg.flags & BV_FLAG_SPARSE_TIMING) || (e->n_launches % 8u) == 0u;
-    e->n_launches += 1;
-    hipEvent_t *ev = nullptr;
-    if (timed) {
-        if (e->ring_count == bv_engine::kRing) {
-            int rc = drain_timings(e, true);  // ring full: fold the oldest submits first
-            if (rc != BV_OK) return rc;
-        }
-        const int slot = e->ring_head;
-        e->ring_head = (e->ring_head + 1) % bv_engine::kRing;
-        e->ring_count += 1;
-        e->last_slot = slot;
-        ev = e->ring[slot];
-        e->ring_one_kernel[slot] = false;
-    }
-    // Rows of at most BV_SHORT_ROW_MAX samples take the short-row forms of pass 1 (bv_pass1_fused.hip; bv_pass1_short.hip)
-    const bool two_kernel = n_samples <= BV_SHORT_ROW_MAX;
-
-    // ---- pass-2 arguments common to every chunk; scratch of the pop-group calls
-    BvPass2Args a2;
-    a2.bs = bs; a2.q = q; a2.mapq = mq; a2.rpr = rp; a2.ref_base = refb; a2.group_id = gid; a2.pitch = P;
-    a2.n_sites = n_sites; a2.n_samples = n_samples; a2.n_groups = n_groups;
-    a2.min_af = e->cfg.min_af; a2.tables = e->d_tables; a2.out = dout; a2.gout = dgout;
-    a2.var_list = e->d_var_list; a2.counters = e->d_counters; a2.n_cu = e->n_cu; a2.flags = e->cfg.flags;
-    a2.gitems = nullptr; a2.gitem_cap = 0; a2.gidp = nullptr;
-    a2.ch = chain;
-    a2.ch_cat = chain_cat ? 1u : 0u;
-    a2.rpr_tag = rpr_tag;
-    if (G && gid && dgout && !(e->cfg.flags & BV_FLAG_GROUP_INLINE)) {
-        // scratch for the group calls of the variant sites (1.5 KiB per site x group), grown on demand and capped at 8 GiB:
-        // the variant sites past the cap keep the one-wave-per-group solver inside the tally kernel.  An allocation that
-        // fails is retried at half the size (the inline path takes what the scratch cannot).
-        const uint64_t want64 = (uint64_t)S * Gr, most = (8192ull << 20) / (sizeof(uint32_t) * BV_P2G_ITEM_WORDS);
-        uint32_t want = (uint32_t)(want64 < most ? want64 : most);
-        if (want > e->gitem_cap) {
-            if (e->d_gitems) BV_HIP(e, hipFree(e->d_gitems));
-            e->d_gitems = nullptr; e->gitem_cap = 0;
-            for (;;) {
-                if (hipMalloc(&e->d_gitems, sizeof(uint32_t) * BV_P2G_ITEM_WORDS * (size_t)want) == hipSuccess) {
-                    e->gitem_cap = want;
-                    break;
-                }
-                (void)hipGetLastError();
-                e->d_gitems = nullptr;
-                if (want < 1024u) break;  // no scratch at all: every group is solved inside the tally kernel
-                want /= 2u;
-            }
-        }
-        a2.gitems = e->d_gitems; a2.gitem_cap = e->gitem_cap;
-        // short rows: the group plane as the streaming group tally wants it
-        const size_t n16 = ((size_t)n_samples + 15) & ~(size_t)15;
-        const int rc = grow_device(e, &e->d_gidp, &e->d_gidp_bytes, n16 + 256);
-        if (rc != BV_OK) return rc;
-        a2.gidp = e->d_gidp;
-        // the group plane as the perm-form tallies read it (short rows: bv_p2g_stream_kernel; long rows: bv_p2_fast_sweep)
-        // (several rounds of groups: prepared per round, below)
-        if (n_rounds == 1) {
-            bv_launch_gid_prepare(gid, e->d_gidp, (uint32_t)n16, n_groups, st);
-            BV_HIP(e, hipGetLastError());
-        }
-    }
-    if (n_rounds > 1) a2.n_groups = (uint32_t)Gr;  // (what the kernel-selection predicates below see)
-
-    e->last_blocks = 1;
-#ifdef BV_TEAM_DEBUG
-    const bool rotate = false;  // (the instrumented builds keep their stamps in the blocks behind the first)
-#else
-    const bool rotate = true;
-#endif
-    uint32_t cb = 0;  // this launch's first counter block
-    if (rotate) {
-        cb = e->ctr_rot % bv_engine::kCtrBlocks;
-        if (cb == 0)  // a new round: the per-launch lines of every block (not the sticky error counters behind them) in one fill
-            BV_HIP(e, hipMemset2DAsync(e->d_counters, sizeof(uint32_t) * BV_CTR_WORDS, 0, sizeof(uint32_t) * BV_CTR_PER_LAUNCH * BV_CTR_STRIDE,
-                                       bv_engine::kCtrBlocks, st));
-        e->ctr_rot += 1;
-    } else {
-        e->ctr_rot = 0;  // (the next rotating launch starts a round of its own)
-        BV_HIP(e, hipMemsetAsync(e->d_counters, 0, sizeof(uint32_t) * BV_CTR_PER_LAUNCH * BV_CTR_STRIDE, st));
-    }
-    e->last_ctr_base = cb;
-    a2.counters = e->d_counters + (size_t)cb * BV_CTR_WORDS;
-    bool pass2_fused = false;  // pass 1's kernel has streamed the pass-2 rows too (bv_pass1_fused.hip)
-    e->last_form = two_kernel ? BV_FORM_SHORT_ROWS : 0u;
-    if (ev) BV_HIP(e, hipEventRecord(ev[0], st));
-    if (two_kernel) {
-        if (n_sites > e->short_sites) {
-            // scratch between the kernels, grown to the largest short-row submit seen: 48 B + 2 KiB + 12 B per site
-            if (e->d_summ) BV_HIP(e, hipFree(e->d_summ));
-            if (e->d_bins) BV_HIP(e, hipFree(e->d_bins));
-            if (e->d_cand_list) BV_HIP(e, hipFree(e->d_cand_list));
-            if (e->d_easy_list) BV_HIP(e, hipFree(e->d_easy_list));
-            if (e->d_easy3_list) BV_HIP(e, hipFree(e->d_easy3_list));
-            if (e->d_ovf) BV_HIP(e, hipFree(e->d_ovf));
-            e->d_ovf = nullptr;
-            e->d_summ = nullptr; e->d_bins = nullptr; e->d_cand_list = nullptr; e->d_easy_list = nullptr; e->d_easy3_list = nullptr; e->short_sites = 0;
-            BV_HIP(e, hipMalloc(&e->d_summ, sizeof(BvSiteSummary) * (size_t)n_sites));
-            BV_HIP(e, hipMalloc(&e->d_bins, sizeof(uint32_t) * BV_S_BIN_STRIDE * (size_t)n_sites));
-            BV_HIP(e, hipMalloc(&e->d_cand_list, sizeof(uint32_t) * (size_t)n_sites));
-            BV_HIP(e, hipMalloc(&e->d_easy_list, sizeof(uint32_t) * (size_t)n_sites));
-            BV_HIP(e, hipMalloc(&e->d_easy3_list, sizeof(uint32_t) * (size_t)n_sites));
-            BV_HIP(e, hipMalloc(&e->d_ovf, sizeof(uint32_t) * 4 * (size_t)n_sites));
-            e->short_sites = n_sites;
-        }
-        BvP1ShortArgs s1;
-        s1.bs = bs; s1.q = q; s1.ref_base = refb; s1.pitch = P; s1.n_sites = n_sites; s1.n_samples = n_samples;
-        s1.flags = e->cfg.flags; s1.n_cu = e->n_cu; s1.min_af = e->cfg.min_af; s1.tables = e->d_tables; s1.out = dout;
-        s1.var_list = e->d_var_list; s1.counters = e->d_counters + (size_t)cb * BV_CTR_WORDS;
-        s1.summ = e->d_summ; s1.bins = e->d_bins;
-        s1.cand_list = e->d_cand_list; s1.easy_list = e->d_easy_list; s1.easy3_list = e->d_easy3_list;
-        s1.ovf = e->d_ovf;
-        s1.ch = chain;
-        s1.mapq = nullptr; s1.rpr = nullptr; s1.rpr_tag = rpr_tag;
-        // Rows of at least three 4 KiB slots: pass 1 as ONE persistent kernel (bv_pass1_fused.hip: solver waves beside the
-        // streaming waves of every workgroup), which streams the variant sites' rank-sum rows (pass 2) too -- with pop-groups
-        // where their tallies stream on their own (<= 7 groups): the launch that follows then carries the group kernels only.
-        // Shorter rows, and BV_FLAG_SHORT_ROW_FORM(9) (tests: an independent realisation): a streaming kernel, a solve
-        // kernel, pass 2 a launch of its own (bv_pass1_short.hip); BV_FLAG_SHORT_ROW_FORM(10): the fused kernel for pass 1 only.
-        const uint32_t form = (e->cfg.flags >> 12) & 0xFu;
-        if (form != 9u && bv_p1s_fused_takes(s1)) {
-            if (ev) e->ring_one_kernel[e->last_slot] = true;
-            // (with pop-groups of any number: the launch behind then carries the group tallies only -- the rank sums of a variant row
-            // cost this kernel 0.12 ms per 100 k sites, the workgroup-per-row group kernel 0.16-0.2)
-            if (form != 10u && mq != nullptr && rp != nullptr && !(e->cfg.flags & BV_FLAG_PASS2_SWEEP)) {
-                s1.mapq = mq; s1.rpr = rp;
-                pass2_fused = true;
-            }
-            bv_launch_p1s_fused(s1, st);
-            BV_HIP(e, hipGetLastError());
-            e->last_form |= BV_FORM_ONE_KERNEL | (pass2_fused ? BV_FORM_PASS2_FUSED : 0u);
-        } else {
-            bv_launch_p1s_stream(s1, st);
-            BV_HIP(e, hipGetLastError());
-            if (ev) BV_HIP(e, hipEventRecord(ev[3], st));
-            bv_launch_p1s_solve(s1, st);
-            BV_HIP(e, hipGetLastError());
-        }
-        if (ev) BV_HIP(e, hipEventRecord(ev[1], st));
-    } else {
-        if (ev) e->ring_one_kernel[e->last_slot] = true;
-        BvPass1Args a1;
-        a1.bs = bs; a1.q = q; a1.ref_base = refb; a1.pitch = P; a1.n_sites = n_sites;
-        a1.n_samples = n_samples; a1.flags = e->cfg.flags; a1.min_af = e->cfg.min_af; a1.tables = e->d_tables; a1.out = dout;
-        a1.var_list = e->d_var_list; a1.counters = e->d_counters + (size_t)cb * BV_CTR_WORDS; a1.n_cu = e->n_cu;
-        a1.ch = chain;
-        bv_launch_pass1(a1, st);
-        BV_HIP(e, hipGetLastError());
-        e->last_form |= BV_FORM_ONE_KERNEL;
-        if (ev) BV_HIP(e, hipEventRecord(ev[1], st));  // (one kernel: no separate event for "the streaming kernel")
-    }
-
-    for (size_t r = 0; r < n_rounds; ++r) {
-        const size_t g_lo = r * Gr, g_n = n_rounds > 1 ? std::min(Gr, G - g_lo) : G;  // this round's groups
-        if (n_rounds > 1) {
-            const size_t n16 = ((size_t)n_samples + 15) & ~(size_t)15;
-            bv_launch_gid_round(gid, e->d_gid_round, (uint32_t)n16, (uint32_t)g_lo, (uint32_t)g_n, st);
-            BV_HIP(e, hipGetLastError());
-            bv_launch_gid_prepare(e->d_gid_round, e->d_gidp, (uint32_t)n16, (uint32_t)g_n, st);
-            BV_HIP(e, hipGetLastError());
-            BV_HIP(e, hipMemsetAsync(e->d_gout_round, 0, S * g_n * sizeof(bv_group_result), st));
-        }
-        BvPass2Args ac = a2;
-        if (n_rounds > 1) { ac.group_id = e->d_gid_round; ac.n_groups = (uint32_t)g_n; ac.gout = e->d_gout_round; }
-        if (pass2_fused || r > 0) {  // the rank sums are formed already (by pass 1's kernel / by round 0): what is left is the pop-groups
-            if (G == 0) continue;
-            ac.mapq = nullptr; ac.rpr = nullptr;
-        }
-        bv_launch_pass2(ac, st);
-        BV_HIP(e, hipGetLastError());
-        bv_launch_p2g_solve16(ac, st);
-        BV_HIP(e, hipGetLastError());
-        if (n_rounds > 1)  // the round's records -> columns [g_lo, g_lo + g_n) of every site's groups
-            BV_HIP(e, hipMemcpy2DAsync(dgout + g_lo, G * sizeof(bv_group_result), e->d_gout_round, g_n * sizeof(bv_group_result),
-                                       g_n * sizeof(bv_group_result), S, hipMemcpyDeviceToDevice, st));
-    }
-    if (ev) BV_HIP(e, hipEventRecord(ev[2], st));
-
-    if (rotate) e->ctr_mirror_stale = true;  // mirrored by bv_engine_wait
-    else BV_HIP(e, hipMemcpyAsync(e->h_counters, e->d_counters, sizeof(uint32_t) * BV_CTR_WORDS * bv_engine::kCtrBlocks, hipMemcpyDeviceToHost, st));
-    const int rc = copy_records_back(e, st);
-    if (rc != BV_OK) return rc;
-    e->submitted = true;
-    return mark_done(e, st);
-}
-
-extern "C" {
-
-int bv_engine_submit(bv_engine *e, const bv_slab *slab, bv_site_result *out, bv_group_result *gout, void *stream_) {
-    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_submit: null engine");
-    if (!slab || !out) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: null slab/out");
-    if (slab->n_sites == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: n_sites == 0");
-    if (slab->n_sites > e->cfg.max_sites)
-        return fail(e, BV_ERR_TOO_LARGE, "bv_engine_submit: n_sites exceeds cfg.max_sites");
-    if (slab->n_samples == 0 || slab->pitch < slab->n_samples || (slab->pitch & 15ull))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: pitch must be >= n_samples and a multiple of 16");
-    if (!slab->base_strand || !slab->qual || !slab->ref_base)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: base_strand, qual and ref_base planes are required");
-    if ((slab->mapq == nullptr) != (slab->rpr == nullptr))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: mapq and rpr planes must be given together");
-    if (slab->n_groups > BV_MAX_GROUPS)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: n_groups exceeds BV_MAX_GROUPS");
-    if (slab->n_groups > 0 && (!slab->group_id || !gout))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: n_groups > 0 needs group_id and gout");
-    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
-    if (misaligned(slab->base_strand) || misaligned(slab->qual) || misaligned(slab->mapq) || misaligned(slab->rpr))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: planes must be 16-byte aligned");
-    if (slab->mem_kind != BV_MEM_HOST && misaligned(out))
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: device record buffers must be 16-byte aligned");
-    if ((slab->layout & ~BV_SLAB_RPR_TAGGED) || slab->reserved_)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit: unknown bv_slab.layout bits (built against another BV_ABI_VERSION?)");
-
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    if ((e->cfg.flags & BV_FLAG_LANES) && !e->is_lane && slab->mem_kind != BV_MEM_HOST) {
-        // two lanes: this submit goes to the child engine whose turn it is, on that child's own stream, ordered behind what
-        // the caller's stream holds now; the caller's stream gets nothing back (bv_engine_join / bv_engine_wait)
-        const int k = (int)(e->lane_next++ % (unsigned)e->n_lanes);
-        if (!e->lane[k]) {
-            bv_engine_config c = e->cfg;
-            c.flags &= ~BV_FLAG_LANES;
-            int rc = bv_engine_create(&c, &e->lane[k]);
-            if (rc != BV_OK) return fail(e, rc, std::string("bv_engine_submit: lane engine: ") + bv_last_error(nullptr));
-            e->lane[k]->is_lane = true;
-        }
-        bv_engine *l = e->lane[k];
-        // (only if that stream holds unfinished work: recording an event on an idle stream and waiting for it on another cost
-        // 0.5-2 ms per submit on this stack -- measured, round 3 -- against ~10 us when the marker follows real work)
-        // NULL means the engine's own stream here too (include/basevar_amd.h): planes written on bv_engine_stream(e) just
-        // before a NULL-stream submit are ordered like those of any other stream.  (A stream that is being captured
-        // answers the query with an error: treated as "holds work", the marker is then part of the capture.)
-        hipStream_t src = stream_ ? (hipStream_t)stream_ : e->stream;
-        if (hipStreamQuery(src) != hipSuccess) {
-            (void)hipGetLastError();  // hipErrorNotReady is the answer, not an error
-            if (!e->ev_entry) BV_HIP(e, hipEventCreateWithFlags(&e->ev_entry, hipEventDisableTiming));
-            BV_HIP(e, hipEventRecord(e->ev_entry, src));
-            BV_HIP(e, hipStreamWaitEvent(l->stream, e->ev_entry, 0));
-        }
-        const int rc = bv_engine_submit(l, slab, out, gout, nullptr);
-        if (rc != BV_OK) return fail(e, rc, bv_last_error(l));
-        e->last_lane = k;
-        e->submitted = true;
-        return BV_OK;
-    }
-    e->last_lane = -1;
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-
-    const uint8_t *bs = slab->base_strand, *q = slab->qual, *mq = slab->mapq, *refb = slab->ref_base,
-                  *gid = slab->group_id;
-    const uint16_t *rp = slab->rpr;
-    bv_site_result *dout = out;
-    bv_group_result *dgout = gout;
-    const size_t S = slab->n_sites, P = slab->pitch, G = slab->n_groups;
-    StageSlot *slot = nullptr;
-    if (slab->mem_kind == BV_MEM_HOST) {
-        // host planes -> a staging slot, copied by the copy stream (under the kernels of the previous submit)
-        HostPlane pl[5] = {{bs, S * P, nullptr}, {q, S * P, nullptr}, {mq, mq ? S * P : 0, nullptr},
-                           {rp, rp ? S * P * 2 : 0, nullptr}, {refb, S, nullptr}};
-        const int rc = stage_records(e, pl, 5, S, G, out, gout, &slot, &dout, &dgout, st);
-        if (rc != BV_OK) return rc;
-        bs = pl[0].dev; q = pl[1].dev; mq = pl[2].dev;
-        rp = reinterpret_cast<const uint16_t *>(pl[3].dev);
-        refb = pl[4].dev;
-    } else {
-        e->host_out = nullptr; e->host_gout = nullptr;
-    }
-    if (G) {
-        int rc = stage_group_ids(e, slab->group_id, slab->n_samples, slab->mem_kind == BV_MEM_HOST, st, &gid);
-        if (rc != BV_OK) return rc;
-    }
-
-    int rc = launch_passes(e, bs, q, mq, rp, refb, gid, P, slab->n_sites, slab->n_samples, slab->n_groups, dout, dgout, st, nullptr, false, slab->layout);
-    if (rc == BV_OK && slot) rc = stage_release(e, slot, st);  // planes read, records copied back: the slot may be refilled
-    return rc;
-}
-
-// Several device-resident slabs of one row length, ONE launch per pass (BvChain): what a host with a few small batches
-// ready should call -- the tail of every batch but the last hides under the next batch's stream.  Falls back to one
-// submit per slab whenever the chained kernels do not apply (short rows, pop-groups, host memory, a forced kernel shape).
-int bv_engine_submit_many(bv_engine *e, uint32_t n_slabs, const bv_slab *slabs, bv_site_result *const *outs, void *stream_) {
-    return bv_engine_submit_many_g(e, n_slabs, slabs, outs, nullptr, stream_);
-}
-
-// The same with pop-groups: gouts[k] = slab k's [n_sites][n_groups] records (NULL array: no slab may have groups).  A queue
-// with groups chains when every slab names the SAME group_id array and group count (one cohort).
-int bv_engine_submit_many_g(bv_engine *e, uint32_t n_slabs, const bv_slab *slabs, bv_site_result *const *outs,
-                            bv_group_result *const *gouts, void *stream_) {
-    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_submit_many: null engine");
-    if (!slabs || !outs || n_slabs == 0) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit_many: null / empty argument");
-    bool chainable = n_slabs > 1;
-    uint64_t total = 0;
-    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
-    // every slab is checked before anything is launched (the checks of bv_engine_submit)
-    for (uint32_t k = 0; k < n_slabs; ++k) {
-        const bv_slab &s = slabs[k];
-        if (!outs[k]) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit_many: null record buffer");
-        if (s.n_sites == 0 || s.n_samples == 0 || s.pitch < s.n_samples || (s.pitch & 15ull) || !s.base_strand || !s.qual || !s.ref_base ||
-            (s.mapq == nullptr) != (s.rpr == nullptr) || misaligned(s.base_strand) || misaligned(s.qual) || misaligned(s.mapq) ||
-            misaligned(s.rpr) || (s.mem_kind != BV_MEM_HOST && misaligned(outs[k])) || s.n_groups > BV_MAX_GROUPS || (s.layout & ~BV_SLAB_RPR_TAGGED) || s.reserved_)
-            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit_many: a slab fails the checks of bv_engine_submit");
-        if (s.n_groups > 0 && (!s.group_id || !gouts || !gouts[k]))
-            return fail(e, BV_ERR_INVALID_ARG, "bv_engine_submit_many: a slab with pop-groups needs group_id and its gouts[k] (bv_engine_submit_many_g)");
-        if (s.n_sites > e->cfg.max_sites) return fail(e, BV_ERR_TOO_LARGE, "bv_engine_submit_many: a slab exceeds cfg.max_sites");
-        // (host memory and the diagnostic kernel choices take kernels that know no chain; a queue is one cohort: one row
-        // length, one pitch, one set of planes, one group assignment)
-        chainable = chainable && s.mem_kind != BV_MEM_HOST && !(e->cfg.flags & (BV_FLAG_PASS2_SWEEP | BV_FLAG_GROUP_INLINE)) &&
-                    s.n_samples == slabs[0].n_samples && s.pitch == slabs[0].pitch && (s.mapq == nullptr) == (slabs[0].mapq == nullptr) &&
-                    s.n_groups == slabs[0].n_groups && (s.n_groups == 0 || s.group_id == slabs[0].group_id) && s.layout == slabs[0].layout;
-        total += s.n_sites;
-    }
-    const uint32_t G = slabs[0].n_groups;
-    // pop-groups chain only when every (site, group) of a launch has an item in the scratch (no inline solves: their kernels
-    // would need the segment look-up too) -- checked per launch below through the 8 GiB cap of launch_passes
-    if (chainable && G && (uint64_t)std::min<uint64_t>(total, e->cfg.max_sites) * G * sizeof(uint32_t) * BV_P2G_ITEM_WORDS > (8192ull << 20)) chainable = false;
-    if (G > BV_GROUPS_PER_ROUND) chainable = false;  // several rounds of groups (launch_passes): slab by slab
-    if (!chainable) {
-        for (uint32_t k = 0; k < n_slabs; ++k) {
-            int rc = bv_engine_submit(e, &slabs[k], outs[k], slabs[k].n_groups ? gouts[k] : nullptr, stream_);
-            if (rc != BV_OK) return rc;
-        }
-        return BV_OK;
-    }
-    if (total > e->cfg.max_sites) return fail(e, BV_ERR_TOO_LARGE, "bv_engine_submit_many: the slabs together exceed cfg.max_sites");
-    BV_HIP(e, hipSetDevice(e->cfg.device));
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    {
-        int rc = use_stream(e, st);
-        if (rc != BV_OK) return rc;
-    }
-    e->host_out = nullptr; e->host_gout = nullptr;
-    e->last_lane = -1;
-    const size_t P = slabs[0].pitch;
-    const bool ranks = slabs[0].mapq != nullptr;
-    const uint8_t *gid = nullptr;
-    if (G) {
-        int rc = stage_group_ids(e, slabs[0].group_id, slabs[0].n_samples, false, st, &gid);
-        if (rc != BV_OK) return rc;
-    }
-    // at most BV_MAX_CHAIN slabs per launch
-    for (uint32_t k0 = 0; k0 < n_slabs; k0 += BV_MAX_CHAIN) {
-        const uint32_t nk = n_slabs - k0 < (uint32_t)BV_MAX_CHAIN ? n_slabs - k0 : (uint32_t)BV_MAX_CHAIN;
-        BvChain ch{};
-        ch.n = nk;
-        uint32_t first = 0;
-        for (uint32_t i = 0; i < nk; ++i) {
-            const bv_slab &s = slabs[k0 + i];
-            const size_t bias = (size_t)first * P;
-            ch.first[i] = first;
-            ch.bs[i] = s.base_strand - bias; ch.q[i] = s.qual - bias;
-            ch.mapq[i] = ranks ? s.mapq - bias : nullptr; ch.rpr[i] = ranks ? s.rpr - bias : nullptr;
-            ch.ref_base[i] = s.ref_base - first;
-            ch.out[i] = outs[k0 + i] - first;
-            ch.gout[i] = G ? gouts[k0 + i] - (size_t)first * G : nullptr;
-            if (G) BV_HIP(e, hipMemsetAsync(gouts[k0 + i], 0, (size_t)s.n_sites * G * sizeof(bv_group_result), st));
-            first += s.n_sites;
-        }
-        const bv_slab &s0 = slabs[k0];
-        bv_group_result *g0 = G ? gouts[k0] : nullptr;
-        if (nk == 1) {
-            int rc = launch_passes(e, s0.base_strand, s0.qual, s0.mapq, s0.rpr, s0.ref_base, gid, P, first, s0.n_samples, G, outs[k0], g0, st, nullptr, false, s0.layout);
-            if (rc != BV_OK) return rc;
-            continue;
-        }
-        // the segment table lives in device memory (a ring of 16: a table is rewritten only 16 chained launches later)
-        if (!e->d_chain) BV_HIP(e, hipMalloc(&e->d_chain, sizeof(BvChain) * 16));
-        BvChain *d_ch = e->d_chain + (e->chain_next++ & 15u);
-        BV_HIP(e, hipMemcpyAsync(d_ch, &ch, sizeof(BvChain), hipMemcpyHostToDevice, st));
-        if (s0.n_samples > BV_SHORT_ROW_MAX) {
-            // long rows: every kernel looks its segment up per site (planes, reference bases, records)
-            int rc = launch_passes(e, s0.base_strand, s0.qual, s0.mapq, s0.rpr, s0.ref_base, gid, P, first, s0.n_samples, G, outs[k0], g0, st, d_ch, false, s0.layout);
-            if (rc != BV_OK) return rc;
-        } else {
-            // short rows: the planes are looked up per row (wave-uniform places only); the per-site reference bases and records,
-            // which the lane-per-site and four-per-wave kernels touch with one site per lane, go through contiguous copies
-            // (the pop-group records are written once per (variant site, group): looked up where they are written)
-            if (!e->d_ref_cat || !e->d_out_cat) {
-                if (e->d_ref_cat) (void)hipFree(e->d_ref_cat);
-                if (e->d_out_cat) (void)hipFree(e->d_out_cat);
-                e->d_ref_cat = nullptr; e->d_out_cat = nullptr;
-                BV_HIP(e, hipMalloc(&e->d_ref_cat, (size_t)e->cfg.max_sites + 256));
-                BV_HIP(e, hipMalloc(&e->d_out_cat, sizeof(bv_site_result) * (size_t)e->cfg.max_sites));
-            }
-            bv_launch_chain_gather_ref(d_ch, first, e->d_ref_cat, st);
-            BV_HIP(e, hipGetLastError());
-            int rc = launch_passes(e, s0.base_strand, s0.qual, s0.mapq, s0.rpr, e->d_ref_cat, gid, P, first, s0.n_samples, G, e->d_out_cat, g0, st, d_ch, true, s0.layout);
-            if (rc != BV_OK) return rc;
-            bv_launch_chain_scatter_out(d_ch, first, e->d_out_cat, st);
-            BV_HIP(e, hipGetLastError());
-            rc = mark_done(e, st);  // the scatter is the end of this submit
-            if (rc != BV_OK) return rc;
-        }
-    }
-    return BV_OK;
-}
-
-
 void *bv_engine_stream(bv_engine *e) { return e ? (void *)e->stream : nullptr; }
-
-#ifdef BV_TEAM_DEBUG
-// bv_p1s_stream_kernel (short rows): when each wave finished its static range of sites, per XCD
-static void bv_stream_debug_report(const uint32_t *h) {
-    const uint32_t *d = h + BV_CTR_WORDS;
-    uint32_t t0 = 0; bool any = false;
-    for (int b = 0; b < 512; ++b)
-        if (d[4096 + b] && (!any || (int32_t)(d[4096 + b] - t0) < 0)) { t0 = d[4096 + b]; any = true; }
-    if (!any) return;
-    std::vector<double> v;
-    struct Acc { double sum = 0; uint32_t n = 0; };
-    Acc by_xcc[8], by_wave[4], by_simd[4], by_cu[16], by_se[8], by_slot[16];
-    for (int w = 0; w < 2048; ++w) {
-        if (!d[w] || !d[4096 + w / 4]) continue;
-        const double t = (double)(int32_t)(d[w] - t0) * 0.01;
-        const uint32_t hw = d[2048 + w];
-        v.push_back(t);
-        auto add = [&](Acc &a) { a.sum += t; a.n++; };
-        add(by_xcc[d[4608 + w / 4] & 7u]); add(by_wave[w & 3]); add(by_simd[(hw >> 4) & 3u]); add(by_cu[(hw >> 8) & 15u]); add(by_se[(hw >> 13) & 7u]);
-        add(by_slot[hw & 15u]);
-    }
-    if (v.empty()) return;
-    std::sort(v.begin(), v.end());
-    const size_t n = v.size();
-    fprintf(stderr, "[stream debug] wave done min %.1f p10 %.1f p25 %.1f p50 %.1f p75 %.1f p90 %.1f max %.1f us (%zu waves)\n", v[0], v[n / 10], v[n / 4],
-            v[n / 2], v[n * 3 / 4], v[n * 9 / 10], v[n - 1], n);
-    auto show = [&](const char *nm, Acc *a, int k) {
-        fprintf(stderr, "[stream debug] mean by %-12s:", nm);
-        for (int i = 0; i < k; ++i) if (a[i].n) fprintf(stderr, " %d:%.0f(%u)", i, a[i].sum / a[i].n, a[i].n);
-        fprintf(stderr, "\n");
-    };
-    show("XCD", by_xcc, 8); show("wave of group", by_wave, 4); show("SIMD", by_simd, 4); show("CU id", by_cu, 16); show("SE/SH bits", by_se, 8);
-    show("wave slot", by_slot, 16);
-}
-#endif
-
-#ifdef BV_TEAM_DEBUG
-// bv_p1s_fused_kernel: per workgroup, when its streaming waves were done, what was left for the solvers then, when it ended
-static void bv_fused_debug_report(const uint32_t *h) {
-    const uint32_t *d = h + BV_CTR_WORDS;
-    uint32_t t0 = 0; bool any = false;
-    for (int b = 0; b < 512; ++b)
-        if (d[b * 8] && (!any || (int32_t)(d[b * 8] - t0) < 0)) { t0 = d[b * 8]; any = true; }
-    if (!any) return;
-    const char *nm[5] = {"entry", "first streaming wave past its pass-1 rows", "last streaming wave past its pass-1 rows", "workgroup done", "last solver job done"};
-    const int col[5] = {0, 1, 2, 3, 5};
-    for (int j = 0; j < 5; ++j) {
-        std::vector<double> v; double sum[8] = {}; uint32_t cnt[8] = {};
-        for (int b = 0; b < 512; ++b) {
-            if (!d[b * 8] || !d[b * 8 + col[j]]) continue;
-            const double t = (double)(int32_t)(d[b * 8 + col[j]] - t0) * 0.01;
-            v.push_back(t); sum[d[b * 8 + 7] & 7u] += t; cnt[d[b * 8 + 7] & 7u]++;
-        }
-        if (v.empty()) continue;
-        std::sort(v.begin(), v.end());
-        const size_t n = v.size();
-        fprintf(stderr, "[fused debug] %-42s min %6.1f p10 %6.1f p50 %6.1f p90 %6.1f max %6.1f us | mean per XCD:", nm[j], v[0], v[n / 10], v[n / 2],
-                v[n * 9 / 10], v[n - 1]);
-        for (int x = 0; x < 8; ++x) fprintf(stderr, " %.1f", cnt[x] ? sum[x] / cnt[x] : 0.);
-        fprintf(stderr, "\n");
-    }
-#ifdef BV_PHASE_DEBUG
-    {
-        const char *pn[12] = {"wait for the slot (vmcnt)", "slot -> registers (4 ds_read_b128)", "request the next slot: the 4 DMA pieces", "tally, pass-1 slot", "tally, pass-2 slot",
-                              "row epilogue, pass 1", "row epilogue, pass 2", "slots", "leaving (drain)", "inside the streaming function", "request the next slot: draw a row", "slot requested -> found landed"};
-        for (int part = 0; part < 2; ++part) {
-            const uint32_t *c = d + 4220 + 12 * part;
-            fprintf(stderr, "[fused phases] -- streaming waves, %s\n", part ? "past their last pass-1 row" : "while they have pass-1 rows");
-            for (int i = 0; i < 12; ++i) {
-                if (i == 7) fprintf(stderr, "[fused phases] %-38s %u\n", pn[i], c[i]);
-                else if (i == 11) fprintf(stderr, "[fused phases] %-38s %12.0f cycles  (%.0f per timed slot, %u timed)\n", pn[i], 16.0 * c[i], d[4244 + part] ? 16.0 * c[i] / d[4244 + part] : 0., d[4244 + part]);
-                else if (i != 9 || part == 0) fprintf(stderr, "[fused phases] %-38s %12.0f cycles  (%.0f per slot)\n", pn[i], 16.0 * c[i], c[7] ? 16.0 * c[i] / c[7] : 0.);
-            }
-        }
-    }
-#endif
-#ifdef BV_PHASE_DEBUG
-    for (int l = 0; l < 2; ++l) {
-        const uint32_t *j = d + 4212 + 4 * l;
-        fprintf(stderr, "[fused phases] 16-lane jobs %s: %u (of them from q3: %u), %.2f sites per job, mean %.0f cycles\n", l ? "after the last pass-1 row" : "while rows stream", j[1], j[3],
-                j[1] ? (double)j[2] / j[1] : 0., j[1] ? 16.0 * j[0] / j[1] : 0.);
-    }
-#endif
-#ifdef BV_PHASE_DEBUG
-    {
-        const char *jn[5] = {"the entry, the summary's and the bins' loads", "phase 1: LRT, the record's first version", "its stores complete, variant sites queued",
-                             "phase 2's loads", "phase 2: rank sum, QUAL, strand-bias tests"};
-        const uint32_t nj = d[4213] + d[4217];
-        for (int i = 0; i < 5; ++i) fprintf(stderr, "[fused phases] a 16-lane job, %-48s %8.0f cycles\n", jn[i], nj ? 16.0 * d[4250 + i] / nj : 0.);
-    }
-#endif
-    const char *qn[3] = {"q3 entries", "q2 entries", "variant rows (or blocks of 64)"};
-    for (int j = 0; j < 3; ++j) {
-        std::vector<uint32_t> v;
-        for (int b = 0; b < 512; ++b) if (d[b * 8]) v.push_back(j == 0 ? (d[b * 8 + 4] & 0xFFFFu) : j == 1 ? (d[b * 8 + 4] >> 16) : d[b * 8 + 6]);
-        std::sort(v.begin(), v.end());
-        fprintf(stderr, "[fused debug] waiting when the last streaming wave was past its pass-1 rows, %-30s: min %u p50 %u p90 %u max %u\n", qn[j], v[0],
-                v[v.size() / 2], v[v.size() * 9 / 10], v.back());
-    }
-}
-#endif
-#ifdef BV_TEAM_DEBUG
-// the stamps of bv_pass1_kernel's team form (see BV_TEAM_STAMP in bv_pass1.hip): distribution over the workgroups, and per XCD
-static void bv_team_debug_report(const uint32_t *h) {
-    fprintf(stderr, "[team debug] team jobs %u (mean %.0f cycles)  solo solves %u (mean %.0f cycles)\n", h[BV_CTR_CANDS],
-            h[BV_CTR_CANDS] ? 64.0 * h[BV_CTR_CANDS + 1] / h[BV_CTR_CANDS] : 0., h[BV_CTR_EASY3],
-            h[BV_CTR_EASY3] ? 64.0 * h[BV_CTR_EASY3 + 1] / h[BV_CTR_EASY3] : 0.);
-    fprintf(stderr, "[team debug] tally waves waiting for a free ring slot: %.0f cycles per workgroup (sum over its rows)\n", 64.0 * h[BV_CTR_EASY] / 1024.0);
-    const uint32_t *d = h + BV_CTR_WORDS;
-    const char *nm[6] = {"entry", "start barrier passed", "first row begins", "tally waves done", "phred tables in LDS", "solver wave done"};
-    uint32_t t0 = 0; bool any = false;
-    for (int b = 0; b < 640; ++b)
-        if (d[b * 8] && (!any || (int32_t)(d[b * 8] - t0) < 0)) { t0 = d[b * 8]; any = true; }
-    if (!any) return;
-    for (int j = 0; j < 6; ++j) {
-        std::vector<double> v; double sum[8] = {}; uint32_t cnt[8] = {};
-        for (int b = 0; b < 640; ++b) {
-            if (!d[b * 8]) continue;
-            const double t = (double)(int32_t)(d[b * 8 + j] - t0) * 0.01;
-            v.push_back(t); sum[d[b * 8 + 7] & 7u] += t; cnt[d[b * 8 + 7] & 7u]++;
-        }
-        std::sort(v.begin(), v.end());
-        const size_t n = v.size();
-        fprintf(stderr, "[team debug] %-22s min %6.1f p10 %6.1f p50 %6.1f p90 %6.1f max %6.1f us | mean per XCD:", nm[j], v[0], v[n / 10], v[n / 2],
-                v[n * 9 / 10], v[n - 1]);
-        for (int x = 0; x < 8; ++x) fprintf(stderr, " %.1f", cnt[x] ? sum[x] / cnt[x] : 0.);
-        fprintf(stderr, "\n");
-    }
-}
-#endif
 
 int bv_engine_wait(bv_engine *e) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_wait: null engine");
@@ -1293,9 +726,7 @@ int bv_engine_last_launch_form(bv_engine *e, uint32_t *form) {
 int bv_engine_last_variant_count(bv_engine *e, uint32_t *n_variant) {
     if (!e || !n_variant) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_last_variant_count: null argument");
     if (e->last_lane >= 0) return bv_engine_last_variant_count(e->lane[e->last_lane], n_variant);
-    uint32_t n = 0;
-    for (uint32_t b = 0; b < e->last_blocks; ++b) n += e->h_counters[(size_t)(e->last_ctr_base + b) * BV_CTR_WORDS + BV_CTR_VARIANTS];
-    *n_variant = n;
+    *n_variant = e->h_counters[(size_t)e->last_ctr_base * BV_CTR_WORDS + BV_CTR_VARIANTS];
     return BV_OK;
 }
 

@@ -1,5 +1,5 @@
-// bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_tiles.hip, bv_text.hip,
-// bv_inflate.hip, bv_deflate.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
+// bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_rows.hip, bv_engine_tiles.hip,
+// bv_text.hip, bv_inflate.hip, bv_deflate.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
 // files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
 #pragma once
 
@@ -35,13 +35,12 @@ struct bv_engine {
     BvTables *d_tables = nullptr;
     double *d_lnfact = nullptr;
     uint32_t *d_var_list = nullptr;
-    // Counter blocks (BV_CTR_* words each, bv_kernels.h): a launch that is cut into chunks (short rows, launch_passes)
-    // gives every chunk a block of its own; everything else uses block 0.
+    // Counter blocks (BV_CTR_* words each, bv_kernels.h): every launch of launch_passes uses ONE block, the launches take the
+    // blocks in turn (ctr_rot, below); everything else uses block 0.
     static constexpr uint32_t kCtrBlocks = 8;
     uint32_t *d_counters = nullptr;    // [kCtrBlocks][BV_CTR_WORDS]
     uint32_t *h_counters = nullptr;    // pinned host mirror
-    uint32_t last_blocks = 1;          // blocks the last launch used (their VARIANTS words add up to its variant count)
-    uint32_t last_ctr_base = 0;        // ... starting at this block
+    uint32_t last_ctr_base = 0;        // the block the last launch used (its VARIANTS word is its variant count)
     // Submits take the counter blocks in turn (launch i: block i % kCtrBlocks): all blocks' per-launch lines are zeroed by ONE
     // 2-D fill every kCtrBlocks launches, and the host mirror is filled by bv_engine_wait, not by a copy behind every submit.
     // (Measured: the 23 KB device-to-host copy behind each submit kept the next submit's first kernel waiting ~10 us --
@@ -56,12 +55,13 @@ struct bv_engine {
     uint32_t n_launches = 0;           // launches since creation (BV_FLAG_SPARSE_TIMING times every eighth)
     uint32_t last_form = 0;            // BV_FORM_* bits of the last launch (bv_engine_last_launch_form)
     double acc1_ms = 0., acc2_ms = 0., acc_stream_ms = 0.;
-    // short rows (bv_pass1_short.hip): HBM scratch between the streaming kernel and the solve kernel
+    // short rows (bv_pass1_short.hip): HBM scratch between the streaming kernel and the solve kernel, an allocation each
+    // (short_scratch in bv_engine_rows.hip: their order and bytes per site)
     BvSiteSummary *d_summ = nullptr;
     uint32_t *d_bins = nullptr, *d_cand_list = nullptr, *d_easy_list = nullptr, *d_easy3_list = nullptr, *d_ovf = nullptr;
-    uint32_t short_sites = 0;          // sites the short-row scratch holds
+    size_t short_bytes[6] = {};
     uint32_t *d_gitems = nullptr;      // pop-group calls handed from the pass-2 tally kernels to bv_p2g_solve16_kernel
-    uint32_t gitem_cap = 0;            // items (of BV_P2G_ITEM_WORDS words) d_gitems holds
+    size_t d_gitems_bytes = 0;         // (items of BV_P2G_ITEM_WORDS words)
     uint8_t *d_gidp = nullptr;         // group ids prepared for bv_p2g_stream_kernel (bv_launch_gid_prepare)
     size_t d_gidp_bytes = 0;
     // more than BV_GROUPS_PER_ROUND pop-groups: pass 2 runs once per round of groups, on the round's own view of the group plane
@@ -73,6 +73,7 @@ struct bv_engine {
     BvChain *d_chain = nullptr;        // segment tables of chained launches (bv_engine_submit_many)
     uint8_t *d_ref_cat = nullptr;      // chained short-row launches: reference bases / records of all segments, contiguous
     bv_site_result *d_out_cat = nullptr;
+    size_t d_chain_bytes = 0, d_ref_cat_bytes = 0, d_out_cat_bytes = 0;
     unsigned chain_next = 0;
     uint32_t acc_n = 0;
     bool submitted = false;
@@ -175,6 +176,21 @@ int grow_device(bv_engine *e, T **buf, size_t *bytes, size_t need) {
     return BV_OK;
 }
 
+// The same for scratch the caller can do with less of: an allocation that fails is no error, it leaves (NULL, 0)
+template <class T>
+int try_grow_device(bv_engine *e, T **buf, size_t *bytes, size_t need) {
+    if (need <= *bytes) return BV_OK;
+    if (*buf) BV_HIP(e, hipFree(*buf));
+    *buf = nullptr; *bytes = 0;
+    if (hipMalloc(buf, need) == hipSuccess) {
+        *bytes = need;
+    } else {
+        (void)hipGetLastError();
+        *buf = nullptr;
+    }
+    return BV_OK;
+}
+
 // ---- stream ordering (bv_engine.hip): work of one engine is serialised, whatever streams the caller alternates
 int use_stream(bv_engine *e, hipStream_t st);  // before an entry point queues on `st`
 int mark_done(bv_engine *e, hipStream_t st);   // what it queued on `st` is the end of the engine's work so far
@@ -207,10 +223,25 @@ int stage_records(bv_engine *e, HostPlane *pl, int n, size_t S, size_t G, bv_sit
 int copy_records_back(bv_engine *e, hipStream_t st);  // (nothing for a device caller: e->host_out == NULL)
 
 int stage_group_ids(bv_engine *e, const uint8_t *gid, uint32_t n_samples, bool host, hipStream_t st, const uint8_t **out);
+int drain_timings(bv_engine *e, bool block);  // the pending event triplets -> the timing accumulators (bv_engine.hip)
+
+// ---- the row path (bv_engine_rows.hip)
+// One launch of the two passes: device-resident planes, and where the records go
+struct RowLaunch {
+    const uint8_t *bs = nullptr, *q = nullptr, *mq = nullptr;  // [n_sites][pitch]; mq NULL together with rp: no rank sums
+    const uint16_t *rp = nullptr;
+    const uint8_t *refb = nullptr;                             // [n_sites]
+    const uint8_t *gid = nullptr;                              // [n_samples] padded (stage_group_ids), or NULL
+    size_t pitch = 0;
+    uint32_t n_sites = 0, n_samples = 0, n_groups = 0;
+    uint32_t layout = 0;                                       // BV_SLAB_*
+    bv_site_result *dout = nullptr;
+    bv_group_result *dgout = nullptr;
+    const BvChain *chain = nullptr;                            // device memory: a chained launch (planes per segment)
+    bool chain_cat = false;                                    // chained short rows: refb / dout are the contiguous copies
+};
 // The two passes over device-resident planes + the copies back (records to a host caller, counters)
-int launch_passes(bv_engine *e, const uint8_t *bs, const uint8_t *q, const uint8_t *mq, const uint16_t *rp, const uint8_t *refb,
-                  const uint8_t *gid, size_t P, uint32_t n_sites, uint32_t n_samples, uint32_t n_groups, bv_site_result *dout,
-                  bv_group_result *dgout, hipStream_t st, const BvChain *chain = nullptr /* device */,
-                  bool chain_cat = false /* chained short rows: refb / dout are contiguous copies */, uint32_t layout = 0 /* BV_SLAB_* */);
+int launch_passes(bv_engine *e, const RowLaunch &L, hipStream_t st);
+void row_scratch_free(bv_engine *e);        // bv_engine_destroy: the row path's grow-on-demand device buffers
 void tile_job_free(bv_engine::TileJob &t);  // bv_engine_destroy: the tile mode's buffers (bv_engine_tiles.hip)
 }  // namespace bv_impl

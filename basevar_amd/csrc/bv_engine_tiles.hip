@@ -2,7 +2,7 @@
 // tiles of columns (bv_engine_tiles_begin / _add* ... / _finish), dense or packed, one tile or many per call.
 //
 // Two realisations behind one protocol: JOINED ROWS -- the tiles are moved to their columns of [n_sites][pitch] planes
-// resident in HBM and the job finishes as one launch_passes over them -- and, where those planes do not fit or
+// resident in HBM and the job finishes as one launch_passes (bv_engine_rows.hip) over them -- and, where those planes do not fit or
 // BV_FLAG_TILE_STATE asks for it, PER-SITE TALLIES that every tile adds to (bv_tiles.hip).  Every add call is a check of its
 // tiles (check_*_tile: nothing changes before every tile of the call has passed) and then one of four ways to launch.
 #include <algorithm>
@@ -286,16 +286,9 @@ int bv_engine_tiles_begin(bv_engine *e, uint32_t n_sites, uint32_t n_samples_tot
         if (!ok) {
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= (free_b + t.rows_bytes) / 10 * 9) {
-                if (t.rows) BV_HIP(e, hipFree(t.rows));
-                t.rows = nullptr;
-                t.rows_bytes = 0;
-                if (hipMalloc(&t.rows, need) == hipSuccess) {
-                    t.rows_bytes = need;
-                    ok = true;
-                } else {
-                    (void)hipGetLastError();
-                    t.rows = nullptr;
-                }
+                const int rc = try_grow_device(e, &t.rows, &t.rows_bytes, need);
+                if (rc != BV_OK) return rc;
+                ok = t.rows != nullptr;
             }
         }
         if (ok) {
@@ -613,8 +606,11 @@ int bv_engine_tiles_finish(bv_engine *e, const uint8_t *ref_base, bv_site_result
                 BV_HIP(e, hipMemset2DAsync(tj.rows + j.o_rp + 2 * (size_t)j.samples_seen, 2 * j.pitch, 0x80,
                                            2 * (size_t)(j.samples_total - j.samples_seen), S, st));
         }
-        int rc = launch_passes(e, tj.rows, tj.rows + j.o_q, joined_mq(e), joined_rp(e), dref, G ? tj.rows + j.o_gid : nullptr, j.pitch,
-                               j.sites, j.samples_total, j.groups, dout, dgout, st, nullptr, false, j.layout);
+        RowLaunch L;
+        L.bs = tj.rows; L.q = tj.rows + j.o_q; L.mq = joined_mq(e); L.rp = joined_rp(e); L.refb = dref; L.gid = G ? tj.rows + j.o_gid : nullptr;
+        L.pitch = j.pitch; L.n_sites = j.sites; L.n_samples = j.samples_total; L.n_groups = j.groups; L.layout = j.layout;
+        L.dout = dout; L.dgout = dgout;
+        int rc = launch_passes(e, L, st);
         if (rc == BV_OK && slot) rc = stage_release(e, slot, st);
         return rc;
     }
@@ -628,7 +624,7 @@ int bv_engine_tiles_finish(bv_engine *e, const uint8_t *ref_base, bv_site_result
     f.out = dout; f.gout = dgout; f.var_list = e->d_var_list; f.counters = e->d_counters;
     bv_launch_tile_finish(f, st);
     BV_HIP(e, hipGetLastError());
-    e->last_blocks = 1; e->last_ctr_base = 0; e->ctr_rot = 0;
+    e->last_ctr_base = 0; e->ctr_rot = 0;
     BV_HIP(e, hipMemcpyAsync(e->h_counters, e->d_counters, sizeof(uint32_t) * BV_CTR_WORDS * bv_engine::kCtrBlocks, hipMemcpyDeviceToHost, st));
     int rc = copy_records_back(e, st);
     if (rc != BV_OK) return rc;

@@ -33,7 +33,7 @@ def long_row_form(k):
 
 
 def expected_form(n, flags=0):
-    """The BV_FORM_* bits a submit of rows of n samples (with rank planes) must report (csrc/bv_engine.hip)."""
+    """The BV_FORM_* bits a submit of rows of n samples (with rank planes) must report (csrc/bv_engine_rows.hip)."""
     if n > 49152:
         return ONE_KERNEL  # the long-row kernel
     form = (flags >> 12) & 0xF
