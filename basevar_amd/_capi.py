@@ -82,6 +82,8 @@ class BgzfCursor(C.Structure):  # bv_bgzf_cursor
 
 BV_ERR_DATA = -6  # include/basevar_amd_bgzf.h
 BV_BGZF_OK, BV_BGZF_BAD_HEADER, BV_BGZF_BAD_DEFLATE, BV_BGZF_BAD_SIZE, BV_BGZF_BAD_CRC = 0, 1, 2, 3, 4
+BV_DEFLATE_FAST, BV_DEFLATE_SMALL = 0, 1
+DEFLATE_LEVELS = {"fast": BV_DEFLATE_FAST, "small": BV_DEFLATE_SMALL}
 
 
 class EngineConfig(C.Structure):
@@ -101,10 +103,10 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_engine_kernel_ms", "bv_engine_timing_reset", "bv_engine_timing_get", "bv_engine_timing_get_ex",
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
            "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form",
-           "bv_engine_text_parse", "bv_engine_text_submit"]
+           "bv_engine_text_parse", "bv_engine_text_submit", "bv_engine_deflate_code_lengths"]
 
 # every symbol include/basevar_amd_bgzf.h declares
-BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch", "bv_engine_bgzf_deflate"]
+BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch", "bv_engine_bgzf_deflate", "bv_engine_bgzf_deflate_level"]
 
 _lib = None
 
@@ -207,5 +209,10 @@ def load():
     L.bv_engine_text_rows_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
     L.bv_engine_bgzf_deflate.restype = C.c_int
     L.bv_engine_bgzf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.bv_engine_bgzf_deflate_level.restype = C.c_int
+    L.bv_engine_bgzf_deflate_level.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_void_p]
+    L.bv_engine_deflate_code_lengths.restype = C.c_int
+    L.bv_engine_deflate_code_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     _lib = L
     return L

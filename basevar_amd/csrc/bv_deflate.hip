@@ -10,6 +10,11 @@
 //
 // A member is first written to a slot of its own (its size is not known before), then the slots of a chunk are compacted on
 // the device -- a prefix sum over the member sizes and a gather -- so that one contiguous run of members is copied back.
+//
+// BV_DEFLATE_SMALL (bv_engine_bgzf_deflate_level) is a second kernel over the same staging, scan and gather: the encoder of
+// bv_deflate_small_core.h, dynamic Huffman codes over 16-, 8- and 4-byte grams.  Its three tables (24 KiB), the text and the
+// Huffman workspace are 103 KiB of LDS: ONE workgroup per CU where the default level has two.  Its tokens wait in device
+// memory between the parse and the coding (4 bytes per byte of text, allocated by the first call at that level).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,7 +23,9 @@
 #include <vector>
 
 #include "../../include/basevar_amd_bgzf.h"
+#include "../../include/basevar_amd_diag.h"
 #include "bv_deflate_core.h"
+#include "bv_deflate_small_core.h"
 #include "bv_chunk_stage.h"
 
 using namespace bv_impl;
@@ -34,7 +41,7 @@ static_assert(BV_DEF_MAX_BLOCK + BV_DEF_MEMBER_EXTRA + 8u <= kSlotStride && kSlo
 struct BvDefBlock {
     uint64_t text_off;  // from the kernel's `text`
     uint32_t n;         // 1 .. BV_DEF_MAX_BLOCK
-    uint32_t reserved_;
+    uint32_t tok_at;    // BV_DEFLATE_SMALL: where the block's tokens wait, in units of 64 tokens; else 0
 };
 
 // the two aligned words around bytes [at, at + 4) of `base` (4-byte aligned), as one little-endian word
@@ -78,6 +85,54 @@ __global__ __launch_bounds__(64) void bv_bgzf_deflate_kernel(const uint8_t *__re
         return c;
     });
     if (lane == 0) sizes[k] = total;
+}
+
+// the text of block m to the window, a word per lane and step.  Its place in memory has any alignment: a word of the window is
+// cut from the two aligned words of global memory around it; the second is read only where it holds a byte of the block.
+__device__ inline void stage_text(const uint8_t *g, uint32_t n, uint8_t *win, uint32_t win_bytes, uint32_t lane) {
+    const uint32_t mis = (uint32_t)((uintptr_t)g & 3u);
+    const uint32_t *ga = reinterpret_cast<const uint32_t *>(g - mis);
+    uint32_t *w = reinterpret_cast<uint32_t *>(win);
+    const uint32_t words = (n + 3u) / 4u;
+    for (uint32_t j = lane; j < words; j += 64u) w[j] = word_at(ga, mis + 4u * j, 4u * j + 4u - mis < n);
+    for (uint32_t j = words + lane; j < words + BV_DEF_TEXT_PAD / 4u && j < win_bytes / 4u; j += 64u) w[j] = 0;
+}
+
+// BV_DEFLATE_SMALL: one wave per block as above, with the encoder of bv_deflate_small_core.h.  tok: the chunk's token runs.
+__global__ __launch_bounds__(64) void bv_bgzf_small_kernel(const uint8_t *__restrict__ text, const BvDefBlock *__restrict__ meta, uint32_t nblk,
+                                                           uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes, uint32_t *tok) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[BV_DEF_MAX_BLOCK + BV_DEF_TEXT_PAD];
+    __shared__ BvDefSmallState S;
+    __shared__ uint32_t crc_tab[1024];
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= nblk) return;
+    const BvDefBlock m = meta[k];
+    if (m.n < 1u || m.n > BV_DEF_MAX_BLOCK) {  // (the host has refused such a block; nothing is read or written for it)
+        if (lane == 0) sizes[k] = 0;
+        return;
+    }
+    bv_inf_crc_tables(crc_tab, lane, 64);
+    stage_text(text + m.text_off, m.n, win, (uint32_t)sizeof(win), lane);
+    __syncthreads();
+    const uint32_t total = bv_def_small_member(win, m.n, slots + (size_t)k * kSlotStride, &S, tok + (size_t)m.tok_at * 64u, crc_tab, lane, 64, [](uint32_t c) {
+        for (int d = 32; d > 0; d >>= 1) c ^= __shfl_xor(c, d, 64);
+        return c;
+    });
+    if (lane == 0) sizes[k] = total;
+}
+
+// bv_engine_deflate_code_lengths: one wave around bv_defs_code_lengths
+__global__ __launch_bounds__(64) void bv_deflate_code_lengths_kernel(const uint32_t *__restrict__ counts, uint32_t nsym, uint32_t limit, uint8_t *__restrict__ lengths,
+                                                                     uint32_t *__restrict__ rounds) {
+    __shared__ BvDefsHuff H;
+    __shared__ uint32_t cnt[BV_DEFS_MAX_SYMS];
+    __shared__ uint8_t len[BV_DEFS_MAX_SYMS];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t i = lane; i < nsym; i += 64u) cnt[i] = counts[i];
+    __syncthreads();
+    const uint32_t r = bv_defs_code_lengths(cnt, nsym, limit, len, &H, lane, 64);
+    for (uint32_t i = lane; i < nsym; i += 64u) lengths[i] = len[i];
+    if (lane == 0) *rounds = r;
 }
 
 // off[0] = 0, off[k + 1] = off[k] + sizes[k]: one workgroup, every thread a contiguous share
@@ -130,9 +185,11 @@ struct BvDeflateState {
     struct Slot {
         uint8_t *d_slots = nullptr, *d_packed = nullptr;
         uint32_t *d_sums = nullptr;  // sizes [kChunkBlocks], then off [kChunkBlocks + 1]
-        size_t slots_cap = 0, packed_cap = 0, sums_cap = 0;
+        uint32_t *d_tok = nullptr;   // BV_DEFLATE_SMALL: the blocks' tokens between parse and coding (never allocated at the default level)
+        size_t slots_cap = 0, packed_cap = 0, sums_cap = 0, tok_cap = 0;
     } slot[2];
-    bool lds_ok = false;  // the kernel's LDS was accepted
+    bool lds_ok = false, lds_ok_small = false;  // the kernel's LDS was accepted
+    uint8_t *d_diag = nullptr;  // bv_engine_deflate_code_lengths: counts, lengths, rounds
 };
 
 void bv_deflate_state_free(BvDeflateState *t) {
@@ -140,8 +197,9 @@ void bv_deflate_state_free(BvDeflateState *t) {
     (void)hipSetDevice(t->device);
     chunk_stage_free(t->in);
     for (BvDeflateState::Slot &sl : t->slot)
-        for (void *b : {(void *)sl.d_slots, (void *)sl.d_packed, (void *)sl.d_sums})
+        for (void *b : {(void *)sl.d_slots, (void *)sl.d_packed, (void *)sl.d_sums, (void *)sl.d_tok})
             if (b) (void)hipFree(b);
+    if (t->d_diag) (void)hipFree(t->d_diag);
     delete t;
 }
 
@@ -152,20 +210,26 @@ struct Chunk {
     uint64_t text_lo, text_bytes;  // the text its blocks span (block_off[first] .. block_off[first + count])
 };
 
-int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host_text, const uint64_t *block_off, uint32_t n, uint8_t *dst,
+int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host_text, const uint64_t *block_off, uint32_t n, int level, uint8_t *dst,
                  uint64_t *member_off, hipStream_t st) {
     BV_HIP(e, hipSetDevice(t->device));
     int rc = chunk_stage_begin(e, t->in, st);
-    if (rc == BV_OK)
+    if (rc == BV_OK && level == BV_DEFLATE_SMALL)
+        rc = kernel_lds_fits(e, "bv_engine_bgzf_deflate_level: the small level's kernel", reinterpret_cast<const void *>(bv_bgzf_small_kernel), t->device, &t->lds_ok_small);
+    else if (rc == BV_OK)
         rc = kernel_lds_fits(e, "bv_engine_bgzf_deflate: the deflate kernel", reinterpret_cast<const void *>(bv_bgzf_deflate_kernel), t->device, &t->lds_ok);
     if (rc != BV_OK) return rc;
     const uint32_t per = (uint32_t)chunk_limit_from_env("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", kChunkBlocks);
     std::vector<Chunk> chunks;
-    size_t in_max = 0;
+    size_t in_max = 0, tok_max = 0;
     for (uint32_t k = 0; k < n; k += per) {
         const uint32_t count = std::min(per, n - k);
         chunks.push_back(Chunk{k, count, block_off[k], block_off[k + count] - block_off[k]});
         in_max = std::max<size_t>(in_max, chunks.back().text_bytes);
+        if (level != BV_DEFLATE_SMALL) continue;
+        size_t room = 0;
+        for (uint32_t j = k; j < k + count; ++j) room += BV_DEFS_TOK_ROOM((uint32_t)(block_off[j + 1] - block_off[j]));
+        tok_max = std::max(tok_max, room);
     }
     const size_t blocks_max = std::min<size_t>(per, n);
     // a staged chunk: the text (host text only; the kernel reads whole words around it), then the block table
@@ -175,6 +239,7 @@ int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host
         if ((rc = grow_device(e, &sl.d_slots, &sl.slots_cap, blocks_max * kSlotStride)) != BV_OK) return rc;
         if ((rc = grow_device(e, &sl.d_packed, &sl.packed_cap, in_max + (size_t)BV_DEF_MEMBER_EXTRA * blocks_max)) != BV_OK) return rc;
         if ((rc = grow_device(e, &sl.d_sums, &sl.sums_cap, sizeof(uint32_t) * (2 * kChunkBlocks + 1))) != BV_OK) return rc;
+        if (level == BV_DEFLATE_SMALL && (rc = grow_device(e, &sl.d_tok, &sl.tok_cap, sizeof(uint32_t) * tok_max)) != BV_OK) return rc;
     }
     // a chunk's packed members are copied back while the next chunk is being coded: `finish` is one chunk behind `issue`
     auto finish = [&](size_t ci) -> int {
@@ -202,19 +267,28 @@ int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host
         const size_t meta_at = host_text ? up16(c.text_bytes + 4) : 0;
         if (host_text) std::memcpy(h_in, text + c.text_lo, c.text_bytes);
         BvDefBlock *h_meta = reinterpret_cast<BvDefBlock *>(h_in + meta_at);
+        size_t tok_at = 0;
         for (uint32_t j = 0; j < c.count; ++j) {
             BvDefBlock &m = h_meta[j];
             const uint64_t a = block_off[c.first + j];
             m.text_off = host_text ? a - c.text_lo : a;
             m.n = (uint32_t)(block_off[c.first + j + 1] - a);
-            m.reserved_ = 0;
+            m.tok_at = 0;
+            if (level == BV_DEFLATE_SMALL) {
+                m.tok_at = (uint32_t)(tok_at / 64u);
+                tok_at += BV_DEFS_TOK_ROOM(m.n);
+            }
         }
         if ((rc = chunk_stage_upload(e, t->in, s, meta_at + sizeof(BvDefBlock) * c.count, st)) != BV_OK) return rc;
         const uint8_t *d_in = t->in.slot[s].d;
         const BvDeflateState::Slot &sl = t->slot[s];
         uint32_t *d_sizes = sl.d_sums, *d_off = sl.d_sums + kChunkBlocks;
-        hipLaunchKernelGGL(bv_bgzf_deflate_kernel, dim3(c.count), dim3(64), 0, st, host_text ? d_in : text,
-                           reinterpret_cast<const BvDefBlock *>(d_in + meta_at), c.count, sl.d_slots, d_sizes);
+        if (level == BV_DEFLATE_SMALL)
+            hipLaunchKernelGGL(bv_bgzf_small_kernel, dim3(c.count), dim3(64), 0, st, host_text ? d_in : text,
+                               reinterpret_cast<const BvDefBlock *>(d_in + meta_at), c.count, sl.d_slots, d_sizes, sl.d_tok);
+        else
+            hipLaunchKernelGGL(bv_bgzf_deflate_kernel, dim3(c.count), dim3(64), 0, st, host_text ? d_in : text,
+                               reinterpret_cast<const BvDefBlock *>(d_in + meta_at), c.count, sl.d_slots, d_sizes);
         BV_HIP(e, hipGetLastError());
         hipLaunchKernelGGL(bv_bgzf_deflate_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)d_sizes, c.count, d_off);
         BV_HIP(e, hipGetLastError());
@@ -234,9 +308,11 @@ int bgzf_deflate(bv_engine *e, BvDeflateState *t, const uint8_t *text, bool host
 
 extern "C" {
 
-int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off, uint32_t n_blocks,
-                           uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream_) {
+int bv_engine_bgzf_deflate_level(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off, uint32_t n_blocks,
+                                 int level, uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: null engine");
+    if (level != BV_DEFLATE_FAST && level != BV_DEFLATE_SMALL)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate_level: level must be BV_DEFLATE_FAST or BV_DEFLATE_SMALL");
     if (!member_off) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: null member_off");
     if (text_mem_kind != BV_MEM_HOST && text_mem_kind != BV_MEM_DEVICE)
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: text_mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
@@ -255,8 +331,38 @@ int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, 
     if (dst_capacity < need)
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_bgzf_deflate: dst_capacity " + std::to_string(dst_capacity) + " < text_bytes + 31 * n_blocks = " +
                                                          std::to_string(need));
-    return bgzf_deflate(e, engine_state(e, e->deflate), static_cast<const uint8_t *>(text), text_mem_kind == BV_MEM_HOST, block_off, n_blocks, dst, member_off,
+    return bgzf_deflate(e, engine_state(e, e->deflate), static_cast<const uint8_t *>(text), text_mem_kind == BV_MEM_HOST, block_off, n_blocks, level, dst,
+                        member_off,
                         stream_ ? (hipStream_t)stream_ : e->stream);
+}
+
+int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off, uint32_t n_blocks,
+                           uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream_) {
+    return bv_engine_bgzf_deflate_level(e, text, text_bytes, text_mem_kind, block_off, n_blocks, BV_DEFLATE_FAST, dst, dst_capacity, member_off, stream_);
+}
+
+int bv_engine_deflate_code_lengths(bv_engine *e, const uint32_t *counts, uint32_t n_symbols, uint32_t limit, uint8_t *lengths_out, uint32_t *rounds_out,
+                                   void *stream_) {
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_deflate_code_lengths: null engine");
+    if (!counts || !lengths_out || !rounds_out) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_deflate_code_lengths: null counts/lengths_out/rounds_out");
+    if (n_symbols < 2 || n_symbols > BV_DEFS_MAX_SYMS || limit < 1 || limit > 15 || n_symbols > (1u << limit))
+        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_deflate_code_lengths: 2 to 286 symbols, a limit of 1 to 15 bits, and no more symbols than 2^limit");
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < n_symbols; ++i) sum += counts[i];
+    if (sum >> 32) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_deflate_code_lengths: the counts add up to 2^32 or more");
+    BvDeflateState *t = engine_state(e, e->deflate);
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    BV_HIP(e, hipSetDevice(t->device));
+    constexpr size_t kLenAt = sizeof(uint32_t) * BV_DEFS_MAX_SYMS, kRoundsAt = kLenAt + 288;
+    if (!t->d_diag) BV_HIP(e, hipMalloc(&t->d_diag, kRoundsAt + sizeof(uint32_t)));
+    BV_HIP(e, hipMemcpyAsync(t->d_diag, counts, sizeof(uint32_t) * n_symbols, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_deflate_code_lengths_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<const uint32_t *>(t->d_diag), n_symbols, limit, t->d_diag + kLenAt,
+                       reinterpret_cast<uint32_t *>(t->d_diag + kRoundsAt));
+    BV_HIP(e, hipGetLastError());
+    BV_HIP(e, hipMemcpyAsync(lengths_out, t->d_diag + kLenAt, n_symbols, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(rounds_out, t->d_diag + kRoundsAt, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
+    return BV_OK;
 }
 
 }  // extern "C"

@@ -539,9 +539,11 @@ class BaseTypeEngine:
         return text, dst_off, status
 
     # ---- text, deflated into BGZF members on the device
-    def bgzf_deflate(self, text, block_bytes=0xff00, block_off=None):
-        """Text in, whole BGZF members out (bv_engine_bgzf_deflate): one member per block of `block_bytes` bytes (1 .. 0xff00;
+    def bgzf_deflate(self, text, block_bytes=0xff00, block_off=None, level="fast"):
+        """Text in, whole BGZF members out (bv_engine_bgzf_deflate_level): one member per block of `block_bytes` bytes (1 .. 0xff00;
         the last block takes what is left), or per block text[block_off[k]:block_off[k + 1]] where `block_off` is given.
+        `level`: "fast" (the default: the fixed Huffman codes, about twice zlib level 6's size) or "small" (dynamic codes over
+        16-, 8- and 4-byte grams: within 7 % of zlib level 6 for more kernel time, one workgroup per CU; README has the measured times).
 
         `text`: bytes / uint8 array, or a uint8 torch tensor on the engine's device, which is read where it lies (the caller has
         synchronised what wrote it).  Returns (members, member_off): the members back to back as one uint8 array, member k at
@@ -564,14 +566,27 @@ class BaseTypeEngine:
         n = int(off.size) - 1
         if n < 0:
             raise ValueError("bgzf_deflate: block_off needs n + 1 entries")
+        if level not in _capi.DEFLATE_LEVELS:
+            raise ValueError("bgzf_deflate: level is 'fast' or 'small'")
         members = np.zeros(size + 31 * n, dtype=np.uint8)
         member_off = np.zeros(n + 1, dtype=np.uint64)
-        rc = self._lib.bv_engine_bgzf_deflate(self._h, ptr, size, kind, off.ctypes.data, n, members.ctypes.data if members.size else None,
-                                              int(members.size), member_off.ctypes.data, None)
+        rc = self._lib.bv_engine_bgzf_deflate_level(self._h, ptr, size, kind, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level],
+                                                    members.ctypes.data if members.size else None, int(members.size), member_off.ctypes.data, None)
         del keep
         if rc != 0:
-            raise RuntimeError("bv_engine_bgzf_deflate failed (%d): %s" % (rc, self._err()), rc)
+            raise RuntimeError("bv_engine_bgzf_deflate_level failed (%d): %s" % (rc, self._err()), rc)
         return members[:int(member_off[n])], member_off
+
+    def deflate_code_lengths(self, counts, limit):
+        """The code lengths the small deflate level gives an alphabet with these counts (bv_engine_deflate_code_lengths, a
+        diagnostic): (lengths uint8 [n], rounds of halving)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        lengths = np.zeros(counts.size, np.uint8)
+        rounds = C.c_uint32(0)
+        rc = self._lib.bv_engine_deflate_code_lengths(self._h, counts.ctypes.data, int(counts.size), int(limit), lengths.ctypes.data, C.byref(rounds), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_deflate_code_lengths failed (%d): %s" % (rc, self._err()), rc)
+        return lengths, int(rounds.value)
 
 
 class TextBatch(BaseTypeBatch):

@@ -328,8 +328,10 @@ public:
     // Text deflated into BGZF members on the device (bv_engine_bgzf_deflate, include/basevar_amd_bgzf.h): block k is
     // text[block_off[k] .. block_off[k + 1]) of host memory, 1 to 0xff00 bytes; member k lands at dst + member_off[k].  `dst`
     // has room for text_bytes + 31 * n_blocks bytes, `member_off` for n_blocks + 1 entries.  Blocks until dst is written.
-    void bgzf_deflate(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off) {
-        if (bv_engine_bgzf_deflate(e_, text, text_bytes, BV_MEM_HOST, block_off, n_blocks, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
+    // `level`: BV_DEFLATE_FAST, or BV_DEFLATE_SMALL for files near zlib level 6's size and more kernel time (README has both).
+    void bgzf_deflate(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off,
+                      int level = BV_DEFLATE_FAST) {
+        if (bv_engine_bgzf_deflate_level(e_, text, text_bytes, BV_MEM_HOST, block_off, n_blocks, level, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
             throw std::runtime_error(bv_last_error(e_));
     }
 

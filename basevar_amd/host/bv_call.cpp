@@ -13,7 +13,7 @@
 //
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
-//           [--timing FILE.json] [--inflate device|host] [--deflate device|host]
+//           [--timing FILE.json] [--inflate device|host] [--deflate device|host] [--deflate-level fast|small]
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -133,7 +133,8 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 
 int main(int argc, char **argv) {
     std::vector<std::string> batchfiles, bams;
-    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host", deflate_arg = "host";
+    std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host", deflate_arg = "host",
+                deflate_level_arg = "fast";
     int mapq_thd = 10, threads = 4, n_gpus = 1;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -151,6 +152,7 @@ int main(int argc, char **argv) {
         else if (a == "--timing") timing_file = next();
         else if (a == "--inflate") inflate_arg = next();
         else if (a == "--deflate") deflate_arg = next();
+        else if (a == "--deflate-level") deflate_level_arg = next();
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--gpus") n_gpus = std::stoi(next());
         else if (a == "--devices") devices_arg = next();
@@ -180,6 +182,10 @@ int main(int argc, char **argv) {
     if (n_gpus < 1) die("[ERROR] --gpus must be >= 1");
     if (inflate_arg != "host" && inflate_arg != "device") die("[ERROR] --inflate wants device or host");
     if (deflate_arg != "host" && deflate_arg != "device") die("[ERROR] --deflate wants device or host");
+    if (deflate_level_arg != "fast" && deflate_level_arg != "small") die("[ERROR] --deflate-level wants fast or small");
+    // (the host path is zlib at its own level: the device encoder's levels do not apply to it)
+    if (deflate_level_arg != "fast" && deflate_arg != "device") die("[ERROR] --deflate-level small needs --deflate device");
+    const int deflate_level = deflate_level_arg == "small" ? BV_DEFLATE_SMALL : BV_DEFLATE_FAST;
     // one engine per entry: --devices a,b,... (an ordinal may repeat: several engines on one GPU), else device, device+1, ...
     std::vector<int> devices;
     if (!devices_arg.empty()) {
@@ -439,7 +445,7 @@ int main(int argc, char **argv) {
                                                  uint64_t *member_off) {
             const double t0 = StageClock::now();
             if (!deflate_engine) deflate_engine.reset(new bvamd::BaseTypeEngine(1, 1, user_min_af, devices[0]));
-            deflate_engine->bgzf_deflate(text, text_bytes, block_off, n_blocks, dst, member_off);
+            deflate_engine->bgzf_deflate(text, text_bytes, block_off, n_blocks, dst, member_off, deflate_level);
             members_deflated += n_blocks;
             deflate_s += StageClock::now() - t0;
         };
@@ -607,7 +613,7 @@ int main(int argc, char **argv) {
         if (device_inflate)
             tf << ", \"inflate\": \"device\", \"members_inflated\": " << raw.members_handed << ", \"members_in_files\": " << raw.members_passed;
         // --deflate device: whole output blocks compressed by the device, and the emitter's seconds inside those calls (part of emit_s)
-        if (device_deflate) tf << ", \"deflate\": \"device\", \"members_deflated\": " << members_deflated << ", \"deflate_s\": " << deflate_s;
+        if (device_deflate) tf << ", \"deflate\": \"device\", \"deflate_level\": \"" << deflate_level_arg << "\", \"members_deflated\": " << members_deflated << ", \"deflate_s\": " << deflate_s;
         tf << "}\n";
     }
     return 0;

@@ -116,6 +116,26 @@ int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uin
 int bv_engine_bgzf_deflate(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off,
                            uint32_t n_blocks, uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream);
 
+/* The same with a level.  The contract, the refusals and the bound of text + 31 bytes a member are bv_engine_bgzf_deflate's;
+ * any other level is BV_ERR_INVALID_ARG, and nothing is written.
+ *   BV_DEFLATE_FAST   what bv_engine_bgzf_deflate writes, byte for byte: one candidate per position from a 4-byte hash, the
+ *                     fixed Huffman codes.  About twice zlib level 6's size on VCF text.
+ *   BV_DEFLATE_SMALL  opt-in: smaller files for more seconds.  Three 12-bit head tables for the 4-, 8- and 16-byte gram at
+ *                     every position; the match at p is the first of 16, 8, 4 whose candidate exists, lies within 32,768 and
+ *                     agrees for at least the gram's bytes; greedy.  The block is written with dynamic Huffman codes (lengths
+ *                     by two-queue Huffman over the symbols sorted by (count, symbol), counts halved while the tree is deeper
+ *                     than 15 bits, or 7 for the code-length alphabet; the header spelled greedily with 16, 17, 18), with the
+ *                     fixed codes or stored, whichever is smallest (fixed on a tie with dynamic, stored on a tie with
+ *                     either).  The definition stands at the head of basevar_amd/csrc/bv_deflate_small_core.h; a member's
+ *                     bytes depend on its text alone.  Sizes: 1.03 to 1.07 times zlib level 6 on VCF, CVG and batchfile
+ *                     text.  The kernel holds 103 KiB of LDS, so ONE workgroup runs per CU where BV_DEFLATE_FAST has two,
+ *                     and the first call at this level allocates 4 bytes of device memory per byte of a staged chunk's
+ *                     text for the tokens.  Times: INTEGRATION.md section 2g. */
+#define BV_DEFLATE_FAST 0
+#define BV_DEFLATE_SMALL 1
+int bv_engine_bgzf_deflate_level(bv_engine *e, const void *text, uint64_t text_bytes, int text_mem_kind, const uint64_t *block_off,
+                                 uint32_t n_blocks, int level, uint8_t *dst, uint64_t dst_capacity, uint64_t *member_off, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,15 @@ int bv_host_log_probe(double *table);
 double bv_host_log_eval(const double *table, double x);
 int bv_engine_host_log_eval(bv_engine *e, const double *x, double *y, uint32_t n);
 
+/* ---- the code lengths of the device DEFLATE encoder's small level (tests) -------
+ * One wave runs the length construction of basevar_amd/csrc/bv_deflate_small_core.h over counts[n_symbols] (host memory):
+ * lengths_out[n_symbols] and the number of rounds in which the counts were halved to keep the tree within `limit` bits come
+ * back (host memory).  Text alone does not drive a DEFLATE alphabet past 15 bits; count vectors do.  BV_ERR_INVALID_ARG for
+ * NULL arguments, n_symbols outside 2 .. 286, limit outside 1 .. 15, n_symbols > 2^limit, or counts that add up to 2^32 or
+ * more.  Blocks until the results are written. */
+int bv_engine_deflate_code_lengths(bv_engine *e, const uint32_t *counts, uint32_t n_symbols, uint32_t limit, uint8_t *lengths_out,
+                                   uint32_t *rounds_out, void *stream);
+
 /* ---- measurement helper (bench only; not part of the reference surface) --------
  * Fill device planes with the synthetic pileup of SURVEY.md section 8(d) using a
  * counter-based RNG (stateless in (seed, site, sample)), so any rank can generate

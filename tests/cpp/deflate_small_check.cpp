@@ -1,0 +1,90 @@
+// deflate_small_check -- the small level of the device DEFLATE encoder (basevar_amd/csrc/bv_deflate_small_core.h) as a plain
+// host program, built under ASan + UBSan and driven by tests/test_deflate_small_cpu.py; the GPU test compares the device's
+// members with this program's, byte for byte.
+//
+//   deflate_small_check TEXT OUT [BLOCK_BYTES | @SIZES]
+//
+// is deflate_core_check's command line: TEXT cut into blocks of BLOCK_BYTES (default 0xff00) or of the lengths listed one per
+// line in the file SIZES, every block coded as lane 0 of 1, the BGZF members written back to back to OUT.  Every member gets a
+// buffer of exactly its worst case, text + 31 bytes, and every token run exactly BV_DEFS_TOK_ROOM, so that ASan sees a write
+// behind either.
+//
+//   deflate_small_check --lengths VECTORS
+//
+// reads one count vector per line of VECTORS, `LIMIT N c0 c1 .. c(N-1)`, and prints per line `ROUNDS l0 l1 .. l(N-1)`: the
+// code lengths of bv_defs_code_lengths and the rounds of halving it took.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <iterator>
+#include <memory>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../basevar_amd/csrc/bv_deflate_small_core.h"
+
+static int lengths_mode(const char *path) {
+    std::ifstream in(path);
+    if (!in) { std::cerr << "cannot read " << path << "\n"; return 2; }
+    std::unique_ptr<BvDefsHuff> H(new BvDefsHuff());
+    std::string line;
+    while (std::getline(in, line)) {
+        if (line.empty()) continue;
+        std::istringstream ls(line);
+        uint32_t limit = 0, n = 0;
+        ls >> limit >> n;
+        if (n < 2 || n > BV_DEFS_MAX_SYMS || limit < 1 || limit > 15 || n > (1u << limit)) { std::cerr << "a vector of " << n << " counts with limit " << limit << "\n"; return 2; }
+        std::vector<uint32_t> counts(n);
+        uint64_t sum = 0;
+        for (uint32_t &c : counts) { ls >> c; sum += c; }
+        if (!ls || sum >> 32) { std::cerr << "a short line, or counts that add up to 2^32 or more\n"; return 2; }
+        std::vector<uint8_t> len(n);
+        const uint32_t rounds = bv_defs_code_lengths(counts.data(), n, limit, len.data(), H.get(), 0, 1);
+        std::cout << rounds;
+        for (uint8_t l : len) std::cout << ' ' << (unsigned)l;
+        std::cout << '\n';
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc == 3 && !std::strcmp(argv[1], "--lengths")) return lengths_mode(argv[2]);
+    if (argc < 3) { std::cerr << "usage: deflate_small_check TEXT OUT [BLOCK_BYTES | @SIZES]\n       deflate_small_check --lengths VECTORS\n"; return 2; }
+    std::ifstream in(argv[1], std::ios::binary);
+    if (!in) { std::cerr << "cannot read " << argv[1] << "\n"; return 2; }
+    const std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    std::vector<size_t> sizes;
+    if (argc > 3 && argv[3][0] == '@') {
+        std::ifstream sf(argv[3] + 1);
+        size_t v, sum = 0;
+        while (sf >> v) { sizes.push_back(v); sum += v; }
+        if (sum != raw.size()) { std::cerr << "the sizes add up to " << sum << ", the text has " << raw.size() << " bytes\n"; return 2; }
+    } else {
+        const size_t block = argc > 3 ? std::strtoull(argv[3], nullptr, 10) : BV_DEF_MAX_BLOCK;
+        if (block < 1) { std::cerr << "block bytes must be positive\n"; return 2; }
+        for (size_t at = 0; at < raw.size(); at += block) sizes.push_back(raw.size() - at < block ? raw.size() - at : block);
+    }
+    std::vector<uint32_t> crc_tab(1024);
+    bv_inf_crc_tables(crc_tab.data(), 0, 1);
+    std::unique_ptr<BvDefSmallState> S(new BvDefSmallState());
+    std::ofstream out(argv[2], std::ios::binary);
+    size_t at = 0;
+    for (size_t n : sizes) {
+        if (n < 1 || n > BV_DEF_MAX_BLOCK) { std::cerr << "a block of " << n << " bytes: 1 to 65280 are coded\n"; return 2; }
+        // (a copy of exactly n bytes: a read behind the block is a finding too)
+        const std::vector<uint8_t> text(raw.begin() + at, raw.begin() + at + n);
+        std::vector<uint8_t> member(n + BV_DEF_MEMBER_EXTRA);
+        std::vector<uint32_t> tok(BV_DEFS_TOK_ROOM((uint32_t)n));
+        const uint32_t total = bv_def_small_member(text.data(), (uint32_t)n, member.data(), S.get(), tok.data(), crc_tab.data(), 0, 1, [](uint32_t v) { return v; });
+        if (total > member.size()) { std::cerr << "a member of " << total << " bytes for " << n << " bytes of text\n"; return 1; }
+        out.write(reinterpret_cast<const char *>(member.data()), total);
+        at += n;
+    }
+    out.close();
+    if (!out) { std::cerr << "cannot write " << argv[2] << "\n"; return 2; }
+    return 0;
+}
