@@ -4,7 +4,7 @@
 // The host writer (host/bgzf_tabix.hpp) compresses every 0xff00-byte block of a `*.vcf.gz` / `*.cvg.gz` with one zlib
 // deflate() on the one thread that keeps the output in order.  Here every block is one single-wave workgroup.  The encoder is
 // bv_deflate_core.h, shared with a CPU harness: the block's text and the match table stay in LDS (63.8 KiB + 8 KiB of table +
-// 0.7 KiB of chunk state + 4 KiB of CRC tables: two workgroups per CU), the lanes share the hashing, the match measuring, the
+// 0.6 KiB of chunk state + 4 KiB of CRC tables: two workgroups per CU), the lanes share the hashing, the match measuring, the
 // table update and the CRC32, and walk the parse together.  What a block becomes depends on its text alone, so the device's
 // members are the CPU build's, byte for byte.
 //
@@ -12,9 +12,10 @@
 // the device -- a prefix sum over the member sizes and a gather -- so that one contiguous run of members is copied back.
 //
 // BV_DEFLATE_SMALL (bv_engine_bgzf_deflate_level) is a second kernel over the same staging, scan and gather: the encoder of
-// bv_deflate_small_core.h, dynamic Huffman codes over 16-, 8- and 4-byte grams.  Its three tables (24 KiB), the text and the
-// Huffman workspace are 103 KiB of LDS: ONE workgroup per CU where the default level has two.  Its tokens wait in device
-// memory between the parse and the coding (4 bytes per byte of text, allocated by the first call at that level).
+// bv_deflate_small_core.h, dynamic Huffman codes over 16-, 8- and 4-byte grams (the same chunk matcher with three grams).
+// Its three tables (24 KiB), the text and the Huffman workspace are 103 KiB of LDS: ONE workgroup per CU where the default
+// level has two.  Its tokens wait in device memory between the parse and the coding (4 bytes per byte of text, allocated by
+// the first call at that level).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +36,7 @@ namespace {
 constexpr uint32_t kSlotStride = 0x10020;  // bytes between two members' slots: 16-byte aligned, > 0xff00 + 31 + the 8 a word-wise reader may touch
 constexpr uint32_t kChunkBlocks = 1024;    // blocks per staged chunk (two chunks in flight)
 constexpr uint32_t kScanThreads = 256;
+constexpr uint32_t kWinBytes = BV_DEF_MAX_BLOCK + BV_DEF_TEXT_PAD;  // a block's text in LDS
 static_assert(BV_DEF_MAX_BLOCK + BV_DEF_MEMBER_EXTRA + 8u <= kSlotStride && kSlotStride % 16u == 0, "a member and a reader's last word fit a slot");
 
 // one block of a staged chunk
@@ -53,72 +55,64 @@ __device__ inline uint32_t word_at(const uint32_t *base, uint32_t at, bool secon
     return (w0 >> sh) | (w1 << (32u - sh));
 }
 
-__global__ __launch_bounds__(64) void bv_bgzf_deflate_kernel(const uint8_t *__restrict__ text, const BvDefBlock *__restrict__ meta, uint32_t nblk,
-                                                             uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes) {
-    __shared__ __attribute__((aligned(16))) uint8_t win[BV_DEF_MAX_BLOCK + BV_DEF_TEXT_PAD];
-    __shared__ BvDefState S;
-    __shared__ uint32_t crc_tab[1024];
-    const uint32_t k = blockIdx.x, lane = threadIdx.x;
-    if (k >= nblk) return;
-    const BvDefBlock m = meta[k];
-    if (m.n < 1u || m.n > BV_DEF_MAX_BLOCK) {  // (the host has refused such a block; nothing is read or written for it)
-        if (lane == 0) sizes[k] = 0;
-        return;
-    }
-    bv_inf_crc_tables(crc_tab, lane, 64);
-    // The text to LDS, a word per lane and step.  Its place in memory has any alignment: a word of the window is cut from the
-    // two aligned words of global memory around it; the second is read only where it holds a byte of the block (an aligned
-    // word with one byte inside the buffer lies inside the buffer's pages).
-    {
-        const uint8_t *g = text + m.text_off;
-        const uint32_t mis = (uint32_t)((uintptr_t)g & 3u);
-        const uint32_t *ga = reinterpret_cast<const uint32_t *>(g - mis);
-        uint32_t *w = reinterpret_cast<uint32_t *>(win);
-        const uint32_t words = (m.n + 3u) / 4u;
-        for (uint32_t j = lane; j < words; j += 64u) w[j] = word_at(ga, mis + 4u * j, 4u * j + 4u - mis < m.n);
-        // (what lies behind the text in the window is read by bv_def_load4 and never used: cleared, so that no run differs)
-        for (uint32_t j = words + lane; j < words + BV_DEF_TEXT_PAD / 4u && j < sizeof(win) / 4u; j += 64u) w[j] = 0;
-    }
-    __syncthreads();
-    const uint32_t total = bv_def_member(win, m.n, slots + (size_t)k * kSlotStride, &S, crc_tab, lane, 64, [](uint32_t c) {
-        for (int d = 32; d > 0; d >>= 1) c ^= __shfl_xor(c, d, 64);
-        return c;
-    });
-    if (lane == 0) sizes[k] = total;
-}
-
-// the text of block m to the window, a word per lane and step.  Its place in memory has any alignment: a word of the window is
-// cut from the two aligned words of global memory around it; the second is read only where it holds a byte of the block.
-__device__ inline void stage_text(const uint8_t *g, uint32_t n, uint8_t *win, uint32_t win_bytes, uint32_t lane) {
+// the text of a block to the window, a word per lane and step.  Its place in memory has any alignment: a word of the window is
+// cut from the two aligned words of global memory around it; the second is read only where it holds a byte of the block (an
+// aligned word with one byte inside the buffer lies inside the buffer's pages).
+__device__ inline void stage_text(const uint8_t *g, uint32_t n, uint8_t *win, uint32_t lane) {
     const uint32_t mis = (uint32_t)((uintptr_t)g & 3u);
     const uint32_t *ga = reinterpret_cast<const uint32_t *>(g - mis);
     uint32_t *w = reinterpret_cast<uint32_t *>(win);
     const uint32_t words = (n + 3u) / 4u;
     for (uint32_t j = lane; j < words; j += 64u) w[j] = word_at(ga, mis + 4u * j, 4u * j + 4u - mis < n);
-    for (uint32_t j = words + lane; j < words + BV_DEF_TEXT_PAD / 4u && j < win_bytes / 4u; j += 64u) w[j] = 0;
+    // (what lies behind the text in the window is read by bv_def_load4 and never used: cleared, so that no run differs)
+    for (uint32_t j = words + lane; j < words + BV_DEF_TEXT_PAD / 4u && j < kWinBytes / 4u; j += 64u) w[j] = 0;
+}
+
+// What both levels' kernels begin with: block k of the launch, its text in `win` and the CRC tables in `crc_tab`.  False:
+// there is nothing to code, and the whole workgroup leaves.
+__device__ inline bool begin_block(const uint8_t *text, const BvDefBlock *meta, uint32_t nblk, uint32_t *sizes, uint8_t *win, uint32_t *crc_tab, BvDefBlock &m) {
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= nblk) return false;
+    m = meta[k];
+    if (m.n < 1u || m.n > BV_DEF_MAX_BLOCK) {  // (the host has refused such a block; nothing is read or written for it)
+        if (lane == 0) sizes[k] = 0;
+        return false;
+    }
+    bv_inf_crc_tables(crc_tab, lane, 64);
+    stage_text(text + m.text_off, m.n, win, lane);
+    __syncthreads();
+    return true;
+}
+
+// the lanes' CRC shares combined: the xor over the wave
+struct WaveXor {
+    __device__ uint32_t operator()(uint32_t c) const {
+        for (int d = 32; d > 0; d >>= 1) c ^= __shfl_xor(c, d, 64);
+        return c;
+    }
+};
+
+__global__ __launch_bounds__(64) void bv_bgzf_deflate_kernel(const uint8_t *__restrict__ text, const BvDefBlock *__restrict__ meta, uint32_t nblk,
+                                                             uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes) {
+    __shared__ __attribute__((aligned(16))) uint8_t win[kWinBytes];
+    __shared__ BvDefState S;
+    __shared__ uint32_t crc_tab[1024];
+    BvDefBlock m;
+    if (!begin_block(text, meta, nblk, sizes, win, crc_tab, m)) return;
+    const uint32_t total = bv_def_member(win, m.n, slots + (size_t)blockIdx.x * kSlotStride, &S, crc_tab, threadIdx.x, 64, WaveXor());
+    if (threadIdx.x == 0) sizes[blockIdx.x] = total;
 }
 
 // BV_DEFLATE_SMALL: one wave per block as above, with the encoder of bv_deflate_small_core.h.  tok: the chunk's token runs.
 __global__ __launch_bounds__(64) void bv_bgzf_small_kernel(const uint8_t *__restrict__ text, const BvDefBlock *__restrict__ meta, uint32_t nblk,
                                                            uint8_t *__restrict__ slots, uint32_t *__restrict__ sizes, uint32_t *tok) {
-    __shared__ __attribute__((aligned(16))) uint8_t win[BV_DEF_MAX_BLOCK + BV_DEF_TEXT_PAD];
+    __shared__ __attribute__((aligned(16))) uint8_t win[kWinBytes];
     __shared__ BvDefSmallState S;
     __shared__ uint32_t crc_tab[1024];
-    const uint32_t k = blockIdx.x, lane = threadIdx.x;
-    if (k >= nblk) return;
-    const BvDefBlock m = meta[k];
-    if (m.n < 1u || m.n > BV_DEF_MAX_BLOCK) {  // (the host has refused such a block; nothing is read or written for it)
-        if (lane == 0) sizes[k] = 0;
-        return;
-    }
-    bv_inf_crc_tables(crc_tab, lane, 64);
-    stage_text(text + m.text_off, m.n, win, (uint32_t)sizeof(win), lane);
-    __syncthreads();
-    const uint32_t total = bv_def_small_member(win, m.n, slots + (size_t)k * kSlotStride, &S, tok + (size_t)m.tok_at * 64u, crc_tab, lane, 64, [](uint32_t c) {
-        for (int d = 32; d > 0; d >>= 1) c ^= __shfl_xor(c, d, 64);
-        return c;
-    });
-    if (lane == 0) sizes[k] = total;
+    BvDefBlock m;
+    if (!begin_block(text, meta, nblk, sizes, win, crc_tab, m)) return;
+    const uint32_t total = bv_def_small_member(win, m.n, slots + (size_t)blockIdx.x * kSlotStride, &S, tok + (size_t)m.tok_at * 64u, crc_tab, threadIdx.x, 64, WaveXor());
+    if (threadIdx.x == 0) sizes[blockIdx.x] = total;
 }
 
 // bv_engine_deflate_code_lengths: one wave around bv_defs_code_lengths

@@ -1,8 +1,9 @@
 // bv_deflate_small_core.h -- the second, opt-in level of the device DEFLATE encoder (BV_DEFLATE_SMALL of
 // bv_engine_bgzf_deflate_level, include/basevar_amd_bgzf.h): dynamic Huffman codes over a parse that looks for 16-, 8- and
-// 4-byte grams.  Written as bv_deflate_core.h is (which it includes and leaves alone): inline functions that the device kernel
-// (bv_deflate.hip) and a plain g++ harness (tests/cpp/deflate_small_check.cpp, run under ASan + UBSan) both compile; `nlanes`
-// lanes execute it, `lane` only selects which part of a wide step a lane does, the CPU runs it as lane 0 of 1.
+// 4-byte grams.  Written as bv_deflate_core.h is, whose chunk matcher, symbol mapping, bit buffer and member frame it uses:
+// inline functions that the device kernel (bv_deflate.hip) and a plain g++ harness (tests/cpp/deflate_core_check.cpp --level
+// small, run under ASan + UBSan) both compile; `nlanes` lanes execute it, `lane` only selects which part of a wide step a lane
+// does, the CPU runs it as lane 0 of 1.
 //
 // One wave codes one block of 1 .. 0xff00 bytes into one whole BGZF member, a single final block, at most its text + 31 bytes.
 //
@@ -43,7 +44,7 @@
 //   sizes follow from the counts before a bit is written, and only the chosen form is written.
 //
 // A serial coder computes exactly this (tests/deflate_small_model.py is one, written from these lines).  Here the parse runs
-// BV_DEF_CHUNK positions at a time as in bv_deflate_core.h, with three tables; the tokens leave the parse 64 at a time for a
+// BV_DEF_CHUNK positions at a time through bv_deflate_core.h's bv_def_chunk, with three tables; the tokens leave the parse 64 at a time for a
 // run of the caller's (`tok`: device memory on the device, one 256-byte store per 64 tokens) and are counted as they leave;
 // one lane builds the trees (a few hundred steps per alphabet; the sort before them is shared); the codes are written 64
 // tokens at a time: every lane looks up its token's bits, the bit counts are summed in front of it, and the bits are ORed
@@ -59,7 +60,6 @@
 #define BV_DEFS_MAX_SYMS 286u
 #define BV_DEFS_SEQ (BV_DEFS_NLL + BV_DEFS_ND)
 #define BV_DEFS_TOK_MATCH 0x80000000u  // a token: a literal's byte (256: the end code), or this | (length - 3) << 15 | (distance - 1)
-#define BV_DEFS_NO_HASH 0xffffu
 #define BV_DEFS_WIN_WORDS 104u         // 31 bits carried + 64 tokens of at most 48 bits, and the two words a token's OR may touch behind
 #define BV_DEFS_FORM_STORED 0u
 #define BV_DEFS_FORM_FIXED 1u
@@ -89,12 +89,7 @@ struct BvDefsHuff {
 
 // State of one block: 24 KiB of tables + 11.5 KiB (LDS on the device).
 struct BvDefSmallState {
-    uint16_t head[3][1u << 12];       // per gram 4, 8, 16: position + 1 of the latest position with this hash; 0: none
-    uint64_t hash[BV_DEF_CHUNK];      // the chunk's three hashes, 16 bits each from bit 0, 16, 32 (BV_DEFS_NO_HASH: too few bytes left)
-    uint16_t cand[3][BV_DEF_CHUNK];   // position + 1 of the candidate from the table; 0: none
-    uint16_t len[BV_DEF_CHUNK];       // match length, 0: a literal
-    uint16_t dist[BV_DEF_CHUNK];      // distance - 1
-    uint8_t last[BV_DEF_CHUNK];       // bit g: no later position of the chunk has this hash of gram g
+    BvDefMatch<3> M;                  // the grams of 4, 8 and 16 bytes
     uint32_t tokbuf[64];              // tokens on their way out
     uint32_t ll_cnt[BV_DEFS_NLL], d_cnt[BV_DEFS_ND + 2u], cl_cnt[BV_DEFS_NCL + 1u];
     uint8_t ll_len[BV_DEFS_NLL + 2u], d_len[BV_DEFS_ND + 2u], cl_len[BV_DEFS_NCL + 1u];
@@ -109,28 +104,9 @@ struct BvDefSmallState {
 
 BV_DEF_FN uint32_t bv_defs_cl_order(uint32_t k) { return (uint32_t)"\x10\x11\x12\x00\x08\x07\x09\x06\x0a\x05\x0b\x04\x0c\x03\x0d\x02\x0e\x01\x0f"[k]; }
 
-// RFC 1951 3.2.5 in closed form.  l = length - 3 (0 .. 255), d = distance - 1 (0 .. 32767)
-BV_DEF_FN void bv_defs_len_sym(uint32_t l, uint32_t &sym, uint32_t &eb, uint32_t &extra) {
-    if (l == 255u) { sym = 285u; eb = 0; extra = 0; }
-    else if (l < 8u) { sym = 257u + l; eb = 0; extra = 0; }
-    else {
-        eb = (31u - (uint32_t)__builtin_clz(l)) - 2u;
-        sym = 261u + 4u * eb + ((l >> eb) & 3u);
-        extra = l & ((1u << eb) - 1u);
-    }
-}
-BV_DEF_FN void bv_defs_dist_sym(uint32_t d, uint32_t &sym, uint32_t &eb, uint32_t &extra) {
-    if (d < 4u) { sym = d; eb = 0; extra = 0; }
-    else {
-        eb = (31u - (uint32_t)__builtin_clz(d)) - 1u;
-        sym = 2u * eb + 2u + ((d >> eb) & 1u);
-        extra = d & ((1u << eb) - 1u);
-    }
-}
+// the extra bits of a length and of a distance symbol (RFC 1951 3.2.5)
 BV_DEF_FN uint32_t bv_defs_len_extra_bits(uint32_t sym) { return sym < 265u || sym == 285u ? 0u : (sym - 261u) / 4u; }
 BV_DEF_FN uint32_t bv_defs_dist_extra_bits(uint32_t sym) { return sym < 4u ? 0u : (sym - 2u) / 2u; }
-BV_DEF_FN uint32_t bv_defs_fixed_len(uint32_t sym) { return sym < 144u ? 8u : sym < 256u ? 9u : sym < 280u ? 7u : 8u; }  // RFC 1951 3.2.6
-BV_DEF_FN uint32_t bv_defs_fixed_code(uint32_t sym) { return sym < 144u ? 0x30u + sym : sym < 256u ? 0x190u + (sym - 144u) : sym < 280u ? sym - 256u : 0xc0u + (sym - 280u); }
 
 // The code lengths of counts[0 .. nsym) with limit L, 2 <= nsym <= BV_DEFS_MAX_SYMS <= 2^L... (nsym <= 2^limit: the rounds end when
 // every count is 1 at the latest, and equal counts give a tree of depth ceil(log2)); the counts add up to less than 2^32.
@@ -219,14 +195,6 @@ BV_DEF_FN void bv_defs_codes(const uint8_t *len, uint32_t nsym, uint16_t *code, 
     BV_DEF_WAVE_SYNC();
 }
 
-// the common prefix of text[p ..) and text[q ..), at most maxl
-BV_DEF_FN uint32_t bv_defs_measure(const uint8_t *text, uint32_t p, uint32_t q, uint32_t maxl) {
-    uint32_t len = 0;
-    while (len + 4u <= maxl && bv_def_load4(text, p + len) == bv_def_load4(text, q + len)) len += 4u;
-    while (len < maxl && text[p + len] == text[q + len]) ++len;
-    return len;
-}
-
 // 64 tokens (m of them) leave S->tokbuf for tok[at ..) and are counted
 BV_DEF_FN void bv_defs_flush(BvDefSmallState *S, uint32_t *tok, uint32_t at, uint32_t m, uint32_t lane, uint32_t nlanes) {
     BV_DEF_WAVE_SYNC();
@@ -235,9 +203,9 @@ BV_DEF_FN void bv_defs_flush(BvDefSmallState *S, uint32_t *tok, uint32_t at, uin
         tok[at + i] = t;
         if (t & BV_DEFS_TOK_MATCH) {
             uint32_t sym, eb, extra;
-            bv_defs_len_sym((t >> 15) & 0xffu, sym, eb, extra);
+            bv_def_len_sym((t >> 15) & 0xffu, sym, eb, extra);
             BV_DEFS_ADD(&S->ll_cnt[sym], 1u);
-            bv_defs_dist_sym(t & 0x7fffu, sym, eb, extra);
+            bv_def_dist_sym(t & 0x7fffu, sym, eb, extra);
             BV_DEFS_ADD(&S->d_cnt[sym], 1u);
         } else {
             BV_DEFS_ADD(&S->ll_cnt[t], 1u);
@@ -248,95 +216,18 @@ BV_DEF_FN void bv_defs_flush(BvDefSmallState *S, uint32_t *tok, uint32_t at, uin
 
 // The parse of text[0 .. n): the tokens to tok[0 ..), the end code behind them, the counts to S.  Returns the number of tokens.
 BV_DEF_FN uint32_t bv_defs_parse(const uint8_t *text, uint32_t n, BvDefSmallState *S, uint32_t *tok, uint32_t lane, uint32_t nlanes) {
-    const uint32_t K = 2654435761u;
-    for (uint32_t i = lane; i < 3u * (1u << 12); i += nlanes) (&S->head[0][0])[i] = 0;
     for (uint32_t i = lane; i < BV_DEFS_NLL; i += nlanes) S->ll_cnt[i] = 0;
     for (uint32_t i = lane; i < BV_DEFS_ND + 2u; i += nlanes) S->d_cnt[i] = 0;
-    BV_DEF_WAVE_SYNC();
+    bv_def_clear(&S->M, lane, nlanes);
     uint32_t cur = 0, ntok = 0;
     for (uint32_t base = 0; base < n; base += BV_DEF_CHUNK) {
-        const bool measure = cur < base + BV_DEF_CHUNK;  // else an earlier match covers the whole chunk: only the tables are kept
-        for (uint32_t i = lane; i < BV_DEF_CHUNK; i += nlanes) {
-            const uint32_t p = base + i;
-            uint32_t h4 = BV_DEFS_NO_HASH, h8 = BV_DEFS_NO_HASH, h16 = BV_DEFS_NO_HASH, c4 = 0, c8 = 0, c16 = 0;
-            if (p + 4u <= n) {
-                uint32_t v = bv_def_load4(text, p);
-                h4 = (v * K) >> 20;
-                c4 = S->head[0][h4];
-                if (p + 8u <= n) {
-                    v = v * K + bv_def_load4(text, p + 4u);
-                    h8 = (v * K) >> 20;
-                    c8 = S->head[1][h8];
-                    if (p + 16u <= n) {
-                        v = v * K + bv_def_load4(text, p + 8u);
-                        v = v * K + bv_def_load4(text, p + 12u);
-                        h16 = (v * K) >> 20;
-                        c16 = S->head[2][h16];
-                    }
-                }
-            }
-            S->hash[i] = (uint64_t)h4 | ((uint64_t)h8 << 16) | ((uint64_t)h16 << 32);
-            S->cand[0][i] = (uint16_t)c4; S->cand[1][i] = (uint16_t)c8; S->cand[2][i] = (uint16_t)c16;
-        }
-        BV_DEF_WAVE_SYNC();
-        for (uint32_t i = lane; i < BV_DEF_CHUNK; i += nlanes) {
-            const uint32_t p = base + i;
-            const uint64_t mine = S->hash[i];
-            const uint32_t h4 = (uint32_t)mine & 0xffffu, h8 = (uint32_t)(mine >> 16) & 0xffffu, h16 = (uint32_t)(mine >> 32) & 0xffffu;
-            uint32_t c4 = S->cand[0][i], c8 = S->cand[1][i], c16 = S->cand[2][i], last = 7u, len = 0, from = 0;
-            if (h4 != BV_DEFS_NO_HASH) {
-                // (a gram this position does not have matches nobody's: no hash is 0xfffe)
-                const uint32_t m8 = h8 == BV_DEFS_NO_HASH ? 0xfffeu : h8, m16 = h16 == BV_DEFS_NO_HASH ? 0xfffeu : h16;
-                for (uint32_t j = 0; j < BV_DEF_CHUNK; ++j) {
-                    const uint64_t x = S->hash[j];
-                    const bool s4 = ((uint32_t)x & 0xffffu) == h4, s8 = ((uint32_t)(x >> 16) & 0xffffu) == m8, s16 = ((uint32_t)(x >> 32) & 0xffffu) == m16;
-                    if (j < i) {
-                        if (s4) c4 = base + j + 1u;
-                        if (s8) c8 = base + j + 1u;
-                        if (s16) c16 = base + j + 1u;
-                    } else if (j > i) {
-                        if (s4) last &= ~1u;
-                        if (s8) last &= ~2u;
-                        if (s16) last &= ~4u;
-                    }
-                }
-            }
-            if (measure && p >= cur && p < n) {
-                const uint32_t maxl = n - p < BV_DEF_MAX_MATCH ? n - p : BV_DEF_MAX_MATCH;
-                if (c16 != 0 && p - (c16 - 1u) <= BV_DEF_WINDOW) {
-                    len = bv_defs_measure(text, p, c16 - 1u, maxl);
-                    from = c16;
-                    if (len < 16u) len = 0;
-                }
-                if (len == 0 && c8 != 0 && p - (c8 - 1u) <= BV_DEF_WINDOW) {
-                    len = bv_defs_measure(text, p, c8 - 1u, maxl);
-                    from = c8;
-                    if (len < 8u) len = 0;
-                }
-                if (len == 0 && c4 != 0 && p - (c4 - 1u) <= BV_DEF_WINDOW) {
-                    len = bv_defs_measure(text, p, c4 - 1u, maxl);
-                    from = c4;
-                    if (len < 4u) len = 0;
-                }
-            }
-            S->last[i] = (uint8_t)last;
-            S->len[i] = (uint16_t)len;
-            S->dist[i] = (uint16_t)(len ? p - (from - 1u) - 1u : 0u);
-        }
-        BV_DEF_WAVE_SYNC();
-        for (uint32_t i = lane; i < BV_DEF_CHUNK; i += nlanes) {
-            const uint64_t mine = S->hash[i];
-            const uint32_t h4 = (uint32_t)mine & 0xffffu, h8 = (uint32_t)(mine >> 16) & 0xffffu, h16 = (uint32_t)(mine >> 32) & 0xffffu, last = S->last[i];
-            if (h4 != BV_DEFS_NO_HASH && (last & 1u)) S->head[0][h4] = (uint16_t)(base + i + 1u);
-            if (h8 != BV_DEFS_NO_HASH && (last & 2u)) S->head[1][h8] = (uint16_t)(base + i + 1u);
-            if (h16 != BV_DEFS_NO_HASH && (last & 4u)) S->head[2][h16] = (uint16_t)(base + i + 1u);
-        }
+        bv_def_chunk(text, n, base, cur, &S->M, lane, nlanes);
         const uint32_t end = base + BV_DEF_CHUNK < n ? base + BV_DEF_CHUNK : n;
         while (cur < end) {
-            const uint32_t i = cur - base, len = S->len[i];
+            const uint32_t i = cur - base, len = S->M.len[i];
             uint32_t t;
             if (len) {
-                t = BV_DEFS_TOK_MATCH | ((len - 3u) << 15) | (uint32_t)S->dist[i];
+                t = BV_DEFS_TOK_MATCH | ((len - 3u) << 15) | (uint32_t)S->M.dist[i];
                 cur += len;
             } else {
                 t = text[cur];
@@ -399,7 +290,7 @@ BV_DEF_FN void bv_defs_plan(uint32_t n, BvDefSmallState *S, uint32_t lane, uint3
         for (uint32_t s = 0; s < BV_DEFS_NCL; ++s) dyn += S->cl_cnt[s] * ((uint32_t)S->cl_len[s] + (s == 16u ? 2u : s == 17u ? 3u : s == 18u ? 7u : 0u));
         for (uint32_t s = 0; s < BV_DEFS_NLL; ++s) {
             const uint32_t c = S->ll_cnt[s];
-            dyn += c * S->ll_len[s]; fix += c * bv_defs_fixed_len(s); extra += c * bv_defs_len_extra_bits(s);
+            dyn += c * S->ll_len[s]; fix += c * bv_def_fixed_len(s); extra += c * bv_defs_len_extra_bits(s);
         }
         for (uint32_t s = 0; s < BV_DEFS_ND; ++s) {
             const uint32_t c = S->d_cnt[s];
@@ -418,8 +309,8 @@ BV_DEF_FN void bv_defs_plan(uint32_t n, BvDefSmallState *S, uint32_t lane, uint3
         bv_defs_codes(S->cl_len, BV_DEFS_NCL, S->cl_code, &S->H, lane);
     } else if (S->form == BV_DEFS_FORM_FIXED) {
         for (uint32_t s = lane; s < BV_DEFS_NLL; s += nlanes) {
-            const uint32_t l = bv_defs_fixed_len(s);
-            S->ll_len[s] = (uint8_t)l; S->ll_code[s] = (uint16_t)bv_def_rev(bv_defs_fixed_code(s), l);
+            const uint32_t l = bv_def_fixed_len(s);
+            S->ll_len[s] = (uint8_t)l; S->ll_code[s] = (uint16_t)bv_def_rev(bv_def_fixed_code(s), l);
         }
         for (uint32_t s = lane; s < BV_DEFS_ND; s += nlanes) { S->d_len[s] = 5u; S->d_code[s] = (uint16_t)bv_def_rev(s, 5); }
         BV_DEF_WAVE_SYNC();
@@ -456,10 +347,10 @@ BV_DEF_FN void bv_defs_emit(uint8_t *out, const uint32_t *tok, uint32_t ntok, Bv
                 const uint32_t t = tok[base + i];
                 if (t & BV_DEFS_TOK_MATCH) {
                     uint32_t sym, eb, extra;
-                    bv_defs_len_sym((t >> 15) & 0xffu, sym, eb, extra);
+                    bv_def_len_sym((t >> 15) & 0xffu, sym, eb, extra);
                     code = S->ll_code[sym]; nb = S->ll_len[sym];
                     code |= (uint64_t)extra << nb; nb += eb;
-                    bv_defs_dist_sym(t & 0x7fffu, sym, eb, extra);
+                    bv_def_dist_sym(t & 0x7fffu, sym, eb, extra);
                     code |= (uint64_t)S->d_code[sym] << nb; nb += S->d_len[sym];
                     code |= (uint64_t)extra << nb; nb += eb;
                 } else {
@@ -492,12 +383,7 @@ BV_DEF_FN void bv_defs_emit(uint8_t *out, const uint32_t *tok, uint32_t ntok, Bv
         const uint32_t full = total >> 5;
         for (uint32_t k = lane; k < full; k += nlanes) {
             if (pos + 4u * k + 4u > b.limit) continue;  // (never: the sizes were counted)
-            const uint32_t w = S->ewin[k];
-#if defined(__HIP_DEVICE_COMPILE__)
-            *reinterpret_cast<uint32_t *>(b.out + pos + 4u * k) = w;
-#else
-            memcpy(b.out + pos + 4u * k, &w, 4);
-#endif
+            bv_def_store_word(b.out + pos + 4u * k, S->ewin[k]);
         }
         const uint32_t carry = S->ewin[full];
         BV_DEF_WAVE_SYNC();
@@ -517,31 +403,10 @@ BV_DEF_FN void bv_defs_emit(uint8_t *out, const uint32_t *tok, uint32_t ntok, Bv
 template <class Reduce>
 BV_DEF_FN uint32_t bv_def_small_member(const uint8_t *text, uint32_t n, uint8_t *out, BvDefSmallState *S, uint32_t *tok, const uint32_t *crc_tab,
                                        uint32_t lane, uint32_t nlanes, Reduce crc_reduce) {
-    uint32_t share = 0;
-    for (uint32_t s = lane; s < 64u; s += nlanes) share ^= bv_inf_crc_share(text, n, s, crc_tab);
-    const uint32_t crc = ~crc_reduce(share);
     const uint32_t ntok = bv_defs_parse(text, n, S, tok, lane, nlanes);
     bv_defs_plan(n, S, lane, nlanes);
-    const uint32_t plen = S->plen;
-    if (S->form == BV_DEFS_FORM_STORED) {
-        if (lane == 0) {
-            out[18] = 1;  // BFINAL = 1, BTYPE = 00
-            out[19] = (uint8_t)n; out[20] = (uint8_t)(n >> 8);
-            out[21] = (uint8_t)~n; out[22] = (uint8_t)(~n >> 8);
-        }
-        for (uint32_t i = lane; i < n; i += nlanes) out[23u + i] = text[i];
-    } else {
-        bv_defs_emit(out, tok, ntok, S, lane, nlanes);
-    }
-    const uint32_t total = 18u + plen + 8u;
-    if (lane == 0) {
-        const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-        for (uint32_t k = 0; k < 16u; ++k) out[k] = head[k];
-        out[16] = (uint8_t)(total - 1u); out[17] = (uint8_t)((total - 1u) >> 8);
-        uint8_t *t = out + 18u + plen;
-        for (uint32_t k = 0; k < 4u; ++k) { t[k] = (uint8_t)(crc >> (8u * k)); t[4u + k] = (uint8_t)(n >> (8u * k)); }
-    }
-    return total;
+    if (S->form != BV_DEFS_FORM_STORED) bv_defs_emit(out, tok, ntok, S, lane, nlanes);
+    return bv_def_frame(text, n, out, S->form == BV_DEFS_FORM_STORED ? 0u : S->plen, crc_tab, lane, nlanes, crc_reduce);
 }
 
 #endif  // BV_DEFLATE_SMALL_CORE_H

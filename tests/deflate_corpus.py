@@ -272,17 +272,55 @@ def assert_edge_conditions(rep):
     assert rep["ties"] >= 1 and rep["stored"] > rep["ties"] and rep["split_258"] >= 1, rep
 
 
-def cpu_members(core_exe, text, sizes, work_dir, sanitize_env=True):
-    """the CPU build of the core over the blocks: the members, back to back"""
+def cpu_members(core_exe, text, sizes, work_dir, sanitize_env=True, level="fast"):
+    """the CPU build of the core (tests/cpp/deflate_core_check.cpp) over the blocks at the level: the members, back to back"""
     tp, op, sp = (os.path.join(str(work_dir), n) for n in ("text.bin", "members.bin", "sizes.txt"))
     with open(tp, "wb") as fh:
         fh.write(text)
     with open(sp, "w") as fh:
         fh.write("\n".join(str(s) for s in sizes) + "\n")
-    p = subprocess.run([core_exe, tp, op, "@" + sp], capture_output=True, text=True, env=dict(os.environ, **SAN_ENV), timeout=1200)
+    p = subprocess.run([core_exe, "--level", level, tp, op, "@" + sp], capture_output=True, text=True, env=dict(os.environ, **SAN_ENV), timeout=1200)
     assert p.returncode == 0, (p.returncode, p.stderr[-3000:])
     with open(op, "rb") as fh:
         return fh.read()
+
+
+def first_difference(got, want):
+    """where two members of one text part, in the tracer's tokens"""
+    try:
+        a, b = traced(got).tokens, traced(want).tokens
+    except Exception as e:  # (not a stream at all)
+        return "the tracer: %r" % (e,)
+    at = 0
+    for k, (x, y) in enumerate(zip(a, b)):
+        if x != y:
+            return "token %d, at byte %d of the text: the encoder wrote %r, the model %r" % (k, at, x, y)
+        at += 1 if isinstance(x, int) else x[0]
+    if len(a) != len(b):
+        return "%d tokens against the model's %d" % (len(a), len(b))
+    return "the same tokens; member bytes %d against %d, first difference at byte %d" % (
+        len(got), len(want), next((i for i, (x, y) in enumerate(zip(got, want)) if x != y), min(len(got), len(want))))
+
+
+def assert_members_are_the_models(names, members, expected):
+    bad = [(name, first_difference(m, e)) for name, m, e in zip(names, members, expected) if m != e]
+    assert not bad, "%d of %d members differ from the model's; the first: %s: %s" % (len(bad), len(members), bad[0][0], bad[0][1])
+
+
+def offsets(sizes):
+    off = np.zeros(len(sizes) + 1, np.uint64)
+    off[1:] = np.cumsum(sizes)
+    return off
+
+
+def assert_members(got, want, sizes, what):
+    """the members back to back against the expected ones; on a difference, the first block that differs"""
+    if got == want:
+        return
+    a, b = split_members(got), split_members(want)
+    k = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+    raise AssertionError("%s: %d members against %d; the first difference is block %d of %d bytes (%d bytes against %d)" % (
+        what, len(a), len(b), k, sizes[k] if k < len(sizes) else -1, len(a[k]) if k < len(a) else -1, len(b[k]) if k < len(b) else -1))
 
 
 def split_members(raw):

@@ -225,5 +225,5 @@ def kraft_is_one(lengths):
 
 
 def format_vectors(vectors):
-    """the count vectors as tests/cpp/deflate_small_check.cpp --lengths reads them"""
+    """the count vectors as tests/cpp/deflate_core_check.cpp --lengths reads them"""
     return "".join("%d %d %s\n" % (limit, len(c), " ".join(str(x) for x in c)) for _, limit, c in vectors)

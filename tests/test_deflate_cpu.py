@@ -156,28 +156,6 @@ def edge(tmp_path_factory):
     return entries, blocks, members, [dm.member(b) for b in blocks]
 
 
-def first_difference(got, want):
-    """where two members of one text part, in the tracer's tokens"""
-    try:
-        a, b = dc.traced(got).tokens, dc.traced(want).tokens
-    except Exception as e:  # (not a stream at all)
-        return "the tracer: %r" % (e,)
-    at = 0
-    for k, (x, y) in enumerate(zip(a, b)):
-        if x != y:
-            return "token %d, at byte %d of the text: the encoder wrote %r, the model %r" % (k, at, x, y)
-        at += 1 if isinstance(x, int) else x[0]
-    if len(a) != len(b):
-        return "%d tokens against the model's %d" % (len(a), len(b))
-    return "the same tokens; member bytes %d against %d, first difference at byte %d" % (
-        len(got), len(want), next((i for i, (x, y) in enumerate(zip(got, want)) if x != y), min(len(got), len(want))))
-
-
-def assert_members_are_the_models(names, members, expected):
-    bad = [(name, first_difference(m, e)) for name, m, e in zip(names, members, expected) if m != e]
-    assert not bad, "%d of %d members differ from the model's; the first: %s: %s" % (len(bad), len(members), bad[0][0], bad[0][1])
-
-
 def test_the_edge_corpus_goes_where_it_is_meant_to_in_the_models_members(edge):
     """the conditions on the corpus, on what the model writes: they hold whatever the encoder does"""
     entries, blocks, _, model = edge
@@ -218,7 +196,7 @@ def test_the_edge_corpus_goes_where_it_is_meant_to_in_the_models_members(edge):
 def test_edge_members_are_the_models_byte_for_byte(edge):
     entries, blocks, members, model = edge
     names = ["%s[%d]" % (name, k) for name, bs in entries for k in range(len(bs))]
-    assert_members_are_the_models(names, members, model)
+    dc.assert_members_are_the_models(names, members, model)
     dc.assert_edge_conditions(dc.edge_report(members, blocks))
 
 
@@ -238,6 +216,6 @@ def test_members_of_the_corpus_are_the_models_byte_for_byte(coded):
     n = 0
     for name, (text, sizes, members) in coded.items():
         blocks = list(dc.blocks_of(text, sizes))
-        assert_members_are_the_models(["%s[%d]" % (name, k) for k in range(len(blocks))], members, [dm.member(b) for b in blocks])
+        dc.assert_members_are_the_models(["%s[%d]" % (name, k) for k in range(len(blocks))], members, [dm.member(b) for b in blocks])
         n += len(blocks)
     assert n > 380

@@ -1,6 +1,6 @@
 """CPU tests (no GPU) of the small level of the device DEFLATE encoder (BV_DEFLATE_SMALL): the core the kernel compiles
 (basevar_amd/csrc/bv_deflate_small_core.h), built with g++ under ASan + UBSan as a stand-alone program
-(tests/cpp/deflate_small_check.cpp), over the corpus and the edge corpus of tests/deflate_corpus.py and the blocks of
+(tests/cpp/deflate_core_check.cpp --level small), over the corpus and the edge corpus of tests/deflate_corpus.py and the blocks of
 tests/deflate_small_corpus.py.  Which bytes it writes is held to tests/deflate_small_model.py, a serial restatement of the
 header's definition that shares no code with the encoder; zlib, the CPU build of the device decoder and the bit-by-bit tracer
 of tests/deflate_writer.py read what it writes; its size is capped against zlib's level 6 and against the fast level's.
@@ -33,7 +33,7 @@ import deflate_small_model as sm  # noqa: E402
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
     d = tmp_path_factory.mktemp("deflate_small")
-    return d, dc.cxx("emit_corpus", d), dc.cxx("deflate_small_check", d, sanitize=True)
+    return d, dc.cxx("emit_corpus", d), dc.cxx("deflate_core_check", d, sanitize=True)
 
 
 @pytest.fixture(scope="module")
@@ -43,7 +43,7 @@ def coded(built):
     fast = dc.cxx("deflate_core_check", d)
     out = {}
     for name, text, sizes in dc.corpus(emit):
-        members = dc.split_members(dc.cpu_members(core, text, sizes, d))
+        members = dc.split_members(dc.cpu_members(core, text, sizes, d, level="small"))
         assert len(members) == len(sizes), name
         out[name] = (text, sizes, members, dc.split_members(dc.cpu_members(fast, text, sizes, d)))
     return out
@@ -55,39 +55,17 @@ def edge(built):
     d, emit, core = built
     entries = dc.edge_corpus() + [("small_" + name, bs) for name, bs in sc.small_edge_corpus(emit)]
     text, sizes = dc.edge_text(entries)
-    members = dc.split_members(dc.cpu_members(core, text, sizes, d))
+    members = dc.split_members(dc.cpu_members(core, text, sizes, d, level="small"))
     assert len(members) == len(sizes)
     blocks = list(dc.blocks_of(text, sizes))
     return entries, blocks, members, [sm.member(b) for b in blocks]
-
-
-def first_difference(got, want):
-    """where two members of one text part, in the tracer's tokens"""
-    try:
-        a, b = dc.traced(got).tokens, dc.traced(want).tokens
-    except Exception as e:  # (not a stream at all)
-        return "the tracer: %r" % (e,)
-    at = 0
-    for k, (x, y) in enumerate(zip(a, b)):
-        if x != y:
-            return "token %d, at byte %d of the text: the encoder wrote %r, the model %r" % (k, at, x, y)
-        at += 1 if isinstance(x, int) else x[0]
-    if len(a) != len(b):
-        return "%d tokens against the model's %d" % (len(a), len(b))
-    return "the same tokens; member bytes %d against %d, first difference at byte %d" % (
-        len(got), len(want), next((i for i, (x, y) in enumerate(zip(got, want)) if x != y), min(len(got), len(want))))
-
-
-def assert_members_are_the_models(names, members, expected):
-    bad = [(name, first_difference(m, e)) for name, m, e in zip(names, members, expected) if m != e]
-    assert not bad, "%d of %d members differ from the model's; the first: %s: %s" % (len(bad), len(members), bad[0][0], bad[0][1])
 
 
 def test_members_of_the_corpus_are_the_models_byte_for_byte(coded):
     n = 0
     for name, (text, sizes, members, _) in coded.items():
         blocks = list(dc.blocks_of(text, sizes))
-        assert_members_are_the_models(["%s[%d]" % (name, k) for k in range(len(blocks))], members, [sm.member(b) for b in blocks])
+        dc.assert_members_are_the_models(["%s[%d]" % (name, k) for k in range(len(blocks))], members, [sm.member(b) for b in blocks])
         n += len(blocks)
     assert n > 380
     sizes_seen = set(s for _, sizes, _, _ in coded.values() for s in sizes)
@@ -97,7 +75,7 @@ def test_members_of_the_corpus_are_the_models_byte_for_byte(coded):
 def test_edge_members_are_the_models_byte_for_byte(edge):
     entries, blocks, members, model = edge
     names = ["%s[%d]" % (name, k) for name, bs in entries for k in range(len(bs))]
-    assert_members_are_the_models(names, members, model)
+    dc.assert_members_are_the_models(names, members, model)
 
 
 def test_zlib_and_the_device_decoders_core_read_every_member_back(coded, edge, tmp_path):

@@ -36,12 +36,6 @@ def eng():
     e.close()
 
 
-def offsets(sizes):
-    off = np.zeros(len(sizes) + 1, np.uint64)
-    off[1:] = np.cumsum(sizes)
-    return off
-
-
 def joined(corpus):
     """the whole corpus as one text and one list of blocks"""
     text = b"".join(t for _, t, _, _ in corpus)
@@ -51,7 +45,7 @@ def joined(corpus):
 
 def test_device_members_are_the_cpu_cores_bytes(eng, corpus):
     for name, text, sizes, expect in corpus:
-        members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+        members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
         assert off[0] == 0 and len(off) == len(sizes) + 1 and int(off[-1]) == members.size, name
         assert members.tobytes() == expect, name
         cut = dc.split_members(members.tobytes())
@@ -78,16 +72,16 @@ def test_text_given_as_a_device_pointer(eng, corpus):
     dev = torch.zeros(3 + len(text), dtype=torch.uint8, device="cuda:0")
     dev[3:] = torch.frombuffer(bytearray(text), dtype=torch.uint8).to("cuda:0")
     torch.cuda.synchronize()
-    members, off = eng.bgzf_deflate(dev[3:], block_off=offsets(sizes))
+    members, off = eng.bgzf_deflate(dev[3:], block_off=dc.offsets(sizes))
     assert members.tobytes() == expect
-    host, off_h = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    host, off_h = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
     assert host.tobytes() == expect and (off == off_h).all()
 
 
 def test_the_file_reads_back_with_gzip_and_with_the_device_inflate(eng, corpus, tmp_path):
     from basevar_amd import _capi
     text, sizes, _ = joined(corpus)
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
     path = tmp_path / "out.gz"
     path.write_bytes(members.tobytes() + dc.EOF_MARKER)
     with gzip.open(path, "rb") as fh:
@@ -102,7 +96,7 @@ def test_a_call_that_crosses_staging_chunks(eng, corpus, monkeypatch):
     text, sizes, expect = joined(corpus)
     assert len(sizes) > 5 * 2 * 3 and len(sizes) % 5
     monkeypatch.setenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", "5")
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
     assert members.tobytes() == expect
     monkeypatch.setenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", "1")
     members, off = eng.bgzf_deflate(text[:400000])
@@ -199,22 +193,12 @@ def edge(tmp_path_factory):
     return entries, text, sizes, model, dc.cpu_members(core, text, sizes, d)
 
 
-def assert_members(got, want, sizes, what):
-    """the members back to back against the expected ones; on a difference, the first block that differs"""
-    if got == want:
-        return
-    a, b = dc.split_members(got), dc.split_members(want)
-    k = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
-    raise AssertionError("%s: %d members against %d; the first difference is block %d of %d bytes (%d bytes against %d)" % (
-        what, len(a), len(b), k, sizes[k] if k < len(sizes) else -1, len(a[k]) if k < len(a) else -1, len(b[k]) if k < len(b) else -1))
-
-
 def test_edge_members_are_the_models_bytes_and_the_cpu_cores(eng, edge):
     _, text, sizes, model, cpu = edge
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
-    assert_members(members.tobytes(), model, sizes, "the device against the model")
-    assert_members(members.tobytes(), cpu, sizes, "the device against the CPU build")
-    assert off.tolist() == offsets([len(m) for m in dc.split_members(model)]).tolist()
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
+    dc.assert_members(members.tobytes(), model, sizes, "the device against the model")
+    dc.assert_members(members.tobytes(), cpu, sizes, "the device against the CPU build")
+    assert off.tolist() == dc.offsets([len(m) for m in dc.split_members(model)]).tolist()
 
 
 def test_edge_text_as_a_device_pointer_at_every_misalignment(eng, edge):
@@ -232,8 +216,8 @@ def test_edge_text_as_a_device_pointer_at_every_misalignment(eng, edge):
         torch.cuda.synchronize()
         view = buf[k:]
         assert view.data_ptr() % 4 == k and view.numel() == sum(ss)
-        members, off = eng.bgzf_deflate(view, block_off=offsets(ss))
-        assert_members(members.tobytes(), model + (model_member(rest) if rest else b""), ss, "a text %d bytes behind an aligned word" % k)
+        members, off = eng.bgzf_deflate(view, block_off=dc.offsets(ss))
+        dc.assert_members(members.tobytes(), model + (model_member(rest) if rest else b""), ss, "a text %d bytes behind an aligned word" % k)
 
 
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 1023, 1024, 1025, 2500])
@@ -247,23 +231,23 @@ def test_member_off_is_the_running_sum_of_the_models_sizes(eng, edge, monkeypatc
     blocks = [pool[(k * 37 + k // len(pool)) % len(pool)] for k in range(n)]
     expect = [model_member(b) for b in blocks]
     assert n < 200 or len({len(m) for m in expect}) > 40
-    members, off = eng.bgzf_deflate(b"".join(blocks), block_off=offsets([len(b) for b in blocks]))
-    assert off.dtype == np.uint64 and off.tolist() == offsets([len(m) for m in expect]).tolist()
-    assert_members(members.tobytes(), b"".join(expect), [len(b) for b in blocks], "%d small blocks" % n)
+    members, off = eng.bgzf_deflate(b"".join(blocks), block_off=dc.offsets([len(b) for b in blocks]))
+    assert off.dtype == np.uint64 and off.tolist() == dc.offsets([len(m) for m in expect]).tolist()
+    dc.assert_members(members.tobytes(), b"".join(expect), [len(b) for b in blocks], "%d small blocks" % n)
 
 
 def test_edge_members_do_not_depend_on_the_staging_chunk(eng, edge, monkeypatch):
     _, text, sizes, model, _ = edge
     monkeypatch.setenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", "3")
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
-    assert_members(members.tobytes(), model, sizes, "three blocks a staging chunk")
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
+    dc.assert_members(members.tobytes(), model, sizes, "three blocks a staging chunk")
     assert int(off[-1]) == len(model)
 
 
 def test_the_device_inflate_reads_the_edge_members_back(eng, edge):
     from basevar_amd import _capi
     _, text, sizes, model, _ = edge
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes))
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes))
     back, dst_off, status = eng.bgzf_inflate(members, off)
     assert (status == _capi.BV_BGZF_OK).all() and back.tobytes() == text
     assert [int(b - a) for a, b in zip(dst_off[:-1], dst_off[1:])] == sizes

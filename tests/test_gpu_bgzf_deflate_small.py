@@ -1,6 +1,6 @@
 """GPU tests of bv_engine_bgzf_deflate_level at BV_DEFLATE_SMALL (include/basevar_amd_bgzf.h): the corpus and the edge corpus of
 tests/deflate_corpus.py and the blocks of tests/deflate_small_corpus.py deflated on the device.  The device's members are,
-byte for byte, those of the CPU build of the same core (tests/cpp/deflate_small_check.cpp; tests/test_deflate_small_cpu.py
+byte for byte, those of the CPU build of the same core (tests/cpp/deflate_core_check.cpp --level small; tests/test_deflate_small_cpu.py
 runs it under ASan + UBSan) and those of tests/deflate_small_model.py, a serial restatement of the level's definition that shares
 no code with the kernel.
 
@@ -28,12 +28,12 @@ def corpus(tmp_path_factory):
     """[(name, text, sizes, the model's members back to back, the CPU core's)]: corpus(), and both edge corpora as one entry"""
     d = tmp_path_factory.mktemp("deflate_small_gpu")
     emit = dc.cxx("emit_corpus", d)
-    core = dc.cxx("deflate_small_check", d)
+    core = dc.cxx("deflate_core_check", d)
     entries = list(dc.corpus(emit))
     edge = dc.edge_corpus() + sc.small_edge_corpus(emit)
     text, sizes = dc.edge_text(edge)
     entries.append(("edge", text, sizes))
-    return [(name, text, sizes, b"".join(sm.member(b) for b in dc.blocks_of(text, sizes)), dc.cpu_members(core, text, sizes, d)) for name, text, sizes in entries]
+    return [(name, text, sizes, b"".join(sm.member(b) for b in dc.blocks_of(text, sizes)), dc.cpu_members(core, text, sizes, d, level="small")) for name, text, sizes in entries]
 
 
 @pytest.fixture()
@@ -44,36 +44,20 @@ def eng():
     e.close()
 
 
-def offsets(sizes):
-    off = np.zeros(len(sizes) + 1, np.uint64)
-    off[1:] = np.cumsum(sizes)
-    return off
-
-
-def assert_members(got, want, sizes, what):
-    """the members back to back against the expected ones; on a difference, the first block that differs"""
-    if got == want:
-        return
-    a, b = dc.split_members(got), dc.split_members(want)
-    k = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
-    raise AssertionError("%s: %d members against %d; the first difference is block %d of %d bytes (%d bytes against %d)" % (
-        what, len(a), len(b), k, sizes[k] if k < len(sizes) else -1, len(a[k]) if k < len(a) else -1, len(b[k]) if k < len(b) else -1))
-
-
 def test_device_members_are_the_models_bytes_and_the_cpu_cores(eng, corpus):
     for name, text, sizes, model, cpu in corpus:
-        members, off = eng.bgzf_deflate(text, block_off=offsets(sizes), level="small")
+        members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes), level="small")
         assert off[0] == 0 and len(off) == len(sizes) + 1 and int(off[-1]) == members.size, name
-        assert_members(members.tobytes(), model, sizes, name + ": the device against the model")
-        assert_members(members.tobytes(), cpu, sizes, name + ": the device against the CPU build")
-        assert off.tolist() == offsets([len(m) for m in dc.split_members(model)]).tolist(), name
+        dc.assert_members(members.tobytes(), model, sizes, name + ": the device against the model")
+        dc.assert_members(members.tobytes(), cpu, sizes, name + ": the device against the CPU build")
+        assert off.tolist() == dc.offsets([len(m) for m in dc.split_members(model)]).tolist(), name
 
 
 def test_size_of_the_device_members_against_zlib_and_the_fast_level(eng, corpus):
     """the cap of tests/test_deflate_small_cpu.py on what the device wrote: VCF, CVG and batchfile text at most 1.15 times zlib's
     level 6, every entry at most the fast level's members plus 4 bytes a block"""
     for name, text, sizes, _, _ in corpus[:-1]:
-        off = offsets(sizes)
+        off = dc.offsets(sizes)
         small, _ = eng.bgzf_deflate(text, block_off=off, level="small")
         fast, _ = eng.bgzf_deflate(text, block_off=off, level="fast")
         l6 = sum(dc.zlib_member_bytes(b, 6) for b in dc.blocks_of(text, sizes))
@@ -99,15 +83,15 @@ def test_edge_text_as_a_device_pointer_at_every_misalignment(eng, corpus):
         torch.cuda.synchronize()
         view = buf[k:]
         assert view.data_ptr() % 4 == k and view.numel() == sum(ss)
-        members, off = eng.bgzf_deflate(view, block_off=offsets(ss), level="small")
-        assert_members(members.tobytes(), model + (sm.member(rest) if rest else b""), ss, "a text %d bytes behind an aligned word" % k)
+        members, off = eng.bgzf_deflate(view, block_off=dc.offsets(ss), level="small")
+        dc.assert_members(members.tobytes(), model + (sm.member(rest) if rest else b""), ss, "a text %d bytes behind an aligned word" % k)
 
 
 def test_members_do_not_depend_on_the_staging_chunk(eng, corpus, monkeypatch):
     _, text, sizes, model, _ = corpus[-1]
     monkeypatch.setenv("BASEVAR_AMD_DEFLATE_CHUNK_BLOCKS", "3")
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes), level="small")
-    assert_members(members.tobytes(), model, sizes, "three blocks a staging chunk")
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes), level="small")
+    dc.assert_members(members.tobytes(), model, sizes, "three blocks a staging chunk")
     assert int(off[-1]) == len(model)
 
 
@@ -119,9 +103,9 @@ def test_1025_small_blocks_in_one_call(eng, corpus, monkeypatch):
     assert len(pool) > 300 and {m[18] >> 1 & 3 for _, m in pool} == {0, 1, 2}
     picked = [pool[(k * 37 + k // len(pool)) % len(pool)] for k in range(1025)]
     blocks, expect = [b for b, _ in picked], [m for _, m in picked]
-    members, off = eng.bgzf_deflate(b"".join(blocks), block_off=offsets([len(b) for b in blocks]), level="small")
-    assert off.tolist() == offsets([len(m) for m in expect]).tolist()
-    assert_members(members.tobytes(), b"".join(expect), [len(b) for b in blocks], "1025 small blocks")
+    members, off = eng.bgzf_deflate(b"".join(blocks), block_off=dc.offsets([len(b) for b in blocks]), level="small")
+    assert off.tolist() == dc.offsets([len(m) for m in expect]).tolist()
+    dc.assert_members(members.tobytes(), b"".join(expect), [len(b) for b in blocks], "1025 small blocks")
 
 
 def raw_call(eng, text, off, level, entry="bv_engine_bgzf_deflate_level"):
@@ -169,7 +153,7 @@ def test_the_file_reads_back_with_gzip_and_with_the_device_inflate(eng, corpus, 
     from basevar_amd import _capi
     text = b"".join(t for _, t, _, _, _ in corpus)
     sizes = [s for _, _, ss, _, _ in corpus for s in ss]
-    members, off = eng.bgzf_deflate(text, block_off=offsets(sizes), level="small")
+    members, off = eng.bgzf_deflate(text, block_off=dc.offsets(sizes), level="small")
     path = tmp_path / "out.gz"
     path.write_bytes(members.tobytes() + dc.EOF_MARKER)
     with gzip.open(path, "rb") as fh:
