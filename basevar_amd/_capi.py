@@ -80,6 +80,11 @@ class BgzfCursor(C.Structure):  # bv_bgzf_cursor
     _fields_ = [("member", C.c_uint32), ("offset", C.c_uint32)]
 
 
+class VcfLines(C.Structure):  # bv_vcf_lines (include/basevar_amd_vcf.h)
+    _fields_ = [("slab", C.POINTER(Slab)), ("site", C.c_void_p), ("head", C.c_void_p), ("head_off", C.c_void_p), ("gt", C.c_void_p),
+                ("n_lines", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 BV_ERR_DATA = -6  # include/basevar_amd_bgzf.h
 BV_BGZF_OK, BV_BGZF_BAD_HEADER, BV_BGZF_BAD_DEFLATE, BV_BGZF_BAD_SIZE, BV_BGZF_BAD_CRC = 0, 1, 2, 3, 4
 BV_DEFLATE_FAST, BV_DEFLATE_SMALL = 0, 1
@@ -103,10 +108,13 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_engine_kernel_ms", "bv_engine_timing_reset", "bv_engine_timing_get", "bv_engine_timing_get_ex",
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
            "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form",
-           "bv_engine_text_parse", "bv_engine_text_submit", "bv_engine_deflate_code_lengths"]
+           "bv_engine_text_parse", "bv_engine_text_submit", "bv_engine_deflate_code_lengths", "bv_vcf_tile_samples"]
 
 # every symbol include/basevar_amd_bgzf.h declares
 BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch", "bv_engine_bgzf_deflate", "bv_engine_bgzf_deflate_level"]
+
+# every symbol include/basevar_amd_vcf.h declares
+VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_deflate"]
 
 _lib = None
 
@@ -214,5 +222,13 @@ def load():
                                                C.c_void_p]
     L.bv_engine_deflate_code_lengths.restype = C.c_int
     L.bv_engine_deflate_code_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
+    L.bv_vcf_tile_samples.restype = C.c_uint32
+    L.bv_vcf_tile_samples.argtypes = []
+    L.bv_engine_vcf_format.restype = C.c_int
+    L.bv_engine_vcf_format.argtypes = [C.c_void_p, C.POINTER(VcfLines), C.c_void_p, C.c_void_p]
+    L.bv_engine_vcf_fetch.restype = C.c_int
+    L.bv_engine_vcf_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.bv_engine_vcf_deflate.restype = C.c_int
+    L.bv_engine_vcf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     _lib = L
     return L

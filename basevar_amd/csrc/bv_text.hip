@@ -393,6 +393,8 @@ struct BvTextState {
     size_t planes_bytes = 0;
     uint8_t *d_sub = nullptr;               // the submitted slab: bs, q, mq [cap][pitch], rp [cap][pitch] u16, ref [cap]
     size_t sub_bytes = 0;
+    uint32_t sub_rows = 0, sub_samples = 0; // rows of the last submit that stand in d_sub (bv_text_kept_rows); 0: none
+    uint64_t sub_pitch = 0;
     uint8_t *d_aux = nullptr;               // depth, pstate, pmax [n_pos] u32, rowflag [n_rows], row_off [n_rows + 1], foff/fsamp
     size_t aux_bytes = 0;
     uint8_t *d_misc = nullptr;              // submit: src [n] i32, host rows, records
@@ -419,6 +421,14 @@ struct BvTextState {
     uint8_t *d_fetch = nullptr;             // rows_fetch: pos_state [n_pos], len u32 [n_rows], off u64 [n_rows + 1], the bytes
     size_t fetch_bytes = 0;
 };
+
+bool bv_text_kept_rows(const BvTextState *t, BvKeptRows *rows) {
+    if (!t || !t->sub_rows) return false;
+    rows->cell = t->d_sub;
+    rows->phred = t->d_sub + (size_t)t->sub_rows * t->sub_pitch;
+    rows->pitch = t->sub_pitch; rows->n_rows = t->sub_rows; rows->n_samples = t->sub_samples;
+    return true;
+}
 
 void bv_text_state_free(BvTextState *t) {
     if (!t) return;
@@ -644,6 +654,7 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     if (n_out && t->n_groups && !gout) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_submit: n_groups > 0 needs gout");
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     t->parsed = false;  // one submit per parse, whatever happens below
+    t->sub_rows = 0;
     if (n_out == 0) return BV_OK;
     BV_HIP(e, hipSetDevice(t->device));
     const uint64_t HP = n_host ? host_rows->pitch : 0;
@@ -707,6 +718,7 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     if (cell) BV_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
     if (phred) BV_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
     BV_HIP(e, hipStreamSynchronize(st));
+    t->sub_rows = n_out; t->sub_samples = N; t->sub_pitch = P;  // (d_sub stands until the next submit, whatever is parsed meanwhile)
     return BV_OK;
 }
 

@@ -577,6 +577,66 @@ class BaseTypeEngine:
             raise RuntimeError("bv_engine_bgzf_deflate_level failed (%d): %s" % (rc, self._err()), rc)
         return members[:int(member_off[n])], member_off
 
+    # ---- VCF sample columns, written on the device (include/basevar_amd_vcf.h)
+    def vcf_format(self, site, heads, gt, slab=None):
+        """The VCF lines of rows `site` (bv_engine_vcf_format): line k is heads[k] (bytes: the record through "GT:AB:SO:BP"), one
+        GT:AB:SO:BP column per sample of row site[k], and a line break.  `gt`: uint8 [n_lines][4], per line and base A, C, G, T
+        the character b"0" (REF), b"." or b"1" .. b"4" (the ALT's number).  `slab`: a _capi.Slab in host or device memory whose
+        base_strand and qual planes are read, or None for the rows kept by this engine's last lrt_text / lrt_bgzf, in record
+        order.  The text stays on the device (vcf_fetch, vcf_deflate); returns line_off uint64 [n_lines + 1]."""
+        site = np.ascontiguousarray(site, dtype=np.uint32)
+        n = int(site.size)
+        if len(heads) != n:
+            raise ValueError("vcf_format: one head per line")
+        head = np.frombuffer(b"".join(bytes(h) for h in heads), dtype=np.uint8)
+        head_off = np.zeros(n + 1, dtype=np.uint64)
+        head_off[1:] = np.cumsum([len(h) for h in heads])
+        gt = np.ascontiguousarray(gt, dtype=np.uint8).reshape(n, 4)
+        lines = _capi.VcfLines(C.pointer(slab) if slab is not None else None, site.ctypes.data, head.ctypes.data if head.size else None,
+                               head_off.ctypes.data, gt.ctypes.data, n, 0)
+        line_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_vcf_format(self._h, C.byref(lines), line_off.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_vcf_format failed (%d): %s" % (rc, self._err()), rc)
+        self._vcf_bytes = int(line_off[n])
+        return line_off
+
+    def vcf_fetch(self, dst_ptr=0, dst_capacity=0):
+        """The text of the last vcf_format (bv_engine_vcf_fetch) as a uint8 array; with `dst_ptr`, a device pointer of
+        `dst_capacity` bytes, it is copied there instead and None is returned."""
+        if dst_ptr:
+            rc = self._lib.bv_engine_vcf_fetch(self._h, int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, None)
+            text = None
+        else:
+            text = np.zeros(getattr(self, "_vcf_bytes", 0), dtype=np.uint8)
+            rc = self._lib.bv_engine_vcf_fetch(self._h, text.ctypes.data if text.size else None, int(text.size), _capi.BV_MEM_HOST, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_vcf_fetch failed (%d): %s" % (rc, self._err()), rc)
+        return text
+
+    def vcf_deflate(self, block_bytes=0xff00, block_off=None, level="fast"):
+        """bgzf_deflate of the last vcf_format's text, read where it lies on the device (bv_engine_vcf_deflate): (members,
+        member_off) as bgzf_deflate returns them, byte for byte what it returns for the fetched text."""
+        size = getattr(self, "_vcf_bytes", 0)
+        if block_off is None:
+            if not 1 <= int(block_bytes) <= 0xff00:
+                raise ValueError("vcf_deflate: block_bytes is 1 to 0xff00")
+            off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
+        else:
+            off = np.ascontiguousarray(block_off, dtype=np.uint64)
+        n = int(off.size) - 1
+        if n < 0:
+            raise ValueError("vcf_deflate: block_off needs n + 1 entries")
+        if level not in _capi.DEFLATE_LEVELS:
+            raise ValueError("vcf_deflate: level is 'fast' or 'small'")
+        members = np.zeros(size + 31 * n, dtype=np.uint8)
+        member_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_vcf_deflate(self._h, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level], members.ctypes.data if members.size else None,
+                                             int(members.size), member_off.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_vcf_deflate failed (%d): %s" % (rc, self._err()), rc)
+        return members[:int(member_off[n])], member_off
+
     def deflate_code_lengths(self, counts, limit):
         """The code lengths the small deflate level gives an alphabet with these counts (bv_engine_deflate_code_lengths, a
         diagnostic): (lengths uint8 [n], rounds of halving)."""

@@ -23,7 +23,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/basevar_amd_bgzf.h"
+#include "../../include/basevar_amd_vcf.h"
 #include "vcf_emit.hpp"  // SiteText
 
 namespace bvamd {
@@ -309,7 +309,8 @@ public:
         std::exception_ptr error;
     };
     template <class HostReader>
-    TextBatch lrt_text(const bv_text_rows &rows, HostReader &&read_host, const uint8_t *group_id = nullptr, uint32_t n_groups = 0) {
+    TextBatch lrt_text(const bv_text_rows &rows, HostReader &&read_host, const uint8_t *group_id = nullptr, uint32_t n_groups = 0,
+                       bool keep_planes = true) {
         TextBatch tb;
         const size_t F = rows.n_files;
         tb.row_state.resize((size_t)rows.n_positions * F);
@@ -321,7 +322,8 @@ public:
             const uint64_t a = rows.row_off[p * F + f], b = rows.row_off[p * F + f + 1];
             return std::string(rows.text + a, (size_t)(b - a - 1));
         };
-        finish_text(tb, rows.n_positions, F, N, row_text, [&](size_t p, size_t f) { return rows.text + rows.row_off[p * F + f]; }, read_host, n_groups);
+        finish_text(tb, rows.n_positions, F, N, row_text, [&](size_t p, size_t f) { return rows.text + rows.row_off[p * F + f]; }, read_host, n_groups,
+                    keep_planes);
         return tb;
     }
 
@@ -332,6 +334,31 @@ public:
     void bgzf_deflate(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off,
                       int level = BV_DEFLATE_FAST) {
         if (bv_engine_bgzf_deflate_level(e_, text, text_bytes, BV_MEM_HOST, block_off, n_blocks, level, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+    }
+
+    // The VCF lines of records, their sample columns written on the device (include/basevar_amd_vcf.h): line k is heads[k] -- the
+    // record through "GT:AB:SO:BP", vcf_emit.hpp's format_vcf_head -- then one column per sample of row site[k] of `slab`, or,
+    // with slab == nullptr, of record site[k] of this engine's last lrt_text / finish_bgzf; gt[4 k ..] are vcf_gt_codes' four
+    // characters.  The text stays on the device; returns line_off [n + 1].  vcf_fetch() copies it to the host; vcf_deflate()
+    // is bgzf_deflate() over it where it lies: block k is text[block_off[k] .. block_off[k + 1]), `dst` has room for
+    // line_off[n] + 31 * n_blocks bytes.
+    std::vector<uint64_t> vcf_format(const std::vector<uint32_t> &site, const std::vector<std::string> &heads, const std::vector<uint8_t> &gt,
+                                     const bv_slab *slab = nullptr) {
+        const size_t n = site.size();
+        if (heads.size() != n || gt.size() != 4 * n) throw std::runtime_error("[ERROR] vcf_format: one head and four gt characters per line");
+        std::string head;
+        std::vector<uint64_t> head_off(n + 1, 0), line_off(n + 1, 0);
+        for (size_t k = 0; k < n; ++k) { head += heads[k]; head_off[k + 1] = head.size(); }
+        const bv_vcf_lines lines{slab, site.data(), head.data(), head_off.data(), gt.data(), (uint32_t)n, 0};
+        if (bv_engine_vcf_format(e_, &lines, line_off.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return line_off;
+    }
+    void vcf_fetch(char *dst, uint64_t bytes) {
+        if (bv_engine_vcf_fetch(e_, dst, bytes, BV_MEM_HOST, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+    }
+    void vcf_deflate(uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off, int level = BV_DEFLATE_FAST) {
+        if (bv_engine_vcf_deflate(e_, block_off, n_blocks, level, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
             throw std::runtime_error(bv_last_error(e_));
     }
 
@@ -358,7 +385,8 @@ public:
         return bp;
     }
     template <class HostReader>
-    TextBatch finish_bgzf(BgzfParse &bp, const uint32_t *file_samples, size_t F, HostReader &&read_host, uint32_t n_groups = 0) {
+    TextBatch finish_bgzf(BgzfParse &bp, const uint32_t *file_samples, size_t F, HostReader &&read_host, uint32_t n_groups = 0,
+                          bool keep_planes = true) {
         TextBatch tb;
         tb.row_state.swap(bp.row_state);
         uint32_t N = 0;
@@ -373,15 +401,17 @@ public:
         const char *text = reinterpret_cast<const char *>(buf.data());
         finish_text(tb, bp.n_positions, F, N,
                     [&](size_t p, size_t f) { return std::string(text + off[p * F + f], (size_t)(off[p * F + f + 1] - off[p * F + f])); },
-                    [&](size_t p, size_t f) { return text + off[p * F + f]; }, read_host, n_groups);
+                    [&](size_t p, size_t f) { return text + off[p * F + f]; }, read_host, n_groups, keep_planes);
         return tb;
     }
 
     // The host's part of a parsed batch and its submit (shared by lrt_text and lrt_bgzf): row_text(p, f) is a row without its
     // line break (whole for the positions left to the host, through its fourth tab at least for file 0's row of any other),
-    // row_ptr(p, f) the first byte of a whole row flagged BV_TEXT_INDEL.
+    // row_ptr(p, f) the first byte of a whole row flagged BV_TEXT_INDEL.  keep_planes = false: the records' cell / phred rows are
+    // not copied back (tb.cell / tb.phred stay empty); they stand on the device for vcf_format().
     template <class RowText, class RowPtr, class HostReader>
-    void finish_text(TextBatch &tb, uint32_t P, size_t F, uint32_t N, RowText &&row_text, RowPtr &&row_ptr, HostReader &&read_host, uint32_t n_groups) {
+    void finish_text(TextBatch &tb, uint32_t P, size_t F, uint32_t N, RowText &&row_text, RowPtr &&row_ptr, HostReader &&read_host, uint32_t n_groups,
+                     bool keep_planes = true) {
         SlabBuilder host(N);
         std::vector<std::string> lines(F);
         uint32_t used = 0;
@@ -423,11 +453,14 @@ public:
         tb.batch.sites.resize(R);
         tb.batch.n_groups = n_groups;
         tb.batch.groups.resize(R * n_groups);
-        tb.cell.resize(R * N);
-        tb.phred.resize(R * N);
+        if (keep_planes) {
+            tb.cell.resize(R * N);
+            tb.phred.resize(R * N);
+        }
         const bv_slab hs = host.slab();
         if (bv_engine_text_submit(e_, tb.row_state.data(), hs.n_sites ? &hs : nullptr, used, tb.batch.sites.data(),
-                                  n_groups ? tb.batch.groups.data() : nullptr, tb.cell.data(), tb.phred.data(), nullptr) != BV_OK)
+                                  n_groups ? tb.batch.groups.data() : nullptr, keep_planes ? tb.cell.data() : nullptr,
+                                  keep_planes ? tb.phred.data() : nullptr, nullptr) != BV_OK)
             throw std::runtime_error(bv_last_error(e_));
         if (R && bv_engine_wait(e_) != BV_OK) throw std::runtime_error(bv_last_error(e_));
     }

@@ -96,6 +96,22 @@ public:
         block_off_ += moff[full];
         buf_.assign(p + (bytes - carry), p + n);
     }
+    // Whole members made elsewhere, appended as they are: what is pending is flushed first as a (short) member of its own.
+    // Member k is members[member_off[k] .. member_off[k + 1]); each is held to the format first.  Returns the file offset of
+    // the first of them.
+    uint64_t write_members(const uint8_t *members, const uint64_t *member_off, size_t n_members) {
+        flush();
+        for (size_t k = 0; k < n_members; ++k) {
+            const uint64_t a = member_off[k], b = member_off[k + 1];
+            if (b < a + 26 || b - a > 0x10000 || members[a] != 0x1f || members[a + 1] != 0x8b ||
+                (uint64_t)(members[a + 16] | (members[a + 17] << 8)) + 1 != b - a)
+                throw std::runtime_error("[ERROR] the block deflater returned something that is not a BGZF member");
+        }
+        const uint64_t base = block_off_, bytes = n_members ? member_off[n_members] - member_off[0] : 0;
+        if (bytes && std::fwrite(members + member_off[0], 1, bytes, f_) != bytes) throw std::runtime_error("[ERROR] write failure on " + path_);
+        block_off_ += bytes;
+        return base;
+    }
     size_t pending() const { return buf_.size(); }
     // end the current block here (a reader can then start at tell() without inflating what came before)
     void flush() { if (!buf_.empty()) flush_block(); }
@@ -304,6 +320,23 @@ public:
             }
             p = e;
         }
+    }
+    // The third way: whole lines that arrive as finished BGZF members -- their text cut into blocks of kBlock bytes counted
+    // from its first byte, the last block may be short (bv_engine_vcf_deflate) -- with line j = text[line_off[j] ..
+    // line_off[j + 1]) and its first two columns in keys[j].  The pending partial block is flushed as a member of its own, the
+    // members follow as they are, and every line is indexed: byte a of the text is block a / kBlock, offset a % kBlock.  The
+    // member cuts so differ from write_lines()'s; the inflated file does not.  Compressed outputs only.
+    void write_members(const uint8_t *members, const uint64_t *member_off, size_t n_members, const uint64_t *line_off,
+                       const std::vector<std::pair<std::string, int64_t>> &keys) {
+        if (!gz_) throw std::runtime_error("[ERROR] write_members: " + path_ + " is not a compressed output");
+        const size_t n_lines = keys.size();
+        if (n_lines == 0) return;
+        const uint64_t total = line_off[n_lines];
+        if ((total + BgzfWriter::kBlock - 1) / BgzfWriter::kBlock != n_members)
+            throw std::runtime_error("[ERROR] write_members: the members are not the text's blocks of 0xff00 bytes");
+        const uint64_t base = bg_.write_members(members, member_off, n_members);
+        auto voff = [&](uint64_t at) { return ((base + member_off[at / BgzfWriter::kBlock] - member_off[0]) << 16) | (uint64_t)(at % BgzfWriter::kBlock); };
+        for (size_t j = 0; j < n_lines; ++j) idx_.add_line(keys[j].first, keys[j].second, voff(line_off[j]), voff(line_off[j + 1]));
     }
     void close() {
         if (gz_) {

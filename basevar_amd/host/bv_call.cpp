@@ -13,7 +13,7 @@
 //
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
-//           [--timing FILE.json] [--inflate device|host] [--deflate device|host] [--deflate-level fast|small]
+//           [--timing FILE.json] [--inflate device|host] [--deflate device|host] [--deflate-level fast|small] [--emit device|host]
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -64,6 +64,14 @@ struct Batch {
     std::vector<uint64_t> row_off;
     uint32_t n_positions = 0;
     std::vector<uint8_t> cell, phred;
+    // --emit device: the VCF lines of the batch's variant records were written on the worker's engine (bv_engine_vcf_format).
+    // line j is text[vcf_line_off[j] .. vcf_line_off[j + 1]) and belongs to record vcf_record[j]; the text comes as BGZF members
+    // of 0xff00 bytes counted from its first byte (a *.vcf.gz output) or as it is (a plain one)
+    bool emit_device = false;
+    std::vector<uint32_t> vcf_record;
+    std::vector<uint64_t> vcf_line_off, vcf_member_off;
+    std::vector<uint8_t> vcf_members;
+    std::string vcf_text;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -134,7 +142,7 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 int main(int argc, char **argv) {
     std::vector<std::string> batchfiles, bams;
     std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host", deflate_arg = "host",
-                deflate_level_arg = "fast";
+                deflate_level_arg = "fast", emit_arg = "host";
     int mapq_thd = 10, threads = 4, n_gpus = 1;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -153,6 +161,7 @@ int main(int argc, char **argv) {
         else if (a == "--inflate") inflate_arg = next();
         else if (a == "--deflate") deflate_arg = next();
         else if (a == "--deflate-level") deflate_level_arg = next();
+        else if (a == "--emit") emit_arg = next();
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--gpus") n_gpus = std::stoi(next());
         else if (a == "--devices") devices_arg = next();
@@ -183,6 +192,7 @@ int main(int argc, char **argv) {
     if (inflate_arg != "host" && inflate_arg != "device") die("[ERROR] --inflate wants device or host");
     if (deflate_arg != "host" && deflate_arg != "device") die("[ERROR] --deflate wants device or host");
     if (deflate_level_arg != "fast" && deflate_level_arg != "small") die("[ERROR] --deflate-level wants fast or small");
+    if (emit_arg != "host" && emit_arg != "device") die("[ERROR] --emit wants device or host");
     // (the host path is zlib at its own level: the device encoder's levels do not apply to it)
     if (deflate_level_arg != "fast" && deflate_arg != "device") die("[ERROR] --deflate-level small needs --deflate device");
     const int deflate_level = deflate_level_arg == "small" ? BV_DEFLATE_SMALL : BV_DEFLATE_FAST;
@@ -277,6 +287,16 @@ int main(int argc, char **argv) {
     }
     uint64_t members_deflated = 0;
     double deflate_s = 0;
+    // --emit device: the sample columns of the VCF lines are written by the engine that called the batch, from the rows its text
+    // submit left on the device (bv_engine_vcf_format), and a *.vcf.gz is deflated there too (bv_engine_vcf_deflate, at
+    // --deflate-level): the planes do not come back and the text does not go up.  Batches of batchfile rows only.
+    bool emit_device = emit_arg == "device";
+    if (emit_device && from_bam) {
+        std::cerr << "[NOTE] --emit device applies to batchfile rows parsed on the device, not to BAM input: the host path is taken" << std::endl;
+        emit_device = false;
+    }
+    const bool vcf_gz = ends_in_gz(out_vcf);
+    uint64_t vcf_lines_device = 0;
 
     // ---- batches are bounded by cells (2^28 cells = 5 x 256 MiB of planes per batch in flight), not by a site count that
     // ignores the row length: a launch carries ~0.1 ms of fill and drain whatever its size, so small batches run the engine
@@ -342,6 +362,37 @@ int main(int argc, char **argv) {
             auto host_reader = [](const std::vector<std::string> &r, size_t n, bvamd::SlabBuilder &sb, bvamd::SiteText &st) {
                 return bvamd::parse_site_rows_fast(r, n, sb, st);
             };
+            // --emit device: heads and gt of the batch's variant records, the lines on this worker's engine, then members or text
+            auto emit_on_device = [&](Batch &b) {
+                b.emit_device = true;
+                std::vector<std::string> heads;
+                std::vector<uint8_t> gt;
+                for (size_t i = 0; i < b.text.size(); ++i) {
+                    if (!b.result.has_variant(i)) continue;
+                    std::string head = bvamd::format_vcf_head(b.text[i], b.result.sites[i], group_names.empty() ? nullptr : &b.result.group(i, 0), group_names);
+                    if (head.empty()) continue;  // (no ALT: format_vcf_line writes nothing)
+                    uint8_t g[4];
+                    bvamd::vcf_gt_codes(b.text[i], b.result.sites[i], g);
+                    b.vcf_record.push_back((uint32_t)i);
+                    heads.push_back(std::move(head));
+                    gt.insert(gt.end(), g, g + 4);
+                }
+                b.vcf_line_off = engine->vcf_format(b.vcf_record, heads, gt);
+                const uint64_t total = b.vcf_line_off.back();
+                if (total == 0) return;
+                if (vcf_gz) {
+                    const size_t nb = (size_t)((total + bvamd::BgzfWriter::kBlock - 1) / bvamd::BgzfWriter::kBlock);
+                    std::vector<uint64_t> block_off(nb + 1);
+                    for (size_t k = 0; k <= nb; ++k) block_off[k] = std::min<uint64_t>(total, (uint64_t)k * bvamd::BgzfWriter::kBlock);
+                    b.vcf_members.resize(total + 31 * nb);
+                    b.vcf_member_off.assign(nb + 1, 0);
+                    engine->vcf_deflate(total, block_off.data(), (uint32_t)nb, b.vcf_members.data(), b.vcf_member_off.data(), deflate_level);
+                    b.vcf_members.resize(b.vcf_member_off[nb]);
+                } else {
+                    b.vcf_text.resize(total);
+                    engine->vcf_fetch(&b.vcf_text[0], total);
+                }
+            };
             while (device_inflate && engine) {
                 BatchPtr b;
                 bvamd::BaseTypeEngine::BgzfParse bp;
@@ -391,15 +442,16 @@ int main(int argc, char **argv) {
                 if (b->error.empty()) {
                     const double t0 = StageClock::now();
                     try {
-                        auto tb = engine->finish_bgzf(bp, file_samples.data(), file_samples.size(), host_reader, (uint32_t)group_names.size());
+                        auto tb = engine->finish_bgzf(bp, file_samples.data(), file_samples.size(), host_reader, (uint32_t)group_names.size(), !emit_device);
                         b->result = std::move(tb.batch);
                         b->text = std::move(tb.text);
                         b->cell = std::move(tb.cell);
                         b->phred = std::move(tb.phred);
+                        if (emit_device) emit_on_device(*b);
                         if (tb.error) {
                             try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b->error = ex.what(); }
                         }
-                    } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); }
+                    } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); b->emit_device = false; }
                     const double dt = StageClock::now() - t0;
                     std::lock_guard<std::mutex> lk(err_mu);
                     clk.engine += dt;
@@ -414,15 +466,17 @@ int main(int argc, char **argv) {
                         try {
                             const bv_text_rows rows{b->rows.data(), b->row_off.data(), file_samples.data(), b->rows.size(), b->n_positions,
                                                     (uint32_t)file_samples.size(), 0};
-                            auto tb = engine->lrt_text(rows, host_reader, group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size());
+                            auto tb = engine->lrt_text(rows, host_reader, group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size(),
+                                                       !emit_device);
                             b->result = std::move(tb.batch);
                             b->text = std::move(tb.text);
                             b->cell = std::move(tb.cell);
                             b->phred = std::move(tb.phred);
+                            if (emit_device) emit_on_device(*b);
                             if (tb.error) {
                                 try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b->error = ex.what(); }
                             }
-                        } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); }
+                        } catch (const std::exception &ex) { b->error = ex.what(); b->text.clear(); b->emit_device = false; }
                         std::string().swap(b->rows);
                     } else {
                         // (the producer's choice of layout: short reads -> the rank words carry the calls, basetype_gpu.hpp)
@@ -470,6 +524,7 @@ int main(int argc, char **argv) {
                     parallel_ranges(d.text.size(), threads, [&](size_t t, size_t lo, size_t hi) {
                         for (size_t i = lo; i < hi; ++i) {
                             cvg_txt[t] += bvamd::format_cvg_line(d.text[i], d.result.sites[i]);
+                            if (d.emit_device) continue;  // (the VCF lines are there already)
                             if (d.result.has_variant(i)) {
                                 vcf_txt[t] += bvamd::format_vcf_line(d.text[i], d.cell_row(i, n_sample), d.phred_row(i, n_sample), n_sample, d.result.sites[i],
                                                                      group_names.empty() ? nullptr : &d.result.group(i, 0), group_names);
@@ -478,7 +533,23 @@ int main(int argc, char **argv) {
                         }
                     });
                     try {
-                        if (device_deflate) {
+                        if (d.emit_device) {
+                            // the CVG lines as ever, the VCF lines as the worker's engine left them
+                            for (size_t t = 1; t < nt; ++t) { cvg_txt[0] += cvg_txt[t]; std::string().swap(cvg_txt[t]); }
+                            if (device_deflate) CVG.write_lines(cvg_txt[0], deflate);
+                            else CVG.write_lines(cvg_txt[0]);
+                            std::string().swap(cvg_txt[0]);
+                            if (vcf_gz) {
+                                std::vector<std::pair<std::string, int64_t>> keys;
+                                for (uint32_t i : d.vcf_record) keys.emplace_back(d.text[i].ref_id, (int64_t)d.text[i].ref_pos);
+                                VCF.write_members(d.vcf_members.data(), d.vcf_member_off.data(), d.vcf_member_off.empty() ? 0 : d.vcf_member_off.size() - 1,
+                                                  d.vcf_line_off.data(), keys);
+                            } else {
+                                VCF.write_lines(d.vcf_text);
+                            }
+                            for (size_t i = 0; i < d.text.size(); ++i) nv[0] += d.result.has_variant(i) ? 1 : 0;
+                            vcf_lines_device += d.vcf_record.size();
+                        } else if (device_deflate) {
                             // one call a file and batch: a call takes as long as its slowest block, however few blocks it has
                             for (size_t t = 1; t < nt; ++t) {
                                 cvg_txt[0] += cvg_txt[t]; std::string().swap(cvg_txt[t]);
@@ -488,7 +559,7 @@ int main(int argc, char **argv) {
                             VCF.write_lines(vcf_txt[0], deflate);
                         }
                         for (size_t t = 0; t < nt; ++t) {
-                            if (!device_deflate) {
+                            if (!device_deflate && !d.emit_device) {
                                 CVG.write_lines(cvg_txt[t]);
                                 VCF.write_lines(vcf_txt[t]);
                             }
@@ -614,6 +685,8 @@ int main(int argc, char **argv) {
             tf << ", \"inflate\": \"device\", \"members_inflated\": " << raw.members_handed << ", \"members_in_files\": " << raw.members_passed;
         // --deflate device: whole output blocks compressed by the device, and the emitter's seconds inside those calls (part of emit_s)
         if (device_deflate) tf << ", \"deflate\": \"device\", \"deflate_level\": \"" << deflate_level_arg << "\", \"members_deflated\": " << members_deflated << ", \"deflate_s\": " << deflate_s;
+        // --emit device: VCF lines whose sample columns the engines wrote (all of them, on batchfile input)
+        if (emit_device) tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << vcf_lines_device;
         tf << "}\n";
     }
     return 0;

@@ -133,26 +133,23 @@ inline void append_info(std::string &s, const bv_site_result &r) {
     }
 }
 
-// One VCF record (the columns of _out_vcf_line, caller.cpp:1103-1209) from the site's slab row: `cell` / `phred` are the n
-// per-sample bytes of the base_strand and qual planes (include/basevar_amd.h).  `groups`/`group_names`: the site's
-// bv_group_result records and the group names in the reference's iteration order (std::map: sorted by name); may be empty.
-inline std::string format_vcf_line(const SiteText &st, const uint8_t *cell, const uint8_t *phred, size_t n, const bv_site_result &r,
-                                   const bv_group_result *groups, const std::vector<std::string> &group_names) {
-    if (r.n_alt == 0) return "";  // caller.cpp:745
-    // FORMAT GT by base: "0/." for the reference base, "./k" for the k-th ALT, "./." for any other call (caller.cpp:1116, 1136-1143)
+// FORMAT GT by base, one character for each of A, C, G, T: '0' the reference base ("0/."), '1' + k the k-th ALT ("./1" ...),
+// '.' any other call ("./.") (caller.cpp:1116, 1136-1143).  What bv_vcf_lines.gt takes (include/basevar_amd_vcf.h).
+inline void vcf_gt_codes(const SiteText &st, const bv_site_result &r, uint8_t out[4]) {
     const char upper_ref = (char)std::toupper((unsigned char)st.ref_base[0]);
-    std::string gt_of[4];
-    for (int b = 0; b < 4; ++b) gt_of[b] = EMIT_BASES[b] == upper_ref ? "0/." : "./.";
+    for (int b = 0; b < 4; ++b) out[b] = EMIT_BASES[b] == upper_ref ? '0' : '.';
     for (int i = 0; i < r.n_alt; ++i)
-        if (EMIT_BASES[r.alt[i] & 3] != upper_ref) gt_of[r.alt[i] & 3] = "./" + std::to_string(i + 1);
-    // BP = std::to_string(1 - eps(q)) depends on the phred byte only: 256 strings, formed once (basetype.cpp:47-48)
-    static const std::vector<std::string> bp_text = [] {
-        std::vector<std::string> t(256);
-        for (int qv = 0; qv < 256; ++qv) append_f6(t[(size_t)qv], 1.0 - std::exp(qv * EMIT_MLN10TO10));
-        return t;
-    }();
+        if (EMIT_BASES[r.alt[i] & 3] != upper_ref) out[r.alt[i] & 3] = (uint8_t)('1' + i);
+}
+
+// One VCF record through its FORMAT column, "...\tGT:AB:SO:BP" (the columns of _out_vcf_line, caller.cpp:1103-1209): what of a
+// line does not depend on the samples' cells.  `groups`/`group_names`: the site's bv_group_result records and the group names
+// in the reference's iteration order (std::map: sorted by name); may be empty.  Empty string when the reference writes nothing.
+inline std::string format_vcf_head(const SiteText &st, const bv_site_result &r, const bv_group_result *groups,
+                                   const std::vector<std::string> &group_names, size_t reserve_behind = 0) {
+    if (r.n_alt == 0) return "";  // caller.cpp:745
     std::string s = st.ref_id;
-    s.reserve(128 + n * 18);
+    s.reserve(128 + reserve_behind);
     s += '\t'; s += std::to_string(st.ref_pos);
     s += "\t.\t"; s += st.ref_base;
     s += '\t';
@@ -168,6 +165,25 @@ inline std::string format_vcf_line(const SiteText &st, const uint8_t *cell, cons
         }
     }
     s += "\tGT:AB:SO:BP";
+    return s;
+}
+
+// One VCF record: the head, then the samples' columns from the site's slab row: `cell` / `phred` are the n per-sample bytes of
+// the base_strand and qual planes (include/basevar_amd.h).
+inline std::string format_vcf_line(const SiteText &st, const uint8_t *cell, const uint8_t *phred, size_t n, const bv_site_result &r,
+                                   const bv_group_result *groups, const std::vector<std::string> &group_names) {
+    if (r.n_alt == 0) return "";  // caller.cpp:745
+    uint8_t gt[4];
+    vcf_gt_codes(st, r, gt);
+    std::string gt_of[4];
+    for (int b = 0; b < 4; ++b) gt_of[b] = gt[b] == '0' ? std::string("0/.") : std::string("./") + (char)gt[b];
+    // BP = std::to_string(1 - eps(q)) depends on the phred byte only: 256 strings, formed once (basetype.cpp:47-48)
+    static const std::vector<std::string> bp_text = [] {
+        std::vector<std::string> t(256);
+        for (int qv = 0; qv < 256; ++qv) append_f6(t[(size_t)qv], 1.0 - std::exp(qv * EMIT_MLN10TO10));
+        return t;
+    }();
+    std::string s = format_vcf_head(st, r, groups, group_names, n * 18);
     // per-sample GT:AB:SO:BP (caller.cpp:1125-1145), appended directly: a VCF line is n_samples fields, and at 10^4 samples the
     // emitter, not the engine, sets the pace of a run (profiles/r3_host_pipeline.txt)
     for (size_t i = 0; i < n; ++i) {

@@ -91,6 +91,10 @@ int bv_engine_host_log_eval(bv_engine *e, const double *x, double *y, uint32_t n
 int bv_engine_deflate_code_lengths(bv_engine *e, const uint32_t *counts, uint32_t n_symbols, uint32_t limit, uint8_t *lengths_out,
                                    uint32_t *rounds_out, void *stream);
 
+/* ---- the tile of bv_engine_vcf_format (include/basevar_amd_vcf.h; tests) ---------
+ * Samples of a row that one wave of its kernels expands: the sizes at which its paths change are this, +- 1, and its 64-sample steps. */
+uint32_t bv_vcf_tile_samples(void);
+
 /* ---- measurement helper (bench only; not part of the reference surface) --------
  * Fill device planes with the synthetic pileup of SURVEY.md section 8(d) using a
  * counter-based RNG (stateless in (seed, site, sample)), so any rank can generate
