@@ -85,6 +85,22 @@ class VcfLines(C.Structure):  # bv_vcf_lines (include/basevar_amd_vcf.h)
                 ("n_lines", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class PileupReads(C.Structure):  # bv_pileup_reads (include/basevar_amd_pileup.h)
+    _fields_ = [("records", C.c_void_p), ("run_off", C.c_void_p), ("run_sample", C.c_void_p), ("pitch", C.c_uint64),
+                ("n_runs", C.c_uint32), ("n_samples", C.c_uint32), ("tid", C.c_int32), ("region_beg", C.c_uint32), ("region_end", C.c_uint32),
+                ("beg", C.c_uint32), ("end", C.c_uint32), ("mapq_thd", C.c_int32), ("mem_kind", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class PileupResult(C.Structure):  # bv_pileup_result
+    _fields_ = [("cell", C.c_void_p), ("qual", C.c_void_p), ("mapq", C.c_void_p), ("rank", C.c_void_p), ("depth", C.c_void_p), ("tokens", C.c_void_p),
+                ("text", C.c_void_p), ("cells_capacity", C.c_uint64), ("rows_capacity", C.c_uint64), ("tokens_capacity", C.c_uint64),
+                ("text_capacity", C.c_uint64), ("cells", C.c_uint64), ("rows", C.c_uint64), ("n_tokens", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("mem_kind", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+PILEUP_TOKEN_DTYPE = np.dtype([("pos", "<u4"), ("sample", "<u4"), ("text_off", "<u8"), ("text_len", "<u4"), ("reserved_", "<u4")])  # bv_pileup_token
+assert PILEUP_TOKEN_DTYPE.itemsize == 24
+
 BV_ERR_DATA = -6  # include/basevar_amd_bgzf.h
 BV_BGZF_OK, BV_BGZF_BAD_HEADER, BV_BGZF_BAD_DEFLATE, BV_BGZF_BAD_SIZE, BV_BGZF_BAD_CRC = 0, 1, 2, 3, 4
 BV_DEFLATE_FAST, BV_DEFLATE_SMALL = 0, 1
@@ -115,6 +131,9 @@ BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engin
 
 # every symbol include/basevar_amd_vcf.h declares
 VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_deflate"]
+
+# every symbol include/basevar_amd_pileup.h declares
+PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
 
 _lib = None
 
@@ -230,5 +249,17 @@ def load():
     L.bv_engine_vcf_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     L.bv_engine_vcf_deflate.restype = C.c_int
     L.bv_engine_vcf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.bv_pileup_max_rows.restype = C.c_uint32
+    L.bv_pileup_max_rows.argtypes = []
+    L.bv_engine_pileup_set_reference.restype = C.c_int
+    L.bv_engine_pileup_set_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.bv_engine_pileup.restype = C.c_int
+    L.bv_engine_pileup.argtypes = [C.c_void_p, C.POINTER(PileupReads), C.POINTER(C.c_uint32), C.c_void_p]
+    L.bv_engine_pileup_fetch.restype = C.c_int
+    L.bv_engine_pileup_fetch.argtypes = [C.c_void_p, C.POINTER(PileupResult), C.c_void_p]
+    L.bv_engine_pileup_rows.restype = C.c_int
+    L.bv_engine_pileup_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(Slab), C.c_void_p, C.c_void_p]
+    L.bv_engine_pileup_submit.restype = C.c_int
+    L.bv_engine_pileup_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L

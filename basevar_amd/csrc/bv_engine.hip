@@ -510,6 +510,7 @@ int bv_engine_destroy(bv_engine *e) {
     bv_bgzf_state_free(e->bgzf);
     bv_deflate_state_free(e->deflate);
     bv_vcf_state_free(e->vcf);
+    bv_pileup_state_free(e->pileup);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

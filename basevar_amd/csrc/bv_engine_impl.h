@@ -1,5 +1,5 @@
 // bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_rows.hip, bv_engine_tiles.hip,
-// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
+// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
 // files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
 #pragma once
 
@@ -19,6 +19,8 @@ struct BvDeflateState;  // bv_engine_bgzf_deflate (bv_deflate.hip)
 void bv_deflate_state_free(BvDeflateState *t);
 struct BvVcfState;      // bv_engine_vcf_format (bv_vcf.hip)
 void bv_vcf_state_free(BvVcfState *t);
+struct BvPileupState;   // bv_engine_pileup (bv_pileup.hip)
+void bv_pileup_state_free(BvPileupState *t);
 // The rows kept by the last bv_engine_text_submit, as they lie in device memory (bv_text.hip): false if there are none
 struct BvKeptRows {
     const uint8_t *cell = nullptr, *phred = nullptr;  // [n_rows][pitch]
@@ -147,6 +149,7 @@ struct bv_engine {
     BvBgzfState *bgzf = nullptr;       // created by the first bv_engine_bgzf_inflate
     BvDeflateState *deflate = nullptr;  // created by the first bv_engine_bgzf_deflate
     BvVcfState *vcf = nullptr;         // created by the first bv_engine_vcf_format
+    BvPileupState *pileup = nullptr;   // created by the first bv_engine_pileup_set_reference
     mutable std::mutex mu;
     std::string err;
 };
@@ -165,7 +168,7 @@ int fail(bv_engine *e, int code, const std::string &msg);
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// e->text, e->bgzf, e->deflate, e->vcf: each is created by the first call that needs it, on the engine's device
+// e->text, e->bgzf, e->deflate, e->vcf, e->pileup: each is created by the first call that needs it, on the engine's device
 template <class S>
 S *engine_state(bv_engine *e, S *&state) {
     if (!state) {

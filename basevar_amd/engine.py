@@ -637,6 +637,110 @@ class BaseTypeEngine:
             raise RuntimeError("bv_engine_vcf_deflate failed (%d): %s" % (rc, self._err()), rc)
         return members[:int(member_off[n])], member_off
 
+    # ---- BAM records, piled up on the device (include/basevar_amd_pileup.h)
+    def pileup_set_reference(self, seq):
+        """The contig's bases (str / bytes / uint8 array, letter case kept) for pileup and pileup_rows (bv_engine_pileup_set_reference)."""
+        if isinstance(seq, str):
+            seq = seq.encode()
+        buf = np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.ascontiguousarray(seq, np.uint8)
+        rc = self._lib.bv_engine_pileup_set_reference(self._h, buf.ctypes.data if buf.size else None, int(buf.size))
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_set_reference failed (%d): %s" % (rc, self._err()), rc)
+
+    def pileup(self, records, run_off, run_sample, n_samples, tid, region, window, mapq_thd, pitch=None, reserved=0):
+        """The samples' raw BAM records piled up into engine-owned planes (bv_engine_pileup); returns the number of covered rows.
+
+        `records`: bytes / uint8 array (host), a uint8 torch tensor on the engine's device, or an int device pointer; run r is
+        records[run_off[r]:run_off[r + 1]], whole records of sample run_sample[r] (non-decreasing), in file order.  `region`:
+        (region_beg, region_end), from where the 500 kb steps are laid out; `window`: (beg, end), 1-based inclusive, inside one step.
+        `pitch`: cells of a plane row, default n_samples rounded up to 16."""
+        keep = records
+        if isinstance(records, int):
+            kind, ptr = _capi.BV_MEM_DEVICE, records
+        elif hasattr(records, "data_ptr"):
+            if records.dtype.itemsize != 1 or not records.is_contiguous():
+                raise ValueError("pileup: a contiguous tensor of bytes")
+            kind, ptr = (_capi.BV_MEM_DEVICE if records.is_cuda else _capi.BV_MEM_HOST), int(records.data_ptr())
+        else:
+            keep = np.frombuffer(records, dtype=np.uint8) if isinstance(records, (bytes, bytearray)) else np.ascontiguousarray(records, np.uint8)
+            kind, ptr = _capi.BV_MEM_HOST, (keep.ctypes.data if keep.size else None)
+        off = np.ascontiguousarray(run_off, dtype=np.uint64)
+        samp = np.ascontiguousarray(run_sample, dtype=np.uint32)
+        n_runs = int(samp.size)
+        if n_runs and off.size != n_runs + 1:
+            raise ValueError("pileup: run_off needs n_runs + 1 entries")
+        pitch = (int(n_samples) + 15) // 16 * 16 if pitch is None else int(pitch)
+        reads = _capi.PileupReads(ptr or None, off.ctypes.data if n_runs else None, samp.ctypes.data if n_runs else None, pitch, n_runs, int(n_samples),
+                                  int(tid), int(region[0]), int(region[1]), int(window[0]), int(window[1]), int(mapq_thd), kind, int(reserved))
+        n_cov = C.c_uint32(0)
+        rc = self._lib.bv_engine_pileup(self._h, C.byref(reads), C.byref(n_cov), None)
+        del keep
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup failed (%d): %s" % (rc, self._err()), rc)
+        self._pileup_covered = int(n_cov.value)
+        return int(n_cov.value)
+
+    def pileup_fetch(self):
+        """The last pileup (bv_engine_pileup_fetch): dict of cell, qual, mapq uint8 [rows][pitch], rank uint16 [rows][pitch], depth
+        uint32 [rows], tokens (_capi.PILEUP_TOKEN_DTYPE, sorted by (pos, sample)) and their text (uint8)."""
+        res = _capi.PileupResult()
+        res.mem_kind = _capi.BV_MEM_HOST
+        rc = self._lib.bv_engine_pileup_fetch(self._h, C.byref(res), None)  # no buffers: the sizes
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_fetch failed (%d): %s" % (rc, self._err()), rc)
+        rows, cells = int(res.rows), int(res.cells)
+        out = dict(cell=np.zeros(cells, np.uint8), qual=np.zeros(cells, np.uint8), mapq=np.zeros(cells, np.uint8), rank=np.zeros(cells, np.uint16),
+                   depth=np.zeros(rows, np.uint32), tokens=np.zeros(int(res.n_tokens), _capi.PILEUP_TOKEN_DTYPE), text=np.zeros(int(res.text_bytes), np.uint8))
+        for k, v in out.items():
+            setattr(res, k, v.ctypes.data if v.size else None)
+        res.cells_capacity, res.rows_capacity, res.tokens_capacity, res.text_capacity = cells, rows, int(res.n_tokens), int(res.text_bytes)
+        rc = self._lib.bv_engine_pileup_fetch(self._h, C.byref(res), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_fetch failed (%d): %s" % (rc, self._err()), rc)
+        pitch = cells // rows
+        for k in ("cell", "qual", "mapq", "rank"):
+            out[k] = out[k].reshape(rows, pitch)
+        return out
+
+    def pileup_rows(self, tagged=False):
+        """The covered rows of the last pileup as a device slab (bv_engine_pileup_rows): (_capi.Slab ready for bv_engine_submit and
+        valid until the next pileup, positions uint32 [n], depths uint32 [n])."""
+        n = getattr(self, "_pileup_covered", 0)
+        slab = _capi.Slab()
+        pos, depth = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        rc = self._lib.bv_engine_pileup_rows(self._h, 1 if tagged else 0, C.byref(slab), pos.ctypes.data if n else None, depth.ctypes.data if n else None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_rows failed (%d): %s" % (rc, self._err()), rc)
+        return slab, pos, depth
+
+    def lrt_pileup(self, records, run_off, run_sample, n_samples, tid, region, window, mapq_thd, pitch=None, tagged=False):
+        """Reads in, records out: pileup, pileup_rows and bv_engine_submit of the device slab.  Returns a PileupBatch: the records
+        of the covered rows, their positions and depths, and the indel tokens {(pos, sample): text}."""
+        self.pileup(records, run_off, run_sample, n_samples, tid, region, window, mapq_thd, pitch=pitch)
+        slab, pos, depth = self.pileup_rows(tagged=tagged)
+        res = _capi.PileupResult()
+        res.mem_kind = _capi.BV_MEM_HOST
+        self._lib.bv_engine_pileup_fetch(self._h, C.byref(res), None)
+        tokens, text = np.zeros(int(res.n_tokens), _capi.PILEUP_TOKEN_DTYPE), np.zeros(int(res.text_bytes), np.uint8)
+        res.tokens, res.text = (tokens.ctypes.data if tokens.size else None), (text.ctypes.data if text.size else None)
+        res.tokens_capacity, res.text_capacity = int(tokens.size), int(text.size)
+        rc = self._lib.bv_engine_pileup_fetch(self._h, C.byref(res), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_fetch failed (%d): %s" % (rc, self._err()), rc)
+        n = int(slab.n_sites)
+        out = np.zeros(n, dtype=_capi.SITE_DTYPE)
+        if n:
+            import torch  # the records of a device slab are device memory: a tensor holds them
+            d_out = torch.zeros(n * _capi.SITE_DTYPE.itemsize, dtype=torch.uint8, device="cuda:%d" % self.device)
+            torch.cuda.synchronize(self.device)
+            if self._lib.bv_engine_submit(self._h, C.byref(slab), int(d_out.data_ptr()), None, None) != 0:
+                raise RuntimeError("bv_engine_submit failed: %s" % self._err())
+            self.wait()
+            out = d_out.cpu().numpy().view(_capi.SITE_DTYPE).copy()
+        ms1, ms2 = self.kernel_ms() if n else (0.0, 0.0)
+        toks = {(int(t["pos"]), int(t["sample"])): text[int(t["text_off"]):int(t["text_off"]) + int(t["text_len"])].tobytes() for t in tokens}
+        return PileupBatch(out, None, self.last_variant_count() if n else 0, ms1, ms2, pos, depth, toks)
+
     def deflate_code_lengths(self, counts, limit):
         """The code lengths the small deflate level gives an alphabet with these counts (bv_engine_deflate_code_lengths, a
         diagnostic): (lengths uint8 [n], rounds of halving)."""
@@ -647,6 +751,17 @@ class BaseTypeEngine:
         if rc != 0:
             raise RuntimeError("bv_engine_deflate_code_lengths failed (%d): %s" % (rc, self._err()), rc)
         return lengths, int(rounds.value)
+
+
+class PileupBatch(BaseTypeBatch):
+    """Records of BaseTypeEngine.lrt_pileup: one per covered row of the window, with the rows' 1-based positions and depths and
+    the window's indel tokens {(pos, sample): text}."""
+
+    def __init__(self, sites, groups, n_variant, pass1_ms, pass2_ms, positions, depth, tokens):
+        BaseTypeBatch.__init__(self, sites, groups, n_variant, pass1_ms, pass2_ms)
+        self.positions = positions
+        self.depth = depth
+        self.tokens = tokens
 
 
 class TextBatch(BaseTypeBatch):

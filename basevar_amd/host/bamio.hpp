@@ -328,6 +328,31 @@ public:
         done_ = true;
         return -1;
     }
+    // The next record of the current fetch as its raw bytes (block_size word + block), appended to `out`: the chunk and seek
+    // handling of next(), and nothing decoded -- so no record is skipped and none ends the query; the reader of the bytes
+    // applies next()'s tests (basevar_amd/csrc/bv_pileup_core.h).  >= 0 on a record, -1 at the end of the chunks / the file.
+    int next_raw(std::vector<uint8_t> &out) {
+        while (!done_) {
+            if (index_.loaded) {
+                while (chunk_i_ < chunks_.size() && bg_.tell() >= chunks_[chunk_i_].second) {
+                    ++chunk_i_;
+                    if (chunk_i_ < chunks_.size() && bg_.tell() < chunks_[chunk_i_].first) bg_.seek(chunks_[chunk_i_].first);
+                }
+                if (chunk_i_ >= chunks_.size()) break;
+            }
+            uint8_t b4[4];
+            if (!bg_.read(b4, 4)) break;
+            const uint32_t block_size = b4[0] | (b4[1] << 8) | (b4[2] << 16) | ((uint32_t)b4[3] << 24);
+            if (block_size < 32) throw std::runtime_error("[ERROR] corrupt BAM record in " + path_);
+            const size_t at = out.size();
+            out.resize(at + 4 + block_size);
+            std::memcpy(out.data() + at, b4, 4);
+            if (!bg_.read(out.data() + at + 4, block_size)) throw std::runtime_error("[ERROR] truncated BAM record in " + path_);
+            return 0;
+        }
+        done_ = true;
+        return -1;
+    }
 
 private:
     uint32_t rd32() {

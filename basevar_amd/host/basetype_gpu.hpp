@@ -282,6 +282,8 @@ public:
     BaseTypeEngine(const BaseTypeEngine &) = delete;
     BaseTypeEngine &operator=(const BaseTypeEngine &) = delete;
 
+    bv_engine *handle() { return e_; }  // for the entry points that have no wrapper here (include/basevar_amd_pileup.h)
+
     BaseTypeBatch lrt(const SlabBuilder &b) {
         BaseTypeBatch out;
         out.sites.resize(b.n_sites());

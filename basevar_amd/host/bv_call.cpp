@@ -14,6 +14,7 @@
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
 //           [--timing FILE.json] [--inflate device|host] [--deflate device|host] [--deflate-level fast|small] [--emit device|host]
+//           [--pileup device|host]
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -45,6 +46,7 @@
 #include "batch_producer.hpp"
 #include "batchfile_fast.hpp"
 #include "pileup.hpp"
+#include "basevar_amd_pileup.h"
 #include "bgzf_tabix.hpp"
 #include "vcf_emit.hpp"
 
@@ -142,7 +144,7 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 int main(int argc, char **argv) {
     std::vector<std::string> batchfiles, bams;
     std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate_arg = "host", deflate_arg = "host",
-                deflate_level_arg = "fast", emit_arg = "host";
+                deflate_level_arg = "fast", emit_arg = "host", pileup_arg = "host";
     int mapq_thd = 10, threads = 4, n_gpus = 1;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -162,6 +164,7 @@ int main(int argc, char **argv) {
         else if (a == "--deflate") deflate_arg = next();
         else if (a == "--deflate-level") deflate_level_arg = next();
         else if (a == "--emit") emit_arg = next();
+        else if (a == "--pileup") pileup_arg = next();
         else if (a == "--device") device = std::stoi(next());
         else if (a == "--gpus") n_gpus = std::stoi(next());
         else if (a == "--devices") devices_arg = next();
@@ -193,6 +196,7 @@ int main(int argc, char **argv) {
     if (deflate_arg != "host" && deflate_arg != "device") die("[ERROR] --deflate wants device or host");
     if (deflate_level_arg != "fast" && deflate_level_arg != "small") die("[ERROR] --deflate-level wants fast or small");
     if (emit_arg != "host" && emit_arg != "device") die("[ERROR] --emit wants device or host");
+    if (pileup_arg != "host" && pileup_arg != "device") die("[ERROR] --pileup wants device or host");
     // (the host path is zlib at its own level: the device encoder's levels do not apply to it)
     if (deflate_level_arg != "fast" && deflate_arg != "device") die("[ERROR] --deflate-level small needs --deflate device");
     const int deflate_level = deflate_level_arg == "small" ? BV_DEFLATE_SMALL : BV_DEFLATE_FAST;
@@ -333,6 +337,17 @@ int main(int argc, char **argv) {
         else if (!raw.open(batchfiles, header_lines)) std::cerr << "[NOTE] --inflate device needs BGZF batchfiles: the host path is taken" << std::endl;
         else device_inflate = true;
     }
+    // --pileup device: the samples' raw BAM records of a window go to an engine of the producer's own, which piles them up
+    // (bv_engine_pileup), gathers the covered rows and submits them where they lie (bv_engine_pileup_rows / _submit); the host
+    // threads only read and inflate.  BAM input on one engine; anything else keeps the host path.
+    bool device_pileup = false;
+    if (pileup_arg == "device") {
+        if (!from_bam) std::cerr << "[NOTE] --pileup device applies to BAM input, not to batchfiles: nothing changes" << std::endl;
+        else if (G > 1) std::cerr << "[NOTE] --pileup device runs on one engine (--gpus 1): the host path is taken" << std::endl;
+        else device_pileup = true;
+    }
+    uint64_t reads_bytes = 0;
+    double pileup_s = 0;
     std::mutex raw_mu;
     bool raw_done = false;
     uint64_t raw_seq = 0;
@@ -598,6 +613,8 @@ int main(int argc, char **argv) {
             std::vector<std::string> region_list;  // "-r chr:beg-end[,chr:beg-end ...]" (caller.cpp:311-356), in the order given
             region_list = bvamd::pieces(regions, ',');
             std::string fa_seq, fa_of;
+            std::unique_ptr<bvamd::BaseTypeEngine> pileup_engine;  // --pileup device
+            std::unique_ptr<bvamd::BamPool> pileup_pool;
             for (const std::string &rg : region_list) {
                 const size_t colon = rg.rfind(':'), dash = rg.rfind('-');
                 if (colon == std::string::npos || dash == std::string::npos || dash < colon) die("--regions wants CHR:BEG-END[,CHR:BEG-END...]");
@@ -606,6 +623,104 @@ int main(int argc, char **argv) {
                 const uint32_t end = (uint32_t)std::stoul(rg.substr(dash + 1));
                 if (fa_of != ref_id) { fa_seq = bvamd::load_fasta_sequence(reference, ref_id); fa_of = ref_id; }
                 if (beg < 1 || end < beg || end > fa_seq.size()) die("[ERROR] region outside " + ref_id);
+                if (device_pileup) {
+                    if (!pileup_engine) pileup_engine.reset(new bvamd::BaseTypeEngine(batch_sites, (uint32_t)n_sample, user_min_af, devices[0]));
+                    if (!pileup_pool) pileup_pool.reset(new bvamd::BamPool(bams, true));
+                    bv_engine *pe = pileup_engine->handle();
+                    auto check = [&](int rc) { if (rc != BV_OK) throw std::runtime_error(bv_last_error(pe)); };
+                    check(bv_engine_pileup_set_reference(pe, fa_seq.data(), fa_seq.size()));
+                    const uint32_t window = std::min<uint32_t>(bvamd::pileup_window(bams.size()), bv_pileup_max_rows());
+                    const size_t n = bams.size();
+                    for (uint32_t sb = beg; sb <= end && still_ok(); sb += bvamd::PILEUP_STEP) {
+                        const uint32_t se = std::min(end, sb + bvamd::PILEUP_STEP - 1);
+                        for (uint32_t wb = sb; wb <= se && still_ok(); wb += window) {
+                            const uint32_t we = std::min(se, wb + window - 1);
+                            // every sample's records of the fetch, undecoded, on `--thread` threads
+                            const double tr0 = StageClock::now();
+                            const uint32_t lo = wb > bvamd::PILEUP_PAD ? wb - bvamd::PILEUP_PAD : 1, hi = we + bvamd::PILEUP_PAD;
+                            std::vector<std::vector<uint8_t>> per(n);
+                            std::vector<int> tids(n, -1);
+                            std::atomic<size_t> next_sample(0);
+                            parallel_ranges((size_t)std::max(1, threads), threads, [&](size_t, size_t, size_t) {
+                                for (size_t i; (i = next_sample.fetch_add(1)) < n;) {
+                                    bvamd::BamPool::Handle h = pileup_pool->get(i);
+                                    tids[i] = h.bf->tid_of(ref_id);
+                                    if (!h.bf->fetch(tids[i], (int64_t)lo - 1, (int64_t)hi)) continue;
+                                    while (h.bf->next_raw(per[i]) >= 0) {}
+                                }
+                            });
+                            int tid = -1;
+                            std::vector<uint8_t> records;
+                            std::vector<uint64_t> run_off(1, 0);
+                            std::vector<uint32_t> run_sample;
+                            for (size_t i = 0; i < n; ++i) {
+                                if (tids[i] < 0 || per[i].empty()) continue;
+                                if (tid >= 0 && tids[i] != tid) throw std::runtime_error("[ERROR] --pileup device needs BAM files that number " + ref_id + " alike: " + bams[i]);
+                                tid = tids[i];
+                                records.insert(records.end(), per[i].begin(), per[i].end());
+                                run_off.push_back(records.size());
+                                run_sample.push_back((uint32_t)i);
+                            }
+                            const double tp0 = StageClock::now();
+                            clk.read += tp0 - tr0;
+                            reads_bytes += records.size();
+                            if (run_sample.empty()) { if (we == UINT32_MAX) break; continue; }
+                            bv_pileup_reads in{};
+                            in.records = records.data(); in.run_off = run_off.data(); in.run_sample = run_sample.data();
+                            in.pitch = (n_sample + 15) / 16 * 16; in.n_runs = (uint32_t)run_sample.size(); in.n_samples = (uint32_t)n_sample;
+                            in.tid = tid; in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq_thd;
+                            in.mem_kind = BV_MEM_HOST;
+                            uint32_t n_cov = 0;
+                            check(bv_engine_pileup(pe, &in, &n_cov, nullptr));
+                            std::vector<uint32_t> pos(n_cov), depth(n_cov);
+                            bv_slab slab;
+                            // (short reads: the rank words carry the calls, as SlabBuilder::tag_ranks chooses on the host path)
+                            if (bv_engine_pileup_rows(pe, 1, &slab, pos.data(), depth.data()) != BV_OK) check(bv_engine_pileup_rows(pe, 0, &slab, pos.data(), depth.data()));
+                            bv_pileup_result res{};
+                            res.mem_kind = BV_MEM_HOST;
+                            check(bv_engine_pileup_fetch(pe, &res, nullptr));  // (no buffers: the sizes)
+                            std::vector<bv_pileup_token> tokens(res.n_tokens);
+                            std::vector<uint8_t> token_text(res.text_bytes);
+                            res.tokens = tokens.data(); res.text = token_text.data();
+                            res.tokens_capacity = tokens.size(); res.text_capacity = token_text.size();
+                            check(bv_engine_pileup_fetch(pe, &res, nullptr));
+                            pileup_s += StageClock::now() - tp0;
+                            clk.parse += StageClock::now() - tp0;
+                            size_t next_token = 0;
+                            for (uint32_t first = 0; first < n_cov && still_ok(); first += batch_sites) {
+                                const uint32_t rows = std::min(batch_sites, n_cov - first);
+                                BatchPtr b(new Batch((uint32_t)n_sample));
+                                b->seq = seq++;
+                                b->from_text = true;  // (its cell / phred rows come back beside the records)
+                                b->result.sites.resize(rows);
+                                b->result.n_groups = (uint32_t)group_names.size();
+                                b->result.groups.resize((size_t)rows * group_names.size());
+                                b->cell.resize((size_t)rows * n_sample);
+                                b->phred.resize((size_t)rows * n_sample);
+                                const double te0 = StageClock::now();
+                                check(bv_engine_pileup_submit(pe, first, rows, group_names.empty() ? nullptr : group_id.data(), (uint32_t)group_names.size(),
+                                                              b->result.sites.data(), group_names.empty() ? nullptr : b->result.groups.data(), b->cell.data(),
+                                                              b->phred.data(), nullptr));
+                                {
+                                    std::lock_guard<std::mutex> lk(err_mu);
+                                    clk.engine += StageClock::now() - te0;
+                                }
+                                for (uint32_t k = 0; k < rows; ++k) {
+                                    bvamd::SiteText st;
+                                    st.ref_id = ref_id; st.ref_pos = pos[first + k]; st.ref_base = std::string(1, fa_seq[st.ref_pos - 1]);
+                                    while (next_token < tokens.size() && tokens[next_token].pos < st.ref_pos) ++next_token;
+                                    for (; next_token < tokens.size() && tokens[next_token].pos == st.ref_pos; ++next_token)
+                                        st.indel_tokens.emplace_back(reinterpret_cast<const char *>(token_text.data()) + tokens[next_token].text_off, tokens[next_token].text_len);
+                                    b->text.push_back(std::move(st));
+                                }
+                                to_emit.push(std::move(b));
+                            }
+                            if (we == UINT32_MAX) break;
+                        }
+                        if (se == UINT32_MAX) break;
+                    }
+                    continue;
+                }
                 const double tp0 = StageClock::now();
                 bvamd::pileup_region(bams, fa_seq, ref_id, beg, end, mapq_thd, true, threads, [&](const bvamd::PileupTile &t) {
                     size_t next_indel = 0;
@@ -687,6 +802,8 @@ int main(int argc, char **argv) {
         if (device_deflate) tf << ", \"deflate\": \"device\", \"deflate_level\": \"" << deflate_level_arg << "\", \"members_deflated\": " << members_deflated << ", \"deflate_s\": " << deflate_s;
         // --emit device: VCF lines whose sample columns the engines wrote (all of them, on batchfile input)
         if (emit_device) tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << vcf_lines_device;
+        // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
+        if (device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << reads_bytes << ", \"pileup_s\": " << pileup_s;
         tf << "}\n";
     }
     return 0;
