@@ -1,6 +1,8 @@
 // bv_pileup.hip -- BAM records piled up on the device (bv_engine_pileup, include/basevar_amd_pileup.h; the contract is
 // INTEGRATION.md section 2i).  The result is defined at the head of bv_pileup_core.h, which a CPU harness compiles too; this
-// file is its schedule.
+// file is its schedule.  Of that header the kernels compile the record decode, the filter and the helpers; wave_walk below states
+// the walk a second time, and tests/test_gpu_pileup.py (BAM corpus) and tests/test_gpu_pileup_raw.py (raw runs, edges) hold it
+// to the first byte for byte.
 //
 // ONE WAVE PER SAMPLE.  A sample's reads are independent of every other sample's, and "the first read wins" is an order inside
 // one sample: so a wave walks its sample's runs record by record, in file order, and first-read-wins is program order.
@@ -136,7 +138,7 @@ __device__ __forceinline__ uint32_t wave_walk(const WalkEnv &a, const uint8_t *r
                     const uint64_t row = (uint64_t)(p - q.beg);
                     const uint32_t bit = 1u << (row & 31u);
                     if (atomicOr(&seen[row >> 5], bit) & bit) continue;  // an earlier read holds the cell
-                    store_cell(row * a.pitch + s, code | strand, qual[qi], r.mapq, qi + 1u);
+                    store_cell(row * a.pitch + s, code | strand, qual[qi], r.mapq, bv_pileup_rank(qi + 1u));
                 }
                 if (__any(over)) return BV_PILEUP_BAD_QUERY;
                 if (__any(bad)) return BV_PILEUP_BAD_BASE;
@@ -155,7 +157,7 @@ __device__ __forceinline__ uint32_t wave_walk(const WalkEnv &a, const uint8_t *r
                 if (!(old & bit)) {
                     const uint64_t k = row * a.pitch + s;
                     if (!TOKENS) {
-                        if (lane == 0) store_cell(k, (ins ? BV_PU_CELL_INS : BV_PU_CELL_DEL) | strand, mean_q, r.mapq, qpos + 1u);
+                        if (lane == 0) store_cell(k, (ins ? BV_PU_CELL_INS : BV_PU_CELL_DEL) | strand, mean_q, r.mapq, bv_pileup_rank(qpos + 1u));
                         if ((uint64_t)rpos - 1u >= q.ref_len) return BV_PILEUP_BAD_REF;
                         if (ins && qpos > r.l_seq) return BV_PILEUP_BAD_QUERY;
                         n_tok += 1u;

@@ -16,6 +16,8 @@
 //                 span (0 / -1 for an unmapped read):  gb > last -> skip;  ge < first -> BREAK;  end + 1 < first -> BREAK;
 //                 beg > last + 1 -> skip, where [gb, ge] is the 500 kb step of the window (bv_pileup_step)
 //     claim       the CIGAR walk below
+//   The stored rank SATURATES at 65,535 (bv_pileup_rank): a claimed cell's rank is never zero, whatever the read's length, so
+//   "claimed <=> rank != 0" holds and the depth of a row is the number of its cells of rank != 0.
 //   BREAK: every later record of that sample is ignored (not even decoded), whichever run it lies in.
 //
 //   The walk keeps rpos (0-based reference position of the next reference base, 64-bit) and qpos (query bases consumed, 32-bit and
@@ -24,10 +26,10 @@
 //     M = X   base i (0 <= i < len) lies at p = rpos + i + 1.  The bases with gb <= p <= ge are looked at: query index qpos + i must be
 //             below l_seq (else BV_PILEUP_BAD_QUERY), its nibble one of A C G T N (else BV_PILEUP_BAD_BASE: the host's "[ERROR] Why
 //             dose the size of aligned base is not 1?", raised for such a base anywhere in the step, claimed or not); then an
-//             attempt on p with (code | strand, qual[q], mapq, (uint16_t)(q + 1)).  Of one operation BAD_QUERY is reported before
+//             attempt on p with (code | strand, qual[q], mapq, min(q + 1, 65535)).  Of one operation BAD_QUERY is reported before
 //             BAD_BASE.  The walk ends behind the operation if it reaches beyond ge (len > 0 and rpos + len > ge).
 //     I D     tested on the UN-anchored position rpos + 1: beyond ge the walk ends; if gb <= rpos + 1 and rpos >= 1, one attempt on
-//             p = rpos (the base to the left) with (BV_CELL_INS / _DEL | strand, mean_q, mapq, (uint16_t)(qpos + 1)), mean_q =
+//             p = rpos (the base to the left) with (BV_CELL_INS / _DEL | strand, mean_q, mapq, min(qpos + 1, 65535)), mean_q =
 //             (uint8_t)(int)(sum of qual / l_seq), 255 for an empty read.  So an indel is refused when the same read's own match
 //             holds its anchor, and an I and then a D at one break point both anchor at the same position.  A claimed indel has a
 //             TOKEN: '+' or '-', the anchor's reference base ref[rpos - 1], then the inserted read letters seq[qpos, qpos + len)
@@ -196,6 +198,9 @@ BV_PU_FN uint8_t bv_pileup_mean_q(uint64_t qual_sum, uint32_t l_seq) {
     return (uint8_t)m;
 }
 
+// The rank a cell stores for read-position rank qpos + 1: saturated at 65,535, so that a claimed cell's rank is never zero
+BV_PU_FN uint32_t bv_pileup_rank(uint32_t rank) { return rank < 65535u ? rank : 65535u; }
+
 // The bases [*i_lo, *i_hi) of a match operation that lie in the step, and whether the walk ends behind the operation
 BV_PU_FN bool bv_pileup_match_range(const BvPileupQuery *q, int64_t rpos, int64_t len, int64_t *i_lo, int64_t *i_hi) {
     const int64_t lo = (int64_t)q->gb - rpos - 1, hi = (int64_t)q->ge - rpos;
@@ -231,7 +236,7 @@ BV_PU_FN bool bv_pileup_attempt(const BvPileupQuery *q, BvPileupSink *k, uint32_
     if (k->seen[row >> 5] & bit) return false;
     k->seen[row >> 5] |= bit;
     const uint64_t c = row * k->pitch + sample;
-    k->cell[c] = (uint8_t)code; k->qual[c] = (uint8_t)qual; k->mapq[c] = (uint8_t)mapq; k->rank[c] = (uint16_t)rank;
+    k->cell[c] = (uint8_t)code; k->qual[c] = (uint8_t)qual; k->mapq[c] = (uint8_t)mapq; k->rank[c] = (uint16_t)bv_pileup_rank(rank);
     return true;
 }
 

@@ -140,7 +140,7 @@ inline void pileup_claim_read(const BamAlignment &al, const std::string &fa, uin
         if (s) return false;  // first read wins
         s = 1;
         const size_t k = t.at((uint32_t)pos1, sample);
-        t.cell[k] = code; t.qual[k] = q; t.mapq[k] = mq; t.rank[k] = (uint16_t)rk;
+        t.cell[k] = code; t.qual[k] = q; t.mapq[k] = mq; t.rank[k] = (uint16_t)(rk < 65535u ? rk : 65535u);  // saturates: claimed <=> rank != 0
         __atomic_fetch_add(&t.depth[(size_t)(pos1 - t.beg)], 1u, __ATOMIC_RELAXED);
         return true;
     };

@@ -1,5 +1,5 @@
 // pileup_core_check.cpp -- CPU harness (a program of its own, built with ASan + UBSan) for basevar_amd/csrc/bv_pileup_core.h,
-// the definition the kernels of bv_pileup.hip compile.
+// the definition of the device pileup (bv_pileup.hip compiles its record decode, filter and helpers, and restates its walk).
 //
 //   pileup_core_check bam <out> <fasta> <ref_id> <region_beg> <region_end> <beg> <end> <mapq_thd> <split> <a.bam> ...
 //       reads the BAM files twice: through BamFile::next + pileup_tile (the host code as it is), and through BamFile::next_raw

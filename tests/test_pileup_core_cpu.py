@@ -1,7 +1,10 @@
-"""CPU tests (no GPU) of the device pileup's definition: basevar_amd/csrc/bv_pileup_core.h -- the code the kernels of
-bv_pileup.hip compile -- against host/pileup.hpp on BAM files inside the stand-alone harness tests/cpp/pileup_core_check.cpp
-(built with ASan + UBSan and run as a program), the harness's result against bam_py.pileup_sample, the core alone on damaged
-records; the new header against the ctypes layer; and the kernels' resources."""
+"""CPU tests (no GPU) of the device pileup's definition, basevar_amd/csrc/bv_pileup_core.h.  The kernels of bv_pileup.hip compile
+its record decode, its filter and its helpers; its walk, bv_pileup_walk, they do not: wave_walk there is the walk's second
+statement, with the lanes across a match's bases, and the GPU tests hold it (test_gpu_pileup.py, test_gpu_pileup_raw.py).  Here:
+the core against host/pileup.hpp on BAM files inside the stand-alone harness tests/cpp/pileup_core_check.cpp (built with ASan +
+UBSan and run as a program), the harness's result against bam_py.pileup_sample, the core alone on damaged records and on every
+raw run the GPU tests will send (pileup_raw_cases.py: a seeded campaign that must be worth running, and hand-built cases); the new
+header against the ctypes layer; and the kernels' resources."""
 import ctypes as C
 import os
 import re
@@ -15,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import bam_py  # noqa: E402
 import pileup_ref as pr  # noqa: E402
+import pileup_raw_cases as rc  # noqa: E402
 
 N_SAMPLES = 6
 
@@ -157,6 +161,7 @@ def test_truncation_at_every_byte_ends_in_a_status(harness, corpus, tmp_path):
     recs = [pr.record_bytes(r) for r in small_run(rng)]
     run = b"".join(recs)
     ends = set(np.cumsum([len(r) for r in recs]).tolist()) | {0}
+    assert [t[1] for t in rc.truncations()] == [run[:cut] for cut in range(len(run))]  # what the GPU test sends: these bytes
     for cut in range(len(run)):
         d, _ = raw(harness, tmp_path, corpus.fa[:4000], [run[:cut]])
         assert d.status == (0 if cut in ends else pr.BAD_RUN), cut
@@ -176,6 +181,134 @@ def test_flipped_length_fields_end_in_a_status(harness, corpus, tmp_path):
             assert 0 <= d.status <= pr.BAD_BASE
             seen.add(d.status)
     assert {pr.BAD_BLOCK, pr.BAD_RUN, pr.BAD_LENGTHS} <= seen
+
+
+# ------------------------------------------------------------------------------------------ the raw runs the GPU tests send
+@pytest.fixture(scope="module")
+def campaign(harness, tmp_path_factory):
+    """every round of the campaign through the core under the sanitizers, once"""
+    tmp = tmp_path_factory.mktemp("pileup_campaign")
+    out = []
+    for seed in rc.CAMPAIGN_SEEDS:
+        case = rc.campaign_round(seed)
+        d, text = pr.run_raw(harness, tmp / "c.bin", tmp, case[4], *case[:4])  # (raises on a sanitizer report)
+        out.append((seed, case, d, text))
+    return out
+
+
+def test_campaign_rounds_end_clean_without_exception(campaign):
+    assert 40 <= len(campaign) <= 60 and sorted(sum(rc.SEED_BLOCKS, [])) == sorted(rc.CAMPAIGN_SEEDS)
+    for seed, case, d, text in campaign:
+        assert d.status == 0 and text.startswith("status 0 "), seed
+        assert rc.campaign_round(seed)[0] == case[0]  # seeded from the seed alone
+
+
+def test_campaign_is_worth_running(campaign):
+    """the GPU campaign cannot pass on nothing: tokens, coverage, every cell code, long token texts, several runs a sample; and
+    what the rounds are drawn over does occur"""
+    codes, longest, with_runs, several = set(), 0, 0, 0
+    seen_n, seen_rows, seen_beg, first_without, last_without, short_ref, abut = set(), set(), set(), 0, 0, 0, set()
+    for seed, (runs, run_sample, n, window, ref), d, _ in campaign:
+        if n >= 5:
+            assert d.n_tokens >= n / 4, seed
+        assert d.n_covered > d.rows / 2, seed
+        codes |= set(np.unique(d.cell[:, :n]).tolist())
+        longest = max([longest] + d.tokens["text_len"].tolist())
+        per = np.bincount(run_sample, minlength=n)
+        with_runs += int((per > 0).sum())
+        several += int((per > 1).sum())
+        seen_n.add(n); seen_rows.add(d.rows); seen_beg.add(window[0] % 32)
+        first_without += n >= 5 and per[0] == 0
+        last_without += n >= 5 and per[-1] == 0
+        short_ref += len(ref) < window[1] + 400
+        abut |= {"first"} if window[0] == rc.GB2 else {"last"} if window[1] == rc.GB2 - 1 else set()
+    assert codes >= {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 0x0A, 0x0C, 0x0D, 0x0E}
+    assert longest > 128 and any(64 < int(x) <= 128 for _, _, d, _ in campaign for x in d.tokens["text_len"])
+    assert 3 * several >= with_runs
+    assert seen_n == set(rc.N_SAMPLES) and seen_rows == set(rc.WINDOW_ROWS) and len(seen_beg) >= 16
+    assert first_without >= 5 and last_without >= 5 and short_ref >= 5 and abut == {"first", "last"}
+    assert any(len(r) == 0 for _, case, _, _ in campaign for r in case[0])  # empty runs
+    assert rc.pack_is_record_bytes()
+
+
+@pytest.fixture(scope="module")
+def directed_dumps(harness, tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("pileup_directed")
+    return {name: pr.run_raw(harness, tmp / (name + ".bin"), tmp, c.ref, c.runs, c.run_sample, c.n_samples, c.window)[0] for name, c in rc.directed().items()}
+
+
+@pytest.mark.parametrize("name", sorted(rc.directed()))
+def test_directed_case_on_the_core(directed_dumps, name):
+    """no sanitizer report (run_raw raises on one), the status the case states, and its stated answer"""
+    c, d = rc.directed()[name], directed_dumps[name]
+    assert rc.directed_cases()[name] == c.tuple()
+    assert d.status == c.status
+    if c.status:
+        assert (d.fail_sample, d.fail_run, d.fail_at) == c.expect["fail"]
+    else:
+        assert d.n_covered > 0
+        rc.check_expectation(c, d)
+
+
+def test_directed_cases_reach_every_status(directed_dumps):
+    assert {d.status for d in directed_dumps.values()} == set(range(7))
+
+
+def test_wide_and_variant_rounds_on_the_core(harness, tmp_path):
+    """the many-sample rounds and the tagging boundary's reads of the GPU tests, under the sanitizers first"""
+    for n in (512, 513, 1040, 4096, 4097, 4113, 20000):
+        for long_rank in (8191, 8192):
+            case = rc.wide_round(n, long_rank=long_rank)
+            d, _ = pr.run_raw(harness, tmp_path / "w.bin", tmp_path, case[4], *case[:4])
+            assert d.status == 0 and d.n_tokens > 3 and int(d.rank.max()) == long_rank == int(d.rank[-1, n - 1])
+            assert sorted(set(case[1])) == case[1] and {0, 1, 63, 64, 511, n - 1} <= set(case[1]) and len(case[1]) < n // 20 + 12
+    for n in (65, 4113):
+        case = rc.variant_round(n)
+        d, _ = pr.run_raw(harness, tmp_path / "v.bin", tmp_path, case[4], *case[:4])
+        assert d.status == 0 and 250 <= d.n_covered <= 300
+
+
+BAM_CASES = sorted(k for k, c in rc.directed().items() if c.recs is not None)
+NOT_IN_BAM_PY = {"operation_codes_9_and_15", "insertion_of_other_nibbles"}  # bam_py knows the nine named operations and prints every letter
+
+
+@pytest.mark.parametrize("name", BAM_CASES)
+def test_directed_case_as_bam_files_host_against_core(harness, corpus, directed_dumps, tmp_path, name):
+    """the cases that are valid BAM, written with records across BGZF members: pileup_tile against the core (inside the harness),
+    one run a sample and a run a record, and both the raw case's result"""
+    c = rc.directed()[name]
+    bams = []
+    for s, recs in enumerate(c.recs):
+        bams.append(str(tmp_path / ("s%d.bam" % s)))
+        bam_py.write_bam(bams[-1], pr.REFS, recs, block_payload=700)
+    d, out = pr.run_bam(harness, tmp_path / "one.bin", corpus, len(bams), c.window, bams=bams)
+    assert d.status == 0 and out.startswith("status 0 ")
+    split, _ = pr.run_bam(harness, tmp_path / "split.bin", corpus, len(bams), c.window, split=True, bams=bams)
+    assert split.n_runs >= d.n_runs
+    same(d, split)
+    same(d, directed_dumps[name])
+    rc.check_expectation(c, d)
+    if name not in NOT_IN_BAM_PY:
+        pr.check_against_bam_py(d, c.recs, corpus.fa, c.window)
+
+
+def test_bam_cases_are_the_ones_the_issue_names():
+    assert set(BAM_CASES) >= {"no_cigar", "zero_length_operations", "quals_255_and_0", "operation_codes_9_and_15", "long_deletions", "long_insertions", "mapq_255_and_0"}
+
+
+@pytest.mark.parametrize("window", [(66500, 66600), (66000, 66100)])
+def test_a_read_of_66000_bases(harness, corpus, tmp_path, window):
+    """query index 65,535 lies at position 66,536: its rank, 65,536, does not fit 16 bits.  The stored rank saturates at 65,535 --
+    host, core and the independent derivation alike -- so the cell stays claimed and depth counts it.  (With a rank that wraps to 0
+    the host counted a cell in `depth` that its row writer and the core take as unclaimed: "DIFFER: depth" on the first window.)"""
+    read = rc.long_read()
+    path = str(tmp_path / "long.bam")
+    bam_py.write_bam(path, pr.REFS, [read])
+    d, out = pr.run_bam(harness, tmp_path / "l.bin", corpus, 1, window, bams=[path])
+    assert d.status == 0 and (d.depth == 1).all() and d.n_covered == d.rows
+    pr.check_against_bam_py(d, [[read]], corpus.fa, window)
+    want = np.minimum(np.arange(window[0], window[1] + 1) - read["pos"], 65535)
+    assert (d.rank[:, 0] == want).all() and (66536 in range(window[0], window[1] + 1)) == bool((want == 65535).any())
 
 
 # ---------------------------------------------------------------------------------------------------------- the header and the kernels
