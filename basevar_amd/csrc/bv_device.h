@@ -460,6 +460,32 @@ __device__ __forceinline__ void bv_hyper_init(BvHyper &h, const BvLnTab &T, int 
     h.lb3 = bv_lnfact(T, n) - bv_lnfact(T, n_1) - bv_lnfact(T, n - n_1);
 }
 
+// Tables of a family whose observed table has q < 2^-511 are carried scaled by 2^512: the walks below start where a tail
+// falls under q * e^-60, and unscaled that first table's exp() is 0 from q ~ 1e-298 on -- a product of ratios that starts at 0
+// stays 0 while the true terms rise past q.  Scaled, every table of at least q * e^-60 is a normal double (q >= 2^-1074 here,
+// no table exceeds 1: nothing overflows); the two-sided sum is scaled back by the exact power of two.
+#define BV_FISHER_SHIFT_LOG (-354.0)              /* just above ln 2^-511                */
+#define BV_FISHER_SHIFT 354.89135644669199        /* 512 ln 2                            */
+__device__ __forceinline__ double bv_fisher_shift(double logq) { return logq < BV_FISHER_SHIFT_LOG ? BV_FISHER_SHIFT : 0.; }
+__device__ __forceinline__ double bv_fisher_unshift(double two, double shift) { return shift != 0. ? two * 0x1p-512 : two; }
+// The same zero threatens wherever a walk STARTS below the double range and rises: the first table of a family with a steep end
+// (log p(imin) of -1000 beside an ordinary q), the start of a tail window when one probe step spans hundreds of nats.  A walk
+// whose first table has log p + shift < BV_FISHER_LIVE starts at the first table that reaches it instead: found by bisection
+// on [lo, hi], hi at most the family's mode, over which log p rises.  The tables passed over are below 1e-304 of the scale on
+// which q is at least 1e-169: nothing to a sum that is at least q.  (A walk that FALLS below the range may go to 0: so do its terms.)
+#define BV_FISHER_LIVE (-700.0)
+__device__ __forceinline__ int bv_fisher_mode(int n1_, int n_1, int n) {
+    return (int)(((long long)(n1_ + 1) * (long long)(n_1 + 1)) / (long long)(n + 2));
+}
+__device__ inline int bv_fisher_first_live(const BvHyper &h, int lo, int hi, double shift) {
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (bv_hyper_logp(h, mid) + shift >= BV_FISHER_LIVE) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 // kt_fisher_exact (two-sided), wave-parallel.  Semantics of the reference's two loops
 // (kfunc.c:291-307): with lo = 0.99999999 q and hi = 1.00000001 q,
 //   L* = first table from the left  with p >= lo,  left  = sum_{i < L*} p(i) + (p(L*) < hi ? p(L*) : 0)
@@ -542,8 +568,11 @@ __device__ inline double bv_fisher_two_sided_wave(int n11, int n12, int n21, int
     }
 
     const double logq = bv_hyper_logp(h, n11);
-    const double q = exp(logq);
-    if (q == 0.0) return 0.0;  // kfunc.c:260-289
+    if (exp(logq) == 0.0) return 0.0;  // kfunc.c:260-289
+    // (scaled where q is tiny, see bv_fisher_shift: unscaled, pbase = exp(log p(wl)) was 0 for q below ~1e-298 and with it every
+    // table of every round -- two came out 0, FS 10000; found by tests/test_gpu_strand_tables.py, "probed R=max q300")
+    const double shift = bv_fisher_shift(logq);
+    const double q = exp(logq + shift);
     const double lo = 0.99999999 * q, hi = 1.00000001 * q;
     const int INF = 0x7fffffff;
     int wl = imin, wr = imax;
@@ -573,7 +602,15 @@ __device__ inline double bv_fisher_two_sided_wave(int n11, int n12, int n21, int
     // step; the reference re-seeds every 11 tables, which matters at 1e-13, not at the 1e-6 bar.)
     double tail = 0., pL = 0., pR = 0.;
     bool seen = false;
-    double pbase = bv_hyper_p(h, wl);
+    double lbase = bv_hyper_logp(h, wl) + shift;
+    if (lbase < BV_FISHER_LIVE) {  // (uniform over the wave; rare)
+        const int top = min(wr, bv_fisher_mode(n1_, n_1, n));
+        if (wl < top) {
+            wl = bv_fisher_first_live(h, wl + 1, top, shift);
+            lbase = bv_hyper_logp(h, wl) + shift;
+        }
+    }
+    double pbase = exp(lbase);
     for (int w = wl; w <= wr; w += BV_WAVE) {
         const int i = w + lane;
         const bool have = i <= wr;
@@ -593,6 +630,7 @@ __device__ inline double bv_fisher_two_sided_wave(int n11, int n12, int n21, int
     double two = bv_wave_sum(tail);
     if (pL < hi) two += pL;
     if (pR < hi) two += pR;
+    two = bv_fisher_unshift(two, shift);
     return two > 1. ? 1. : two;
 }
 

@@ -141,8 +141,13 @@ __device__ inline double bv_fisher_two_sided_g16(int n11, int n12, int n21, int 
     double seed_n = (narrow && i0n <= imax) ? bv_hyper_logp(h, i0n) : 0.;
     asm volatile("" : "+v"(seed_n));  // (read here, not where it is used)
     const double logq = bv_hyper_logp(h, n11);
-    const double q = exp(logq);
-    if (q == 0.0) return 0.0;  // kfunc.c:260-289
+    if (exp(logq) == 0.0) return 0.0;  // kfunc.c:260-289
+    // q below 2^-511: every table is carried scaled by 2^512 (BV_FISHER_SHIFT, bv_device.h) and the sum scaled back at the end.
+    // Unscaled, a block that starts at a table of q * e^-60 (where a probed tail ends) is seeded with exp() == 0 once q nears
+    // the smallest double, and stays 0 while the true terms rise past q: the tail's sum was lost, and with it the observed
+    // table when it lay in that block (found by tests/test_gpu_strand_tables.py, "probed R=max q300": p came out halved).
+    const double shift = bv_fisher_shift(logq);
+    const double q = exp(logq + shift);
     const double lo = 0.99999999 * q, hi = 1.00000001 * q;
     const int INF = 0x7fffffff;
     int wl = imin, wr = imax;
@@ -170,10 +175,19 @@ __device__ inline double bv_fisher_two_sided_g16(int n11, int n12, int n21, int 
     // lane, against a 16-lane prefix product, two broadcasts and a ballot per 16 tables in the round form this replaces
     // (the Fisher tests were 45 % of the solver's instructions).
     const int Lb = (wr - wl + 16) >> 4;  // tables per lane
-    const int i0 = wl + gl * Lb;
+    int i0 = wl + gl * Lb;
     const int i1 = min(i0 + Lb - 1, wr);
     const bool mine = i0 <= wr;
-    double p = mine ? exp(narrow ? seed_n : bv_hyper_logp(h, i0)) : 0.;
+    double ls = (narrow ? seed_n : bv_hyper_logp(h, mine ? i0 : wr)) + shift;
+    if (mine && ls < BV_FISHER_LIVE) {
+        // a block that starts below the double range and rises (bv_fisher_first_live, bv_device.h): it starts where its tables do
+        const int top = min(i1, bv_fisher_mode(n1_, n_1, n));
+        if (i0 < top) {
+            i0 = bv_fisher_first_live(h, i0 + 1, top, shift);
+            ls = bv_hyper_logp(h, i0) + shift;
+        }
+    }
+    double p = mine ? exp(ls) : 0.;
     double tail = 0., pfirst = 0., plast = 0.;
     bool seen = false;
     for (int t = 0; t < Lb; ++t) {
@@ -193,6 +207,7 @@ __device__ inline double bv_fisher_two_sided_g16(int n11, int n12, int n21, int 
         if (pL < hi) two += pL;
         if (pR < hi) two += pR;
     }
+    two = bv_fisher_unshift(two, shift);
     return two > 1. ? 1. : two;
 }
 
