@@ -98,6 +98,17 @@ class PileupResult(C.Structure):  # bv_pileup_result
                 ("mem_kind", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class PileupTile(C.Structure):  # bv_pileup_tile (include/basevar_amd_pileup_text.h)
+    _fields_ = [("cell", C.c_void_p), ("qual", C.c_void_p), ("mapq", C.c_void_p), ("rank", C.c_void_p), ("tokens", C.c_void_p), ("text", C.c_void_p),
+                ("pitch", C.c_uint64), ("n_tokens", C.c_uint64), ("text_bytes", C.c_uint64), ("beg", C.c_uint32), ("rows", C.c_uint32),
+                ("n_samples", C.c_uint32), ("mem_kind", C.c_uint32)]
+
+
+class PileupText(C.Structure):  # bv_pileup_text
+    _fields_ = [("tile", C.POINTER(PileupTile)), ("chrom", C.c_char_p), ("chrom_len", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
 PILEUP_TOKEN_DTYPE = np.dtype([("pos", "<u4"), ("sample", "<u4"), ("text_off", "<u8"), ("text_len", "<u4"), ("reserved_", "<u4")])  # bv_pileup_token
 assert PILEUP_TOKEN_DTYPE.itemsize == 24
 
@@ -134,6 +145,9 @@ VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_def
 
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
+
+# every symbol include/basevar_amd_pileup_text.h declares
+PILEUP_TEXT_EXPORTS = ["bv_pileup_text_tile_samples", "bv_engine_pileup_text", "bv_engine_pileup_text_fetch", "bv_engine_pileup_text_deflate"]
 
 _lib = None
 
@@ -261,5 +275,13 @@ def load():
     L.bv_engine_pileup_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(Slab), C.c_void_p, C.c_void_p]
     L.bv_engine_pileup_submit.restype = C.c_int
     L.bv_engine_pileup_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_pileup_text_tile_samples.restype = C.c_uint32
+    L.bv_pileup_text_tile_samples.argtypes = []
+    L.bv_engine_pileup_text.restype = C.c_int
+    L.bv_engine_pileup_text.argtypes = [C.c_void_p, C.POINTER(PileupText), C.c_void_p, C.c_void_p]
+    L.bv_engine_pileup_text_fetch.restype = C.c_int
+    L.bv_engine_pileup_text_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
+    L.bv_engine_pileup_text_deflate.restype = C.c_int
+    L.bv_engine_pileup_text_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     _lib = L
     return L

@@ -511,6 +511,7 @@ int bv_engine_destroy(bv_engine *e) {
     bv_deflate_state_free(e->deflate);
     bv_vcf_state_free(e->vcf);
     bv_pileup_state_free(e->pileup);
+    bv_ptext_state_free(e->ptext);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

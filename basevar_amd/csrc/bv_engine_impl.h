@@ -1,5 +1,5 @@
 // bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_rows.hip, bv_engine_tiles.hip,
-// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
+// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip, bv_pileup_text.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
 // files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
 #pragma once
 
@@ -21,6 +21,27 @@ struct BvVcfState;      // bv_engine_vcf_format (bv_vcf.hip)
 void bv_vcf_state_free(BvVcfState *t);
 struct BvPileupState;   // bv_engine_pileup (bv_pileup.hip)
 void bv_pileup_state_free(BvPileupState *t);
+struct BvPtextState;    // bv_engine_pileup_text (bv_pileup_text.hip)
+void bv_ptext_state_free(BvPtextState *t);
+struct BvPileupToken;   // bv_pileup_core.h
+// The last completed bv_engine_pileup and the uploaded reference, as they lie (bv_pileup.hip): have_ref / done say what is there
+struct BvPileupView {
+    bool have_ref = false, done = false;
+    const uint8_t *d_ref = nullptr;
+    uint64_t ref_len = 0;
+    const uint8_t *cell = nullptr, *qual = nullptr, *mapq = nullptr;  // device [rows][pitch]
+    const uint16_t *rank = nullptr;
+    uint64_t pitch = 0;
+    uint32_t rows = 0, n_samples = 0, beg = 0;
+    const uint32_t *depth = nullptr;          // host [rows]
+    const BvPileupToken *tokens = nullptr;    // host, sorted by (pos, sample)
+    uint64_t n_tokens = 0;
+    const uint8_t *d_text = nullptr;          // device: the tokens' text
+    uint64_t text_bytes = 0;
+};
+void bv_pileup_view(const BvPileupState *t, BvPileupView *v);
+// bv_pileup.hip's depth kernel over device ranks [rows][pitch]: depth[rows] and max_rank[rows] (device), queued on `st`
+hipError_t bv_pileup_depth_launch(const uint16_t *rank, uint64_t pitch, uint32_t rows, uint32_t *depth, uint32_t *max_rank, hipStream_t st);
 // The rows kept by the last bv_engine_text_submit, as they lie in device memory (bv_text.hip): false if there are none
 struct BvKeptRows {
     const uint8_t *cell = nullptr, *phred = nullptr;  // [n_rows][pitch]
@@ -150,6 +171,7 @@ struct bv_engine {
     BvDeflateState *deflate = nullptr;  // created by the first bv_engine_bgzf_deflate
     BvVcfState *vcf = nullptr;         // created by the first bv_engine_vcf_format
     BvPileupState *pileup = nullptr;   // created by the first bv_engine_pileup_set_reference
+    BvPtextState *ptext = nullptr;     // created by the first bv_engine_pileup_text
     mutable std::mutex mu;
     std::string err;
 };
@@ -168,7 +190,7 @@ int fail(bv_engine *e, int code, const std::string &msg);
 
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// e->text, e->bgzf, e->deflate, e->vcf, e->pileup: each is created by the first call that needs it, on the engine's device
+// e->text, e->bgzf, e->deflate, e->vcf, e->pileup, e->ptext: each is created by the first call that needs it, on the engine's device
 template <class S>
 S *engine_state(bv_engine *e, S *&state) {
     if (!state) {

@@ -327,6 +327,11 @@ void bv_pileup_state_free(BvPileupState *t) {
     delete t;
 }
 
+hipError_t bv_pileup_depth_launch(const uint16_t *rank, uint64_t pitch, uint32_t rows, uint32_t *depth, uint32_t *max_rank, hipStream_t st) {
+    hipLaunchKernelGGL(bv_pileup_depth_kernel, dim3((rows + 3u) / 4u), dim3(256), 0, st, rank, pitch, rows, depth, max_rank);
+    return hipGetLastError();
+}
+
 namespace {
 
 struct PlaneOffsets {
@@ -445,6 +450,22 @@ int pileup(bv_engine *e, BvPileupState *t, const bv_pileup_reads *in, const BvPi
 }
 
 }  // namespace
+
+// what bv_pileup_text.hip reads of the state: the reference, and the completed pileup where it lies
+void bv_pileup_view(const BvPileupState *t, BvPileupView *v) {
+    *v = BvPileupView();
+    if (!t) return;
+    v->have_ref = t->have_ref; v->d_ref = t->d_ref; v->ref_len = t->ref_len;
+    if (!t->done) return;
+    const PlaneOffsets P((size_t)t->rows * t->pitch);
+    v->done = true;
+    v->cell = t->d_planes; v->qual = t->d_planes + P.o_qual; v->mapq = t->d_planes + P.o_mapq;
+    v->rank = reinterpret_cast<const uint16_t *>(t->d_planes + P.o_rank);
+    v->pitch = t->pitch; v->rows = t->rows; v->n_samples = t->n_samples; v->beg = t->beg;
+    v->depth = t->depth.data();
+    v->tokens = t->tokens.data(); v->n_tokens = t->tokens.size();
+    v->d_text = t->d_text; v->text_bytes = t->text_bytes;
+}
 
 extern "C" {
 

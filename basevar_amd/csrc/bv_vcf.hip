@@ -25,6 +25,7 @@
 #include "../../include/basevar_amd_vcf.h"
 #include "../../include/basevar_amd_diag.h"
 #include "bv_chunk_stage.h"
+#include "bv_device_text.h"
 #include "bv_vcf_core.h"
 
 using namespace bv_impl;
@@ -253,6 +254,13 @@ int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptR
     return BV_OK;
 }
 
+// the formatted text as bv_device_text.h's fetch and deflate take it
+DeviceText vcf_text(const BvVcfState *t) {
+    DeviceText d;
+    if (t) { d.device = t->device; d.d_text = t->d_text; d.bytes = t->text_bytes; d.formatted = t->formatted; }
+    return d;
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,29 +311,15 @@ int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off
 }
 
 int bv_engine_vcf_fetch(bv_engine *e, void *dst, uint64_t dst_capacity, int dst_mem_kind, void *stream_) {
-    const std::string who = "bv_engine_vcf_fetch: ";
-    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, who + "null engine");
-    BvVcfState *t = e->vcf;
-    if (!t || !t->formatted) return fail(e, BV_ERR_INVALID_ARG, who + "no bv_engine_vcf_format before it");
-    if (dst_mem_kind != BV_MEM_HOST && dst_mem_kind != BV_MEM_DEVICE) return fail(e, BV_ERR_INVALID_ARG, who + "dst_mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
-    if (dst_capacity < t->text_bytes)
-        return fail(e, BV_ERR_INVALID_ARG, who + "dst_capacity " + std::to_string(dst_capacity) + " < the text's " + std::to_string(t->text_bytes) + " bytes");
-    if (t->text_bytes == 0) return BV_OK;
-    if (!dst) return fail(e, BV_ERR_INVALID_ARG, who + "null dst");
-    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
-    BV_HIP(e, hipSetDevice(t->device));
-    BV_HIP(e, hipMemcpyAsync(dst, t->d_text, t->text_bytes, dst_mem_kind == BV_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-    BV_HIP(e, hipStreamSynchronize(st));
-    return BV_OK;
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_vcf_fetch: null engine");
+    return device_text_fetch(e, "bv_engine_vcf_fetch: ", "bv_engine_vcf_format", vcf_text(e->vcf), dst, dst_capacity, dst_mem_kind, stream_);
 }
 
 int bv_engine_vcf_deflate(bv_engine *e, const uint64_t *block_off, uint32_t n_blocks, int level, uint8_t *dst, uint64_t dst_capacity,
                           uint64_t *member_off, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_vcf_deflate: null engine");
-    BvVcfState *t = e->vcf;
-    if (!t || !t->formatted) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_vcf_deflate: no bv_engine_vcf_format before it");
-    // the one encoder path: the formatted text is device text to bv_engine_bgzf_deflate_level, which checks the rest
-    return bv_engine_bgzf_deflate_level(e, t->d_text, t->text_bytes, BV_MEM_DEVICE, block_off, n_blocks, level, dst, dst_capacity, member_off, stream_);
+    return device_text_deflate(e, "bv_engine_vcf_deflate: ", "bv_engine_vcf_format", vcf_text(e->vcf), block_off, n_blocks, level, dst, dst_capacity, member_off,
+                               stream_);
 }
 
 }  // extern "C"

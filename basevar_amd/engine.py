@@ -678,6 +678,7 @@ class BaseTypeEngine:
         if rc != 0:
             raise RuntimeError("bv_engine_pileup failed (%d): %s" % (rc, self._err()), rc)
         self._pileup_covered = int(n_cov.value)
+        self._pileup_window_rows = int(window[1]) - int(window[0]) + 1
         return int(n_cov.value)
 
     def pileup_fetch(self):
@@ -740,6 +741,83 @@ class BaseTypeEngine:
         ms1, ms2 = self.kernel_ms() if n else (0.0, 0.0)
         toks = {(int(t["pos"]), int(t["sample"])): text[int(t["text_off"]):int(t["text_off"]) + int(t["text_len"])].tobytes() for t in tokens}
         return PileupBatch(out, None, self.last_variant_count() if n else 0, ms1, ms2, pos, depth, toks)
+
+    # ---- batchfile rows, written on the device from piled-up planes (include/basevar_amd_pileup_text.h)
+    def pileup_text(self, chrom, first=0, n=None, tile=None):
+        """The batchfile rows of rows [first, first + n) of a tile (bv_engine_pileup_text): CHROM, pos, REF, Depth and the five
+        lists of mapq, base, quality, rank and strand tokens, as host/pileup.hpp's pileup_rows_text writes them.  `tile` None: the
+        last pileup where it lies on the device (n None: all its rows from `first`).  Else a dict: cell, qual, mapq (uint8) and
+        rank (uint16) planes [rows][pitch] as numpy arrays (host) or torch tensors on the engine's device, beg, n_samples, tokens
+        (_capi.PILEUP_TOKEN_DTYPE, ascending by (pos, sample)) and text (uint8, the tokens' text).  The text stays on the device
+        (pileup_text_fetch, pileup_text_deflate); returns row_off uint64 [n + 1]."""
+        chrom = chrom.encode() if isinstance(chrom, str) else bytes(chrom)
+        keep, t = [], None
+        if tile is not None:
+            planes = [tile[k] for k in ("cell", "qual", "mapq", "rank")]
+            on_device = hasattr(planes[0], "data_ptr")
+            if on_device:
+                if any(not p.is_cuda or not p.is_contiguous() for p in planes):
+                    raise ValueError("pileup_text: contiguous planes, all on the device or all numpy arrays")
+                rows, pitch = int(planes[0].shape[0]), int(planes[0].shape[1])
+                ptrs = [int(p.data_ptr()) for p in planes]
+            else:
+                planes = [np.ascontiguousarray(p, np.uint16 if i == 3 else np.uint8) for i, p in enumerate(planes)]
+                rows, pitch = planes[0].shape
+                ptrs = [p.ctypes.data for p in planes]
+            tok = np.ascontiguousarray(tile.get("tokens", np.zeros(0, _capi.PILEUP_TOKEN_DTYPE)), _capi.PILEUP_TOKEN_DTYPE)
+            text = np.ascontiguousarray(tile.get("text", np.zeros(0, np.uint8)), np.uint8)
+            keep = [planes, tok, text]
+            t = _capi.PileupTile(ptrs[0], ptrs[1], ptrs[2], ptrs[3], tok.ctypes.data if tok.size else None, text.ctypes.data if text.size else None,
+                                 int(tile.get("pitch", pitch)), int(tok.size), int(text.size), int(tile["beg"]), int(tile.get("rows", rows)), int(tile["n_samples"]),
+                                 int(tile.get("mem_kind", _capi.BV_MEM_DEVICE if on_device else _capi.BV_MEM_HOST)))
+            total = int(t.rows)
+        else:
+            total = getattr(self, "_pileup_window_rows", 0)
+        n = max(total - int(first), 0) if n is None else int(n)
+        req = _capi.PileupText(C.pointer(t) if t is not None else None, chrom, len(chrom), int(first), n, 0)
+        row_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_pileup_text(self._h, C.byref(req), row_off.ctypes.data, None)
+        del keep
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_text failed (%d): %s" % (rc, self._err()), rc)
+        self._ptext_bytes = int(row_off[n])
+        return row_off
+
+    def pileup_text_fetch(self, dst_ptr=0, dst_capacity=0):
+        """The text of the last pileup_text (bv_engine_pileup_text_fetch) as a uint8 array; with `dst_ptr`, a device pointer of
+        `dst_capacity` bytes, it is copied there instead and None is returned."""
+        if dst_ptr:
+            rc = self._lib.bv_engine_pileup_text_fetch(self._h, int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, None)
+            text = None
+        else:
+            text = np.zeros(getattr(self, "_ptext_bytes", 0), dtype=np.uint8)
+            rc = self._lib.bv_engine_pileup_text_fetch(self._h, text.ctypes.data if text.size else None, int(text.size), _capi.BV_MEM_HOST, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_text_fetch failed (%d): %s" % (rc, self._err()), rc)
+        return text
+
+    def pileup_text_deflate(self, block_bytes=0xff00, block_off=None, level="fast"):
+        """bgzf_deflate of the last pileup_text's text, read where it lies on the device (bv_engine_pileup_text_deflate): (members,
+        member_off) as bgzf_deflate returns them, byte for byte what it returns for the fetched text."""
+        size = getattr(self, "_ptext_bytes", 0)
+        if block_off is None:
+            if not 1 <= int(block_bytes) <= 0xff00:
+                raise ValueError("pileup_text_deflate: block_bytes is 1 to 0xff00")
+            off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
+        else:
+            off = np.ascontiguousarray(block_off, dtype=np.uint64)
+        n = int(off.size) - 1
+        if n < 0:
+            raise ValueError("pileup_text_deflate: block_off needs n + 1 entries")
+        if level not in _capi.DEFLATE_LEVELS:
+            raise ValueError("pileup_text_deflate: level is 'fast' or 'small'")
+        members = np.zeros(size + 31 * n, dtype=np.uint8)
+        member_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_pileup_text_deflate(self._h, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level], members.ctypes.data if members.size else None,
+                                                     int(members.size), member_off.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_text_deflate failed (%d): %s" % (rc, self._err()), rc)
+        return members[:int(member_off[n])], member_off
 
     def deflate_code_lengths(self, counts, limit):
         """The code lengths the small deflate level gives an alphabet with these counts (bv_engine_deflate_code_lengths, a

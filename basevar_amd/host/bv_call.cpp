@@ -46,6 +46,7 @@
 #include "batch_producer.hpp"
 #include "batchfile_fast.hpp"
 #include "pileup.hpp"
+#include "raw_reads.hpp"
 #include "basevar_amd_pileup.h"
 #include "bgzf_tabix.hpp"
 #include "vcf_emit.hpp"
@@ -630,37 +631,18 @@ int main(int argc, char **argv) {
                     auto check = [&](int rc) { if (rc != BV_OK) throw std::runtime_error(bv_last_error(pe)); };
                     check(bv_engine_pileup_set_reference(pe, fa_seq.data(), fa_seq.size()));
                     const uint32_t window = std::min<uint32_t>(bvamd::pileup_window(bams.size()), bv_pileup_max_rows());
-                    const size_t n = bams.size();
                     for (uint32_t sb = beg; sb <= end && still_ok(); sb += bvamd::PILEUP_STEP) {
                         const uint32_t se = std::min(end, sb + bvamd::PILEUP_STEP - 1);
                         for (uint32_t wb = sb; wb <= se && still_ok(); wb += window) {
                             const uint32_t we = std::min(se, wb + window - 1);
                             // every sample's records of the fetch, undecoded, on `--thread` threads
                             const double tr0 = StageClock::now();
-                            const uint32_t lo = wb > bvamd::PILEUP_PAD ? wb - bvamd::PILEUP_PAD : 1, hi = we + bvamd::PILEUP_PAD;
-                            std::vector<std::vector<uint8_t>> per(n);
-                            std::vector<int> tids(n, -1);
-                            std::atomic<size_t> next_sample(0);
-                            parallel_ranges((size_t)std::max(1, threads), threads, [&](size_t, size_t, size_t) {
-                                for (size_t i; (i = next_sample.fetch_add(1)) < n;) {
-                                    bvamd::BamPool::Handle h = pileup_pool->get(i);
-                                    tids[i] = h.bf->tid_of(ref_id);
-                                    if (!h.bf->fetch(tids[i], (int64_t)lo - 1, (int64_t)hi)) continue;
-                                    while (h.bf->next_raw(per[i]) >= 0) {}
-                                }
-                            });
-                            int tid = -1;
-                            std::vector<uint8_t> records;
-                            std::vector<uint64_t> run_off(1, 0);
-                            std::vector<uint32_t> run_sample;
-                            for (size_t i = 0; i < n; ++i) {
-                                if (tids[i] < 0 || per[i].empty()) continue;
-                                if (tid >= 0 && tids[i] != tid) throw std::runtime_error("[ERROR] --pileup device needs BAM files that number " + ref_id + " alike: " + bams[i]);
-                                tid = tids[i];
-                                records.insert(records.end(), per[i].begin(), per[i].end());
-                                run_off.push_back(records.size());
-                                run_sample.push_back((uint32_t)i);
-                            }
+                            bvamd::WindowReads reads;
+                            bvamd::read_window_raw(*pileup_pool, bams, ref_id, wb, we, threads, reads);
+                            const int tid = reads.tid;
+                            const std::vector<uint8_t> &records = reads.records;
+                            const std::vector<uint64_t> &run_off = reads.run_off;
+                            const std::vector<uint32_t> &run_sample = reads.run_sample;
                             const double tp0 = StageClock::now();
                             clk.read += tp0 - tr0;
                             reads_bytes += records.size();

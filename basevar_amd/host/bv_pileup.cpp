@@ -1,10 +1,17 @@
 // bv_pileup.cpp -- batchfile creation phase of `basevar basetype` (_create_batchfiles ->
 // __create_a_batchfile, src/basetype_caller.cpp:412-470, 800-874) without htslib: BAM files of one
 // batch of samples + the reference FASTA + a region -> one reference-format batchfile, which
-// `bv_call --batchfiles` (or the reference's own calling phase) consumes.  Host-only: no GPU involved.
+// `bv_call --batchfiles` (or the reference's own calling phase) consumes.  Host-only by default: no GPU involved.
 //
 //   bv_pileup -R ref.fa[.gz] --regions CHR:BEG-END [--mapq 10] -I a.bam [-I b.bam ...] [-L bam.list]
 //             [--filename-has-samplename] [--no-index] [--thread T] [--window POSITIONS] -o out.bf[.gz]
+//             [--rows host|device] [--deflate-level fast|small] [--rows-per-call N]
+//
+// --rows device (builds with -DBV_PILEUP_DEVICE; the engine library beside the tool is loaded on demand, so the default route
+// needs neither it nor a GPU): the host threads read the samples' raw records, one engine piles them up
+// (bv_engine_pileup) and writes the rows where the planes lie (bv_engine_pileup_text, include/basevar_amd_pileup_text.h), a
+// sub-range of rows a call; a `.gz` output takes each sub-range as BGZF members deflated on the device, a plain one as text.  The
+// inflated output is the default route's byte for byte; neither --window nor --rows-per-call changes it.
 //
 // Sample ids come from the first @RG SM tag of each BAM (BamHeader::get_sample_name) or, with
 // --filename-has-samplename, from the file name up to its first '.' (src/basetype_caller.cpp:262-294).
@@ -19,6 +26,13 @@
 
 #include "bgzf_tabix.hpp"
 #include "pileup.hpp"
+#ifdef BV_PILEUP_DEVICE
+#include <dlfcn.h>
+#include <unistd.h>
+
+#include "../../include/basevar_amd_pileup_text.h"
+#include "raw_reads.hpp"
+#endif
 
 namespace {
 [[noreturn]] void die(const std::string &m) {
@@ -29,6 +43,116 @@ std::string basename_of(const std::string &p) {
     const size_t s = p.find_last_of('/');
     return s == std::string::npos ? p : p.substr(s + 1);
 }
+
+#ifdef BV_PILEUP_DEVICE
+// The engine library, loaded when --rows device asks for it: $BASEVAR_AMD_LIB, else libbasevar_amd.so beside this program
+struct EngineLib {
+    void *so = nullptr;
+    decltype(&bv_engine_create) create = nullptr;
+    decltype(&bv_engine_destroy) destroy = nullptr;
+    decltype(&bv_last_error) last_error = nullptr;
+    decltype(&bv_pileup_max_rows) max_rows = nullptr;
+    decltype(&bv_engine_pileup_set_reference) set_reference = nullptr;
+    decltype(&bv_engine_pileup) pileup = nullptr;
+    decltype(&bv_engine_pileup_text) text = nullptr;
+    decltype(&bv_engine_pileup_text_fetch) fetch = nullptr;
+    decltype(&bv_engine_pileup_text_deflate) deflate = nullptr;
+
+    template <typename F>
+    void sym(F &f, const char *name) {
+        f = reinterpret_cast<F>(dlsym(so, name));
+        if (!f) throw std::runtime_error(std::string("[ERROR] --rows device: ") + name + " is not in the engine library");
+    }
+    void load() {
+        std::string path;
+        if (const char *env = std::getenv("BASEVAR_AMD_LIB")) path = env;
+        if (path.empty()) {
+            char exe[4096];
+            const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
+            if (n <= 0) throw std::runtime_error("[ERROR] --rows device: cannot find this program's directory");
+            path = std::string(exe, (size_t)n);
+            path = path.substr(0, path.find_last_of('/') + 1) + "libbasevar_amd.so";
+        }
+        so = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!so) throw std::runtime_error(std::string("[ERROR] --rows device: ") + dlerror());
+        sym(create, "bv_engine_create"); sym(destroy, "bv_engine_destroy"); sym(last_error, "bv_last_error"); sym(max_rows, "bv_pileup_max_rows");
+        sym(set_reference, "bv_engine_pileup_set_reference"); sym(pileup, "bv_engine_pileup"); sym(text, "bv_engine_pileup_text");
+        sym(fetch, "bv_engine_pileup_text_fetch"); sym(deflate, "bv_engine_pileup_text_deflate");
+    }
+};
+
+// The rows of the region through the engine; `members(bytes, member_off, n)` / `plain(text)` receive a sub-range each
+template <typename Members, typename Plain>
+bool device_rows(const std::vector<std::string> &bams, const std::string &fa_seq, const std::string &ref_id, uint32_t beg, uint32_t end, int mapq,
+                 int threads, uint32_t window, uint32_t rows_per_call, int level, bool gz, Members members, Plain plain) {
+    EngineLib L;
+    L.load();
+    bv_engine_config cfg{};
+    cfg.device = 0; cfg.max_sites = 64; cfg.max_samples = (uint32_t)bams.size(); cfg.min_af = 0.01;
+    bv_engine *e = nullptr;
+    if (L.create(&cfg, &e) != BV_OK) throw std::runtime_error(std::string("[ERROR] --rows device: ") + L.last_error(nullptr));
+    auto check = [&](int rc) { if (rc != BV_OK) throw std::runtime_error(L.last_error(e)); };
+    bool has_data = false;
+    try {
+        check(L.set_reference(e, fa_seq.data(), fa_seq.size()));
+        bvamd::BamPool pool(bams, true);
+        const size_t n = bams.size();
+        if (window == 0) window = bvamd::pileup_window(n);
+        window = std::min<uint32_t>(window, L.max_rows());
+        std::vector<uint8_t> buf;
+        std::vector<uint64_t> row_off, block_off, member_off;
+        for (uint32_t sb = beg; sb <= end; sb += bvamd::PILEUP_STEP) {
+            const uint32_t se = std::min(end, sb + bvamd::PILEUP_STEP - 1);
+            for (uint32_t wb = sb; wb <= se; wb += window) {
+                const uint32_t we = std::min(se, wb + window - 1), rows = we - wb + 1;
+                bvamd::WindowReads reads;
+                bvamd::read_window_raw(pool, bams, ref_id, wb, we, threads, reads);
+                // (a window without any run is piled up all the same: every row of it is placeholders)
+                bv_pileup_reads in{};
+                in.records = reads.records.data(); in.run_off = reads.run_off.data(); in.run_sample = reads.run_sample.data();
+                in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)reads.run_sample.size(); in.n_samples = (uint32_t)n;
+                in.tid = std::max(reads.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
+                in.mem_kind = BV_MEM_HOST;
+                uint32_t n_cov = 0;
+                check(L.pileup(e, &in, &n_cov, nullptr));
+                has_data = has_data || n_cov != 0;
+                // rows a call from a fixed text budget: 16 bytes a cell and the window's token text bound a sub-range's text
+                uint32_t step = rows_per_call;
+                if (step == 0) step = (uint32_t)std::max<uint64_t>(1, ((uint64_t)1 << 28) / (16ull * std::max<size_t>(n, 1)));
+                for (uint32_t first = 0; first < rows; first += step) {
+                    const uint32_t cnt = std::min(step, rows - first);
+                    bv_pileup_text req{};
+                    req.tile = nullptr; req.chrom = ref_id.data(); req.chrom_len = (uint32_t)ref_id.size(); req.first_row = first; req.n_rows = cnt;
+                    row_off.assign((size_t)cnt + 1, 0);
+                    check(L.text(e, &req, row_off.data(), nullptr));
+                    const uint64_t bytes = row_off[cnt];
+                    if (gz) {
+                        block_off.clear();
+                        for (uint64_t o = 0; o < bytes; o += bvamd::BgzfWriter::kBlock) block_off.push_back(o);
+                        block_off.push_back(bytes);
+                        const uint32_t nb = (uint32_t)block_off.size() - 1;
+                        buf.resize(bytes + 31ull * nb);
+                        member_off.assign((size_t)nb + 1, 0);
+                        check(L.deflate(e, block_off.data(), nb, level, buf.data(), buf.size(), member_off.data(), nullptr));
+                        members(buf.data(), member_off.data(), (size_t)nb);
+                    } else {
+                        buf.resize(bytes);
+                        check(L.fetch(e, buf.data(), buf.size(), BV_MEM_HOST, nullptr));
+                        plain(buf.data(), (size_t)bytes);
+                    }
+                }
+                if (we == UINT32_MAX) break;
+            }
+            if (se == UINT32_MAX) break;
+        }
+    } catch (...) {
+        L.destroy(e);
+        throw;
+    }
+    L.destroy(e);
+    return has_data;
+}
+#endif
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -38,6 +162,8 @@ int main(int argc, char **argv) {
     int threads = 1;
     uint32_t window = 0;  // positions per pileup window (0 = from a cell budget); the rows do not depend on it
     bool name_from_file = false, use_index = true;
+    std::string rows_arg = "host", level_arg = "fast";
+    uint32_t rows_per_call = 0;  // --rows device: rows a bv_engine_pileup_text call (0 = from a text budget); the rows do not depend on it
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> std::string { if (i + 1 >= argc) die("missing value for " + a); return argv[++i]; };
@@ -51,6 +177,9 @@ int main(int argc, char **argv) {
         else if (a == "--no-index") use_index = false;
         else if (a == "-t" || a == "--thread") threads = std::stoi(next());
         else if (a == "--window") window = (uint32_t)std::stoul(next());
+        else if (a == "--rows") rows_arg = next();
+        else if (a == "--deflate-level") level_arg = next();
+        else if (a == "--rows-per-call") rows_per_call = (uint32_t)std::stoul(next());
         else die("unknown argument " + a);
     }
     if (!bam_list.empty()) {  // get_firstcolumn_from_file, src/basetype_caller.cpp:114-117
@@ -63,6 +192,8 @@ int main(int argc, char **argv) {
             bams.push_back(e == std::string::npos ? line : line.substr(0, e));
         }
     }
+    if (rows_arg != "host" && rows_arg != "device") die("--rows wants host or device");
+    if (level_arg != "fast" && level_arg != "small") die("--deflate-level wants fast or small");
     if (bams.empty() || fasta.empty() || regions.empty() || out_path.empty())
         die("usage: bv_pileup -R ref.fa --regions CHR:BEG-END [--mapq Q] -I a.bam [-I ...] [-L list] -o out.bf[.gz]");
     try {
@@ -101,7 +232,23 @@ int main(int argc, char **argv) {
             if (gz) zf.write(s);
             else if (std::fwrite(s.data(), 1, s.size(), pf) != s.size()) throw std::runtime_error("[ERROR] fail to write data");
         };
-        const bool has_data = bvamd::create_a_batchfile(bams, sample_ids, fa_seq, std::make_tuple(ref_id, beg, end), mapq, sink, use_index, threads, window);
+        bool has_data = false;
+        if (rows_arg == "device") {
+#ifdef BV_PILEUP_DEVICE
+            // the header goes through the host writer; flush(): the device's members follow on a member boundary
+            sink(bvamd::batchfile_header(sample_ids));
+            if (gz) zf.flush();
+            has_data = device_rows(bams, fa_seq, ref_id, beg, end, mapq, threads, window, rows_per_call, level_arg == "small" ? 1 : 0, gz,
+                                   [&](const uint8_t *m, const uint64_t *off, size_t nm) { zf.write_members(m, off, nm); },
+                                   [&](const uint8_t *p, size_t nb) {
+                                       if (nb && std::fwrite(p, 1, nb, pf) != nb) throw std::runtime_error("[ERROR] fail to write data");
+                                   });
+#else
+            die("[ERROR] --rows device: this bv_pileup was built without the device route");
+#endif
+        } else {
+            has_data = bvamd::create_a_batchfile(bams, sample_ids, fa_seq, std::make_tuple(ref_id, beg, end), mapq, sink, use_index, threads, window);
+        }
         if (gz) zf.close(); else std::fclose(pf);
         std::cerr << "[INFO] " << out_path << ": " << bams.size() << " samples, " << ref_id << ":" << beg << "-" << end
                   << (has_data ? "" : " (no covering reads)") << std::endl;
