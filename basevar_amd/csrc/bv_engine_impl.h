@@ -1,5 +1,7 @@
 // bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_rows.hip, bv_engine_tiles.hip,
-// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip, bv_pileup_text.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  Host-only; the
+// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip, bv_pileup_text.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  (bv_vcf.hip and
+// bv_pileup_text.hip share two more headers: bv_device_text.h, the text they leave on the device, and bv_text_image.h, the
+// kernels' side of writing it.)  Host-only; the
 // files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
 #pragma once
 

@@ -13,12 +13,11 @@
 //          the heads meanwhile (they need the depths and n_rows bytes of the reference).
 //   write  the tile's four plane rows go to LDS with 16-byte loads; then list by list, 64 samples a step: a wave prefix sum of
 //          the token lengths gives lane l its token's place in an LDS image of the tile's piece of the list, which is laid out
-//          as the text is modulo 16.  A step without a claimed cell (a 64-bit ballot) skips the prefix sum: its tokens are the
-//          2-byte placeholders at 2 l.  The image is stored with 16-byte stores over the aligned interior and byte stores on the
-//          at most 15 bytes at each edge: neighbouring tiles, lists and rows share 16-byte words, and every byte of the text has
-//          exactly one writer.  The image has kImage bytes: where a list's piece is longer -- ranks of five digits, indel tokens
-//          of any length -- the whole words are stored, the rest moves to the image's front and the list goes on; a step whose
-//          tokens exceed the image goes token by token, the wave across a token's bytes.  Tile 0 copies the head.
+//          as the text is modulo 16 (bv_text_image.h).  A step without a claimed cell (a 64-bit ballot) skips the prefix sum: its
+//          tokens are the 2-byte placeholders at 2 l.  Neighbouring tiles, lists and rows share 16-byte words, and every byte of
+//          the text has exactly one writer.  The image has kImage bytes: where a list's piece is longer -- ranks of five digits,
+//          indel tokens of any length -- the whole words are stored, the rest moves to the image's front and the list goes on; a
+//          step whose tokens exceed the image goes token by token, the wave across a token's bytes.  Tile 0 copies the head.
 // No atomics, no scratch, vector stores only.  Cells at pitch positions at or beyond n_samples are loaded with their 16-byte
 // word and never looked at.
 #include <hip/hip_runtime.h>
@@ -33,6 +32,7 @@
 #include "bv_device_text.h"
 #include "bv_pileup_core.h"
 #include "bv_pileup_text_core.h"
+#include "bv_text_image.h"
 
 using namespace bv_impl;
 
@@ -71,33 +71,20 @@ struct TileRows {
     uint16_t rank[BV_PTEXT_TILE];
 };
 
-// 16 bytes of a plane row, or zeros where the tile has no sample there
-__device__ __forceinline__ uint4 load16(const void *p, bool in) {
-    if (!in) return make_uint4(0, 0, 0, 0);
-    return *reinterpret_cast<const uint4 *>(p);
-}
-
 // the tile's piece of the four plane rows to LDS; lanes beyond the tile's samples store zeros (rank 0: never looked at anyway)
 __device__ __forceinline__ void tile_stage(TileRows *t, const PtextArgs &a, uint32_t k, uint32_t tile, uint32_t cnt, uint32_t lane) {
-    const size_t at = (size_t)(a.row0 + k) * a.pitch + (size_t)tile * BV_PTEXT_TILE + 16u * lane;
-    const bool in = 16u * lane < cnt;
-    reinterpret_cast<uint4 *>(t->cell)[lane] = load16(a.cell + at, in);
-    reinterpret_cast<uint4 *>(t->qual)[lane] = load16(a.qual + at, in);
-    reinterpret_cast<uint4 *>(t->mapq)[lane] = load16(a.mapq + at, in);
-    reinterpret_cast<uint4 *>(t->rank)[2u * lane] = load16(a.rank + at, in);
-    reinterpret_cast<uint4 *>(t->rank)[2u * lane + 1u] = load16(a.rank + at + 8u, in);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
+    const size_t at = (size_t)(a.row0 + k) * a.pitch + (size_t)tile * BV_PTEXT_TILE;
+    reinterpret_cast<uint4 *>(t->cell)[lane] = tile_load16(a.cell + at, cnt, lane);
+    reinterpret_cast<uint4 *>(t->qual)[lane] = tile_load16(a.qual + at, cnt, lane);
+    reinterpret_cast<uint4 *>(t->mapq)[lane] = tile_load16(a.mapq + at, cnt, lane);
+    tile_load16x2(a.rank + at, cnt, lane, reinterpret_cast<uint4 *>(t->rank) + 2u * lane);
 }
 
 __global__ __launch_bounds__(64) void bv_ptext_count_kernel(PtextArgs a) {
     __shared__ __attribute__((aligned(16))) TileRows rows;
-    const uint32_t k = blockIdx.x / a.n_tiles, tile = blockIdx.x % a.n_tiles, lane = threadIdx.x;
+    const auto [k, tile, cnt] = tile_of_block(a.n_tiles, a.n_samples, BV_PTEXT_TILE);
+    const uint32_t lane = threadIdx.x, pos = a.pos0 + k;
     if (k >= a.n_rows) return;
-    const uint32_t cnt = min(BV_PTEXT_TILE, a.n_samples - tile * BV_PTEXT_TILE), pos = a.pos0 + k;
     tile_stage(&rows, a, k, tile, cnt, lane);
     __syncthreads();
     uint32_t m = 0, b = 0, r = 0, miss = kNoSample;
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(64) void bv_ptext_count_kernel(PtextArgs a) {
         }
     }
     m = wave_sum(m); b = wave_sum(b); r = wave_sum(r);
-    for (int d = 32; d > 0; d >>= 1) miss = min(miss, (uint32_t)__shfl_xor(miss, d, 64));
+    miss = wave_min(miss);
     if (lane == 0) a.tile_sum[(size_t)k * a.n_tiles + tile] = make_uint4(m, b, r, miss);
 }
 
@@ -131,49 +118,6 @@ __global__ __launch_bounds__(256) void bv_ptext_scan_kernel(PtextArgs a) {
         run.x += v.x; run.y += v.y; run.z += v.z; run.w = min(run.w, v.w);
     }
     a.row_sum[k] = run;
-}
-
-// A piece of the text under construction: image[i] is the byte of the text at g + i, and g is 16-byte aligned.  The piece owns
-// image [lo, fill); `left` bytes of the text are the piece's to write, whatever the planes say by now.  All of it is wave-uniform.
-struct Piece {
-    uint8_t *g;
-    uint32_t lo, fill;
-    uint64_t left;
-};
-
-__device__ __forceinline__ void piece_open(Piece &p, uint8_t *text, uint64_t dst, uint64_t bytes) {
-    const uint32_t shift = (uint32_t)(dst & 15u);
-    p.g = text + (dst - shift);
-    p.lo = p.fill = shift;
-    p.left = bytes;
-}
-
-// Store the piece's bytes: all of them (last), or its whole 16-byte words, the rest moving to the image's front.
-__device__ __forceinline__ void piece_flush(Piece &p, uint8_t *image, bool last, uint32_t lane) {
-    __syncthreads();
-    const uint32_t lo = p.lo, hi = lo + (uint32_t)min((uint64_t)(p.fill - lo), p.left);
-    const uint32_t w_lo = (lo + 15u) / 16u, w_hi = hi / 16u;
-    if (last) {
-        const uint32_t lead_end = min(16u * w_lo, hi), tail_at = max(16u * w_hi, lead_end);
-        for (uint32_t i = lo + lane; i < lead_end; i += 64u) p.g[i] = image[i];
-        for (uint32_t w = w_lo + lane; w < w_hi; w += 64u) reinterpret_cast<uint4 *>(p.g)[w] = reinterpret_cast<const uint4 *>(image)[w];
-        for (uint32_t i = tail_at + lane; i < hi; i += 64u) p.g[i] = image[i];
-        p.left -= hi - lo;
-        p.lo = p.fill = hi;
-        return;
-    }
-    const uint32_t cut = 16u * w_hi;  // the last word boundary inside the piece
-    if (cut <= lo) { p.fill = hi; return; }
-    for (uint32_t i = lo + lane; i < 16u * w_lo; i += 64u) p.g[i] = image[i];
-    for (uint32_t w = w_lo + lane; w < w_hi; w += 64u) reinterpret_cast<uint4 *>(p.g)[w] = reinterpret_cast<const uint4 *>(image)[w];
-    const uint32_t keep = hi - cut;  // < 16
-    const uint8_t v = lane < keep ? image[cut + lane] : (uint8_t)0;
-    __syncthreads();
-    if (lane < keep) image[lane] = v;
-    p.g += cut;
-    p.left -= cut - lo;
-    p.lo = 0; p.fill = keep;
-    __syncthreads();
 }
 
 // One list of the tile: LIST 0 .. 4 = M B Q R S
@@ -204,12 +148,7 @@ __device__ __forceinline__ void write_list(const PtextArgs &a, const TileRows &r
                 const uint64_t t = bv_ptext_find(a.tokens, a.n_tokens, pos, sample);
                 if (t != a.n_tokens) { is_tok = true; len = a.tokens[t].text_len; tok_off = a.tokens[t].text_off; }  // (the count pass refused the row otherwise)
             }
-            uint32_t incl = active ? len + 1u : 0u;
-            const uint32_t mine = incl;
-            for (uint32_t d = 1; d < 64u; d <<= 1) {
-                const uint32_t up = __shfl_up(incl, d, 64);
-                if (lane >= d) incl += up;
-            }
+            const uint32_t mine = active ? len + 1u : 0u, incl = wave_incl_scan(mine, lane);
             at = incl - mine;
             total = __shfl(incl, 63, 64);
         }
@@ -254,16 +193,15 @@ __device__ __forceinline__ void write_list(const PtextArgs &a, const TileRows &r
 __global__ __launch_bounds__(64) void bv_ptext_write_kernel(PtextArgs a) {
     __shared__ __attribute__((aligned(16))) TileRows rows;
     __shared__ __attribute__((aligned(16))) uint8_t image[kImage];
-    const uint32_t k = blockIdx.x / a.n_tiles, tile = blockIdx.x % a.n_tiles, lane = threadIdx.x;
+    const auto [k, tile, cnt] = tile_of_block(a.n_tiles, a.n_samples, BV_PTEXT_TILE);
+    const uint32_t lane = threadIdx.x, n = a.n_samples, pos = a.pos0 + k;
     if (k >= a.n_rows) return;
-    const uint32_t n = a.n_samples, cnt = min(BV_PTEXT_TILE, n - tile * BV_PTEXT_TILE), pos = a.pos0 + k;
     tile_stage(&rows, a, k, tile, cnt, lane);
     const uint64_t head_at = a.head_off[k], head_bytes = a.head_off[k + 1] - head_at, row_at = a.row_off[k];
     const uint4 before = a.tile_sum[(size_t)k * a.n_tiles + tile], row = a.row_sum[k];
     const uint4 next = tile + 1u < a.n_tiles ? a.tile_sum[(size_t)k * a.n_tiles + tile + 1u] : row;
     __syncthreads();
-    if (tile == 0)
-        for (uint64_t i = lane; i < head_bytes; i += 64u) a.text[row_at + i] = a.head[head_at + i];
+    if (tile == 0) head_copy(a.text + row_at, a.head + head_at, head_bytes, lane);
     // where the five lists of the row begin, and the tile's piece of each: the samples before it took their tokens and one byte each
     const uint64_t first = (uint64_t)tile * BV_PTEXT_TILE;
     const uint64_t at_m = row_at + head_bytes, at_b = at_m + row.x + n, at_q = at_b + row.y + n, at_r = at_q + 2ull * n, at_s = at_r + row.z + n;
@@ -278,32 +216,23 @@ __global__ __launch_bounds__(64) void bv_ptext_write_kernel(PtextArgs a) {
 
 // Per-engine state of bv_engine_pileup_text: the formatted text and what the kernels read beside the planes.
 struct BvPtextState {
-    int device = 0;
-    uint8_t *d_text = nullptr;   // the rows back to back, and room for the words a reader takes around them
+    DeviceText text;             // the formatted rows
     uint8_t *d_tok = nullptr;    // the tokens of the call's rows; behind them an explicit tile's token text
     uint8_t *d_head = nullptr;   // head_off u64 [n + 1], row_off u64 [n + 1], the heads
     uint8_t *d_sum = nullptr;    // tile_sum uint4 [n][tiles], row_sum uint4 [n], depth + max_rank u32 [2 n], ref bytes [n]
     uint8_t *d_rows = nullptr;   // an explicit tile's rows of the call, packed: cell, qual, mapq [n][P], rank [n][P]
-    size_t text_cap = 0, tok_cap = 0, head_cap = 0, sum_cap = 0, rows_cap = 0;
-    bool formatted = false;      // d_text holds text_bytes bytes of a completed bv_engine_pileup_text
-    uint64_t text_bytes = 0;
+    size_t tok_cap = 0, head_cap = 0, sum_cap = 0, rows_cap = 0;
 };
 
 void bv_ptext_state_free(BvPtextState *t) {
     if (!t) return;
-    (void)hipSetDevice(t->device);
-    for (uint8_t *b : {t->d_text, t->d_tok, t->d_head, t->d_sum, t->d_rows})
+    (void)hipSetDevice(t->text.device);
+    for (uint8_t *b : {t->text.d_text, t->d_tok, t->d_head, t->d_sum, t->d_rows})
         if (b) (void)hipFree(b);
     delete t;
 }
 
 namespace {
-
-DeviceText ptext_text(const BvPtextState *t) {
-    DeviceText d;
-    if (t) { d.device = t->device; d.d_text = t->d_text; d.bytes = t->text_bytes; d.formatted = t->formatted; }
-    return d;
-}
 
 // the tile of a call, resolved: device planes of the engine's pileup, or an explicit tile's host / device planes
 struct TileView {
@@ -321,7 +250,7 @@ struct TileView {
 int ptext_format(bv_engine *e, BvPtextState *t, const bv_pileup_text *in, const TileView &v, const BvPileupView &pv, uint64_t *row_off, hipStream_t st) {
     const std::string who = "bv_engine_pileup_text: ";
     const uint32_t n = in->n_rows, N = v.n_samples, n_tiles = (N + BV_PTEXT_TILE - 1u) / BV_PTEXT_TILE, pos0 = v.beg + in->first_row;
-    BV_HIP(e, hipSetDevice(t->device));
+    BV_HIP(e, hipSetDevice(t->text.device));
     // the tokens of the rows: [t_lo, t_hi) by position
     const BvPtextToken *t_lo = std::lower_bound(v.tokens, v.tokens + v.n_tokens, pos0, [](const BvPtextToken &x, uint32_t p) { return x.pos < p; });
     const BvPtextToken *t_hi = std::lower_bound(t_lo, v.tokens + v.n_tokens, (uint64_t)pos0 + n, [](const BvPtextToken &x, uint64_t p) { return x.pos < p; });
@@ -414,21 +343,19 @@ int ptext_format(bv_engine *e, BvPtextState *t, const bv_pileup_text *in, const 
     }
     const uint64_t total = off[2ull * n + 1];
     const size_t o_heads = 16ull * (n + 1);
-    // (16 bytes behind the text: bv_deflate.hip's kernels read the whole aligned words around a block)
-    rc = grow_device(e, &t->d_text, &t->text_cap, up256(total + 16));
+    rc = device_text_reserve(e, t->text, total);
     if (rc == BV_OK) rc = grow_device(e, &t->d_head, &t->head_cap, up256(o_heads + heads.size()));
     if (rc != BV_OK) return rc;
     BV_HIP(e, hipMemcpyAsync(t->d_head, off.data(), o_heads, hipMemcpyHostToDevice, st));
     BV_HIP(e, hipMemcpyAsync(t->d_head + o_heads, heads.data(), heads.size(), hipMemcpyHostToDevice, st));
     a.head_off = reinterpret_cast<const uint64_t *>(t->d_head); a.row_off = a.head_off + (n + 1);
     a.head = t->d_head + o_heads;
-    a.text = t->d_text;
+    a.text = t->text.d_text;
     hipLaunchKernelGGL(bv_ptext_write_kernel, dim3(n * n_tiles), dim3(64), 0, st, a);
     BV_HIP(e, hipGetLastError());
     BV_HIP(e, hipStreamSynchronize(st));
     std::memcpy(row_off, off.data() + (n + 1), 8ull * (n + 1));
-    t->text_bytes = total;
-    t->formatted = true;
+    device_text_done(t->text, total);
     return BV_OK;
 }
 
@@ -441,7 +368,8 @@ uint32_t bv_pileup_text_tile_samples(void) { return BV_PTEXT_TILE; }
 int bv_engine_pileup_text(bv_engine *e, const bv_pileup_text *in, uint64_t *row_off, void *stream_) {
     const std::string who = "bv_engine_pileup_text: ";
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, who + "null engine");
-    if (e->ptext) e->ptext->formatted = false;  // whatever comes of this call, the last text is gone
+    // deliberately on entry, not behind the checks as in bv_engine_vcf_format: whatever comes of this call, the last text is gone
+    if (e->ptext) e->ptext->text.formatted = false;
     if (!in || !row_off) return fail(e, BV_ERR_INVALID_ARG, who + "null in/row_off");
     if (in->reserved_) return fail(e, BV_ERR_INVALID_ARG, who + "reserved_ must be zero");
     if (!in->chrom || in->chrom_len < 1u || in->chrom_len > 255u) return fail(e, BV_ERR_INVALID_ARG, who + "chrom must have 1 to 255 bytes");
@@ -485,25 +413,20 @@ int bv_engine_pileup_text(bv_engine *e, const bv_pileup_text *in, uint64_t *row_
     // one workgroup per (row, tile): a launch's grid has room for 2^26 of them; the sums of a row are 32-bit
     if (v.n_samples >= (1u << 28) || (uint64_t)in->n_rows * ((v.n_samples + BV_PTEXT_TILE - 1u) / BV_PTEXT_TILE) >= (1ull << 26))
         return fail(e, BV_ERR_TOO_LARGE, who + "n_rows x tiles of a row reaches 2^26: format fewer rows a call");
-    BvPtextState *t = engine_state(e, e->ptext);
-    if (in->n_rows == 0) {
-        row_off[0] = 0;
-        t->text_bytes = 0;
-        t->formatted = true;
-        return BV_OK;
-    }
+    BvPtextState *t = text_state(e, e->ptext);
+    if (in->n_rows == 0) return device_text_empty(t->text, row_off);
     return ptext_format(e, t, in, v, pv, row_off, stream_ ? (hipStream_t)stream_ : e->stream);
 }
 
 int bv_engine_pileup_text_fetch(bv_engine *e, void *dst, uint64_t dst_capacity, int dst_mem_kind, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_pileup_text_fetch: null engine");
-    return device_text_fetch(e, "bv_engine_pileup_text_fetch: ", "bv_engine_pileup_text", ptext_text(e->ptext), dst, dst_capacity, dst_mem_kind, stream_);
+    return device_text_fetch(e, "bv_engine_pileup_text_fetch: ", "bv_engine_pileup_text", e->ptext ? &e->ptext->text : nullptr, dst, dst_capacity, dst_mem_kind, stream_);
 }
 
 int bv_engine_pileup_text_deflate(bv_engine *e, const uint64_t *block_off, uint32_t n_blocks, int level, uint8_t *dst, uint64_t dst_capacity,
                                   uint64_t *member_off, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_pileup_text_deflate: null engine");
-    return device_text_deflate(e, "bv_engine_pileup_text_deflate: ", "bv_engine_pileup_text", ptext_text(e->ptext), block_off, n_blocks, level, dst, dst_capacity,
+    return device_text_deflate(e, "bv_engine_pileup_text_deflate: ", "bv_engine_pileup_text", e->ptext ? &e->ptext->text : nullptr, block_off, n_blocks, level, dst, dst_capacity,
                                member_off, stream_);
 }
 

@@ -9,10 +9,9 @@
 //          lengths and line_off are then summed on the HOST: the call cannot size the text buffer before it knows the total,
 //          so it waits for the counts in any case, and n_lines additions are nothing beside that wait.
 //   write  64 samples a step: a 64-bit ballot of "covered" gives lane l its token's place, 4 l + 13 popc(mask below l) behind
-//          the step's base, in an LDS image of the tile's output that is laid out as the text is modulo 16.  The wave then
-//          stores the image with 16-byte stores over the aligned interior and byte stores on the at most 15 bytes at each
-//          edge: neighbouring tiles and lines share 16-byte words, and every byte of the text has exactly one writer.  Tile 0
-//          copies the head, the last tile appends the '\n'.
+//          the step's base, in an LDS image of the tile's output that is laid out as the text is modulo 16 and stored as one
+//          piece (bv_text_image.h): neighbouring tiles and lines share 16-byte words, and every byte of the text has exactly
+//          one writer.  Tile 0 copies the head, the last tile appends the '\n'.
 // No atomics, no scratch, vector stores only.  Cells at pitch positions at or beyond n_samples are loaded with their 16-byte
 // word and never looked at.
 #include <hip/hip_runtime.h>
@@ -26,6 +25,7 @@
 #include "../../include/basevar_amd_diag.h"
 #include "bv_chunk_stage.h"
 #include "bv_device_text.h"
+#include "bv_text_image.h"
 #include "bv_vcf_core.h"
 
 using namespace bv_impl;
@@ -55,17 +55,14 @@ struct VcfArgs {
     uint32_t n_lines, n_samples, n_tiles;
 };
 
-// the lane's 16 bytes of a tile's row, or nothing where the tile has no sample there
-__device__ inline uint4 tile_load(const uint8_t *plane, uint64_t pitch, uint32_t row, uint32_t tile, uint32_t cnt, uint32_t lane) {
-    if (16u * lane >= cnt) return make_uint4(0, 0, 0, 0);
-    return *reinterpret_cast<const uint4 *>(plane + (size_t)row * pitch + (size_t)tile * BV_VCF_TILE + 16u * lane);
-}
+// where the tile's cells of line k begin in a plane
+__device__ inline size_t tile_at(const VcfArgs &a, uint32_t k, uint32_t tile) { return (size_t)a.row[k] * a.pitch + (size_t)tile * BV_VCF_TILE; }
 
 __global__ __launch_bounds__(64) void bv_vcf_count_kernel(VcfArgs a) {
-    const uint32_t k = blockIdx.x / a.n_tiles, tile = blockIdx.x % a.n_tiles, lane = threadIdx.x;
+    const auto [k, tile, cnt] = tile_of_block(a.n_tiles, a.n_samples, BV_VCF_TILE);
+    const uint32_t lane = threadIdx.x;
     if (k >= a.n_lines) return;
-    const uint32_t cnt = min(BV_VCF_TILE, a.n_samples - tile * BV_VCF_TILE);
-    const uint4 c = tile_load(a.cell, a.pitch, a.row[k], tile, cnt, lane);
+    const uint4 c = tile_load16(a.cell + tile_at(a, k, tile), cnt, lane);
     const uint32_t valid = 16u * lane >= cnt ? 0u : min(16u, cnt - 16u * lane);  // the lane's bytes that are samples
     const uint32_t w[4] = {c.x, c.y, c.z, c.w};
     uint32_t n = 0;
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(64) void bv_vcf_count_kernel(VcfArgs a) {
         const uint32_t bytes = v == 4u ? 0xffffffffu : (1u << (8u * v)) - 1u;
         n += __popc(~w[i] & 0x08080808u & bytes);
     }
-    for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d, 64);
+    n = wave_sum(n);
     if (lane == 0) a.tile_cov[(size_t)k * a.n_tiles + tile] = n;
 }
 
@@ -98,12 +95,12 @@ __global__ __launch_bounds__(64) void bv_vcf_write_kernel(VcfArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t s_phred[BV_VCF_TILE];
     __shared__ __attribute__((aligned(16))) uint8_t s_bp[kBpBytes];
     __shared__ uint8_t s_gt[4];
-    const uint32_t k = blockIdx.x / a.n_tiles, tile = blockIdx.x % a.n_tiles, lane = threadIdx.x;
+    const auto [k, tile, cnt] = tile_of_block(a.n_tiles, a.n_samples, BV_VCF_TILE);
+    const uint32_t lane = threadIdx.x;
     if (k >= a.n_lines) return;
-    const uint32_t cnt = min(BV_VCF_TILE, a.n_samples - tile * BV_VCF_TILE);
-    const uint32_t row = a.row[k];
-    reinterpret_cast<uint4 *>(s_cell)[lane] = tile_load(a.cell, a.pitch, row, tile, cnt, lane);
-    reinterpret_cast<uint4 *>(s_phred)[lane] = tile_load(a.phred, a.pitch, row, tile, cnt, lane);
+    const size_t at = tile_at(a, k, tile);
+    reinterpret_cast<uint4 *>(s_cell)[lane] = tile_load16(a.cell + at, cnt, lane);
+    reinterpret_cast<uint4 *>(s_phred)[lane] = tile_load16(a.phred + at, cnt, lane);
     for (uint32_t j = lane; j < kBpBytes / 16u; j += 64u) reinterpret_cast<uint4 *>(s_bp)[j] = reinterpret_cast<const uint4 *>(a.bp)[j];
     if (lane < 4u) s_gt[lane] = a.gt[4u * (size_t)k + lane];
     const uint64_t head_at = a.head_off[k], head_bytes = a.head_off[k + 1] - head_at, line_at = a.line_off[k];
@@ -126,38 +123,30 @@ __global__ __launch_bounds__(64) void bv_vcf_write_kernel(VcfArgs a) {
         if (lane == 0) image[base] = '\n';
         base += 1u;
     }
-    __syncthreads();
-    if (tile == 0)
-        for (uint64_t i = lane; i < head_bytes; i += 64u) a.text[line_at + i] = a.head[head_at + i];
-    // image[i] is the byte of the text at g + i, and g is 16-byte aligned: the tile owns [shift, base)
-    uint8_t *g = a.text + (dst0 - shift);
-    const uint32_t lo = shift, hi = base;
-    const uint32_t w_lo = (lo + 15u) / 16u, w_hi = hi / 16u;
-    const uint32_t lead_end = min(16u * w_lo, hi), tail_at = max(16u * w_hi, lead_end);
-    for (uint32_t i = lo + lane; i < lead_end; i += 64u) g[i] = image[i];
-    for (uint32_t w = w_lo + lane; w < w_hi; w += 64u) reinterpret_cast<uint4 *>(g)[w] = reinterpret_cast<const uint4 *>(image)[w];
-    for (uint32_t i = tail_at + lane; i < hi; i += 64u) g[i] = image[i];
+    if (tile == 0) head_copy(a.text + line_at, a.head + head_at, head_bytes, lane);
+    // the tile's whole output is one piece of image [shift, base): the image has room for a tile, nothing was flushed on the way
+    Piece p;
+    piece_open(p, a.text, dst0, base - shift);
+    p.fill = base;
+    piece_flush(p, image, true, lane);
 }
 
 }  // namespace
 
 // Per-engine state of bv_engine_vcf_format: the formatted text and what the kernels read beside the planes.
 struct BvVcfState {
-    int device = 0;
-    uint8_t *d_text = nullptr;   // the lines back to back, and room for the words a reader takes around them
+    DeviceText text;             // the formatted lines
     uint8_t *d_meta = nullptr;   // rows u32 [n], gt [n][4], head_off u64 [n + 1], the heads, line_off u64 [n + 1]
     uint8_t *d_cov = nullptr;    // tile_cov u32 [n][tiles], line_cov u32 [n]
     uint8_t *d_rows = nullptr;   // a host slab's named rows: cell [n][pitch], phred [n][pitch]
     uint8_t *d_bp = nullptr;     // BP [256][8]
-    size_t text_cap = 0, meta_cap = 0, cov_cap = 0, rows_cap = 0;
-    bool formatted = false;      // d_text holds text_bytes bytes of a completed bv_engine_vcf_format
-    uint64_t text_bytes = 0;
+    size_t meta_cap = 0, cov_cap = 0, rows_cap = 0;
 };
 
 void bv_vcf_state_free(BvVcfState *t) {
     if (!t) return;
-    (void)hipSetDevice(t->device);
-    for (uint8_t *b : {t->d_text, t->d_meta, t->d_cov, t->d_rows, t->d_bp})
+    (void)hipSetDevice(t->text.device);
+    for (uint8_t *b : {t->text.d_text, t->d_meta, t->d_cov, t->d_rows, t->d_bp})
         if (b) (void)hipFree(b);
     delete t;
 }
@@ -178,7 +167,7 @@ const char *check_planes(const bv_slab *s) {
 int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptRows &rows, bool host_rows, uint64_t *line_off, hipStream_t st) {
     const uint32_t n = L->n_lines, N = rows.n_samples;
     const uint32_t n_tiles = (N + BV_VCF_TILE - 1u) / BV_VCF_TILE;
-    BV_HIP(e, hipSetDevice(t->device));
+    BV_HIP(e, hipSetDevice(t->text.device));
     if (!t->d_bp) {
         std::vector<uint8_t> bp(kBpBytes);
         if (!bv_vcf_bp_table(bp.data()))
@@ -240,25 +229,16 @@ int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptR
         if (cov[k] > N) return fail(e, BV_ERR_HIP, "bv_engine_vcf_format: line " + std::to_string(k) + " came back with more covered cells than samples");
         off[k + 1] = off[k] + bv_vcf_line_bytes(L->head_off[k + 1] - L->head_off[k], N, cov[k]);
     }
-    // (16 bytes behind the text: bv_deflate.hip's kernels read the whole aligned words around a block)
-    rc = grow_device(e, &t->d_text, &t->text_cap, up256(off[n] + 16));
+    rc = device_text_reserve(e, t->text, off[n]);
     if (rc != BV_OK) return rc;
-    a.text = t->d_text;
+    a.text = t->text.d_text;
     BV_HIP(e, hipMemcpyAsync(t->d_meta + o_loff, off.data(), 8ull * (n + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bv_vcf_write_kernel, dim3(n * n_tiles), dim3(64), 0, st, a);
     BV_HIP(e, hipGetLastError());
     BV_HIP(e, hipStreamSynchronize(st));
     std::memcpy(line_off, off.data(), 8ull * (n + 1));
-    t->text_bytes = off[n];
-    t->formatted = true;
+    device_text_done(t->text, off[n]);
     return BV_OK;
-}
-
-// the formatted text as bv_device_text.h's fetch and deflate take it
-DeviceText vcf_text(const BvVcfState *t) {
-    DeviceText d;
-    if (t) { d.device = t->device; d.d_text = t->d_text; d.bytes = t->text_bytes; d.formatted = t->formatted; }
-    return d;
 }
 
 }  // namespace
@@ -299,26 +279,21 @@ int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off
         if ((uint64_t)n * ((rows.n_samples + BV_VCF_TILE - 1u) / BV_VCF_TILE) >= (1ull << 26))
             return fail(e, BV_ERR_TOO_LARGE, who + "n_lines x tiles of a row exceeds 2^26: format fewer lines a call");
     }
-    BvVcfState *t = engine_state(e, e->vcf);
-    t->formatted = false;
-    if (n == 0) {
-        line_off[0] = 0;
-        t->text_bytes = 0;
-        t->formatted = true;
-        return BV_OK;
-    }
+    BvVcfState *t = text_state(e, e->vcf);
+    t->text.formatted = false;  // deliberately here, not on entry as in bv_engine_pileup_text: a call whose arguments fail leaves the last text
+    if (n == 0) return device_text_empty(t->text, line_off);
     return vcf_format(e, t, L, rows, host_rows, line_off, stream_ ? (hipStream_t)stream_ : e->stream);
 }
 
 int bv_engine_vcf_fetch(bv_engine *e, void *dst, uint64_t dst_capacity, int dst_mem_kind, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_vcf_fetch: null engine");
-    return device_text_fetch(e, "bv_engine_vcf_fetch: ", "bv_engine_vcf_format", vcf_text(e->vcf), dst, dst_capacity, dst_mem_kind, stream_);
+    return device_text_fetch(e, "bv_engine_vcf_fetch: ", "bv_engine_vcf_format", e->vcf ? &e->vcf->text : nullptr, dst, dst_capacity, dst_mem_kind, stream_);
 }
 
 int bv_engine_vcf_deflate(bv_engine *e, const uint64_t *block_off, uint32_t n_blocks, int level, uint8_t *dst, uint64_t dst_capacity,
                           uint64_t *member_off, void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_vcf_deflate: null engine");
-    return device_text_deflate(e, "bv_engine_vcf_deflate: ", "bv_engine_vcf_format", vcf_text(e->vcf), block_off, n_blocks, level, dst, dst_capacity, member_off,
+    return device_text_deflate(e, "bv_engine_vcf_deflate: ", "bv_engine_vcf_format", e->vcf ? &e->vcf->text : nullptr, block_off, n_blocks, level, dst, dst_capacity, member_off,
                                stream_);
 }
 

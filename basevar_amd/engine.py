@@ -557,25 +557,41 @@ class BaseTypeEngine:
         else:
             keep = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
             kind, ptr, size = _capi.BV_MEM_HOST, (keep.ctypes.data if keep.size else None), int(keep.size)
+        return self._deflate("bgzf_deflate", "bv_engine_bgzf_deflate_level", size, block_bytes, block_off, level, (ptr, size, kind))  # (`keep` lives through it)
+
+    def _deflate(self, who, symbol, size, block_bytes, block_off, level, text=()):
+        """What bgzf_deflate, vcf_deflate and pileup_text_deflate share: the blocks of a text of `size` bytes, the level, room for
+        the members, the call `symbol` (`text`: its arguments that name the text, if it takes any) and (members, member_off)."""
         if block_off is None:
             if not 1 <= int(block_bytes) <= 0xff00:
-                raise ValueError("bgzf_deflate: block_bytes is 1 to 0xff00")
+                raise ValueError("%s: block_bytes is 1 to 0xff00" % who)
             off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
         else:
             off = np.ascontiguousarray(block_off, dtype=np.uint64)
         n = int(off.size) - 1
         if n < 0:
-            raise ValueError("bgzf_deflate: block_off needs n + 1 entries")
+            raise ValueError("%s: block_off needs n + 1 entries" % who)
         if level not in _capi.DEFLATE_LEVELS:
-            raise ValueError("bgzf_deflate: level is 'fast' or 'small'")
+            raise ValueError("%s: level is 'fast' or 'small'" % who)
         members = np.zeros(size + 31 * n, dtype=np.uint8)
         member_off = np.zeros(n + 1, dtype=np.uint64)
-        rc = self._lib.bv_engine_bgzf_deflate_level(self._h, ptr, size, kind, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level],
-                                                    members.ctypes.data if members.size else None, int(members.size), member_off.ctypes.data, None)
-        del keep
+        rc = getattr(self._lib, symbol)(self._h, *text, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level], members.ctypes.data if members.size else None,
+                                        int(members.size), member_off.ctypes.data, None)
         if rc != 0:
-            raise RuntimeError("bv_engine_bgzf_deflate_level failed (%d): %s" % (rc, self._err()), rc)
+            raise RuntimeError("%s failed (%d): %s" % (symbol, rc, self._err()), rc)
         return members[:int(member_off[n])], member_off
+
+    def _text_fetch(self, symbol, size, dst_ptr, dst_capacity):
+        """vcf_fetch and pileup_text_fetch: the `size` bytes of the text behind the call `symbol`, or its copy to `dst_ptr`"""
+        if dst_ptr:
+            rc = getattr(self._lib, symbol)(self._h, int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, None)
+            text = None
+        else:
+            text = np.zeros(size, dtype=np.uint8)
+            rc = getattr(self._lib, symbol)(self._h, text.ctypes.data if text.size else None, int(text.size), _capi.BV_MEM_HOST, None)
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (symbol, rc, self._err()), rc)
+        return text
 
     # ---- VCF sample columns, written on the device (include/basevar_amd_vcf.h)
     def vcf_format(self, site, heads, gt, slab=None):
@@ -604,38 +620,12 @@ class BaseTypeEngine:
     def vcf_fetch(self, dst_ptr=0, dst_capacity=0):
         """The text of the last vcf_format (bv_engine_vcf_fetch) as a uint8 array; with `dst_ptr`, a device pointer of
         `dst_capacity` bytes, it is copied there instead and None is returned."""
-        if dst_ptr:
-            rc = self._lib.bv_engine_vcf_fetch(self._h, int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, None)
-            text = None
-        else:
-            text = np.zeros(getattr(self, "_vcf_bytes", 0), dtype=np.uint8)
-            rc = self._lib.bv_engine_vcf_fetch(self._h, text.ctypes.data if text.size else None, int(text.size), _capi.BV_MEM_HOST, None)
-        if rc != 0:
-            raise RuntimeError("bv_engine_vcf_fetch failed (%d): %s" % (rc, self._err()), rc)
-        return text
+        return self._text_fetch("bv_engine_vcf_fetch", getattr(self, "_vcf_bytes", 0), dst_ptr, dst_capacity)
 
     def vcf_deflate(self, block_bytes=0xff00, block_off=None, level="fast"):
         """bgzf_deflate of the last vcf_format's text, read where it lies on the device (bv_engine_vcf_deflate): (members,
         member_off) as bgzf_deflate returns them, byte for byte what it returns for the fetched text."""
-        size = getattr(self, "_vcf_bytes", 0)
-        if block_off is None:
-            if not 1 <= int(block_bytes) <= 0xff00:
-                raise ValueError("vcf_deflate: block_bytes is 1 to 0xff00")
-            off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
-        else:
-            off = np.ascontiguousarray(block_off, dtype=np.uint64)
-        n = int(off.size) - 1
-        if n < 0:
-            raise ValueError("vcf_deflate: block_off needs n + 1 entries")
-        if level not in _capi.DEFLATE_LEVELS:
-            raise ValueError("vcf_deflate: level is 'fast' or 'small'")
-        members = np.zeros(size + 31 * n, dtype=np.uint8)
-        member_off = np.zeros(n + 1, dtype=np.uint64)
-        rc = self._lib.bv_engine_vcf_deflate(self._h, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level], members.ctypes.data if members.size else None,
-                                             int(members.size), member_off.ctypes.data, None)
-        if rc != 0:
-            raise RuntimeError("bv_engine_vcf_deflate failed (%d): %s" % (rc, self._err()), rc)
-        return members[:int(member_off[n])], member_off
+        return self._deflate("vcf_deflate", "bv_engine_vcf_deflate", getattr(self, "_vcf_bytes", 0), block_bytes, block_off, level)
 
     # ---- BAM records, piled up on the device (include/basevar_amd_pileup.h)
     def pileup_set_reference(self, seq):
@@ -786,38 +776,12 @@ class BaseTypeEngine:
     def pileup_text_fetch(self, dst_ptr=0, dst_capacity=0):
         """The text of the last pileup_text (bv_engine_pileup_text_fetch) as a uint8 array; with `dst_ptr`, a device pointer of
         `dst_capacity` bytes, it is copied there instead and None is returned."""
-        if dst_ptr:
-            rc = self._lib.bv_engine_pileup_text_fetch(self._h, int(dst_ptr), int(dst_capacity), _capi.BV_MEM_DEVICE, None)
-            text = None
-        else:
-            text = np.zeros(getattr(self, "_ptext_bytes", 0), dtype=np.uint8)
-            rc = self._lib.bv_engine_pileup_text_fetch(self._h, text.ctypes.data if text.size else None, int(text.size), _capi.BV_MEM_HOST, None)
-        if rc != 0:
-            raise RuntimeError("bv_engine_pileup_text_fetch failed (%d): %s" % (rc, self._err()), rc)
-        return text
+        return self._text_fetch("bv_engine_pileup_text_fetch", getattr(self, "_ptext_bytes", 0), dst_ptr, dst_capacity)
 
     def pileup_text_deflate(self, block_bytes=0xff00, block_off=None, level="fast"):
         """bgzf_deflate of the last pileup_text's text, read where it lies on the device (bv_engine_pileup_text_deflate): (members,
         member_off) as bgzf_deflate returns them, byte for byte what it returns for the fetched text."""
-        size = getattr(self, "_ptext_bytes", 0)
-        if block_off is None:
-            if not 1 <= int(block_bytes) <= 0xff00:
-                raise ValueError("pileup_text_deflate: block_bytes is 1 to 0xff00")
-            off = np.append(np.arange(0, size, int(block_bytes), dtype=np.uint64), np.uint64(size)) if size else np.zeros(1, np.uint64)
-        else:
-            off = np.ascontiguousarray(block_off, dtype=np.uint64)
-        n = int(off.size) - 1
-        if n < 0:
-            raise ValueError("pileup_text_deflate: block_off needs n + 1 entries")
-        if level not in _capi.DEFLATE_LEVELS:
-            raise ValueError("pileup_text_deflate: level is 'fast' or 'small'")
-        members = np.zeros(size + 31 * n, dtype=np.uint8)
-        member_off = np.zeros(n + 1, dtype=np.uint64)
-        rc = self._lib.bv_engine_pileup_text_deflate(self._h, off.ctypes.data, n, _capi.DEFLATE_LEVELS[level], members.ctypes.data if members.size else None,
-                                                     int(members.size), member_off.ctypes.data, None)
-        if rc != 0:
-            raise RuntimeError("bv_engine_pileup_text_deflate failed (%d): %s" % (rc, self._err()), rc)
-        return members[:int(member_off[n])], member_off
+        return self._deflate("pileup_text_deflate", "bv_engine_pileup_text_deflate", getattr(self, "_ptext_bytes", 0), block_bytes, block_off, level)
 
     def deflate_code_lengths(self, counts, limit):
         """The code lengths the small deflate level gives an alphabet with these counts (bv_engine_deflate_code_lengths, a
