@@ -98,6 +98,21 @@ class PileupResult(C.Structure):  # bv_pileup_result
                 ("mem_kind", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class PileupBgzfRun(C.Structure):  # bv_pileup_bgzf_run (include/basevar_amd_pileup_bgzf.h)
+    _fields_ = [("sample", C.c_uint32), ("first_member", C.c_uint32), ("n_members", C.c_uint32), ("begin", C.c_uint32), ("end", C.c_uint32),
+                ("reserved_", C.c_uint32)]
+
+
+class PileupBgzf(C.Structure):  # bv_pileup_bgzf
+    _fields_ = [("members", BgzfMembers), ("runs", C.c_void_p), ("pitch", C.c_uint64), ("n_runs", C.c_uint32), ("n_samples", C.c_uint32),
+                ("tid", C.c_int32), ("region_beg", C.c_uint32), ("region_end", C.c_uint32), ("beg", C.c_uint32), ("end", C.c_uint32),
+                ("mapq_thd", C.c_int32), ("reserved_", C.c_uint32)]
+
+
+PILEUP_BGZF_RUN_DTYPE = np.dtype([("sample", "<u4"), ("first_member", "<u4"), ("n_members", "<u4"), ("begin", "<u4"), ("end", "<u4"), ("reserved_", "<u4")])
+assert PILEUP_BGZF_RUN_DTYPE.itemsize == C.sizeof(PileupBgzfRun) == 24
+
+
 class PileupTile(C.Structure):  # bv_pileup_tile (include/basevar_amd_pileup_text.h)
     _fields_ = [("cell", C.c_void_p), ("qual", C.c_void_p), ("mapq", C.c_void_p), ("rank", C.c_void_p), ("tokens", C.c_void_p), ("text", C.c_void_p),
                 ("pitch", C.c_uint64), ("n_tokens", C.c_uint64), ("text_bytes", C.c_uint64), ("beg", C.c_uint32), ("rows", C.c_uint32),
@@ -145,6 +160,9 @@ VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_def
 
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
+
+# every symbol include/basevar_amd_pileup_bgzf.h declares
+PILEUP_BGZF_EXPORTS = ["bv_engine_pileup_bgzf"]
 
 # every symbol include/basevar_amd_pileup_text.h declares
 PILEUP_TEXT_EXPORTS = ["bv_pileup_text_tile_samples", "bv_engine_pileup_text", "bv_engine_pileup_text_fetch", "bv_engine_pileup_text_deflate"]
@@ -275,6 +293,8 @@ def load():
     L.bv_engine_pileup_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(Slab), C.c_void_p, C.c_void_p]
     L.bv_engine_pileup_submit.restype = C.c_int
     L.bv_engine_pileup_submit.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_engine_pileup_bgzf.restype = C.c_int
+    L.bv_engine_pileup_bgzf.argtypes = [C.c_void_p, C.POINTER(PileupBgzf), C.POINTER(C.c_uint32), C.c_void_p]
     L.bv_pileup_text_tile_samples.restype = C.c_uint32
     L.bv_pileup_text_tile_samples.argtypes = []
     L.bv_engine_pileup_text.restype = C.c_int

@@ -1,6 +1,7 @@
 // bv_pileup.hip -- BAM records piled up on the device (bv_engine_pileup, include/basevar_amd_pileup.h; the contract is
-// INTEGRATION.md section 2i).  The result is defined at the head of bv_pileup_core.h, which a CPU harness compiles too; this
-// file is its schedule.  Of that header the kernels compile the record decode, the filter and the helpers; wave_walk below states
+// INTEGRATION.md section 2i), and the same from BGZF members that are still compressed (bv_engine_pileup_bgzf,
+// include/basevar_amd_pileup_bgzf.h, section 2k): bv_inflate.hip's kernel inflates them back to back, the runs are cut out of
+// that.  The result is defined at the head of bv_pileup_core.h, which a CPU harness compiles too; this file is its schedule.  Of that header the kernels compile the record decode, the filter and the helpers; wave_walk below states
 // the walk a second time, and tests/test_gpu_pileup.py (BAM corpus) and tests/test_gpu_pileup_raw.py (raw runs, edges) hold it
 // to the first byte for byte.
 //
@@ -30,7 +31,9 @@
 #include <vector>
 
 #include "../../include/basevar_amd_pileup.h"
+#include "../../include/basevar_amd_pileup_bgzf.h"
 #include "bv_chunk_stage.h"
+#include "bv_inflate_core.h"
 #include "bv_pileup_core.h"
 
 using namespace bv_impl;
@@ -44,8 +47,8 @@ namespace {
 
 struct PileupArgs {
     BvPileupQuery q;
-    const uint8_t *records;    // run r is records[run_off[r] ..] (of host records: their device copy less run_off[0])
-    const uint64_t *run_off;   // [n_runs + 1]
+    const uint8_t *records;    // run r is records[run_at[2 r] .. run_at[2 r + 1]) (of host records: their device copy less run_off[0])
+    const uint64_t *run_at;    // [n_runs][2]: where a run begins and ends; runs need not be neighbours (bv_engine_pileup_bgzf)
     const uint32_t *samp_run;  // [n_samples + 1]: the runs of sample s are [samp_run[s], samp_run[s + 1])
     const uint8_t *ref;
     uint8_t *planes;           // cell, qual, mapq (plane_bytes apart) and rank, [rows][pitch] each
@@ -203,7 +206,7 @@ __global__ __launch_bounds__(64) void bv_pileup_kernel(PileupArgs) {
     bool live = true;
     const uint32_t run_hi = kern_args()->samp_run[s + 1];
     for (uint32_t r = kern_args()->samp_run[s]; live && r < run_hi; ++r) {
-        const uint64_t lo = kern_args()->run_off[r], bytes = kern_args()->run_off[r + 1] - lo;
+        const uint64_t lo = kern_args()->run_at[2u * r], bytes = kern_args()->run_at[2u * r + 1u] - lo;
         for (uint64_t at = 0; at < bytes;) {
             const uint8_t *run = kern_args()->records + lo;
             BvPileupRec rec;
@@ -304,6 +307,8 @@ struct BvPileupState {
     int device = 0;
     uint8_t *d_ref = nullptr, *d_records = nullptr, *d_meta = nullptr, *d_planes = nullptr, *d_depth = nullptr, *d_tok = nullptr, *d_text = nullptr,
             *d_slab = nullptr, *d_out = nullptr;
+    uint8_t *d_inflated = nullptr;  // bv_engine_pileup_bgzf: the members' text, back to back (the sum of their ISIZE fields; kept, only grows)
+    size_t inflated_cap = 0;
     size_t ref_cap = 0, rec_cap = 0, meta_cap = 0, planes_cap = 0, depth_cap = 0, tok_cap = 0, text_cap = 0, slab_cap = 0, out_cap = 0;
     bv_slab slab{};          // what the last bv_engine_pileup_rows filled
     bool have_slab = false;
@@ -322,7 +327,7 @@ void bv_pileup_state_free(BvPileupState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     chunk_stage_free(t->stage);
-    for (uint8_t *b : {t->d_ref, t->d_records, t->d_meta, t->d_planes, t->d_depth, t->d_tok, t->d_text, t->d_slab, t->d_out})
+    for (uint8_t *b : {t->d_ref, t->d_records, t->d_meta, t->d_planes, t->d_depth, t->d_tok, t->d_text, t->d_slab, t->d_out, t->d_inflated})
         if (b) (void)hipFree(b);
     delete t;
 }
@@ -359,38 +364,40 @@ int upload_records(bv_engine *e, BvPileupState *t, const uint8_t *src, uint64_t 
     return BV_OK;
 }
 
-int pileup(bv_engine *e, BvPileupState *t, const bv_pileup_reads *in, const BvPileupQuery &q, uint32_t *n_covered, hipStream_t st) {
-    const std::string who = "bv_engine_pileup: ";
+// What one call piles up: run r is the bytes [run_at[2 r], run_at[2 r + 1]) behind `records` (device memory, complete on the stream)
+struct PileJob {
+    const char *who;             // "bv_engine_pileup: "
+    const uint8_t *records;
+    const uint64_t *run_at;      // host [n_runs][2]
+    const uint32_t *run_sample;  // host [n_runs]
+    uint64_t pitch;
+    uint32_t n_runs, n_samples, beg, end;
+};
+
+int pileup(bv_engine *e, BvPileupState *t, const PileJob *in, const BvPileupQuery &q, uint32_t *n_covered, hipStream_t st) {
+    const std::string who = in->who;
     const uint32_t n = in->n_samples, n_runs = in->n_runs, rows = in->end - in->beg + 1u;
     const PlaneOffsets P((size_t)rows * in->pitch);
     BV_HIP(e, hipSetDevice(t->device));
-    // run_off u64 [n_runs + 1], samp_run u32 [n + 1], per [n], tok_base u64 [n], text_base u64 [n]
-    const size_t o_samp = up16(8ull * (n_runs + 1)), o_per = o_samp + up16(4ull * (n + 1)), o_tokb = o_per + 32ull * n, o_textb = o_tokb + 8ull * n,
+    // run_at u64 [n_runs][2], samp_run u32 [n + 1], per [n], tok_base u64 [n], text_base u64 [n]
+    const size_t o_samp = up16(16ull * n_runs), o_per = o_samp + up16(4ull * (n + 1)), o_tokb = o_per + 32ull * n, o_textb = o_tokb + 8ull * n,
                  meta = o_textb + 8ull * n;
     int rc = grow_device(e, &t->d_meta, &t->meta_cap, meta);
     if (rc == BV_OK) rc = grow_device(e, &t->d_planes, &t->planes_cap, P.bytes);
     if (rc == BV_OK) rc = grow_device(e, &t->d_depth, &t->depth_cap, 8ull * rows);
     if (rc != BV_OK) return rc;
     std::vector<uint8_t> h(o_per, 0);
-    uint64_t *h_off = reinterpret_cast<uint64_t *>(h.data());
     uint32_t *h_samp = reinterpret_cast<uint32_t *>(h.data() + o_samp);
-    const uint64_t rec_lo = n_runs ? in->run_off[0] : 0, total = n_runs ? in->run_off[n_runs] - rec_lo : 0;
-    if (n_runs) std::memcpy(h_off, in->run_off, 8ull * (n_runs + 1));
+    if (n_runs) std::memcpy(h.data(), in->run_at, 16ull * n_runs);
     for (uint32_t r = 0; r < n_runs; ++r) h_samp[in->run_sample[r] + 1] = r + 1;
     for (uint32_t s = 0; s < n; ++s) h_samp[s + 1] = std::max(h_samp[s + 1], h_samp[s]);
     PileupArgs a;
     a.q = q;
     a.records = in->records;
-    if (in->mem_kind == BV_MEM_HOST) {
-        rc = grow_device(e, &t->d_records, &t->rec_cap, up256(total + 16));
-        if (rc == BV_OK) rc = upload_records(e, t, in->records + rec_lo, total, st);
-        if (rc != BV_OK) return rc;
-        a.records = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(t->d_records) - rec_lo);
-    }
     BV_HIP(e, hipMemcpyAsync(t->d_meta, h.data(), o_per, hipMemcpyHostToDevice, st));
     BV_HIP(e, hipMemsetAsync(t->d_planes, BV_CELL_N, P.o_qual, st));
     BV_HIP(e, hipMemsetAsync(t->d_planes + P.o_qual, 0, P.bytes - P.o_qual, st));
-    a.run_off = reinterpret_cast<const uint64_t *>(t->d_meta); a.samp_run = reinterpret_cast<const uint32_t *>(t->d_meta + o_samp);
+    a.run_at = reinterpret_cast<const uint64_t *>(t->d_meta); a.samp_run = reinterpret_cast<const uint32_t *>(t->d_meta + o_samp);
     a.ref = t->d_ref;
     a.planes = t->d_planes; a.plane_bytes = P.o_qual; a.pitch = in->pitch;
     a.per = reinterpret_cast<BvPileupSample *>(t->d_meta + o_per);
@@ -518,7 +525,94 @@ int bv_engine_pileup(bv_engine *e, const bv_pileup_reads *in, uint32_t *n_covere
     if (in->end > t->ref_len) return fail(e, BV_ERR_INVALID_ARG, who + "the window ends beyond the reference's " + std::to_string(t->ref_len) + " bases");
     BvPileupQuery q;
     bv_pileup_query(in->tid, in->beg, in->end, gb, ge, in->mapq_thd, t->ref_len, &q);
-    return pileup(e, t, in, q, n_covered, stream_ ? (hipStream_t)stream_ : e->stream);
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    // neighbours of one offset array as the pairs the kernels read
+    std::vector<uint64_t> run_at(2ull * in->n_runs);
+    for (uint32_t r = 0; r < in->n_runs; ++r) { run_at[2ull * r] = in->run_off[r]; run_at[2ull * r + 1] = in->run_off[r + 1]; }
+    PileJob job{"bv_engine_pileup: ", in->records, run_at.data(), in->run_sample, in->pitch, in->n_runs, in->n_samples, in->beg, in->end};
+    if (in->mem_kind == BV_MEM_HOST) {
+        const uint64_t rec_lo = in->n_runs ? in->run_off[0] : 0, total = in->n_runs ? in->run_off[in->n_runs] - rec_lo : 0;
+        BV_HIP(e, hipSetDevice(t->device));
+        int rc = grow_device(e, &t->d_records, &t->rec_cap, up256(total + 16));
+        if (rc == BV_OK) rc = upload_records(e, t, in->records + rec_lo, total, st);
+        if (rc != BV_OK) return rc;
+        job.records = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(t->d_records) - rec_lo);
+    }
+    return pileup(e, t, &job, q, n_covered, st);
+}
+
+int bv_engine_pileup_bgzf(bv_engine *e, const bv_pileup_bgzf *in, uint32_t *n_covered, void *stream_) {
+    const std::string who = "bv_engine_pileup_bgzf: ";
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, who + "null engine");
+    if (e->pileup) e->pileup->done = e->pileup->have_slab = false;  // whatever comes of this call, the last pileup is gone
+    if (!in || !n_covered) return fail(e, BV_ERR_INVALID_ARG, who + "null members-and-runs/n_covered");
+    if (in->reserved_ || in->members.reserved_) return fail(e, BV_ERR_INVALID_ARG, who + "reserved_ must be zero");
+    if (in->n_samples == 0 || in->pitch < in->n_samples || (in->pitch & 15ull)) return fail(e, BV_ERR_INVALID_ARG, who + "pitch must be >= n_samples >= 1 and a multiple of 16");
+    if (in->tid < 0) return fail(e, BV_ERR_INVALID_ARG, who + "tid must not be negative");
+    if (in->end >= in->beg && (uint64_t)in->end - in->beg + 1u > BV_PILEUP_MAX_ROWS)
+        return fail(e, BV_ERR_TOO_LARGE, who + "a window of " + std::to_string((uint64_t)in->end - in->beg + 1u) + " rows: more than bv_pileup_max_rows() = " + std::to_string(BV_PILEUP_MAX_ROWS));
+    uint32_t gb = 0, ge = 0;
+    if (!bv_pileup_step(in->region_beg, in->region_end, in->beg, in->end, &gb, &ge))
+        return fail(e, BV_ERR_INVALID_ARG, who + "a window must lie inside the region and must not cross the 500 kb step grid laid out from region_beg");
+    const bv_bgzf_members *mb = &in->members;
+    const uint32_t n_mem = mb->n_members, n_runs = in->n_runs;
+    if (n_mem && (!mb->data || !mb->member_off)) return fail(e, BV_ERR_INVALID_ARG, who + "null data/member_off");
+    if (n_runs && !in->runs) return fail(e, BV_ERR_INVALID_ARG, who + "null runs");
+    std::vector<BvBgzfMember> hd;
+    std::vector<uint8_t> pre;
+    int rc = bv_bgzf_headers(e, "bv_engine_pileup_bgzf", mb, hd, pre);
+    if (rc != BV_OK) return rc;
+    std::vector<uint64_t> dst_off(n_mem + 1ull, 0);
+    for (uint32_t k = 0; k < n_mem; ++k) dst_off[k + 1] = dst_off[k] + hd[k].isize;
+    std::vector<uint64_t> run_at(2ull * n_runs);
+    std::vector<uint32_t> run_sample(n_runs);
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        const bv_pileup_bgzf_run &u = in->runs[r];
+        const std::string run = "run " + std::to_string(r);
+        if (u.reserved_) return fail(e, BV_ERR_INVALID_ARG, who + run + ": reserved_ must be zero");
+        if (u.sample >= in->n_samples) return fail(e, BV_ERR_INVALID_ARG, who + "sample of " + run + " is beyond n_samples");
+        if (r && u.sample < in->runs[r - 1].sample) return fail(e, BV_ERR_INVALID_ARG, who + "sample descends at " + run);
+        if (u.n_members == 0) return fail(e, BV_ERR_INVALID_ARG, who + run + " has no member");
+        if ((uint64_t)u.first_member + u.n_members > n_mem)
+            return fail(e, BV_ERR_INVALID_ARG, who + run + ": members " + std::to_string(u.first_member) + " + " + std::to_string(u.n_members) + " are beyond the " + std::to_string(n_mem) + " given");
+        // (a member that its header already refuses has no ISIZE to hold a cut point to: it ends the call as BV_ERR_DATA below)
+        const uint32_t last = u.first_member + u.n_members - 1u;
+        if (pre[u.first_member] == BV_BGZF_OK && u.begin > hd[u.first_member].isize)
+            return fail(e, BV_ERR_INVALID_ARG, who + run + ": begin " + std::to_string(u.begin) + " is above its first member's ISIZE " + std::to_string(hd[u.first_member].isize));
+        if (pre[last] == BV_BGZF_OK && u.end > hd[last].isize)
+            return fail(e, BV_ERR_INVALID_ARG, who + run + ": end " + std::to_string(u.end) + " is above its last member's ISIZE " + std::to_string(hd[last].isize));
+        if (u.n_members == 1 && u.begin > u.end) return fail(e, BV_ERR_INVALID_ARG, who + run + ": begin " + std::to_string(u.begin) + " > end " + std::to_string(u.end) + " inside one member");
+        run_at[2ull * r] = dst_off[u.first_member] + u.begin;
+        run_at[2ull * r + 1] = std::max(run_at[2ull * r], dst_off[last] + u.end);  // (behind a refused member only: the call ends before the pile)
+        run_sample[r] = u.sample;
+    }
+    BvPileupState *t = e->pileup;
+    if (!t || !t->have_ref) return fail(e, BV_ERR_INVALID_ARG, who + "no reference set: bv_engine_pileup_set_reference comes first");
+    if (in->end > t->ref_len) return fail(e, BV_ERR_INVALID_ARG, who + "the window ends beyond the reference's " + std::to_string(t->ref_len) + " bases");
+    BvPileupQuery q;
+    bv_pileup_query(in->tid, in->beg, in->end, gb, ge, in->mapq_thd, t->ref_len, &q);
+    hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    BV_HIP(e, hipSetDevice(t->device));
+    if (n_mem) {
+        // the members once each, back to back; the call returns with their statuses on the host: the one wait before the pile
+        if ((rc = grow_device(e, &t->d_inflated, &t->inflated_cap, up256(dst_off[n_mem] + 16))) != BV_OK) return rc;
+        std::vector<uint8_t> status(n_mem);
+        if ((rc = bv_bgzf_inflate_placed(e, mb, hd, pre, dst_off.data(), t->d_inflated, status.data(), st)) != BV_OK) return rc;
+        for (uint32_t k = 0; k < n_mem; ++k) {
+            if (status[k] == BV_BGZF_OK) continue;
+            static const char *const kWhat[] = {"ok", "bad header", "bad DEFLATE stream", "bad size", "bad CRC"};
+            std::string used = "used by no run";
+            for (uint32_t r = 0; r < n_runs; ++r)
+                if (k >= in->runs[r].first_member && k - in->runs[r].first_member < in->runs[r].n_members) {
+                    used = "first used by sample " + std::to_string(in->runs[r].sample) + ", run " + std::to_string(r);
+                    break;
+                }
+            return fail(e, BV_ERR_DATA, who + "member " + std::to_string(k) + " did not inflate: status " + std::to_string(status[k]) + " (" +
+                                            (status[k] < 5 ? kWhat[status[k]] : "?") + "), " + used);
+        }
+    }
+    const PileJob job{"bv_engine_pileup_bgzf: ", t->d_inflated, run_at.data(), run_sample.data(), in->pitch, n_runs, in->n_samples, in->beg, in->end};
+    return pileup(e, t, &job, q, n_covered, st);
 }
 
 int bv_engine_pileup_fetch(bv_engine *e, bv_pileup_result *out, void *stream_) {

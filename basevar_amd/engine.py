@@ -704,10 +704,50 @@ class BaseTypeEngine:
             raise RuntimeError("bv_engine_pileup_rows failed (%d): %s" % (rc, self._err()), rc)
         return slab, pos, depth
 
+    def pileup_bgzf(self, members_bytes, member_off, runs, n_samples, tid, region, window, mapq_thd, pitch=None, reserved=0):
+        """pileup() from BGZF members that are still compressed (bv_engine_pileup_bgzf); returns the number of covered rows.
+
+        Member k is members_bytes[member_off[k]:member_off[k + 1]] (host: bytes / uint8 array), as bgzf_inflate takes them.
+        `runs`: an array of _capi.PILEUP_BGZF_RUN_DTYPE, or rows of (sample, first_member, n_members, begin, end): run r is cut
+        from the text of its members, from `begin` bytes into the first to `end` bytes of the last.  The rest as in pileup()."""
+        buf = np.frombuffer(members_bytes, dtype=np.uint8) if isinstance(members_bytes, (bytes, bytearray)) else np.ascontiguousarray(members_bytes, np.uint8)
+        off = np.ascontiguousarray(member_off, dtype=np.uint64)
+        if isinstance(runs, np.ndarray) and runs.dtype == _capi.PILEUP_BGZF_RUN_DTYPE:
+            rr = np.ascontiguousarray(runs)
+        else:
+            rows = np.asarray(runs, dtype=np.uint32).reshape(-1, 5)
+            rr = np.zeros(len(rows), _capi.PILEUP_BGZF_RUN_DTYPE)
+            for k, f in enumerate(("sample", "first_member", "n_members", "begin", "end")):
+                rr[f] = rows[:, k]
+        n_members = max(int(off.size) - 1, 0)
+        pitch = (int(n_samples) + 15) // 16 * 16 if pitch is None else int(pitch)
+        arg = _capi.PileupBgzf()
+        arg.members = _capi.BgzfMembers(buf.ctypes.data if buf.size else None, off.ctypes.data if off.size else None, int(buf.size), n_members, 0)
+        arg.runs = rr.ctypes.data if rr.size else None
+        arg.pitch, arg.n_runs, arg.n_samples, arg.tid = pitch, int(rr.size), int(n_samples), int(tid)
+        arg.region_beg, arg.region_end, arg.beg, arg.end = int(region[0]), int(region[1]), int(window[0]), int(window[1])
+        arg.mapq_thd, arg.reserved_ = int(mapq_thd), int(reserved)
+        n_cov = C.c_uint32(0)
+        rc = self._lib.bv_engine_pileup_bgzf(self._h, C.byref(arg), C.byref(n_cov), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_bgzf failed (%d): %s" % (rc, self._err()), rc)
+        self._pileup_covered = int(n_cov.value)
+        self._pileup_window_rows = int(window[1]) - int(window[0]) + 1
+        return int(n_cov.value)
+
+    def lrt_pileup_bgzf(self, members_bytes, member_off, runs, n_samples, tid, region, window, mapq_thd, pitch=None, tagged=False):
+        """lrt_pileup from compressed members: pileup_bgzf, pileup_rows and bv_engine_submit of the device slab; a PileupBatch."""
+        self.pileup_bgzf(members_bytes, member_off, runs, n_samples, tid, region, window, mapq_thd, pitch=pitch)
+        return self._lrt_piled(tagged)
+
     def lrt_pileup(self, records, run_off, run_sample, n_samples, tid, region, window, mapq_thd, pitch=None, tagged=False):
         """Reads in, records out: pileup, pileup_rows and bv_engine_submit of the device slab.  Returns a PileupBatch: the records
         of the covered rows, their positions and depths, and the indel tokens {(pos, sample): text}."""
         self.pileup(records, run_off, run_sample, n_samples, tid, region, window, mapq_thd, pitch=pitch)
+        return self._lrt_piled(tagged)
+
+    def _lrt_piled(self, tagged):
+        """the engine's pileup through pileup_rows and bv_engine_submit"""
         slab, pos, depth = self.pileup_rows(tagged=tagged)
         res = _capi.PileupResult()
         res.mem_kind = _capi.BV_MEM_HOST

@@ -37,6 +37,9 @@ public:
     BgzfReader &operator=(const BgzfReader &) = delete;
 
     uint64_t tell() const { return (block_addr_ << 16) | (uint64_t)pos_; }
+    // the open file, for a reader of whole compressed members (host/raw_members.hpp): every load here seeks first, so the
+    // two may take turns on it
+    std::FILE *file() const { return f_; }
     void seek(uint64_t voffset) {
         const uint64_t addr = voffset >> 16;
         if (addr != block_addr_ || !have_block_) load_block(addr);
@@ -262,6 +265,11 @@ public:
     const std::string &header_text() const { return text_; }
     const std::vector<BamRef> &refs() const { return refs_; }
     bool has_index() const { return index_.loaded; }
+    // what host/raw_members.hpp plans a fetch from without inflating anything: the file, where its records begin, the index
+    const std::string &path() const { return path_; }
+    std::FILE *raw_file() const { return bg_.file(); }
+    uint64_t first_record() const { return first_record_; }
+    const BaiIndex &index() const { return index_; }
     int tid_of(const std::string &name) const {
         for (size_t i = 0; i < refs_.size(); ++i)
             if (refs_[i].name == name) return (int)i;

@@ -14,7 +14,7 @@
 //   bv_call --batchfiles a.bf.gz,b.bf.gz --output-vcf out.vcf --output-cvg out.cvg
 //           [--pop-group FILE] [--min-af 0.01] [--batch-sites N (default: 2^28 cells / samples, at most 65536)]
 //           [--timing FILE.json] [--inflate device|host] [--deflate device|host] [--deflate-level fast|small] [--emit device|host]
-//           [--pileup device|host]
+//           [--pileup device|host]   (BAM input; with it, --inflate device also hands the BAM files' BGZF members to the engine compressed)
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
@@ -46,8 +46,10 @@
 #include "batch_producer.hpp"
 #include "batchfile_fast.hpp"
 #include "pileup.hpp"
+#include "raw_members.hpp"
 #include "raw_reads.hpp"
 #include "basevar_amd_pileup.h"
+#include "basevar_amd_pileup_bgzf.h"
 #include "bgzf_tabix.hpp"
 #include "vcf_emit.hpp"
 
@@ -332,7 +334,7 @@ int main(int argc, char **argv) {
     // host reader, submit and records overlap the next worker's parse.  Anything else keeps the host path.
     bvamd::BgzfRawReader raw;
     bool device_inflate = false;
-    if (inflate_arg == "device") {
+    if (inflate_arg == "device" && !(from_bam && pileup_arg == "device")) {  // (with --pileup device: the BAM files' own members, below)
         if (from_bam) std::cerr << "[NOTE] --inflate device applies to BGZF batchfiles, not to BAM input: the host path is taken" << std::endl;
         else if (G > 1) std::cerr << "[NOTE] --inflate device runs on one engine (--gpus 1): the host path is taken" << std::endl;
         else if (!raw.open(batchfiles, header_lines)) std::cerr << "[NOTE] --inflate device needs BGZF batchfiles: the host path is taken" << std::endl;
@@ -347,6 +349,19 @@ int main(int argc, char **argv) {
         else if (G > 1) std::cerr << "[NOTE] --pileup device runs on one engine (--gpus 1): the host path is taken" << std::endl;
         else device_pileup = true;
     }
+    // --pileup device --inflate device: the host threads inflate nothing either -- they read the compressed BGZF members of every
+    // sample's fetch and the cut points (host/raw_members.hpp), and the engine inflates and piles up (bv_engine_pileup_bgzf)
+    bool bam_inflate_device = false;
+    if (from_bam && pileup_arg == "device" && inflate_arg == "device") {
+        bam_inflate_device = device_pileup;
+        if (!device_pileup) std::cerr << "[NOTE] --inflate device on BAM input runs with --pileup device on one engine: the host threads read and inflate" << std::endl;
+        for (size_t i = 0; bam_inflate_device && i < bams.size(); ++i)
+            if (!bvamd::bam_members_supported(bams[i])) {
+                std::cerr << "[NOTE] --inflate device: the BGZF members of " << bams[i] << " are not of the XLEN = 6 packing: the host threads read and inflate" << std::endl;
+                bam_inflate_device = false;
+            }
+    }
+    uint64_t bam_members_inflated = 0, bam_members_bytes = 0;
     uint64_t reads_bytes = 0;
     double pileup_s = 0;
     std::mutex raw_mu;
@@ -638,22 +653,33 @@ int main(int argc, char **argv) {
                             // every sample's records of the fetch, undecoded, on `--thread` threads
                             const double tr0 = StageClock::now();
                             bvamd::WindowReads reads;
-                            bvamd::read_window_raw(*pileup_pool, bams, ref_id, wb, we, threads, reads);
-                            const int tid = reads.tid;
-                            const std::vector<uint8_t> &records = reads.records;
-                            const std::vector<uint64_t> &run_off = reads.run_off;
-                            const std::vector<uint32_t> &run_sample = reads.run_sample;
+                            bvamd::WindowMembers wm;
+                            if (bam_inflate_device) bvamd::read_window_members(*pileup_pool, bams, ref_id, wb, we, threads, wm);
+                            else bvamd::read_window_raw(*pileup_pool, bams, ref_id, wb, we, threads, reads);
                             const double tp0 = StageClock::now();
                             clk.read += tp0 - tr0;
-                            reads_bytes += records.size();
-                            if (run_sample.empty()) { if (we == UINT32_MAX) break; continue; }
-                            bv_pileup_reads in{};
-                            in.records = records.data(); in.run_off = run_off.data(); in.run_sample = run_sample.data();
-                            in.pitch = (n_sample + 15) / 16 * 16; in.n_runs = (uint32_t)run_sample.size(); in.n_samples = (uint32_t)n_sample;
-                            in.tid = tid; in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq_thd;
-                            in.mem_kind = BV_MEM_HOST;
                             uint32_t n_cov = 0;
-                            check(bv_engine_pileup(pe, &in, &n_cov, nullptr));
+                            if (bam_inflate_device) {
+                                if (wm.plan.runs.empty()) { if (we == UINT32_MAX) break; continue; }
+                                static_assert(sizeof(bvamd::MemberRun) == sizeof(bv_pileup_bgzf_run), "one run layout");
+                                bv_pileup_bgzf in{};
+                                in.members.data = wm.plan.data.data(); in.members.member_off = wm.plan.member_off.data(); in.members.data_bytes = wm.plan.data.size();
+                                in.members.n_members = (uint32_t)wm.plan.member_pos.size();
+                                in.runs = reinterpret_cast<const bv_pileup_bgzf_run *>(wm.plan.runs.data());
+                                in.pitch = (n_sample + 15) / 16 * 16; in.n_runs = (uint32_t)wm.plan.runs.size(); in.n_samples = (uint32_t)n_sample;
+                                in.tid = wm.tid; in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq_thd;
+                                bam_members_inflated += in.members.n_members; bam_members_bytes += in.members.data_bytes;
+                                check(bv_engine_pileup_bgzf(pe, &in, &n_cov, nullptr));
+                            } else {
+                                reads_bytes += reads.records.size();
+                                if (reads.run_sample.empty()) { if (we == UINT32_MAX) break; continue; }
+                                bv_pileup_reads in{};
+                                in.records = reads.records.data(); in.run_off = reads.run_off.data(); in.run_sample = reads.run_sample.data();
+                                in.pitch = (n_sample + 15) / 16 * 16; in.n_runs = (uint32_t)reads.run_sample.size(); in.n_samples = (uint32_t)n_sample;
+                                in.tid = reads.tid; in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq_thd;
+                                in.mem_kind = BV_MEM_HOST;
+                                check(bv_engine_pileup(pe, &in, &n_cov, nullptr));
+                            }
                             std::vector<uint32_t> pos(n_cov), depth(n_cov);
                             bv_slab slab;
                             // (short reads: the rank words carry the calls, as SlabBuilder::tag_ranks chooses on the host path)
@@ -786,6 +812,8 @@ int main(int argc, char **argv) {
         if (emit_device) tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << vcf_lines_device;
         // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
         if (device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << reads_bytes << ", \"pileup_s\": " << pileup_s;
+        // ... --inflate device with it: the BAM files' compressed members handed to the engine instead, and their bytes
+        if (bam_inflate_device) tf << ", \"bam_inflate\": \"device\", \"members_inflated\": " << bam_members_inflated << ", \"members_bytes\": " << bam_members_bytes;
         tf << "}\n";
     }
     return 0;

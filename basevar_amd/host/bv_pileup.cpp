@@ -5,13 +5,17 @@
 //
 //   bv_pileup -R ref.fa[.gz] --regions CHR:BEG-END [--mapq 10] -I a.bam [-I b.bam ...] [-L bam.list]
 //             [--filename-has-samplename] [--no-index] [--thread T] [--window POSITIONS] -o out.bf[.gz]
-//             [--rows host|device] [--deflate-level fast|small] [--rows-per-call N]
+//             [--rows host|device] [--inflate host|device] [--deflate-level fast|small] [--rows-per-call N]
 //
 // --rows device (builds with -DBV_PILEUP_DEVICE; the engine library beside the tool is loaded on demand, so the default route
 // needs neither it nor a GPU): the host threads read the samples' raw records, one engine piles them up
 // (bv_engine_pileup) and writes the rows where the planes lie (bv_engine_pileup_text, include/basevar_amd_pileup_text.h), a
 // sub-range of rows a call; a `.gz` output takes each sub-range as BGZF members deflated on the device, a plain one as text.  The
 // inflated output is the default route's byte for byte; neither --window nor --rows-per-call changes it.
+// --inflate device (with --rows device): the host threads inflate nothing -- they read the compressed BGZF members of every
+// sample's fetch and the cut points (host/raw_members.hpp) and the engine inflates and piles up (bv_engine_pileup_bgzf,
+// include/basevar_amd_pileup_bgzf.h).  Without --rows device, or on files whose members are not of the XLEN = 6 packing, a
+// note is printed and the host reads as before.
 //
 // Sample ids come from the first @RG SM tag of each BAM (BamHeader::get_sample_name) or, with
 // --filename-has-samplename, from the file name up to its first '.' (src/basetype_caller.cpp:262-294).
@@ -30,7 +34,9 @@
 #include <dlfcn.h>
 #include <unistd.h>
 
+#include "../../include/basevar_amd_pileup_bgzf.h"
 #include "../../include/basevar_amd_pileup_text.h"
+#include "raw_members.hpp"
 #include "raw_reads.hpp"
 #endif
 
@@ -54,6 +60,7 @@ struct EngineLib {
     decltype(&bv_pileup_max_rows) max_rows = nullptr;
     decltype(&bv_engine_pileup_set_reference) set_reference = nullptr;
     decltype(&bv_engine_pileup) pileup = nullptr;
+    decltype(&bv_engine_pileup_bgzf) pileup_bgzf = nullptr;
     decltype(&bv_engine_pileup_text) text = nullptr;
     decltype(&bv_engine_pileup_text_fetch) fetch = nullptr;
     decltype(&bv_engine_pileup_text_deflate) deflate = nullptr;
@@ -76,7 +83,7 @@ struct EngineLib {
         so = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!so) throw std::runtime_error(std::string("[ERROR] --rows device: ") + dlerror());
         sym(create, "bv_engine_create"); sym(destroy, "bv_engine_destroy"); sym(last_error, "bv_last_error"); sym(max_rows, "bv_pileup_max_rows");
-        sym(set_reference, "bv_engine_pileup_set_reference"); sym(pileup, "bv_engine_pileup"); sym(text, "bv_engine_pileup_text");
+        sym(set_reference, "bv_engine_pileup_set_reference"); sym(pileup, "bv_engine_pileup"); sym(pileup_bgzf, "bv_engine_pileup_bgzf"); sym(text, "bv_engine_pileup_text");
         sym(fetch, "bv_engine_pileup_text_fetch"); sym(deflate, "bv_engine_pileup_text_deflate");
     }
 };
@@ -84,7 +91,8 @@ struct EngineLib {
 // The rows of the region through the engine; `members(bytes, member_off, n)` / `plain(text)` receive a sub-range each
 template <typename Members, typename Plain>
 bool device_rows(const std::vector<std::string> &bams, const std::string &fa_seq, const std::string &ref_id, uint32_t beg, uint32_t end, int mapq,
-                 int threads, uint32_t window, uint32_t rows_per_call, int level, bool gz, Members members, Plain plain) {
+                 int threads, uint32_t window, uint32_t rows_per_call, int level, bool gz, bool inflate_device, uint64_t *members_inflated,
+                 uint64_t *members_bytes, Members members, Plain plain) {
     EngineLib L;
     L.load();
     bv_engine_config cfg{};
@@ -105,16 +113,30 @@ bool device_rows(const std::vector<std::string> &bams, const std::string &fa_seq
             const uint32_t se = std::min(end, sb + bvamd::PILEUP_STEP - 1);
             for (uint32_t wb = sb; wb <= se; wb += window) {
                 const uint32_t we = std::min(se, wb + window - 1), rows = we - wb + 1;
-                bvamd::WindowReads reads;
-                bvamd::read_window_raw(pool, bams, ref_id, wb, we, threads, reads);
-                // (a window without any run is piled up all the same: every row of it is placeholders)
-                bv_pileup_reads in{};
-                in.records = reads.records.data(); in.run_off = reads.run_off.data(); in.run_sample = reads.run_sample.data();
-                in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)reads.run_sample.size(); in.n_samples = (uint32_t)n;
-                in.tid = std::max(reads.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
-                in.mem_kind = BV_MEM_HOST;
                 uint32_t n_cov = 0;
-                check(L.pileup(e, &in, &n_cov, nullptr));
+                // (a window without any run is piled up all the same: every row of it is placeholders)
+                if (inflate_device) {
+                    bvamd::WindowMembers wm;
+                    bvamd::read_window_members(pool, bams, ref_id, wb, we, threads, wm);
+                    static_assert(sizeof(bvamd::MemberRun) == sizeof(bv_pileup_bgzf_run), "one run layout");
+                    bv_pileup_bgzf in{};
+                    in.members.data = wm.plan.data.data(); in.members.member_off = wm.plan.member_off.data(); in.members.data_bytes = wm.plan.data.size();
+                    in.members.n_members = (uint32_t)wm.plan.member_pos.size();
+                    in.runs = reinterpret_cast<const bv_pileup_bgzf_run *>(wm.plan.runs.data());
+                    in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)wm.plan.runs.size(); in.n_samples = (uint32_t)n;
+                    in.tid = std::max(wm.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
+                    check(L.pileup_bgzf(e, &in, &n_cov, nullptr));
+                    *members_inflated += in.members.n_members; *members_bytes += in.members.data_bytes;
+                } else {
+                    bvamd::WindowReads reads;
+                    bvamd::read_window_raw(pool, bams, ref_id, wb, we, threads, reads);
+                    bv_pileup_reads in{};
+                    in.records = reads.records.data(); in.run_off = reads.run_off.data(); in.run_sample = reads.run_sample.data();
+                    in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)reads.run_sample.size(); in.n_samples = (uint32_t)n;
+                    in.tid = std::max(reads.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
+                    in.mem_kind = BV_MEM_HOST;
+                    check(L.pileup(e, &in, &n_cov, nullptr));
+                }
                 has_data = has_data || n_cov != 0;
                 // rows a call from a fixed text budget: 16 bytes a cell and the window's token text bound a sub-range's text
                 uint32_t step = rows_per_call;
@@ -162,7 +184,7 @@ int main(int argc, char **argv) {
     int threads = 1;
     uint32_t window = 0;  // positions per pileup window (0 = from a cell budget); the rows do not depend on it
     bool name_from_file = false, use_index = true;
-    std::string rows_arg = "host", level_arg = "fast";
+    std::string rows_arg = "host", level_arg = "fast", inflate_arg = "host";
     uint32_t rows_per_call = 0;  // --rows device: rows a bv_engine_pileup_text call (0 = from a text budget); the rows do not depend on it
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -178,6 +200,7 @@ int main(int argc, char **argv) {
         else if (a == "-t" || a == "--thread") threads = std::stoi(next());
         else if (a == "--window") window = (uint32_t)std::stoul(next());
         else if (a == "--rows") rows_arg = next();
+        else if (a == "--inflate") inflate_arg = next();
         else if (a == "--deflate-level") level_arg = next();
         else if (a == "--rows-per-call") rows_per_call = (uint32_t)std::stoul(next());
         else die("unknown argument " + a);
@@ -194,6 +217,11 @@ int main(int argc, char **argv) {
     }
     if (rows_arg != "host" && rows_arg != "device") die("--rows wants host or device");
     if (level_arg != "fast" && level_arg != "small") die("--deflate-level wants fast or small");
+    if (inflate_arg != "host" && inflate_arg != "device") die("--inflate wants host or device");
+    bool inflate_device = inflate_arg == "device";
+#ifndef BV_PILEUP_DEVICE
+    if (inflate_device) die("[ERROR] --inflate device: this bv_pileup was built without the device route");
+#endif
     if (bams.empty() || fasta.empty() || regions.empty() || out_path.empty())
         die("usage: bv_pileup -R ref.fa --regions CHR:BEG-END [--mapq Q] -I a.bam [-I ...] [-L list] -o out.bf[.gz]");
     try {
@@ -233,12 +261,24 @@ int main(int argc, char **argv) {
             else if (std::fwrite(s.data(), 1, s.size(), pf) != s.size()) throw std::runtime_error("[ERROR] fail to write data");
         };
         bool has_data = false;
+        uint64_t members_inflated = 0, members_bytes = 0;
+#ifdef BV_PILEUP_DEVICE
+        if (inflate_device && rows_arg != "device") {
+            std::cerr << "[NOTE] --inflate device takes effect with --rows device; the host threads read and inflate the BAM files" << std::endl;
+            inflate_device = false;
+        }
+        for (size_t i = 0; inflate_device && i < bams.size(); ++i)
+            if (!bvamd::bam_members_supported(bams[i])) {
+                std::cerr << "[NOTE] --inflate device: the BGZF members of " << bams[i] << " are not of the XLEN = 6 packing; the host threads read and inflate the BAM files" << std::endl;
+                inflate_device = false;
+            }
+#endif
         if (rows_arg == "device") {
 #ifdef BV_PILEUP_DEVICE
             // the header goes through the host writer; flush(): the device's members follow on a member boundary
             sink(bvamd::batchfile_header(sample_ids));
             if (gz) zf.flush();
-            has_data = device_rows(bams, fa_seq, ref_id, beg, end, mapq, threads, window, rows_per_call, level_arg == "small" ? 1 : 0, gz,
+            has_data = device_rows(bams, fa_seq, ref_id, beg, end, mapq, threads, window, rows_per_call, level_arg == "small" ? 1 : 0, gz, inflate_device, &members_inflated, &members_bytes,
                                    [&](const uint8_t *m, const uint64_t *off, size_t nm) { zf.write_members(m, off, nm); },
                                    [&](const uint8_t *p, size_t nb) {
                                        if (nb && std::fwrite(p, 1, nb, pf) != nb) throw std::runtime_error("[ERROR] fail to write data");
@@ -251,7 +291,9 @@ int main(int argc, char **argv) {
         }
         if (gz) zf.close(); else std::fclose(pf);
         std::cerr << "[INFO] " << out_path << ": " << bams.size() << " samples, " << ref_id << ":" << beg << "-" << end
-                  << (has_data ? "" : " (no covering reads)") << std::endl;
+                  << (has_data ? "" : " (no covering reads)");
+        if (inflate_device) std::cerr << "; BAM members inflated on the device: " << members_inflated << " (" << members_bytes << " bytes)";
+        std::cerr << std::endl;
     } catch (const std::exception &ex) {
         die(ex.what());
     }
