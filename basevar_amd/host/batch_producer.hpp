@@ -95,6 +95,33 @@ private:
     bool eof_ = false;
 };
 
+// The header scan (caller.cpp:637-665): every batchfile opened and read through its '#' lines, the sample ids of the
+// ##SampleIDs= lines in batchfile order.  What it leaves is what BatchfileProducer starts from.
+struct BatchfileHeaders {
+    std::vector<GzLineReader> readers;   // one per file, behind its header
+    std::vector<std::string> sample_ids;
+    std::vector<uint32_t> file_samples;  // samples per file
+    std::vector<size_t> header_lines;    // lines in front of the first data row
+    std::vector<std::string> first_row;  // the data row the scan has already taken from the file, if have_row
+    std::vector<bool> have_row;
+};
+inline void scan_batchfile_headers(const std::vector<std::string> &paths, BatchfileHeaders &h) {
+    const size_t n = paths.size();
+    h.readers = std::vector<GzLineReader>(n);
+    h.file_samples.assign(n, 0); h.header_lines.assign(n, 0); h.first_row.assign(n, std::string()); h.have_row.assign(n, false);
+    for (size_t b = 0; b < n; ++b) {
+        if (!h.readers[b].open(paths[b])) throw std::runtime_error("[ERROR] " + paths[b] + " open failure.");
+        std::string line;
+        while (h.readers[b].getline(line)) {
+            if (line.empty() || line[0] != '#') { h.first_row[b] = line; h.have_row[b] = !line.empty(); h.header_lines[b] += line.empty() ? 1 : 0; break; }
+            const size_t before = h.sample_ids.size();
+            parse_sample_ids(line, h.sample_ids);
+            h.file_samples[b] += (uint32_t)(h.sample_ids.size() - before);
+            ++h.header_lines[b];
+        }
+    }
+}
+
 // A fixed set of worker threads that run queued tasks (no task waits for another task: the bookkeeping below queues a task
 // only when it can run to its end).
 class TaskPool {

@@ -25,6 +25,7 @@
 
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -41,6 +42,20 @@ namespace bvamd {
 // n_blocks + 1 entries.  (basetype_gpu.hpp's BaseTypeEngine::bgzf_deflate is one.)
 typedef std::function<void(const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off)>
     BlockDeflater;
+
+// a name that ends in ".gz": a compressed output
+inline bool ends_in_gz(const std::string &s) { return s.size() > 3 && s.compare(s.size() - 3, 3, ".gz") == 0; }
+
+// The cut of `total` bytes of text into blocks of kBlock = 0xff00 bytes counted from its first byte, the last one may be short:
+// block k is [off[k], off[k + 1]), off.size() - 1 blocks (none for an empty text).  What a BlockDeflater and the engine's
+// *_deflate entry points take as block_off.
+inline std::vector<uint64_t> bgzf_block_table(uint64_t total) {
+    const uint64_t kBlock = 0xff00;
+    const size_t nb = (size_t)((total + kBlock - 1) / kBlock);
+    std::vector<uint64_t> off(nb + 1);
+    for (size_t k = 0; k <= nb; ++k) off[k] = std::min<uint64_t>(total, (uint64_t)k * kBlock);
+    return off;
+}
 
 class BgzfWriter {
 public:
@@ -81,8 +96,8 @@ public:
             buf_.insert(buf_.end(), p, p + (bytes - carry));
             text = buf_.data();
         }
-        std::vector<uint64_t> off(full + 1), moff(full + 1, 0);
-        for (size_t k = 0; k <= full; ++k) off[k] = k * kBlock;
+        const std::vector<uint64_t> off = bgzf_block_table(bytes);
+        std::vector<uint64_t> moff(full + 1, 0);
         members_.resize(bytes + 31 * full);
         deflate(text, bytes, off.data(), (uint32_t)full, members_.data(), moff.data());
         for (size_t k = 0; k < full; ++k) {  // what came back is written as it is: hold it to the format first
@@ -275,7 +290,7 @@ class TextOut {
 public:
     void open(const std::string &path) {
         path_ = path;
-        gz_ = path.size() > 3 && path.compare(path.size() - 3, 3, ".gz") == 0;
+        gz_ = ends_in_gz(path);
         if (gz_) bg_.open(path);
         else {
             f_ = std::fopen(path.c_str(), "w");

@@ -34,10 +34,8 @@
 #include <dlfcn.h>
 #include <unistd.h>
 
-#include "../../include/basevar_amd_pileup_bgzf.h"
 #include "../../include/basevar_amd_pileup_text.h"
-#include "raw_members.hpp"
-#include "raw_reads.hpp"
+#include "device_pileup.hpp"
 #endif
 
 namespace {
@@ -107,66 +105,53 @@ bool device_rows(const std::vector<std::string> &bams, const std::string &fa_seq
         const size_t n = bams.size();
         if (window == 0) window = bvamd::pileup_window(n);
         window = std::min<uint32_t>(window, L.max_rows());
+        bvamd::PileupRegionCall call;
+        call.entry.pileup = L.pileup; call.entry.pileup_bgzf = L.pileup_bgzf; call.entry.last_error = L.last_error;
+        call.engine = e;
+        call.n_samples = (uint32_t)n; call.region_beg = beg; call.region_end = end; call.mapq_thd = mapq;
+        call.skip_empty = false;  // (a window without any run is piled up all the same: every row of it is placeholders)
+        call.clamp_tid = true;
         std::vector<uint8_t> buf;
-        std::vector<uint64_t> row_off, block_off, member_off;
-        for (uint32_t sb = beg; sb <= end; sb += bvamd::PILEUP_STEP) {
-            const uint32_t se = std::min(end, sb + bvamd::PILEUP_STEP - 1);
-            for (uint32_t wb = sb; wb <= se; wb += window) {
-                const uint32_t we = std::min(se, wb + window - 1), rows = we - wb + 1;
-                uint32_t n_cov = 0;
-                // (a window without any run is piled up all the same: every row of it is placeholders)
-                if (inflate_device) {
-                    bvamd::WindowMembers wm;
-                    bvamd::read_window_members(pool, bams, ref_id, wb, we, threads, wm);
-                    static_assert(sizeof(bvamd::MemberRun) == sizeof(bv_pileup_bgzf_run), "one run layout");
-                    bv_pileup_bgzf in{};
-                    in.members.data = wm.plan.data.data(); in.members.member_off = wm.plan.member_off.data(); in.members.data_bytes = wm.plan.data.size();
-                    in.members.n_members = (uint32_t)wm.plan.member_pos.size();
-                    in.runs = reinterpret_cast<const bv_pileup_bgzf_run *>(wm.plan.runs.data());
-                    in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)wm.plan.runs.size(); in.n_samples = (uint32_t)n;
-                    in.tid = std::max(wm.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
-                    check(L.pileup_bgzf(e, &in, &n_cov, nullptr));
-                    *members_inflated += in.members.n_members; *members_bytes += in.members.data_bytes;
-                } else {
-                    bvamd::WindowReads reads;
-                    bvamd::read_window_raw(pool, bams, ref_id, wb, we, threads, reads);
-                    bv_pileup_reads in{};
-                    in.records = reads.records.data(); in.run_off = reads.run_off.data(); in.run_sample = reads.run_sample.data();
-                    in.pitch = (n + 15) / 16 * 16; in.n_runs = (uint32_t)reads.run_sample.size(); in.n_samples = (uint32_t)n;
-                    in.tid = std::max(reads.tid, 0); in.region_beg = beg; in.region_end = end; in.beg = wb; in.end = we; in.mapq_thd = mapq;
-                    in.mem_kind = BV_MEM_HOST;
-                    check(L.pileup(e, &in, &n_cov, nullptr));
-                }
-                has_data = has_data || n_cov != 0;
-                // rows a call from a fixed text budget: 16 bytes a cell and the window's token text bound a sub-range's text
-                uint32_t step = rows_per_call;
-                if (step == 0) step = (uint32_t)std::max<uint64_t>(1, ((uint64_t)1 << 28) / (16ull * std::max<size_t>(n, 1)));
-                for (uint32_t first = 0; first < rows; first += step) {
-                    const uint32_t cnt = std::min(step, rows - first);
-                    bv_pileup_text req{};
-                    req.tile = nullptr; req.chrom = ref_id.data(); req.chrom_len = (uint32_t)ref_id.size(); req.first_row = first; req.n_rows = cnt;
-                    row_off.assign((size_t)cnt + 1, 0);
-                    check(L.text(e, &req, row_off.data(), nullptr));
-                    const uint64_t bytes = row_off[cnt];
-                    if (gz) {
-                        block_off.clear();
-                        for (uint64_t o = 0; o < bytes; o += bvamd::BgzfWriter::kBlock) block_off.push_back(o);
-                        block_off.push_back(bytes);
-                        const uint32_t nb = (uint32_t)block_off.size() - 1;
-                        buf.resize(bytes + 31ull * nb);
-                        member_off.assign((size_t)nb + 1, 0);
-                        check(L.deflate(e, block_off.data(), nb, level, buf.data(), buf.size(), member_off.data(), nullptr));
-                        members(buf.data(), member_off.data(), (size_t)nb);
-                    } else {
-                        buf.resize(bytes);
-                        check(L.fetch(e, buf.data(), buf.size(), BV_MEM_HOST, nullptr));
-                        plain(buf.data(), (size_t)bytes);
-                    }
-                }
-                if (we == UINT32_MAX) break;
+        std::vector<uint64_t> row_off, member_off;
+        bvamd::for_each_pileup_window(beg, end, window, [&](uint32_t wb, uint32_t we) {
+            const uint32_t rows = we - wb + 1;
+            uint32_t n_cov = 0;
+            if (inflate_device) {
+                bvamd::WindowMembers wm;
+                bvamd::read_window_members(pool, bams, ref_id, wb, we, threads, wm);
+                bvamd::pileup_window_members(call, wm, wb, we, &n_cov);
+                *members_inflated += wm.plan.member_pos.size(); *members_bytes += wm.plan.data.size();
+            } else {
+                bvamd::WindowReads reads;
+                bvamd::read_window_raw(pool, bams, ref_id, wb, we, threads, reads);
+                bvamd::pileup_window_reads(call, reads, wb, we, &n_cov);
             }
-            if (se == UINT32_MAX) break;
-        }
+            has_data = has_data || n_cov != 0;
+            // rows a call from a fixed text budget: 16 bytes a cell and the window's token text bound a sub-range's text
+            uint32_t step = rows_per_call;
+            if (step == 0) step = (uint32_t)std::max<uint64_t>(1, ((uint64_t)1 << 28) / (16ull * std::max<size_t>(n, 1)));
+            for (uint32_t first = 0; first < rows; first += step) {
+                const uint32_t cnt = std::min(step, rows - first);
+                bv_pileup_text req{};
+                req.tile = nullptr; req.chrom = ref_id.data(); req.chrom_len = (uint32_t)ref_id.size(); req.first_row = first; req.n_rows = cnt;
+                row_off.assign((size_t)cnt + 1, 0);
+                check(L.text(e, &req, row_off.data(), nullptr));
+                const uint64_t bytes = row_off[cnt];
+                if (gz) {
+                    const std::vector<uint64_t> block_off = bvamd::bgzf_block_table(bytes);
+                    const uint32_t nb = (uint32_t)block_off.size() - 1;
+                    buf.resize(bytes + 31ull * nb);
+                    member_off.assign((size_t)nb + 1, 0);
+                    check(L.deflate(e, block_off.data(), nb, level, buf.data(), buf.size(), member_off.data(), nullptr));
+                    members(buf.data(), member_off.data(), (size_t)nb);
+                } else {
+                    buf.resize(bytes);
+                    check(L.fetch(e, buf.data(), buf.size(), BV_MEM_HOST, nullptr));
+                    plain(buf.data(), (size_t)bytes);
+                }
+            }
+            return true;
+        });
     } catch (...) {
         L.destroy(e);
         throw;
@@ -205,16 +190,7 @@ int main(int argc, char **argv) {
         else if (a == "--rows-per-call") rows_per_call = (uint32_t)std::stoul(next());
         else die("unknown argument " + a);
     }
-    if (!bam_list.empty()) {  // get_firstcolumn_from_file, src/basetype_caller.cpp:114-117
-        std::ifstream f(bam_list);
-        if (!f) die("[ERROR] cannot open " + bam_list);
-        std::string line;
-        while (std::getline(f, line)) {
-            if (line.empty() || line[0] == '#') continue;
-            const size_t e = line.find_first_of(" \t");
-            bams.push_back(e == std::string::npos ? line : line.substr(0, e));
-        }
-    }
+    if (!bam_list.empty() && !bvamd::read_first_column(bam_list, bams)) die("[ERROR] cannot open " + bam_list);
     if (rows_arg != "host" && rows_arg != "device") die("--rows wants host or device");
     if (level_arg != "fast" && level_arg != "small") die("--deflate-level wants fast or small");
     if (inflate_arg != "host" && inflate_arg != "device") die("--inflate wants host or device");
@@ -225,12 +201,10 @@ int main(int argc, char **argv) {
     if (bams.empty() || fasta.empty() || regions.empty() || out_path.empty())
         die("usage: bv_pileup -R ref.fa --regions CHR:BEG-END [--mapq Q] -I a.bam [-I ...] [-L list] -o out.bf[.gz]");
     try {
-        // "chr:beg-end", 1-based inclusive (the chromosome name may itself contain ':')
-        const size_t colon = regions.rfind(':'), dash = regions.rfind('-');
-        if (colon == std::string::npos || dash == std::string::npos || dash < colon) die("--regions wants CHR:BEG-END");
-        const std::string ref_id = regions.substr(0, colon);
-        const uint32_t beg = (uint32_t)std::stoul(regions.substr(colon + 1, dash - colon - 1));
-        const uint32_t end = (uint32_t)std::stoul(regions.substr(dash + 1));
+        bvamd::Region rg;
+        if (!bvamd::parse_region(regions, rg)) die("--regions wants CHR:BEG-END");
+        const std::string &ref_id = rg.ref_id;
+        const uint32_t beg = rg.beg, end = rg.end;
         if (beg < 1 || end < beg) die("--regions wants 1 <= BEG <= END");
 
         std::vector<std::string> sample_ids;
@@ -248,7 +222,7 @@ int main(int argc, char **argv) {
         const std::string fa_seq = bvamd::load_fasta_sequence(fasta, ref_id);
         if (end > fa_seq.size()) die("[ERROR] region end beyond the end of " + ref_id);
 
-        const bool gz = out_path.size() > 3 && out_path.compare(out_path.size() - 3, 3, ".gz") == 0;
+        const bool gz = bvamd::ends_in_gz(out_path);
         // `.gz`: BGZF, as the reference writes its batchfiles ("must be compressed by BGZF", src/basetype_caller.cpp:428) -- a chain
         // of independent gzip members, which bv_call inflates in parallel (batch_producer.hpp); gzip tools read it as they read .gz
         bvamd::BgzfWriter zf;

@@ -1,0 +1,675 @@
+// call_pipeline.hpp -- the stages of bv_call (bv_call.cpp) and what they hand each other, apart from the command line.
+//
+//   one producer  --to_gpu-->  engine workers  --to_emit-->  OrderedEmitter  -->  the VCF and CVG outputs
+//
+// Batches of consecutive sites, numbered in genomic order (Batch::seq).  The three producers run on the caller's thread:
+//   produce_batchfile_text   blocks of batchfile rows as text, parsed on the device by the workers      -> to_gpu
+//   produce_bam_host         BAM files piled up on the host threads (pileup.hpp), slab rows             -> to_gpu
+//   produce_bam_device       BAM windows piled up and called on an engine of its own (device_pileup.hpp) -> to_emit
+// (`--inflate device` on batchfiles has none: the workers take turns at the raw reader, RawReaderTurns.)  A new BAM route
+// provides one such function: it takes the CallContext, the BamInput, the queue it feeds, the StageClock and the ErrorSink, walks
+// the regions with for_each_bam_region and pushes batches in seq order.
+// An engine worker (EngineWorker: a thread, an engine on one GPU) shares with the emitter the to_emit queue and nothing else; all
+// stages share the CallContext (immutable), the StageClock and the ErrorSink (a mutex of their own each).  The emitter
+// (OrderedEmitter: a thread) alone writes the outputs and counts sites, VCF records and device-written lines.
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <exception>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "basetype_gpu.hpp"
+#include "batch_producer.hpp"
+#include "bgzf_tabix.hpp"
+#include "device_pileup.hpp"
+#include "pileup.hpp"
+#include "vcf_emit.hpp"
+
+namespace bvamd {
+
+// One batch of consecutive sites on its way through the pipeline.
+struct Batch {
+    uint64_t seq = 0;
+    SlabBuilder slab;
+    std::vector<SiteText> text;
+    BaseTypeBatch result;
+    std::string error;
+    // batchfile input: the block's rows as text (parsed on the device by the engine worker, bv_engine_text_parse), and the
+    // cell / phred rows of the records that come back; `error` then follows the records before the offending position
+    bool from_text = false;
+    std::string rows;
+    std::vector<uint64_t> row_off;
+    uint32_t n_positions = 0;
+    std::vector<uint8_t> cell, phred;
+    // --emit device: the VCF lines of the batch's variant records were written on the worker's engine (bv_engine_vcf_format).
+    // line j is text[vcf_line_off[j] .. vcf_line_off[j + 1]) and belongs to record vcf_record[j]; the text comes as BGZF members
+    // of 0xff00 bytes counted from its first byte (a *.vcf.gz output) or as it is (a plain one)
+    bool emit_device = false;
+    std::vector<uint32_t> vcf_record;
+    std::vector<uint64_t> vcf_line_off, vcf_member_off;
+    std::vector<uint8_t> vcf_members;
+    std::string vcf_text;
+    explicit Batch(uint32_t n_samples) : slab(n_samples) {}
+    const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
+    const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
+};
+typedef std::unique_ptr<Batch> BatchPtr;
+
+// Bounded hand-off queue (mutex + condition variables); close() lets the consumers drain and stop.
+class BatchQueue {
+public:
+    explicit BatchQueue(size_t cap) : cap_(cap) {}
+    void push(BatchPtr b) {
+        std::unique_lock<std::mutex> lk(mu_);
+        not_full_.wait(lk, [&] { return q_.size() < cap_; });
+        q_.push_back(std::move(b));
+        not_empty_.notify_one();
+    }
+    BatchPtr pop() {  // nullptr once closed and empty
+        std::unique_lock<std::mutex> lk(mu_);
+        not_empty_.wait(lk, [&] { return !q_.empty() || closed_; });
+        if (q_.empty()) return nullptr;
+        BatchPtr b = std::move(q_.front());
+        q_.pop_front();
+        not_full_.notify_one();
+        return b;
+    }
+    void close() {
+        std::lock_guard<std::mutex> lk(mu_);
+        closed_ = true;
+        not_empty_.notify_all();
+    }
+private:
+    size_t cap_;
+    std::deque<BatchPtr> q_;
+    bool closed_ = false;
+    std::mutex mu_;
+    std::condition_variable not_full_, not_empty_;
+};
+
+// Wall-clock seconds per stage, the way the reference prints its phases (src/basetype_caller.cpp:193-215, 625-632).  Any thread adds.
+class StageClock {
+public:
+    enum Field { READ, PARSE, ENGINE, EMIT };  // ENGINE: summed over the workers; READ / PARSE: thread-seconds of the producer's side
+    void add(Field f, double seconds) { std::lock_guard<std::mutex> lk(mu_); s_[f] += seconds; }
+    double get(Field f) const { std::lock_guard<std::mutex> lk(mu_); return s_[f]; }
+    static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+private:
+    mutable std::mutex mu_;
+    double s_[4] = {0, 0, 0, 0};
+};
+
+// The run's error: the first one reported wins, the producers and the raw reader stop once there is one.
+class ErrorSink {
+public:
+    void fail(const std::string &m) { std::lock_guard<std::mutex> lk(mu_); if (first_.empty()) first_ = m; }
+    bool ok() const { std::lock_guard<std::mutex> lk(mu_); return first_.empty(); }
+    std::string first() const { std::lock_guard<std::mutex> lk(mu_); return first_; }
+private:
+    mutable std::mutex mu_;
+    std::string first_;
+};
+
+// fn(t, lo, hi) over [0, n) on up to `threads` threads (contiguous ranges; the caller's thread takes the first)
+// An exception in any range (a malformed row, bad_alloc under large batches) is caught on its thread and the first one rethrown
+// on the caller's thread once all ranges are done -- the tool's "[ERROR] ..." exit path, not std::terminate.
+template <typename Fn>
+void parallel_ranges(size_t n, int threads, Fn fn) {
+    const size_t nt = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, threads), n));
+    if (nt <= 1) { fn(0, 0, n); return; }
+    std::vector<std::thread> pool;
+    std::vector<std::exception_ptr> errs(nt);
+    for (size_t t = 1; t < nt; ++t)
+        pool.emplace_back([&, t]() { try { fn(t, n * t / nt, n * (t + 1) / nt); } catch (...) { errs[t] = std::current_exception(); } });
+    try { fn(0, 0, n / nt); } catch (...) { errs[0] = std::current_exception(); }
+    for (auto &th : pool) th.join();
+    for (auto &e : errs) if (e) std::rethrow_exception(e);
+}
+
+// Which way each stage goes, resolved from the options and the inputs before any thread starts (bv_call.cpp: resolve_routes)
+struct Routes {
+    bool device_inflate = false;      // --inflate device: BGZF batchfiles reach the engine compressed (RawReaderTurns)
+    bool device_deflate = false;      // --deflate device: the emitter's whole output blocks are compressed by an engine
+    bool emit_device = false;         // --emit device: the VCF lines' sample columns are written on the worker's engine
+    bool device_pileup = false;       // --pileup device: produce_bam_device
+    bool bam_inflate_device = false;  // ... with --inflate device: the BAM files' members reach the engine compressed
+};
+
+// What every stage reads and none writes: built once before any thread starts, passed as const &
+struct CallContext {
+    std::vector<std::string> sample_ids, group_names;
+    std::vector<uint8_t> group_id;       // [samples]: index into group_names, BV_NO_GROUP
+    std::vector<uint32_t> file_samples;  // samples per batchfile, in batchfile order (the header scan)
+    uint32_t batch_sites = 0;
+    std::vector<int> devices;            // one engine per entry
+    int threads = 4;
+    float user_min_af = 0.01f;
+    int deflate_level = BV_DEFLATE_FAST;
+    bool from_bam = false, vcf_gz = false;
+    Routes routes;
+    size_t n_sample() const { return sample_ids.size(); }
+    uint32_t n_groups() const { return (uint32_t)group_names.size(); }
+    const uint8_t *group_ids() const { return group_names.empty() ? nullptr : group_id.data(); }
+};
+
+// BAM input: the files, the FASTA and the regions in the order given
+struct BamInput {
+    std::vector<std::string> bams;
+    std::string reference;
+    std::vector<Region> regions;
+    int mapq_thd = 10;
+};
+
+// ---------------------------------------------------------------------------------------------------------------- the emitter
+
+// Writes the batches in seq order, whatever order they arrive in.  A failed slab batch stops everything from itself on; a
+// failed text batch (its host reader refused a position) first writes its records, which lie before that position.  The lines
+// of a batch are formatted by `ctx.threads` threads (ranges of consecutive sites, a text buffer each) and written in site order.
+// `deflate` (may be empty; used with routes.device_deflate): compresses the whole blocks a batch completes, bgzf_tabix.hpp.  It
+// is let go in finish(), on the emitter's thread.  Without one nothing here needs an engine.
+class OrderedEmitter {
+public:
+    OrderedEmitter(const CallContext &ctx, TextOut &vcf, TextOut &cvg, StageClock &clk, ErrorSink &errors, BlockDeflater deflate = nullptr)
+        : ctx_(ctx), vcf_(vcf), cvg_(cvg), clk_(clk), errors_(errors), inner_(std::move(deflate)) {
+        deflate_ = [this](const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off) {
+            const double t0 = StageClock::now();
+            inner_(text, text_bytes, block_off, n_blocks, dst, member_off);
+            members_deflated_ += n_blocks;
+            deflate_s_ += StageClock::now() - t0;
+        };
+    }
+    OrderedEmitter(const OrderedEmitter &) = delete;
+    OrderedEmitter &operator=(const OrderedEmitter &) = delete;
+
+    void run(BatchQueue &in) {  // the thread's body
+        for (BatchPtr b; (b = in.pop());) accept(std::move(b));
+        finish();
+    }
+    void accept(BatchPtr b) {
+        const uint64_t seq = b->seq;
+        waiting_[seq] = std::move(b);
+        for (auto it = waiting_.find(next_seq_); it != waiting_.end(); it = waiting_.find(next_seq_)) {
+            Batch &d = *it->second;
+            if (stopped_) {
+            } else if (!d.error.empty() && !d.from_text) {
+                stopped_ = true;
+                errors_.fail(d.error);
+            } else {
+                write(d);
+                if (!d.error.empty()) { stopped_ = true; errors_.fail(d.error); }
+            }
+            waiting_.erase(it);
+            ++next_seq_;
+        }
+    }
+    // No more batches: what still waits behind a gap is dropped, and both outputs are closed (a *.gz gets its last block, its
+    // end-of-file member and its index) whether or not the run failed.
+    void finish() {
+        waiting_.clear();
+        inner_ = nullptr;
+        try { vcf_.close(); cvg_.close(); } catch (const std::exception &ex) { errors_.fail(ex.what()); }
+    }
+    // (for the thread that joined the emitter's)
+    size_t n_sites() const { return n_sites_; }
+    size_t n_variants() const { return n_variants_; }
+    uint64_t vcf_lines_device() const { return vcf_lines_device_; }
+    uint64_t members_deflated() const { return members_deflated_; }
+    double deflate_s() const { return deflate_s_; }
+
+private:
+    void write(Batch &d) {
+        const double t0 = StageClock::now();
+        const size_t nt = (size_t)std::max(1, ctx_.threads), n_sample = ctx_.n_sample();
+        const bool device_deflate = ctx_.routes.device_deflate;
+        std::vector<std::string> cvg_txt(nt), vcf_txt(nt);
+        std::vector<size_t> nv(nt, 0);
+        parallel_ranges(d.text.size(), ctx_.threads, [&](size_t t, size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                cvg_txt[t] += format_cvg_line(d.text[i], d.result.sites[i]);
+                if (d.emit_device) continue;  // (the VCF lines are there already)
+                if (d.result.has_variant(i)) {
+                    vcf_txt[t] += format_vcf_line(d.text[i], d.cell_row(i, n_sample), d.phred_row(i, n_sample), n_sample, d.result.sites[i],
+                                                  ctx_.group_names.empty() ? nullptr : &d.result.group(i, 0), ctx_.group_names);
+                    ++nv[t];
+                }
+            }
+        });
+        try {
+            if (d.emit_device || device_deflate) {
+                // one piece a file and batch (a deflate call takes as long as its slowest block, however few blocks it has)
+                for (size_t t = 1; t < nt; ++t) {
+                    cvg_txt[0] += cvg_txt[t]; std::string().swap(cvg_txt[t]);
+                    vcf_txt[0] += vcf_txt[t]; std::string().swap(vcf_txt[t]);
+                }
+                if (device_deflate) cvg_.write_lines(cvg_txt[0], deflate_);
+                else cvg_.write_lines(cvg_txt[0]);
+                std::string().swap(cvg_txt[0]);
+                if (d.emit_device) write_device_lines(d, nv[0]);
+                else vcf_.write_lines(vcf_txt[0], deflate_);
+            } else {
+                for (size_t t = 0; t < nt; ++t) {
+                    cvg_.write_lines(cvg_txt[t]);
+                    vcf_.write_lines(vcf_txt[t]);
+                }
+            }
+            for (size_t t = 0; t < nt; ++t) n_variants_ += nv[t];
+        } catch (const std::exception &ex) { errors_.fail(ex.what()); }
+        n_sites_ += d.text.size();
+        clk_.add(StageClock::EMIT, StageClock::now() - t0);
+    }
+    // --emit device: the VCF lines as the worker's engine left them
+    void write_device_lines(const Batch &d, size_t &n_variant) {
+        if (ctx_.vcf_gz) {
+            std::vector<std::pair<std::string, int64_t>> keys;
+            for (uint32_t i : d.vcf_record) keys.emplace_back(d.text[i].ref_id, (int64_t)d.text[i].ref_pos);
+            vcf_.write_members(d.vcf_members.data(), d.vcf_member_off.data(), d.vcf_member_off.empty() ? 0 : d.vcf_member_off.size() - 1, d.vcf_line_off.data(),
+                               keys);
+        } else {
+            vcf_.write_lines(d.vcf_text);
+        }
+        for (size_t i = 0; i < d.text.size(); ++i) n_variant += d.result.has_variant(i) ? 1 : 0;
+        vcf_lines_device_ += d.vcf_record.size();
+    }
+
+    const CallContext &ctx_;
+    TextOut &vcf_, &cvg_;
+    StageClock &clk_;
+    ErrorSink &errors_;
+    BlockDeflater inner_, deflate_;
+    std::map<uint64_t, BatchPtr> waiting_;  // finished out of order
+    uint64_t next_seq_ = 0;
+    bool stopped_ = false;  // a batch failed: nothing behind it is written
+    size_t n_sites_ = 0, n_variants_ = 0;
+    uint64_t vcf_lines_device_ = 0, members_deflated_ = 0;
+    double deflate_s_ = 0;
+};
+
+// --deflate device: an engine is not re-entrant and the workers' engines are busy, so the emitter gets a small one of its own
+// on the first engine's device, made when its first batch arrives
+inline BlockDeflater device_block_deflater(const CallContext &ctx) {
+    std::shared_ptr<std::unique_ptr<BaseTypeEngine>> engine(new std::unique_ptr<BaseTypeEngine>());
+    const float min_af = ctx.user_min_af;
+    const int device = ctx.devices[0], level = ctx.deflate_level;
+    return [engine, min_af, device, level](const char *text, uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off) {
+        if (!*engine) engine->reset(new BaseTypeEngine(1, 1, min_af, device));
+        (*engine)->bgzf_deflate(text, text_bytes, block_off, n_blocks, dst, member_off, level);
+    };
+}
+
+// ---------------------------------------------------------------------------------------------------------- the engine workers
+
+// --inflate device: BGZF batchfiles go to the engine compressed (bv_engine_text_parse_bgzf inflates, finds the lines and
+// parses).  There is no producer then: the engine workers take turns at the raw reader -- a worker reads the next runs from the
+// cursors, parses them on its engine, hands the new cursors back and only then lets go of the reader, so its row fetch, host
+// reader, submit and records overlap the next worker's parse.
+class RawReaderTurns {
+public:
+    RawReaderTurns(const CallContext &ctx, BgzfRawReader &raw, size_t target) : ctx_(ctx), raw_(raw), target_(target) {}
+    // One turn: the next batch, numbered and parsed on `engine` (`bp`: for its finish_bgzf), or with the error that ends the
+    // file; nullptr when the files are at their end or the run has failed.
+    BatchPtr take(BaseTypeEngine &engine, BaseTypeEngine::BgzfParse &bp, StageClock &clk, const ErrorSink &errors) {
+        std::lock_guard<std::mutex> lk(mu_);
+        while (!done_) {
+            if (!errors.ok()) { done_ = true; break; }
+            std::string error;
+            BgzfRawRuns runs;
+            try {
+                const double t0 = StageClock::now();
+                raw_.next(runs, target_);
+                const double t1 = StageClock::now();
+                const bv_bgzf_rows rows{runs.data.data(), runs.member_off.data(), runs.data.size(), runs.file_member.data(), ctx_.file_samples.data(),
+                                        runs.skip_bytes.data(), runs.skip_lines.data(), (uint32_t)ctx_.file_samples.size(), ctx_.batch_sites,
+                                        runs.at_end ? 1u : 0u, 0};
+                bp = engine.parse_bgzf(rows, ctx_.batch_sites, ctx_.group_ids(), ctx_.n_groups());
+                clk.add(StageClock::READ, t1 - t0);
+                clk.add(StageClock::ENGINE, StageClock::now() - t1);
+            } catch (const BaseTypeEngine::BgzfDataError &ex) {
+                // the message the host reader has for such a file
+                error = std::strstr(ex.what(), "bad header") ? "[ERROR] not a BGZF member where one was expected (truncated or damaged batchfile)"
+                                                            : "[ERROR] a BGZF member does not inflate to its recorded size";
+            } catch (const std::exception &ex) { error = ex.what(); }
+            if (error.empty() && bp.n_positions == 0) {
+                if (runs.at_end) { done_ = true; break; }
+                target_ *= 2;  // not one complete row in every run: longer runs
+                continue;
+            }
+            BatchPtr b(new Batch((uint32_t)ctx_.n_sample()));
+            b->from_text = true;
+            b->seq = seq_++;
+            if (!error.empty()) {
+                b->error = error;
+                done_ = true;
+            } else {
+                std::vector<uint32_t> cm(bp.cursor.size()), co(bp.cursor.size());
+                for (size_t f = 0; f < bp.cursor.size(); ++f) { cm[f] = bp.cursor[f].member; co[f] = bp.cursor[f].offset; }
+                raw_.advance(runs, cm.data(), co.data());
+            }
+            return b;
+        }
+        return nullptr;
+    }
+private:
+    const CallContext &ctx_;
+    BgzfRawReader &raw_;
+    std::mutex mu_;
+    bool done_ = false;
+    uint64_t seq_ = 0;
+    size_t target_;
+};
+
+// One worker thread: an engine on devices[w % G], batches from `in` (or from its turns at the raw reader) to `out`
+class EngineWorker {
+public:
+    EngineWorker(const CallContext &ctx, size_t w, BatchQueue &in, BatchQueue &out, RawReaderTurns *raw, StageClock &clk, ErrorSink &errors)
+        : ctx_(ctx), device_(ctx.devices[w % ctx.devices.size()]), in_(in), out_(out), raw_(raw), clk_(clk), errors_(errors) {}
+
+    void run() {  // the thread's body
+        // this worker feeds one GPU: keep it (and the staging memory it touches first) on the CPUs of that GPU's NUMA node
+        (void)bv_bind_thread_to_device_node(device_);
+        try {
+            engine_.reset(new BaseTypeEngine(ctx_.batch_sites, (uint32_t)ctx_.n_sample(), ctx_.user_min_af, device_));
+        } catch (const std::exception &ex) { errors_.fail(ex.what()); }
+        if (raw_ && engine_) run_raw_turns();
+        for (BatchPtr b; (b = in_.pop());) {
+            if (engine_) {
+                const double t0 = StageClock::now();
+                if (b->from_text) call_text_rows(*b);
+                else call_slab(*b);
+                clk_.add(StageClock::ENGINE, StageClock::now() - t0);
+            } else {
+                b->error = "no engine on device " + std::to_string(device_);
+            }
+            out_.push(std::move(b));
+        }
+        engine_.reset();  // (here, on this thread and beside the other workers', while the emitter still writes the last batches)
+    }
+
+private:
+    static bool host_reader(const std::vector<std::string> &r, size_t n, SlabBuilder &sb, SiteText &st) { return parse_site_rows_fast(r, n, sb, st); }
+
+    void run_raw_turns() {
+        for (;;) {
+            BaseTypeEngine::BgzfParse bp;
+            BatchPtr b = raw_->take(*engine_, bp, clk_, errors_);
+            if (!b) break;
+            if (b->error.empty()) {
+                const double t0 = StageClock::now();
+                text_batch(*b, [&]() {
+                    return engine_->finish_bgzf(bp, ctx_.file_samples.data(), ctx_.file_samples.size(), host_reader, ctx_.n_groups(), !ctx_.routes.emit_device);
+                });
+                clk_.add(StageClock::ENGINE, StageClock::now() - t0);
+            }
+            out_.push(std::move(b));
+        }
+    }
+    // the device parses the rows; the positions it leaves to the host go to the host reader in between
+    void call_text_rows(Batch &b) {
+        text_batch(b, [&]() {
+            const bv_text_rows rows{b.rows.data(), b.row_off.data(), ctx_.file_samples.data(), b.rows.size(), b.n_positions, (uint32_t)ctx_.file_samples.size(), 0};
+            return engine_->lrt_text(rows, host_reader, ctx_.group_ids(), ctx_.n_groups(), !ctx_.routes.emit_device);
+        });
+        std::string().swap(b.rows);
+    }
+    // (the producer's choice of layout: short reads -> the rank words carry the calls, basetype_gpu.hpp)
+    void call_slab(Batch &b) {
+        try { b.slab.tag_ranks(); b.result = engine_->lrt(b.slab); } catch (const std::exception &ex) { b.error = ex.what(); }
+    }
+    // a text batch through `make`, which parses and calls it; a failure of the engine leaves the batch without records
+    template <class Make>
+    void text_batch(Batch &b, Make make) {
+        try { take_text_result(b, make()); } catch (const std::exception &ex) { b.error = ex.what(); b.text.clear(); b.emit_device = false; }
+    }
+    // the records of a text batch into the batch; what the host reader threw becomes the batch's error, behind its records
+    void take_text_result(Batch &b, BaseTypeEngine::TextBatch &&tb) {
+        b.result = std::move(tb.batch);
+        b.text = std::move(tb.text);
+        b.cell = std::move(tb.cell);
+        b.phred = std::move(tb.phred);
+        if (ctx_.routes.emit_device) emit_on_device(b);
+        if (tb.error) {
+            try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b.error = ex.what(); }
+        }
+    }
+    // --emit device: heads and gt of the batch's variant records, the lines on this worker's engine (from the rows its text
+    // submit left on the device: the planes do not come back and the text does not go up), then BGZF members deflated there
+    // too (a *.vcf.gz, at --deflate-level) or the text
+    void emit_on_device(Batch &b) {
+        b.emit_device = true;
+        std::vector<std::string> heads;
+        std::vector<uint8_t> gt;
+        for (size_t i = 0; i < b.text.size(); ++i) {
+            if (!b.result.has_variant(i)) continue;
+            std::string head = format_vcf_head(b.text[i], b.result.sites[i], ctx_.group_names.empty() ? nullptr : &b.result.group(i, 0), ctx_.group_names);
+            if (head.empty()) continue;  // (no ALT: format_vcf_line writes nothing)
+            uint8_t g[4];
+            vcf_gt_codes(b.text[i], b.result.sites[i], g);
+            b.vcf_record.push_back((uint32_t)i);
+            heads.push_back(std::move(head));
+            gt.insert(gt.end(), g, g + 4);
+        }
+        b.vcf_line_off = engine_->vcf_format(b.vcf_record, heads, gt);
+        const uint64_t total = b.vcf_line_off.back();
+        if (total == 0) return;
+        if (ctx_.vcf_gz) {
+            const std::vector<uint64_t> block_off = bgzf_block_table(total);
+            const size_t nb = block_off.size() - 1;
+            b.vcf_members.resize(total + 31 * nb);
+            b.vcf_member_off.assign(nb + 1, 0);
+            engine_->vcf_deflate(total, block_off.data(), (uint32_t)nb, b.vcf_members.data(), b.vcf_member_off.data(), ctx_.deflate_level);
+            b.vcf_members.resize(b.vcf_member_off[nb]);
+        } else {
+            b.vcf_text.resize(total);
+            engine_->vcf_fetch(&b.vcf_text[0], total);
+        }
+    }
+
+    const CallContext &ctx_;
+    const int device_;
+    BatchQueue &in_, &out_;
+    RawReaderTurns *raw_;
+    StageClock &clk_;
+    ErrorSink &errors_;
+    std::unique_ptr<BaseTypeEngine> engine_;
+};
+
+// --------------------------------------------------------------------------------------------------------------- the producers
+
+inline BatchPtr new_slab_batch(const CallContext &ctx, uint64_t seq) {
+    BatchPtr b(new Batch((uint32_t)ctx.n_sample()));
+    if (!ctx.from_bam) b->slab.reserve_rows(ctx.batch_sites);  // (address space; the pages come as the rows do -- no regrowth copies)
+    if (!ctx.group_names.empty()) b->slab.set_groups(ctx.group_id, ctx.n_groups());
+    b->seq = seq;
+    return b;
+}
+
+// One row from every batchfile per position (caller.cpp:586-611), on `ctx.threads` host threads: files read and positions cut
+// in blocks by a pipeline of tasks (batch_producer.hpp), joined here in position order.  Every block goes to the engines as its
+// rows' text: the device parses them (bv_engine_text_parse), the engine worker re-reads with the host reader only the positions
+// the device leaves to it.  A block is one batch; text is about twice the 5 B per cell of planes, so a batch carries half the
+// cells of the planes' budget.
+inline void produce_batchfile_text(const CallContext &ctx, BatchfileHeaders &headers, const std::vector<std::string> &batchfiles, size_t block_bytes,
+                                   BatchQueue &to_gpu, StageClock &clk, const ErrorSink &errors) {
+    BatchfileProducer producer(headers.readers, headers.first_row, headers.have_row, ctx.n_sample(), ctx.threads);
+    producer.set_paths(batchfiles, headers.header_lines);  // BGZF files (what the reference writes): members inflated in parallel
+    struct AddClock {  // (whether run_text returns or throws)
+        const BatchfileProducer &p; StageClock &clk;
+        ~AddClock() { clk.add(StageClock::READ, p.clock.read); clk.add(StageClock::PARSE, p.clock.parse); }
+    } add_clock{producer, clk};
+    uint64_t seq = 0;
+    producer.run_text([&](std::string &rows, std::vector<uint64_t> &row_off, size_t n_positions) {
+        BatchPtr b = new_slab_batch(ctx, seq++);
+        b->from_text = true;
+        b->rows.swap(rows);
+        b->row_off.swap(row_off);
+        b->n_positions = (uint32_t)n_positions;
+        to_gpu.push(std::move(b));
+        return errors.ok();
+    }, block_bytes, ctx.batch_sites);
+}
+
+// fn(region, fa_seq) for the regions in the order given ("-r chr:beg-end[,chr:beg-end ...]", caller.cpp:311-356), with the
+// sequence of the region's contig; a region that is not inside its contig is thrown
+template <class Fn>
+void for_each_bam_region(const BamInput &in, Fn fn) {
+    std::string fa_seq, fa_of;
+    for (const Region &rg : in.regions) {
+        if (fa_of != rg.ref_id) { fa_seq = load_fasta_sequence(in.reference, rg.ref_id); fa_of = rg.ref_id; }
+        if (rg.beg < 1 || rg.end < rg.beg || rg.end > fa_seq.size()) throw std::runtime_error("[ERROR] region outside " + rg.ref_id);
+        fn(rg, fa_seq);
+    }
+}
+
+// Pileup windows -> slab rows, straight from the tile planes (no text round trip); a site is a position that at least one
+// sample covers (the reference skips rows of total depth 0, caller.cpp:718)
+inline void produce_bam_host(const CallContext &ctx, const BamInput &in, BatchQueue &to_gpu, StageClock &clk, const ErrorSink &errors) {
+    uint64_t seq = 0;
+    BatchPtr cur;
+    for_each_bam_region(in, [&](const Region &rg, const std::string &fa_seq) {
+        const double tp0 = StageClock::now();
+        pileup_region(in.bams, fa_seq, rg.ref_id, rg.beg, rg.end, in.mapq_thd, true, ctx.threads, [&](const PileupTile &t) {
+            size_t next_indel = 0;
+            for (uint32_t pos = t.beg; pos <= t.end && errors.ok(); ++pos) {
+                if (t.depth[pos - t.beg] == 0) continue;
+                if (!cur) cur = new_slab_batch(ctx, seq++);
+                const size_t k = t.at(pos, 0);
+                const char rb = fa_seq[pos - 1];
+                cur->slab.add_row(&t.cell[k], &t.qual[k], &t.mapq[k], &t.rank[k], (uint8_t)base_code((char)std::toupper((unsigned char)rb)));
+                SiteText st;
+                st.ref_id = rg.ref_id; st.ref_pos = pos; st.ref_base = std::string(1, rb);
+                while (next_indel < t.indels.size() && t.indels[next_indel].pos < pos) ++next_indel;
+                for (; next_indel < t.indels.size() && t.indels[next_indel].pos == pos; ++next_indel) st.indel_tokens.push_back(t.indels[next_indel].text);
+                cur->text.push_back(std::move(st));
+                if (cur->slab.n_sites() == ctx.batch_sites) to_gpu.push(std::move(cur));
+            }
+        });
+        clk.add(StageClock::PARSE, StageClock::now() - tp0);
+    });
+    if (cur) to_gpu.push(std::move(cur));  // (a batch in the making has a row)
+}
+
+// --pileup device: the samples' raw BAM records of a window go to an engine of the producer's own, which piles them up
+// (bv_engine_pileup), gathers the covered rows and submits them where they lie (bv_engine_pileup_rows / _submit); the host
+// threads only read and inflate -- or, with routes.bam_inflate_device, read the compressed BGZF members of every sample's fetch
+// and the cut points (raw_members.hpp), which the engine inflates too (bv_engine_pileup_bgzf).  Its batches are called already:
+// they go to the emitter's queue.
+class DevicePileupProducer {
+public:
+    struct Stats {
+        uint64_t reads_bytes = 0;                       // raw BAM records handed to the engine
+        uint64_t members_inflated = 0, members_bytes = 0;  // ... or the compressed members handed to it instead
+        double pileup_s = 0;                            // seconds inside the pileup calls (part of PARSE)
+    };
+    DevicePileupProducer(const CallContext &ctx, const BamInput &in, BatchQueue &to_emit, StageClock &clk, const ErrorSink &errors)
+        : ctx_(ctx), in_(in), out_(to_emit), clk_(clk), errors_(errors) {}
+
+    void run() {
+        struct LetGo {  // the engine and the open files go when the last window is through (or an error ends the walk), not with the producer:
+            DevicePileupProducer &p;  // the emitter still writes the last batches then
+            ~LetGo() { p.engine_.reset(); p.pool_.reset(); }
+        } let_go{*this};
+        for_each_bam_region(in_, [&](const Region &rg, const std::string &fa_seq) {
+            if (!engine_) engine_.reset(new BaseTypeEngine(ctx_.batch_sites, (uint32_t)ctx_.n_sample(), ctx_.user_min_af, ctx_.devices[0]));
+            if (!pool_) pool_.reset(new BamPool(in_.bams, true));
+            check(bv_engine_pileup_set_reference(engine_->handle(), fa_seq.data(), fa_seq.size()));
+            PileupRegionCall call;
+            call.entry.pileup = bv_engine_pileup; call.entry.pileup_bgzf = bv_engine_pileup_bgzf; call.entry.last_error = bv_last_error;
+            call.engine = engine_->handle();
+            call.n_samples = (uint32_t)ctx_.n_sample(); call.region_beg = rg.beg; call.region_end = rg.end; call.mapq_thd = in_.mapq_thd;
+            call.skip_empty = true;
+            const uint32_t window = std::min<uint32_t>(pileup_window(in_.bams.size()), bv_pileup_max_rows());
+            for_each_pileup_window(rg.beg, rg.end, window, [&](uint32_t wb, uint32_t we) {
+                if (errors_.ok()) this->window(call, rg.ref_id, fa_seq, wb, we);
+                return errors_.ok();
+            });
+        });
+    }
+    const Stats &stats() const { return stats_; }
+
+private:
+    void check(int rc) { if (rc != BV_OK) throw std::runtime_error(bv_last_error(engine_->handle())); }
+
+    void window(const PileupRegionCall &call, const std::string &ref_id, const std::string &fa_seq, uint32_t wb, uint32_t we) {
+        // every sample's records of the fetch, undecoded (or the members that hold them), on `threads` threads
+        const double tr0 = StageClock::now();
+        WindowReads reads;
+        WindowMembers wm;
+        if (ctx_.routes.bam_inflate_device) read_window_members(*pool_, in_.bams, ref_id, wb, we, ctx_.threads, wm);
+        else read_window_raw(*pool_, in_.bams, ref_id, wb, we, ctx_.threads, reads);
+        const double tp0 = StageClock::now();
+        clk_.add(StageClock::READ, tp0 - tr0);
+        uint32_t n_cov = 0;
+        if (ctx_.routes.bam_inflate_device) {
+            if (!wm.plan.runs.empty()) { stats_.members_inflated += wm.plan.member_pos.size(); stats_.members_bytes += wm.plan.data.size(); }
+            if (!pileup_window_members(call, wm, wb, we, &n_cov)) return;
+        } else {
+            stats_.reads_bytes += reads.records.size();
+            if (!pileup_window_reads(call, reads, wb, we, &n_cov)) return;
+        }
+        bv_engine *pe = engine_->handle();
+        std::vector<uint32_t> pos(n_cov), depth(n_cov);
+        bv_slab slab;
+        // (short reads: the rank words carry the calls, as SlabBuilder::tag_ranks chooses on the host path)
+        if (bv_engine_pileup_rows(pe, 1, &slab, pos.data(), depth.data()) != BV_OK) check(bv_engine_pileup_rows(pe, 0, &slab, pos.data(), depth.data()));
+        bv_pileup_result res{};
+        res.mem_kind = BV_MEM_HOST;
+        check(bv_engine_pileup_fetch(pe, &res, nullptr));  // (no buffers: the sizes)
+        std::vector<bv_pileup_token> tokens(res.n_tokens);
+        std::vector<uint8_t> token_text(res.text_bytes);
+        res.tokens = tokens.data(); res.text = token_text.data();
+        res.tokens_capacity = tokens.size(); res.text_capacity = token_text.size();
+        check(bv_engine_pileup_fetch(pe, &res, nullptr));
+        const double dt = StageClock::now() - tp0;
+        stats_.pileup_s += dt;
+        clk_.add(StageClock::PARSE, dt);
+        size_t next_token = 0;
+        for (uint32_t first = 0; first < n_cov && errors_.ok(); first += ctx_.batch_sites)
+            call_rows(ref_id, fa_seq, pos, tokens, token_text, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
+    }
+    // rows [first, first + rows) of the window's covered positions: called where they lie, their records and planes into a batch
+    void call_rows(const std::string &ref_id, const std::string &fa_seq, const std::vector<uint32_t> &pos, const std::vector<bv_pileup_token> &tokens,
+                   const std::vector<uint8_t> &token_text, size_t &next_token, uint32_t first, uint32_t rows) {
+        const size_t n_sample = ctx_.n_sample();
+        BatchPtr b(new Batch((uint32_t)n_sample));
+        b->seq = seq_++;
+        b->from_text = true;  // (its cell / phred rows come back beside the records)
+        b->result.sites.resize(rows);
+        b->result.n_groups = ctx_.n_groups();
+        b->result.groups.resize((size_t)rows * ctx_.n_groups());
+        b->cell.resize((size_t)rows * n_sample);
+        b->phred.resize((size_t)rows * n_sample);
+        const double te0 = StageClock::now();
+        check(bv_engine_pileup_submit(engine_->handle(), first, rows, ctx_.group_ids(), ctx_.n_groups(), b->result.sites.data(),
+                                      ctx_.group_names.empty() ? nullptr : b->result.groups.data(), b->cell.data(), b->phred.data(), nullptr));
+        clk_.add(StageClock::ENGINE, StageClock::now() - te0);
+        for (uint32_t k = 0; k < rows; ++k) {
+            SiteText st;
+            st.ref_id = ref_id; st.ref_pos = pos[first + k]; st.ref_base = std::string(1, fa_seq[st.ref_pos - 1]);
+            while (next_token < tokens.size() && tokens[next_token].pos < st.ref_pos) ++next_token;
+            for (; next_token < tokens.size() && tokens[next_token].pos == st.ref_pos; ++next_token)
+                st.indel_tokens.emplace_back(reinterpret_cast<const char *>(token_text.data()) + tokens[next_token].text_off, tokens[next_token].text_len);
+            b->text.push_back(std::move(st));
+        }
+        out_.push(std::move(b));
+    }
+
+    const CallContext &ctx_;
+    const BamInput &in_;
+    BatchQueue &out_;
+    StageClock &clk_;
+    const ErrorSink &errors_;
+    std::unique_ptr<BaseTypeEngine> engine_;
+    std::unique_ptr<BamPool> pool_;
+    Stats stats_;
+    uint64_t seq_ = 0;
+};
+
+}  // namespace bvamd

@@ -33,6 +33,7 @@
 #include <iterator>
 #include <chrono>
 #include <cstdlib>
+#include <fstream>
 #include <map>
 #include <mutex>
 #include <string>
@@ -82,8 +83,53 @@ inline std::string load_fasta_sequence(const std::string &path, const std::strin
 
 typedef std::tuple<std::string, uint32_t, uint32_t> GenomeRegionTuple;  // [chr, start, end], 1-based
 
+// "chr:beg-end", 1-based inclusive; the last ':' and the last '-' split it, because the chromosome name may itself contain ':'.
+// false: not of that form (the bounds are the caller's to check).
+struct Region {
+    std::string ref_id;
+    uint32_t beg = 0, end = 0;
+};
+inline bool parse_region(const std::string &s, Region &out) {
+    const size_t colon = s.rfind(':'), dash = s.rfind('-');
+    if (colon == std::string::npos || dash == std::string::npos || dash < colon) return false;
+    try {
+        out.ref_id = s.substr(0, colon);
+        out.beg = (uint32_t)std::stoul(s.substr(colon + 1, dash - colon - 1));
+        out.end = (uint32_t)std::stoul(s.substr(dash + 1));
+    } catch (const std::logic_error &) { return false; }  // (no number where one belongs)
+    return true;
+}
+
+// The first column of every line of a list file that is neither empty nor a '#' comment, appended to `out`
+// (get_firstcolumn_from_file, src/basetype_caller.cpp:114-117); false: the file cannot be opened
+inline bool read_first_column(const std::string &path, std::vector<std::string> &out) {
+    std::ifstream f(path);
+    if (!f) return false;
+    std::string line;
+    while (std::getline(f, line)) {
+        if (line.empty() || line[0] == '#') continue;
+        const size_t e = line.find_first_of(" \t");
+        out.push_back(e == std::string::npos ? line : line.substr(0, e));
+    }
+    return true;
+}
+
 static const uint32_t PILEUP_STEP = 500000;   // the reference's sub-region length, caller.cpp:826
 static const uint32_t PILEUP_PAD = 200;       // REG_EXPEND_SIZE, caller.cpp:883
+
+// fn(wb, we) for the consecutive windows of at most `window` positions that cover [beg, end]: the region is cut into the
+// reference's steps of PILEUP_STEP positions counted from beg, and no window crosses a step's edge.  fn returns whether to go
+// on.  (The counters are 64-bit: a region may end at UINT32_MAX, where a 32-bit one would wrap around and never pass `end`.)
+template <typename Fn>
+inline void for_each_pileup_window(uint32_t beg, uint32_t end, uint32_t window, Fn fn) {
+    for (uint64_t sb = beg; sb <= end; sb += PILEUP_STEP) {
+        const uint64_t se = std::min<uint64_t>(end, sb + PILEUP_STEP - 1);
+        for (uint64_t wb = sb; wb <= se; wb += window) {
+            const uint64_t we = std::min<uint64_t>(se, wb + window - 1);
+            if (!fn((uint32_t)wb, (uint32_t)we)) return;
+        }
+    }
+}
 
 // Dense first-read-wins cells of a window of positions [beg, end] (1-based, inclusive) for n samples.
 // Row = position, column = sample; a cell is claimed <=> its rank is non-zero (ranks start at 1).
@@ -295,16 +341,11 @@ inline void pileup_region(const std::vector<std::string> &bams, const std::strin
     if (window == 0) window = pileup_window(bams.size());
     BamPool pool(bams, use_index);
     PileupTile t;
-    for (uint32_t sb = beg; sb <= end; sb += PILEUP_STEP) {
-        const uint32_t se = std::min(end, sb + PILEUP_STEP - 1);
-        for (uint32_t wb = sb; wb <= se; wb += window) {
-            const uint32_t we = std::min(se, wb + window - 1);
-            pileup_tile(pool, fa, ref_id, beg, end, wb, we, mapq_thd, n_threads, t);
-            fn(t);
-            if (we == UINT32_MAX) return;
-        }
-        if (se == UINT32_MAX) return;
-    }
+    for_each_pileup_window(beg, end, window, [&](uint32_t wb, uint32_t we) {
+        pileup_tile(pool, fa, ref_id, beg, end, wb, we, mapq_thd, n_threads, t);
+        fn(t);
+        return true;
+    });
 }
 
 // The text of the tile's rows in the reference's batchfile format, every position of the window, covered or not

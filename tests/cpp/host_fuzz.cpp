@@ -1,7 +1,7 @@
 // host_fuzz.cpp -- the reader and the emitter of bv_call WITHOUT an engine, for the sanitizer builds (make -C basevar_amd/csrc
 // sanitize) and the damaged-input corpus of tests/test_sanitize_cpu.py:
 //   host_fuzz THREADS a.bf[.gz],b.bf[.gz],...
-// header scan (sample ids), then every position through the pipelined producer (basevar_amd/host/batch_producer.hpp: read /
+// bv_call's own header scan (scan_batchfile_headers: sample ids), then every position through the pipelined producer (basevar_amd/host/batch_producer.hpp: read /
 // inflate / parse tasks on THREADS threads, reused buffers) into slab rows, and every delivered site through the CVG / VCF
 // formatters (basevar_amd/host/vcf_emit.hpp) with a record made up from the row itself -- depths, an ALT for every base seen
 // beside the reference, NaN / huge / negative floats -- so that the emitter's string tables and buffers see arbitrary content.
@@ -29,24 +29,12 @@ int main(int argc, char **argv) {
         }
     }
     try {
-        std::vector<bvamd::GzLineReader> readers(files.size());
-        std::vector<std::string> first_row(files.size());
-        std::vector<bool> have_row(files.size(), false);
-        std::vector<size_t> header_lines(files.size(), 0);
-        std::vector<std::string> ids;
-        for (size_t b = 0; b < files.size(); ++b) {
-            if (!readers[b].open(files[b])) throw std::runtime_error("[ERROR] cannot open " + files[b]);
-            std::string line;
-            while (readers[b].getline(line)) {
-                if (line.empty() || line[0] != '#') { first_row[b] = line; have_row[b] = !line.empty(); header_lines[b] += line.empty() ? 1 : 0; break; }
-                bvamd::parse_sample_ids(line, ids);
-                ++header_lines[b];
-            }
-        }
-        const size_t n = ids.size();
+        bvamd::BatchfileHeaders h;
+        bvamd::scan_batchfile_headers(files, h);
+        const size_t n = h.sample_ids.size();
         if (n == 0) throw std::runtime_error("[ERROR] no sample ids in the batchfile headers");
-        bvamd::BatchfileProducer prod(readers, first_row, have_row, n, threads);
-        prod.set_paths(files, header_lines);
+        bvamd::BatchfileProducer prod(h.readers, h.first_row, h.have_row, n, threads);
+        prod.set_paths(files, h.header_lines);
         size_t sites = 0, bytes = 0;
         const std::vector<std::string> group_names = {"g1", "g2"};
         prod.run([&](bvamd::SlabBuilder &part, std::vector<bvamd::SiteText> &text) {
