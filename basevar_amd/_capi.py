@@ -85,6 +85,16 @@ class VcfLines(C.Structure):  # bv_vcf_lines (include/basevar_amd_vcf.h)
                 ("n_lines", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class RecordLines(C.Structure):  # bv_record_lines (include/basevar_amd_record_text.h)
+    _fields_ = [("records", C.c_void_p), ("groups", C.c_void_p), ("pos", C.c_void_p), ("ref_char", C.c_void_p), ("chrom", C.c_void_p),
+                ("group_names", C.c_void_p), ("group_name_off", C.c_void_p), ("host_text", C.c_void_p), ("host_text_off", C.c_void_p),
+                ("indel", C.c_void_p), ("indel_off", C.c_void_p), ("slab", C.POINTER(Slab)), ("site", C.c_void_p),
+                ("n_lines", C.c_uint32), ("n_groups", C.c_uint32), ("chrom_len", C.c_uint32), ("mem_kind", C.c_int32), ("reserved_", C.c_uint32)]
+
+
+RECORD_TEXT_NAME_MAX, RECORD_TEXT_INDEL_MAX = 255, 16384
+
+
 class PileupReads(C.Structure):  # bv_pileup_reads (include/basevar_amd_pileup.h)
     _fields_ = [("records", C.c_void_p), ("run_off", C.c_void_p), ("run_sample", C.c_void_p), ("pitch", C.c_uint64),
                 ("n_runs", C.c_uint32), ("n_samples", C.c_uint32), ("tid", C.c_int32), ("region_beg", C.c_uint32), ("region_end", C.c_uint32),
@@ -157,6 +167,9 @@ BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engin
 
 # every symbol include/basevar_amd_vcf.h declares
 VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_deflate"]
+
+# every symbol include/basevar_amd_record_text.h declares
+RECORD_TEXT_EXPORTS = ["bv_record_text_on_device", "bv_engine_cvg_format", "bv_engine_cvg_fetch", "bv_engine_cvg_deflate", "bv_engine_vcf_format_records"]
 
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
@@ -281,6 +294,15 @@ def load():
     L.bv_engine_vcf_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     L.bv_engine_vcf_deflate.restype = C.c_int
     L.bv_engine_vcf_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.bv_record_text_on_device.restype = C.c_int
+    L.bv_record_text_on_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    for name in ("bv_engine_cvg_format", "bv_engine_vcf_format_records"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(RecordLines), C.c_void_p, C.c_void_p]
+    L.bv_engine_cvg_fetch.restype = C.c_int
+    L.bv_engine_cvg_fetch.argtypes = L.bv_engine_vcf_fetch.argtypes
+    L.bv_engine_cvg_deflate.restype = C.c_int
+    L.bv_engine_cvg_deflate.argtypes = L.bv_engine_vcf_deflate.argtypes
     L.bv_pileup_max_rows.restype = C.c_uint32
     L.bv_pileup_max_rows.argtypes = []
     L.bv_engine_pileup_set_reference.restype = C.c_int

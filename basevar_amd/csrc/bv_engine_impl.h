@@ -25,6 +25,8 @@ struct BvPileupState;   // bv_engine_pileup (bv_pileup.hip)
 void bv_pileup_state_free(BvPileupState *t);
 struct BvPtextState;    // bv_engine_pileup_text (bv_pileup_text.hip)
 void bv_ptext_state_free(BvPtextState *t);
+struct BvRtextState;    // bv_engine_cvg_format / bv_engine_vcf_format_records (bv_record_text.hip)
+void bv_rtext_state_free(BvRtextState *t);
 struct BvPileupToken;   // bv_pileup_core.h
 // The last completed bv_engine_pileup and the uploaded reference, as they lie (bv_pileup.hip): have_ref / done say what is there
 struct BvPileupView {
@@ -51,6 +53,18 @@ struct BvKeptRows {
     uint32_t n_rows = 0, n_samples = 0;
 };
 bool bv_text_kept_rows(const BvTextState *t, BvKeptRows *rows);
+
+// bv_engine_vcf_format's checks and pipeline (bv_vcf.hip) for lines whose heads and gt characters are not host bytes: `fill`
+// queues on `st` the kernels that write gt [n_lines][4] and the heads, at head_off (given here on the host, from 0, and there
+// on the device), where the copy of L->gt and L->head would have put them.  H == NULL: bv_engine_vcf_format itself.
+struct BvVcfDeviceHeads {
+    const uint64_t *head_off;  // host [n_lines + 1]
+    int (*fill)(void *ctx, uint8_t *d_gt, uint8_t *d_head, const uint64_t *d_head_off, hipStream_t st);
+    void *ctx;
+};
+struct bv_vcf_lines;
+void bv_vcf_text_drop(bv_engine *e);  // the engine holds no formatted VCF text any more
+int bv_vcf_format_lines(bv_engine *e, const char *who, const bv_vcf_lines *L, const BvVcfDeviceHeads *H, uint64_t *line_off, void *stream);
 
 struct bv_engine {
     bv_engine_config cfg;
@@ -174,6 +188,7 @@ struct bv_engine {
     BvVcfState *vcf = nullptr;         // created by the first bv_engine_vcf_format
     BvPileupState *pileup = nullptr;   // created by the first bv_engine_pileup_set_reference
     BvPtextState *ptext = nullptr;     // created by the first bv_engine_pileup_text
+    BvRtextState *rtext = nullptr;     // created by the first bv_engine_cvg_format / bv_engine_vcf_format_records
     mutable std::mutex mu;
     std::string err;
 };

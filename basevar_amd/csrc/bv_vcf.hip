@@ -2,7 +2,8 @@
 // include/basevar_amd_vcf.h; the contract is INTEGRATION.md section 2h).  The bytes are defined at the head of bv_vcf_core.h,
 // which a CPU harness compiles too; this file is their schedule.
 //
-// A line is its head (host text, uploaded) and one token of 4 or 17 bytes per sample.  Lines are cut into tiles of
+// A line is its head (host text, uploaded -- or written in its place by bv_record_text.hip's kernel: bv_vcf_format_lines with
+// BvVcfDeviceHeads) and one token of 4 or 17 bytes per sample.  Lines are cut into tiles of
 // BV_VCF_TILE samples; one wave handles one (line, tile):
 //   count  the tile's cell bytes, one 16-byte load a lane, -> covered cells of the tile
 //   scan   one thread a line: the tile counts become the tiles' prefixes, their sum the line's covered count.  The line
@@ -164,7 +165,8 @@ const char *check_planes(const bv_slab *s) {
     return nullptr;
 }
 
-int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptRows &rows, bool host_rows, uint64_t *line_off, hipStream_t st) {
+// H: the heads and gt characters are not L's host bytes: H->fill queues the kernels that write them where the copy would
+int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvVcfDeviceHeads *H, const BvKeptRows &rows, bool host_rows, uint64_t *line_off, hipStream_t st) {
     const uint32_t n = L->n_lines, N = rows.n_samples;
     const uint32_t n_tiles = (N + BV_VCF_TILE - 1u) / BV_VCF_TILE;
     BV_HIP(e, hipSetDevice(t->text.device));
@@ -182,7 +184,8 @@ int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptR
         t->d_bp = d;
     }
     // what the kernels read beside the planes, one upload: rows, gt, head_off, heads; line_off follows the counts
-    const uint64_t head_lo = L->head_off[0], head_bytes = L->head_off[n] - head_lo;
+    const uint64_t *hoff = H ? H->head_off : L->head_off;
+    const uint64_t head_lo = hoff[0], head_bytes = hoff[n] - head_lo;
     const size_t o_gt = up16(4ull * n), o_hoff = o_gt + up16(4ull * n), o_head = o_hoff + up16(8ull * (n + 1)), o_loff = o_head + up16(head_bytes),
                  meta = o_loff + up16(8ull * (n + 1));
     int rc = grow_device(e, &t->d_meta, &t->meta_cap, meta);
@@ -192,10 +195,14 @@ int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptR
     uint32_t *h_row = reinterpret_cast<uint32_t *>(h.data());
     uint64_t *h_hoff = reinterpret_cast<uint64_t *>(h.data() + o_hoff);
     for (uint32_t k = 0; k < n; ++k) h_row[k] = host_rows ? k : L->site[k];
-    std::memcpy(h.data() + o_gt, L->gt, 4ull * n);
-    for (uint32_t k = 0; k <= n; ++k) h_hoff[k] = L->head_off[k] - head_lo;
-    if (head_bytes) std::memcpy(h.data() + o_head, L->head + head_lo, head_bytes);
+    if (!H) std::memcpy(h.data() + o_gt, L->gt, 4ull * n);
+    for (uint32_t k = 0; k <= n; ++k) h_hoff[k] = hoff[k] - head_lo;
+    if (!H && head_bytes) std::memcpy(h.data() + o_head, L->head + head_lo, head_bytes);
     BV_HIP(e, hipMemcpyAsync(t->d_meta, h.data(), o_loff, hipMemcpyHostToDevice, st));
+    if (H) {
+        rc = H->fill(H->ctx, t->d_meta + o_gt, t->d_meta + o_head, reinterpret_cast<const uint64_t *>(t->d_meta + o_hoff), st);
+        if (rc != BV_OK) return rc;
+    }
     VcfArgs a;
     a.cell = rows.cell; a.phred = rows.phred; a.pitch = rows.pitch;
     std::vector<uint8_t> up;
@@ -227,7 +234,7 @@ int vcf_format(bv_engine *e, BvVcfState *t, const bv_vcf_lines *L, const BvKeptR
     std::vector<uint64_t> off(n + 1, 0);
     for (uint32_t k = 0; k < n; ++k) {
         if (cov[k] > N) return fail(e, BV_ERR_HIP, "bv_engine_vcf_format: line " + std::to_string(k) + " came back with more covered cells than samples");
-        off[k + 1] = off[k] + bv_vcf_line_bytes(L->head_off[k + 1] - L->head_off[k], N, cov[k]);
+        off[k + 1] = off[k] + bv_vcf_line_bytes(hoff[k + 1] - hoff[k], N, cov[k]);
     }
     rc = device_text_reserve(e, t->text, off[n]);
     if (rc != BV_OK) return rc;
@@ -247,8 +254,14 @@ extern "C" {
 
 uint32_t bv_vcf_tile_samples(void) { return BV_VCF_TILE; }
 
-int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off, void *stream_) {
-    const std::string who = "bv_engine_vcf_format: ";
+}  // extern "C"
+
+void bv_vcf_text_drop(bv_engine *e) {
+    if (e->vcf) e->vcf->text.formatted = false;
+}
+
+int bv_vcf_format_lines(bv_engine *e, const char *who_, const bv_vcf_lines *L, const BvVcfDeviceHeads *H, uint64_t *line_off, void *stream_) {
+    const std::string who = who_;
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, who + "null engine");
     if (!L || !line_off) return fail(e, BV_ERR_INVALID_ARG, who + "null lines/line_off");
     if (L->reserved_) return fail(e, BV_ERR_INVALID_ARG, who + "reserved_ must be zero");
@@ -256,11 +269,11 @@ int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off
     BvKeptRows rows;
     bool host_rows = false;
     if (n) {
-        if (!L->site || !L->head_off || !L->gt) return fail(e, BV_ERR_INVALID_ARG, who + "null site/head_off/gt");
-        for (uint32_t k = 0; k < n; ++k)
+        if (!L->site || (!H && (!L->head_off || !L->gt))) return fail(e, BV_ERR_INVALID_ARG, who + "null site/head_off/gt");
+        for (uint32_t k = 0; !H && k < n; ++k)
             if (L->head_off[k + 1] < L->head_off[k]) return fail(e, BV_ERR_INVALID_ARG, who + "head_off out of order at line " + std::to_string(k));
-        if (!L->head && L->head_off[n] != L->head_off[0]) return fail(e, BV_ERR_INVALID_ARG, who + "null head");
-        for (size_t i = 0; i < 4ull * n; ++i)
+        if (!H && !L->head && L->head_off[n] != L->head_off[0]) return fail(e, BV_ERR_INVALID_ARG, who + "null head");
+        for (size_t i = 0; !H && i < 4ull * n; ++i)
             if (!bv_vcf_gt_char_ok(L->gt[i]))
                 return fail(e, BV_ERR_INVALID_ARG, who + "gt of line " + std::to_string(i / 4) + ", base " + "ACGT"[i & 3] + " is none of '0', '.', '1' .. '4'");
         if (L->slab) {
@@ -282,7 +295,13 @@ int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off
     BvVcfState *t = text_state(e, e->vcf);
     t->text.formatted = false;  // deliberately here, not on entry as in bv_engine_pileup_text: a call whose arguments fail leaves the last text
     if (n == 0) return device_text_empty(t->text, line_off);
-    return vcf_format(e, t, L, rows, host_rows, line_off, stream_ ? (hipStream_t)stream_ : e->stream);
+    return vcf_format(e, t, L, H, rows, host_rows, line_off, stream_ ? (hipStream_t)stream_ : e->stream);
+}
+
+extern "C" {
+
+int bv_engine_vcf_format(bv_engine *e, const bv_vcf_lines *L, uint64_t *line_off, void *stream_) {
+    return bv_vcf_format_lines(e, "bv_engine_vcf_format: ", L, nullptr, line_off, stream_);
 }
 
 int bv_engine_vcf_fetch(bv_engine *e, void *dst, uint64_t dst_capacity, int dst_mem_kind, void *stream_) {

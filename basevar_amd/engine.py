@@ -627,6 +627,114 @@ class BaseTypeEngine:
         member_off) as bgzf_deflate returns them, byte for byte what it returns for the fetched text."""
         return self._deflate("vcf_deflate", "bv_engine_vcf_deflate", getattr(self, "_vcf_bytes", 0), block_bytes, block_off, level)
 
+    # ---- whole VCF records and CVG rows from the records, written on the device (include/basevar_amd_record_text.h)
+    @staticmethod
+    def record_text_on_device(sites, groups=None):
+        """Per record, whether every number its VCF head and CVG row print lies inside the device formatter's domains
+        (bv_record_text_on_device): bool [n].  `sites`: SITE_DTYPE [n]; `groups`: GROUP_DTYPE [n][n_groups] or None."""
+        lib = _capi.load()
+        sites = np.ascontiguousarray(sites, dtype=_capi.SITE_DTYPE).reshape(-1)
+        n = int(sites.size)
+        g = None if groups is None else np.ascontiguousarray(groups, dtype=_capi.GROUP_DTYPE).reshape(n, -1)
+        G = 0 if g is None else int(g.shape[1])
+        out = np.zeros(n, dtype=bool)
+        for k in range(n):
+            out[k] = bool(lib.bv_record_text_on_device(sites[k:k + 1].ctypes.data, g[k].ctypes.data if G else None, G))
+        return out
+
+    def _record_lines(self, who, sites, groups, chrom, pos, ref_char, group_names, host_text, n):
+        """The bv_record_lines both calls share, and what it points into (to be kept alive through the call).  `sites` /
+        `groups`: numpy arrays, or (device pointer, n) / (device pointer, n_groups)."""
+        keep = []
+        def arr(a, dtype):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            keep.append(a)
+            return a
+        def texts(items):  # offsets and bytes of per-line texts; None entries are empty
+            if items is None:
+                return None, None
+            if len(items) != n:
+                raise ValueError("%s: one text (or None) per line" % who)
+            items = [b"" if t is None else bytes(t) for t in items]
+            off = np.zeros(n + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(t) for t in items])
+            buf = np.frombuffer(b"".join(items) or b"\0", dtype=np.uint8)
+            keep.extend([off, buf])
+            return off.ctypes.data, buf.ctypes.data
+        L = _capi.RecordLines()
+        if isinstance(sites, tuple):
+            L.records, L.mem_kind = int(sites[0]), _capi.BV_MEM_DEVICE
+            L.groups = int(groups[0]) if groups is not None else None
+            G = int(groups[1]) if groups is not None else 0
+        else:
+            s = arr(sites, _capi.SITE_DTYPE).reshape(-1)
+            L.records, L.mem_kind = s.ctypes.data if n else None, _capi.BV_MEM_HOST
+            G = 0
+            if groups is not None:
+                g = arr(groups, _capi.GROUP_DTYPE).reshape(n, -1)
+                G = int(g.shape[1])
+                L.groups = g.ctypes.data if g.size else None
+        names = [bytes(x) for x in (group_names or ())]
+        if len(names) != G:
+            raise ValueError("%s: one name per group" % who)
+        chrom = bytes(chrom)
+        cbuf, nbuf = arr(np.frombuffer(chrom or b"\0", dtype=np.uint8), np.uint8), arr(np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8), np.uint8)
+        noff = np.zeros(G + 1, dtype=np.uint32)
+        noff[1:] = np.cumsum([len(x) for x in names])
+        keep.append(noff)
+        p, r = arr(pos, np.uint32).reshape(-1), arr(np.frombuffer(bytes(ref_char), dtype=np.uint8) if isinstance(ref_char, (bytes, bytearray)) else ref_char, np.uint8).reshape(-1)
+        if p.size != n or r.size != n:
+            raise ValueError("%s: one pos and one ref_char per line" % who)
+        L.pos, L.ref_char = (p.ctypes.data, r.ctypes.data) if n else (None, None)
+        L.chrom, L.chrom_len = cbuf.ctypes.data, len(chrom)
+        L.group_names, L.group_name_off = (nbuf.ctypes.data, noff.ctypes.data) if G else (None, None)
+        L.host_text_off, L.host_text = texts(host_text)
+        L.n_lines, L.n_groups, L.reserved_ = n, G, 0
+        return L, keep, texts
+
+    def cvg_format(self, sites, chrom, pos, ref_char, indel=None, host_text=None, groups=None, group_names=()):
+        """The CVG rows of the records (bv_engine_cvg_format): row k from sites[k], `chrom`, pos[k], ref_char[k] and the row's
+        indel column indel[k] (bytes; None or b"": "."), or host_text[k] where that is given (the whole row with its line break:
+        the records bv_record_text_on_device refuses).  `sites`: SITE_DTYPE [n], or (device pointer, n).  The text stays on the
+        device (cvg_fetch, cvg_deflate); returns line_off uint64 [n + 1]."""
+        n = int(sites[1]) if isinstance(sites, tuple) else int(np.asarray(sites).size)
+        L, keep, texts = self._record_lines("cvg_format", sites, groups, chrom, pos, ref_char, group_names, host_text, n)
+        L.indel_off, L.indel = texts(indel)
+        line_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_cvg_format(self._h, C.byref(L), line_off.ctypes.data, None)
+        if rc != 0:
+            self._cvg_bytes = 0
+            raise RuntimeError("bv_engine_cvg_format failed (%d): %s" % (rc, self._err()), rc)
+        self._cvg_bytes = int(line_off[n])
+        return line_off
+
+    def cvg_fetch(self, dst_ptr=0, dst_capacity=0):
+        """The text of the last cvg_format (bv_engine_cvg_fetch), as vcf_fetch returns vcf_format's."""
+        return self._text_fetch("bv_engine_cvg_fetch", getattr(self, "_cvg_bytes", 0), dst_ptr, dst_capacity)
+
+    def cvg_deflate(self, block_bytes=0xff00, block_off=None, level="fast"):
+        """bgzf_deflate of the last cvg_format's text, read where it lies on the device (bv_engine_cvg_deflate)."""
+        return self._deflate("cvg_deflate", "bv_engine_cvg_deflate", getattr(self, "_cvg_bytes", 0), block_bytes, block_off, level)
+
+    def vcf_format_records(self, site, sites, chrom, pos, ref_char, groups=None, group_names=(), host_text=None, slab=None):
+        """Whole VCF lines from the records (bv_engine_vcf_format_records): line k is the head of sites[k] -- formatted on the
+        device, or host_text[k] (CHROM through "GT:AB:SO:BP") where that is given -- and the sample columns of row site[k] as
+        vcf_format writes them, the gt characters derived from ref_char[k] and the record's ALTs.  A record without ALT and
+        without host text gives an empty line.  `sites`, `groups`: numpy arrays ([n], [n][n_groups]) or (device pointer, n) /
+        (device pointer, n_groups); `slab` as vcf_format's.  The text is vcf_fetch's / vcf_deflate's; returns line_off [n + 1]."""
+        site = np.ascontiguousarray(site, dtype=np.uint32)
+        n = int(site.size)
+        L, keep, _ = self._record_lines("vcf_format_records", sites, groups, chrom, pos, ref_char, group_names, host_text, n)
+        L.site = site.ctypes.data if n else None
+        if slab is not None:
+            L.slab = C.pointer(slab)
+        line_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_vcf_format_records(self._h, C.byref(L), line_off.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_vcf_format_records failed (%d): %s" % (rc, self._err()), rc)
+        self._vcf_bytes = int(line_off[n])
+        return line_off
+
     # ---- BAM records, piled up on the device (include/basevar_amd_pileup.h)
     def pileup_set_reference(self, seq):
         """The contig's bases (str / bytes / uint8 array, letter case kept) for pileup and pileup_rows (bv_engine_pileup_set_reference)."""

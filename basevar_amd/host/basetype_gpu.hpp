@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/basevar_amd_record_text.h"
 #include "../../include/basevar_amd_vcf.h"
 #include "vcf_emit.hpp"  // SiteText
 
@@ -362,6 +363,27 @@ public:
     void vcf_deflate(uint64_t text_bytes, const uint64_t *block_off, uint32_t n_blocks, uint8_t *dst, uint64_t *member_off, int level = BV_DEFLATE_FAST) {
         if (bv_engine_vcf_deflate(e_, block_off, n_blocks, level, dst, text_bytes + 31ull * n_blocks, member_off, nullptr) != BV_OK)
             throw std::runtime_error(bv_last_error(e_));
+    }
+
+    // Whole VCF lines and CVG rows written on the device from the records (include/basevar_amd_record_text.h): the heads and the
+    // rows are vcf_emit.hpp's format_vcf_head and format_cvg_line, byte for byte, for every record record_text_on_device()
+    // accepts; the others go in as host text.  vcf_format_records() leaves vcf_format()'s text (vcf_fetch, vcf_deflate);
+    // cvg_format() a text of its own (cvg_fetch).  Both return line_off [n_lines + 1].
+    static bool record_text_on_device(const bv_site_result &r, const bv_group_result *groups, uint32_t n_groups) {
+        return bv_record_text_on_device(&r, groups, n_groups) != 0;
+    }
+    std::vector<uint64_t> vcf_format_records(const bv_record_lines &in) {
+        std::vector<uint64_t> line_off((size_t)in.n_lines + 1, 0);
+        if (bv_engine_vcf_format_records(e_, &in, line_off.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return line_off;
+    }
+    std::vector<uint64_t> cvg_format(const bv_record_lines &in) {
+        std::vector<uint64_t> line_off((size_t)in.n_lines + 1, 0);
+        if (bv_engine_cvg_format(e_, &in, line_off.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return line_off;
+    }
+    void cvg_fetch(char *dst, uint64_t bytes) {
+        if (bv_engine_cvg_fetch(e_, dst, bytes, BV_MEM_HOST, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
     }
 
     // lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf, include/basevar_amd_bgzf.h), in two steps so

@@ -192,12 +192,6 @@ bvamd::Routes resolve_routes(const Options &o, const bvamd::BatchfileHeaders &he
             std::cerr << "[NOTE] --deflate device applies to *.gz outputs: " << (r.device_deflate ? (vcf_gz ? o.out_cvg : o.out_vcf) : "both outputs")
                       << " take" << (r.device_deflate ? "s" : "") << " the host path" << std::endl;
     }
-    // --emit device: batches of batchfile rows only (EngineWorker::emit_on_device)
-    r.emit_device = o.emit == "device";
-    if (r.emit_device && from_bam) {
-        std::cerr << "[NOTE] --emit device applies to batchfile rows parsed on the device, not to BAM input: the host path is taken" << std::endl;
-        r.emit_device = false;
-    }
     // --inflate device on batchfiles (RawReaderTurns); anything else keeps the host path
     if (o.inflate == "device" && !(from_bam && o.pileup == "device")) {  // (with --pileup device: the BAM files' own members, below)
         if (from_bam) std::cerr << "[NOTE] --inflate device applies to BGZF batchfiles, not to BAM input: the host path is taken" << std::endl;
@@ -210,6 +204,12 @@ bvamd::Routes resolve_routes(const Options &o, const bvamd::BatchfileHeaders &he
         if (!from_bam) std::cerr << "[NOTE] --pileup device applies to BAM input, not to batchfiles: nothing changes" << std::endl;
         else if (G > 1) std::cerr << "[NOTE] --pileup device runs on one engine (--gpus 1): the host path is taken" << std::endl;
         else r.device_pileup = true;
+    }
+    // --emit device (emit_records_on_device): batches of batchfile rows parsed on the device, and BAM input piled up there
+    r.emit_device = o.emit == "device";
+    if (r.emit_device && from_bam && !r.device_pileup) {
+        std::cerr << "[NOTE] --emit device on BAM input needs --pileup device (on one engine): the host path is taken" << std::endl;
+        r.emit_device = false;
     }
     // --pileup device --inflate device: the host threads inflate nothing either
     if (from_bam && o.pileup == "device" && o.inflate == "device") {
@@ -252,8 +252,11 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
     if (ctx.routes.device_deflate)
         tf << ", \"deflate\": \"device\", \"deflate_level\": \"" << o.deflate_level << "\", \"members_deflated\": " << emitter.members_deflated()
            << ", \"deflate_s\": " << emitter.deflate_s();
-    // --emit device: VCF lines whose sample columns the engines wrote (all of them, on batchfile input)
-    if (ctx.routes.emit_device) tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << emitter.vcf_lines_device();
+    // --emit device: VCF lines and CVG rows the engines wrote, and the records among them that the host formatted (numbers the
+    // device's formats do not cover: a NaN AF)
+    if (ctx.routes.emit_device)
+        tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << emitter.vcf_lines_device() << ", \"cvg_lines_device\": " << emitter.cvg_lines_device()
+           << ", \"lines_host_formatted\": " << emitter.lines_host_formatted();
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
     // ... --inflate device with it: the BAM files' compressed members handed to the engine instead, and their bytes

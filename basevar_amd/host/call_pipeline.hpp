@@ -58,6 +58,11 @@ struct Batch {
     std::vector<uint64_t> vcf_line_off, vcf_member_off;
     std::vector<uint8_t> vcf_members;
     std::string vcf_text;
+    // ... and its CVG rows there too (bv_engine_cvg_format): the batch's rows back to back; rows the device wrote, and records
+    // that the host formatted because the device's number formats do not cover them
+    bool cvg_device = false;
+    std::string cvg_text;
+    uint64_t cvg_lines_device = 0, lines_host_formatted = 0;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -139,7 +144,7 @@ void parallel_ranges(size_t n, int threads, Fn fn) {
 struct Routes {
     bool device_inflate = false;      // --inflate device: BGZF batchfiles reach the engine compressed (RawReaderTurns)
     bool device_deflate = false;      // --deflate device: the emitter's whole output blocks are compressed by an engine
-    bool emit_device = false;         // --emit device: the VCF lines' sample columns are written on the worker's engine
+    bool emit_device = false;         // --emit device: the VCF lines and the CVG rows are written on the worker's / the pileup's engine
     bool device_pileup = false;       // --pileup device: produce_bam_device
     bool bam_inflate_device = false;  // ... with --inflate device: the BAM files' members reach the engine compressed
 };
@@ -222,6 +227,8 @@ public:
     size_t n_sites() const { return n_sites_; }
     size_t n_variants() const { return n_variants_; }
     uint64_t vcf_lines_device() const { return vcf_lines_device_; }
+    uint64_t cvg_lines_device() const { return cvg_lines_device_; }
+    uint64_t lines_host_formatted() const { return lines_host_formatted_; }
     uint64_t members_deflated() const { return members_deflated_; }
     double deflate_s() const { return deflate_s_; }
 
@@ -232,7 +239,8 @@ private:
         const bool device_deflate = ctx_.routes.device_deflate;
         std::vector<std::string> cvg_txt(nt), vcf_txt(nt);
         std::vector<size_t> nv(nt, 0);
-        parallel_ranges(d.text.size(), ctx_.threads, [&](size_t t, size_t lo, size_t hi) {
+        if (d.cvg_device) cvg_txt[0].swap(d.cvg_text);  // (the CVG rows are there already, and with them the VCF lines)
+        else parallel_ranges(d.text.size(), ctx_.threads, [&](size_t t, size_t lo, size_t hi) {
             for (size_t i = lo; i < hi; ++i) {
                 cvg_txt[t] += format_cvg_line(d.text[i], d.result.sites[i]);
                 if (d.emit_device) continue;  // (the VCF lines are there already)
@@ -278,6 +286,8 @@ private:
         }
         for (size_t i = 0; i < d.text.size(); ++i) n_variant += d.result.has_variant(i) ? 1 : 0;
         vcf_lines_device_ += d.vcf_record.size();
+        cvg_lines_device_ += d.cvg_lines_device;
+        lines_host_formatted_ += d.lines_host_formatted;
     }
 
     const CallContext &ctx_;
@@ -289,7 +299,7 @@ private:
     uint64_t next_seq_ = 0;
     bool stopped_ = false;  // a batch failed: nothing behind it is written
     size_t n_sites_ = 0, n_variants_ = 0;
-    uint64_t vcf_lines_device_ = 0, members_deflated_ = 0;
+    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, members_deflated_ = 0;
     double deflate_s_ = 0;
 };
 
@@ -367,6 +377,110 @@ private:
 };
 
 // One worker thread: an engine on devices[w % G], batches from `in` (or from its turns at the raw reader) to `out`
+// --emit device: the VCF lines of the batch's variant records and its CVG rows, written on `engine` from the records
+// (bv_engine_vcf_format_records, bv_engine_cvg_format) over the rows that lie there -- row first_row + i of `slab` for record i,
+// or, with slab == nullptr, the rows the engine's text submit kept.  The few records whose numbers the device does not format
+// (BaseTypeEngine::record_text_on_device: a NaN AF), or whose place is not the batch's first CHROM and one REF character, or
+// whose indel column is too long, are formatted here and go in as host text.  The VCF text comes back as BGZF members
+// deflated there too (a *.vcf.gz, at --deflate-level) or as it is; the CVG text as it is.
+inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engine, Batch &b, const bv_slab *slab, uint32_t first_row) {
+    b.emit_device = true;
+    const size_t n = b.text.size();
+    if (n == 0) return;
+    const uint32_t G = ctx.n_groups();
+    const std::string &chrom = b.text[0].ref_id;
+    std::string names;
+    std::vector<uint32_t> name_off(1, 0);
+    for (const std::string &g : ctx.group_names) { names += g; name_off.push_back((uint32_t)names.size()); }
+    bool names_fit = !chrom.empty() && chrom.size() <= BV_RECORD_TEXT_NAME_MAX;
+    for (const std::string &g : ctx.group_names) names_fit = names_fit && g.size() <= BV_RECORD_TEXT_NAME_MAX;
+    std::vector<uint32_t> pos(n), site;
+    std::string ref(n, 'N'), cvg_host, indel, vcf_host;
+    std::vector<uint64_t> cvg_host_off(1, 0), indel_off(1, 0), vcf_host_off(1, 0);
+    std::vector<bv_site_result> vrec;
+    std::vector<bv_group_result> vgrp;
+    std::vector<uint32_t> vpos, vidx;
+    std::string vref;
+    // the predicate and the indel tallies (sorted host maps, as the emitter built them) on the run's host threads
+    std::vector<std::string> columns(n);
+    std::vector<uint8_t> fits(n, 0);
+    parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            const SiteText &st = b.text[i];
+            if (!st.indel_tokens.empty()) columns[i] = indel_string(st.indel_tokens);
+            fits[i] = names_fit && st.ref_id == chrom && st.ref_base.size() == 1 &&
+                      BaseTypeEngine::record_text_on_device(b.result.sites[i], G ? &b.result.group(i, 0) : nullptr, G);
+        }
+    });
+    for (size_t i = 0; i < n; ++i) {
+        const SiteText &st = b.text[i];
+        const bv_site_result &r = b.result.sites[i];
+        const bv_group_result *g = G ? &b.result.group(i, 0) : nullptr;
+        pos[i] = st.ref_pos;
+        if (st.ref_base.size() == 1) ref[i] = st.ref_base[0];
+        const std::string &column = columns[i];
+        const bool on_device = fits[i] != 0;
+        if (!on_device) ++b.lines_host_formatted;
+        if (!on_device || column.size() > BV_RECORD_TEXT_INDEL_MAX) cvg_host += format_cvg_line(st, r);
+        else if (column != ".") indel += column;
+        cvg_host_off.push_back(cvg_host.size());
+        indel_off.push_back(indel.size());
+        if (!b.result.has_variant(i)) continue;
+        vrec.push_back(r);
+        if (G) vgrp.insert(vgrp.end(), g, g + G);
+        vpos.push_back(st.ref_pos);
+        vref.push_back(ref[i]);
+        vidx.push_back((uint32_t)i);
+        site.push_back(first_row + (uint32_t)i);
+        if (!on_device) vcf_host += format_vcf_head(st, r, g, ctx.group_names);
+        vcf_host_off.push_back(vcf_host.size());
+    }
+    bv_record_lines in;
+    std::memset(&in, 0, sizeof in);
+    in.mem_kind = BV_MEM_HOST;
+    in.chrom = names_fit ? chrom.data() : "-"; in.chrom_len = names_fit ? (uint32_t)chrom.size() : 1u;
+    in.n_groups = names_fit ? G : 0u;  // (names that do not fit: every line is host text, and no name is looked at)
+    in.group_names = names.data(); in.group_name_off = name_off.data();
+    // the VCF lines first: on BAM input the slab's rows are the pileup's, which the next window overwrites
+    in.records = vrec.data(); in.groups = in.n_groups ? vgrp.data() : nullptr;
+    in.pos = vpos.data(); in.ref_char = vref.data();
+    in.host_text = vcf_host.data(); in.host_text_off = vcf_host_off.data();
+    in.slab = slab; in.site = site.data();
+    in.n_lines = (uint32_t)vrec.size();
+    const std::vector<uint64_t> off = engine.vcf_format_records(in);
+    b.vcf_line_off.assign(1, 0);
+    for (size_t k = 0; k < vrec.size(); ++k) {
+        if (off[k + 1] == off[k]) continue;  // (no ALT: format_vcf_line writes nothing)
+        b.vcf_record.push_back(vidx[k]);
+        b.vcf_line_off.push_back(off[k + 1]);
+    }
+    const uint64_t total = off.back();
+    if (total && ctx.vcf_gz) {
+        const std::vector<uint64_t> block_off = bgzf_block_table(total);
+        const size_t nb = block_off.size() - 1;
+        b.vcf_members.resize(total + 31 * nb);
+        b.vcf_member_off.assign(nb + 1, 0);
+        engine.vcf_deflate(total, block_off.data(), (uint32_t)nb, b.vcf_members.data(), b.vcf_member_off.data(), ctx.deflate_level);
+        b.vcf_members.resize(b.vcf_member_off[nb]);
+    } else if (total) {
+        b.vcf_text.resize(total);
+        engine.vcf_fetch(&b.vcf_text[0], total);
+    }
+    // the CVG rows of every record
+    in.records = b.result.sites.data(); in.groups = in.n_groups ? b.result.groups.data() : nullptr;
+    in.pos = pos.data(); in.ref_char = ref.data();
+    in.host_text = cvg_host.data(); in.host_text_off = cvg_host_off.data();
+    in.indel = indel.data(); in.indel_off = indel_off.data();
+    in.slab = nullptr; in.site = nullptr;
+    in.n_lines = (uint32_t)n;
+    const std::vector<uint64_t> coff = engine.cvg_format(in);
+    b.cvg_device = true;
+    b.cvg_text.resize(coff.back());
+    if (coff.back()) engine.cvg_fetch(&b.cvg_text[0], coff.back());
+    for (size_t i = 0; i < n; ++i)
+        if (coff[i + 1] != coff[i] && cvg_host_off[i + 1] == cvg_host_off[i]) ++b.cvg_lines_device;
+}
+
 class EngineWorker {
 public:
     EngineWorker(const CallContext &ctx, size_t w, BatchQueue &in, BatchQueue &out, RawReaderTurns *raw, StageClock &clk, ErrorSink &errors)
@@ -426,7 +540,7 @@ private:
     // a text batch through `make`, which parses and calls it; a failure of the engine leaves the batch without records
     template <class Make>
     void text_batch(Batch &b, Make make) {
-        try { take_text_result(b, make()); } catch (const std::exception &ex) { b.error = ex.what(); b.text.clear(); b.emit_device = false; }
+        try { take_text_result(b, make()); } catch (const std::exception &ex) { b.error = ex.what(); b.text.clear(); b.emit_device = b.cvg_device = false; }
     }
     // the records of a text batch into the batch; what the host reader threw becomes the batch's error, behind its records
     void take_text_result(Batch &b, BaseTypeEngine::TextBatch &&tb) {
@@ -434,44 +548,11 @@ private:
         b.text = std::move(tb.text);
         b.cell = std::move(tb.cell);
         b.phred = std::move(tb.phred);
-        if (ctx_.routes.emit_device) emit_on_device(b);
+        if (ctx_.routes.emit_device) emit_records_on_device(ctx_, *engine_, b, nullptr, 0);  // (over the rows the text submit kept)
         if (tb.error) {
             try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b.error = ex.what(); }
         }
     }
-    // --emit device: heads and gt of the batch's variant records, the lines on this worker's engine (from the rows its text
-    // submit left on the device: the planes do not come back and the text does not go up), then BGZF members deflated there
-    // too (a *.vcf.gz, at --deflate-level) or the text
-    void emit_on_device(Batch &b) {
-        b.emit_device = true;
-        std::vector<std::string> heads;
-        std::vector<uint8_t> gt;
-        for (size_t i = 0; i < b.text.size(); ++i) {
-            if (!b.result.has_variant(i)) continue;
-            std::string head = format_vcf_head(b.text[i], b.result.sites[i], ctx_.group_names.empty() ? nullptr : &b.result.group(i, 0), ctx_.group_names);
-            if (head.empty()) continue;  // (no ALT: format_vcf_line writes nothing)
-            uint8_t g[4];
-            vcf_gt_codes(b.text[i], b.result.sites[i], g);
-            b.vcf_record.push_back((uint32_t)i);
-            heads.push_back(std::move(head));
-            gt.insert(gt.end(), g, g + 4);
-        }
-        b.vcf_line_off = engine_->vcf_format(b.vcf_record, heads, gt);
-        const uint64_t total = b.vcf_line_off.back();
-        if (total == 0) return;
-        if (ctx_.vcf_gz) {
-            const std::vector<uint64_t> block_off = bgzf_block_table(total);
-            const size_t nb = block_off.size() - 1;
-            b.vcf_members.resize(total + 31 * nb);
-            b.vcf_member_off.assign(nb + 1, 0);
-            engine_->vcf_deflate(total, block_off.data(), (uint32_t)nb, b.vcf_members.data(), b.vcf_member_off.data(), ctx_.deflate_level);
-            b.vcf_members.resize(b.vcf_member_off[nb]);
-        } else {
-            b.vcf_text.resize(total);
-            engine_->vcf_fetch(&b.vcf_text[0], total);
-        }
-    }
-
     const CallContext &ctx_;
     const int device_;
     BatchQueue &in_, &out_;
@@ -632,10 +713,12 @@ private:
         clk_.add(StageClock::PARSE, dt);
         size_t next_token = 0;
         for (uint32_t first = 0; first < n_cov && errors_.ok(); first += ctx_.batch_sites)
-            call_rows(ref_id, fa_seq, pos, tokens, token_text, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
+            call_rows(slab, ref_id, fa_seq, pos, tokens, token_text, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
     }
     // rows [first, first + rows) of the window's covered positions: called where they lie, their records and planes into a batch
-    void call_rows(const std::string &ref_id, const std::string &fa_seq, const std::vector<uint32_t> &pos, const std::vector<bv_pileup_token> &tokens,
+    // -- or, with --emit device, their records alone: the lines are written from the rows where they lie, before the next window's
+    // pileup takes the slab's place, and only the text (or its BGZF members) comes back
+    void call_rows(const bv_slab &slab, const std::string &ref_id, const std::string &fa_seq, const std::vector<uint32_t> &pos, const std::vector<bv_pileup_token> &tokens,
                    const std::vector<uint8_t> &token_text, size_t &next_token, uint32_t first, uint32_t rows) {
         const size_t n_sample = ctx_.n_sample();
         BatchPtr b(new Batch((uint32_t)n_sample));
@@ -644,11 +727,15 @@ private:
         b->result.sites.resize(rows);
         b->result.n_groups = ctx_.n_groups();
         b->result.groups.resize((size_t)rows * ctx_.n_groups());
-        b->cell.resize((size_t)rows * n_sample);
-        b->phred.resize((size_t)rows * n_sample);
+        const bool emit_device = ctx_.routes.emit_device;
+        if (!emit_device) {
+            b->cell.resize((size_t)rows * n_sample);
+            b->phred.resize((size_t)rows * n_sample);
+        }
         const double te0 = StageClock::now();
         check(bv_engine_pileup_submit(engine_->handle(), first, rows, ctx_.group_ids(), ctx_.n_groups(), b->result.sites.data(),
-                                      ctx_.group_names.empty() ? nullptr : b->result.groups.data(), b->cell.data(), b->phred.data(), nullptr));
+                                      ctx_.group_names.empty() ? nullptr : b->result.groups.data(), emit_device ? nullptr : b->cell.data(),
+                                      emit_device ? nullptr : b->phred.data(), nullptr));
         clk_.add(StageClock::ENGINE, StageClock::now() - te0);
         for (uint32_t k = 0; k < rows; ++k) {
             SiteText st;
@@ -657,6 +744,11 @@ private:
             for (; next_token < tokens.size() && tokens[next_token].pos == st.ref_pos; ++next_token)
                 st.indel_tokens.emplace_back(reinterpret_cast<const char *>(token_text.data()) + tokens[next_token].text_off, tokens[next_token].text_len);
             b->text.push_back(std::move(st));
+        }
+        if (emit_device) {
+            const double tw0 = StageClock::now();
+            emit_records_on_device(ctx_, *engine_, *b, &slab, first);
+            clk_.add(StageClock::ENGINE, StageClock::now() - tw0);
         }
         out_.push(std::move(b));
     }

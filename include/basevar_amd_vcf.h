@@ -3,7 +3,8 @@
  * (INTEGRATION.md section 2h).
  *
  * A VCF record of the reference (_out_vcf_line, src/basetype_caller.cpp:1103-1209) is a head of a few hundred bytes -- CHROM
- * through FORMAT, "%f" / "%g" formatting that stays on the host -- and one column per sample whose bytes depend only on the
+ * through FORMAT, "%f" / "%g" formatting that these calls take as host text (basevar_amd_record_text.h formats it on the device
+ * too) -- and one column per sample whose bytes depend only on the
  * sample's cell and phred bytes, four characters per line and a table of 256 strings.  Here those columns are expanded from
  * the planes where they lie in device memory (basevar_amd/csrc/bv_vcf.hip; the bytes are defined at the head of
  * basevar_amd/csrc/bv_vcf_core.h) and deflated from there (basevar_amd/csrc/bv_deflate.hip).
