@@ -95,6 +95,11 @@ class RecordLines(C.Structure):  # bv_record_lines (include/basevar_amd_record_t
 RECORD_TEXT_NAME_MAX, RECORD_TEXT_INDEL_MAX = 255, 16384
 
 
+class IndelTokens(C.Structure):  # bv_indel_tokens (include/basevar_amd_indel.h)
+    _fields_ = [("tokens", C.c_void_p), ("text", C.c_void_p), ("n_tokens", C.c_uint64), ("text_bytes", C.c_uint64), ("mem_kind", C.c_int32),
+                ("reserved_", C.c_uint32)]
+
+
 class PileupReads(C.Structure):  # bv_pileup_reads (include/basevar_amd_pileup.h)
     _fields_ = [("records", C.c_void_p), ("run_off", C.c_void_p), ("run_sample", C.c_void_p), ("pitch", C.c_uint64),
                 ("n_runs", C.c_uint32), ("n_samples", C.c_uint32), ("tid", C.c_int32), ("region_beg", C.c_uint32), ("region_end", C.c_uint32),
@@ -170,6 +175,9 @@ VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_def
 
 # every symbol include/basevar_amd_record_text.h declares
 RECORD_TEXT_EXPORTS = ["bv_record_text_on_device", "bv_engine_cvg_format", "bv_engine_cvg_fetch", "bv_engine_cvg_deflate", "bv_engine_vcf_format_records"]
+
+# every symbol include/basevar_amd_indel.h declares
+INDEL_EXPORTS = ["bv_indel_row_tokens_max", "bv_engine_indel_tally", "bv_engine_indel_fetch", "bv_engine_cvg_format_tallied"]
 
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
@@ -303,6 +311,14 @@ def load():
     L.bv_engine_cvg_fetch.argtypes = L.bv_engine_vcf_fetch.argtypes
     L.bv_engine_cvg_deflate.restype = C.c_int
     L.bv_engine_cvg_deflate.argtypes = L.bv_engine_vcf_deflate.argtypes
+    L.bv_indel_row_tokens_max.restype = C.c_uint32
+    L.bv_indel_row_tokens_max.argtypes = []
+    L.bv_engine_indel_tally.restype = C.c_int
+    L.bv_engine_indel_tally.argtypes = [C.c_void_p, C.POINTER(IndelTokens), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_engine_indel_fetch.restype = C.c_int
+    L.bv_engine_indel_fetch.argtypes = L.bv_engine_vcf_fetch.argtypes
+    L.bv_engine_cvg_format_tallied.restype = C.c_int
+    L.bv_engine_cvg_format_tallied.argtypes = [C.c_void_p, C.POINTER(RecordLines), C.c_void_p, C.c_void_p]
     L.bv_pileup_max_rows.restype = C.c_uint32
     L.bv_pileup_max_rows.argtypes = []
     L.bv_engine_pileup_set_reference.restype = C.c_int

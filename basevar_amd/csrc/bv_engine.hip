@@ -513,6 +513,7 @@ int bv_engine_destroy(bv_engine *e) {
     bv_pileup_state_free(e->pileup);
     bv_ptext_state_free(e->ptext);
     bv_rtext_state_free(e->rtext);
+    bv_indel_state_free(e->indel);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

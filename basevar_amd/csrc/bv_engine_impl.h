@@ -1,5 +1,5 @@
 // bv_engine_impl.h -- the engine as its own translation units see it (bv_engine.hip, bv_engine_rows.hip, bv_engine_tiles.hip,
-// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip, bv_pileup_text.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  (bv_vcf.hip and
+// bv_text.hip, bv_inflate.hip, bv_deflate.hip, bv_vcf.hip, bv_pileup.hip, bv_pileup_text.hip, bv_record_text.hip, bv_indel_tally.hip): struct bv_engine, the error path, and the plumbing every entry point shares.  (bv_vcf.hip and
 // bv_pileup_text.hip share two more headers: bv_device_text.h, the text they leave on the device, and bv_text_image.h, the
 // kernels' side of writing it.)  Host-only; the
 // files that hold the calling kernels (pass 1, pass 2, tiles) know the launch-argument blocks of bv_kernels.h and nothing of this.
@@ -27,6 +27,17 @@ struct BvPtextState;    // bv_engine_pileup_text (bv_pileup_text.hip)
 void bv_ptext_state_free(BvPtextState *t);
 struct BvRtextState;    // bv_engine_cvg_format / bv_engine_vcf_format_records (bv_record_text.hip)
 void bv_rtext_state_free(BvRtextState *t);
+struct BvIndelState;    // bv_engine_indel_tally (bv_indel_tally.hip)
+void bv_indel_state_free(BvIndelState *t);
+// The last completed bv_engine_indel_tally, as it lies (bv_indel_tally.hip): bv_engine_cvg_format_tallied reads it
+struct BvIndelView {
+    bool done = false;
+    uint32_t n = 0;
+    const uint8_t *d_text = nullptr;   // device: the columns back to back
+    const uint64_t *d_off = nullptr;   // device [n + 1]
+    const uint8_t *flag = nullptr;     // host [n]
+};
+void bv_indel_view(const BvIndelState *t, BvIndelView *v);
 struct BvPileupToken;   // bv_pileup_core.h
 // The last completed bv_engine_pileup and the uploaded reference, as they lie (bv_pileup.hip): have_ref / done say what is there
 struct BvPileupView {
@@ -189,6 +200,7 @@ struct bv_engine {
     BvPileupState *pileup = nullptr;   // created by the first bv_engine_pileup_set_reference
     BvPtextState *ptext = nullptr;     // created by the first bv_engine_pileup_text
     BvRtextState *rtext = nullptr;     // created by the first bv_engine_cvg_format / bv_engine_vcf_format_records
+    BvIndelState *indel = nullptr;     // created by the first bv_engine_indel_tally
     mutable std::mutex mu;
     std::string err;
 };

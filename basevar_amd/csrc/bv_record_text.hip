@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/basevar_amd_indel.h"
 #include "../../include/basevar_amd_record_text.h"
 #include "bv_chunk_stage.h"
 #include "bv_device_text.h"
@@ -203,7 +204,9 @@ struct Prepared {
     std::vector<uint32_t> len;  // [n] bytes of the line / head (of its host text, where it has one)
 };
 
-int prepare(bv_engine *e, const std::string &who, BvRtextState *t, const bv_record_lines *in, bool cvg, hipStream_t st, Prepared *out) {
+// `tallied` (CVG rows, in->indel NULL): the indel columns are those of a completed tally, read where they lie
+int prepare(bv_engine *e, const std::string &who, BvRtextState *t, const bv_record_lines *in, bool cvg, hipStream_t st, Prepared *out,
+            const BvIndelView *tallied = nullptr) {
     const uint32_t n = in->n_lines, G = in->n_groups;
     const bool up_rec = in->mem_kind == BV_MEM_HOST;
     const uint64_t ht_lo = in->host_text_off ? in->host_text_off[0] : 0, ht_bytes = in->host_text_off ? in->host_text_off[n] - ht_lo : 0;
@@ -251,6 +254,7 @@ int prepare(bv_engine *e, const std::string &who, BvRtextState *t, const bv_reco
     a.htext = t->d_in + o_ht;
     a.indel_off = indel ? reinterpret_cast<const uint64_t *>(t->d_in + o_ioff) : nullptr;
     a.indel = t->d_in + o_id;
+    if (tallied) { a.indel_off = tallied->d_off; a.indel = tallied->d_text; }
     a.line_of = reinterpret_cast<const uint32_t *>(t->d_in + o_lineof);
     a.text_off = reinterpret_cast<const uint64_t *>(t->d_in + o_toff);
     a.len = reinterpret_cast<uint32_t *>(t->d_out); a.bad = a.len + n;
@@ -305,17 +309,32 @@ int bv_record_text_on_device(const bv_site_result *record, const bv_group_result
     return bv_rt_on_device(record, groups, n_groups) ? 1 : 0;
 }
 
-int bv_engine_cvg_format(bv_engine *e, const bv_record_lines *in, uint64_t *line_off, void *stream_) {
-    const std::string who = "bv_engine_cvg_format: ";
+}  // extern "C"
+
+namespace {
+
+// bv_engine_cvg_format, and bv_engine_cvg_format_tallied with the last tally's columns
+int cvg_format(bv_engine *e, const std::string &who, const bv_record_lines *in, uint64_t *line_off, void *stream_, bool from_tally) {
     int rc = entry_checks(e, who, in, line_off, true);
     if (rc != BV_OK) return rc;
+    BvIndelView tally;
+    if (from_tally) {
+        if (in->indel || in->indel_off) return fail(e, BV_ERR_INVALID_ARG, who + "indel / indel_off must be NULL: the columns are the last tally's");
+        bv_indel_view(e->indel, &tally);
+        if (!tally.done) return fail(e, BV_ERR_INVALID_ARG, who + "no bv_engine_indel_tally before it");
+        if (tally.n != in->n_lines)
+            return fail(e, BV_ERR_INVALID_ARG, who + "the last tally has " + std::to_string(tally.n) + " rows, not n_lines = " + std::to_string(in->n_lines));
+        for (uint32_t k = 0; k < in->n_lines; ++k)
+            if (tally.flag[k] && !(in->host_text_off && in->host_text_off[k + 1] != in->host_text_off[k]))
+                return fail(e, BV_ERR_INVALID_ARG, who + "line " + std::to_string(k) + ": the tally left its indel column to the caller, and the line brings no host text");
+    }
     BvRtextState *t = text_state(e, e->rtext);
     t->text.formatted = false;
     const uint32_t n = in->n_lines;
     if (n == 0) return device_text_empty(t->text, line_off);
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     Prepared p;
-    rc = prepare(e, who, t, in, true, st, &p);
+    rc = prepare(e, who, t, in, true, st, &p, from_tally ? &tally : nullptr);
     if (rc != BV_OK) return rc;
     std::vector<uint64_t> off(n + 1, 0);
     for (uint32_t k = 0; k < n; ++k) off[k + 1] = off[k] + p.len[k];
@@ -330,6 +349,18 @@ int bv_engine_cvg_format(bv_engine *e, const bv_record_lines *in, uint64_t *line
     std::memcpy(line_off, off.data(), 8ull * (n + 1));
     device_text_done(t->text, off[n]);
     return BV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bv_engine_cvg_format(bv_engine *e, const bv_record_lines *in, uint64_t *line_off, void *stream) {
+    return cvg_format(e, "bv_engine_cvg_format: ", in, line_off, stream, false);
+}
+
+int bv_engine_cvg_format_tallied(bv_engine *e, const bv_record_lines *in, uint64_t *line_off, void *stream) {
+    return cvg_format(e, "bv_engine_cvg_format_tallied: ", in, line_off, stream, true);
 }
 
 int bv_engine_cvg_fetch(bv_engine *e, void *dst, uint64_t dst_capacity, int dst_mem_kind, void *stream_) {

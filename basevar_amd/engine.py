@@ -716,6 +716,58 @@ class BaseTypeEngine:
         """bgzf_deflate of the last cvg_format's text, read where it lies on the device (bv_engine_cvg_deflate)."""
         return self._deflate("cvg_deflate", "bv_engine_cvg_deflate", getattr(self, "_cvg_bytes", 0), block_bytes, block_off, level)
 
+    # ---- the CVG rows' indel columns, tallied on the device (include/basevar_amd_indel.h)
+    @staticmethod
+    def indel_row_tokens_max():
+        """The most tokens a row of indel_tally may have (bv_indel_row_tokens_max)."""
+        return int(_capi.load().bv_indel_row_tokens_max())
+
+    def indel_tally(self, key, tokens=None, text=None):
+        """The indel columns of rows `key` (bv_engine_indel_tally): row k's tokens are those whose pos equals key[k].  `tokens`:
+        a PILEUP_TOKEN_DTYPE array ascending by pos with `text` (bytes or uint8 array) in host memory; or (device pointer,
+        n_tokens) with `text` = (device pointer, text_bytes); or None: the tokens of this engine's last pileup, where they lie.
+        The columns stay on the device (indel_fetch, cvg_format_tallied); returns (col_off uint64 [n + 1], row_flag uint8 [n]:
+        1 where the row is outside the tally's domain and its zero-length column is the caller's)."""
+        key = np.ascontiguousarray(key, dtype=np.uint32).reshape(-1)
+        n = int(key.size)
+        T = None
+        if tokens is not None:
+            T = _capi.IndelTokens()
+            if isinstance(tokens, tuple):
+                T.tokens, T.n_tokens, T.mem_kind = int(tokens[0]) or None, int(tokens[1]), _capi.BV_MEM_DEVICE
+                T.text, T.text_bytes = int(text[0]) or None, int(text[1])
+            else:
+                tk = np.ascontiguousarray(tokens, dtype=_capi.PILEUP_TOKEN_DTYPE).reshape(-1)
+                tx = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
+                T.tokens, T.n_tokens, T.mem_kind = tk.ctypes.data if tk.size else None, int(tk.size), _capi.BV_MEM_HOST
+                T.text, T.text_bytes = tx.ctypes.data if tx.size else None, int(tx.size)
+            T.reserved_ = 0
+        col_off = np.zeros(n + 1, dtype=np.uint64)
+        row_flag = np.zeros(n, dtype=np.uint8)
+        rc = self._lib.bv_engine_indel_tally(self._h, C.byref(T) if T is not None else None, key.ctypes.data if n else None, n, col_off.ctypes.data,
+                                             row_flag.ctypes.data if n else None, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_indel_tally failed (%d): %s" % (rc, self._err()), rc)
+        self._indel_bytes = int(col_off[n])
+        return col_off, row_flag
+
+    def indel_fetch(self, dst_ptr=0, dst_capacity=0):
+        """The columns of the last indel_tally back to back (bv_engine_indel_fetch), as vcf_fetch returns vcf_format's text."""
+        return self._text_fetch("bv_engine_indel_fetch", getattr(self, "_indel_bytes", 0), dst_ptr, dst_capacity)
+
+    def cvg_format_tallied(self, sites, chrom, pos, ref_char, host_text=None, groups=None, group_names=()):
+        """cvg_format with row k's indel column taken from column k of the last indel_tally, where it lies
+        (bv_engine_cvg_format_tallied).  A row the tally flagged brings its host text."""
+        n = int(sites[1]) if isinstance(sites, tuple) else int(np.asarray(sites).size)
+        L, keep, _ = self._record_lines("cvg_format_tallied", sites, groups, chrom, pos, ref_char, group_names, host_text, n)
+        line_off = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_cvg_format_tallied(self._h, C.byref(L), line_off.ctypes.data, None)
+        if rc != 0:
+            self._cvg_bytes = 0
+            raise RuntimeError("bv_engine_cvg_format_tallied failed (%d): %s" % (rc, self._err()), rc)
+        self._cvg_bytes = int(line_off[n])
+        return line_off
+
     def vcf_format_records(self, site, sites, chrom, pos, ref_char, groups=None, group_names=(), host_text=None, slab=None):
         """Whole VCF lines from the records (bv_engine_vcf_format_records): line k is the head of sites[k] -- formatted on the
         device, or host_text[k] (CHROM through "GT:AB:SO:BP") where that is given -- and the sample columns of row site[k] as

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/basevar_amd_indel.h"
 #include "../../include/basevar_amd_record_text.h"
 #include "../../include/basevar_amd_vcf.h"
 #include "vcf_emit.hpp"  // SiteText
@@ -384,6 +385,26 @@ public:
     }
     void cvg_fetch(char *dst, uint64_t bytes) {
         if (bv_engine_cvg_fetch(e_, dst, bytes, BV_MEM_HOST, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+    }
+
+    // The CVG rows' indel columns tallied on the device (include/basevar_amd_indel.h): indel_string's bytes for every row inside
+    // the tally's domain.  indel_tally() leaves the columns of rows `key` on the device and returns col_off [n + 1]; row_flag [n]
+    // says which rows it left to the caller.  `tok` == nullptr: the tokens of this engine's last pileup, where they lie.
+    // cvg_format_tallied() is cvg_format() with those columns; indel_fetch() copies them out.
+    std::vector<uint64_t> indel_tally(const bv_indel_tokens *tok, const std::vector<uint32_t> &key, std::vector<uint8_t> &row_flag) {
+        std::vector<uint64_t> col_off(key.size() + 1, 0);
+        row_flag.assign(key.size(), 0);
+        if (bv_engine_indel_tally(e_, tok, key.data(), (uint32_t)key.size(), col_off.data(), row_flag.data(), nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+        return col_off;
+    }
+    void indel_fetch(char *dst, uint64_t bytes) {
+        if (bv_engine_indel_fetch(e_, dst, bytes, BV_MEM_HOST, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+    }
+    std::vector<uint64_t> cvg_format_tallied(const bv_record_lines &in) {
+        std::vector<uint64_t> line_off((size_t)in.n_lines + 1, 0);
+        if (bv_engine_cvg_format_tallied(e_, &in, line_off.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return line_off;
     }
 
     // lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf, include/basevar_amd_bgzf.h), in two steps so

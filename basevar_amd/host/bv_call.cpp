@@ -253,10 +253,12 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
         tf << ", \"deflate\": \"device\", \"deflate_level\": \"" << o.deflate_level << "\", \"members_deflated\": " << emitter.members_deflated()
            << ", \"deflate_s\": " << emitter.deflate_s();
     // --emit device: VCF lines and CVG rows the engines wrote, and the records among them that the host formatted (numbers the
-    // device's formats do not cover: a NaN AF)
+    // device's formats do not cover: a NaN AF); and the rows whose indel column is not ".", by who wrote the row (the
+    // device's own are tallied there too)
     if (ctx.routes.emit_device)
         tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << emitter.vcf_lines_device() << ", \"cvg_lines_device\": " << emitter.cvg_lines_device()
-           << ", \"lines_host_formatted\": " << emitter.lines_host_formatted();
+           << ", \"lines_host_formatted\": " << emitter.lines_host_formatted() << ", \"indel_columns_device\": " << emitter.indel_columns_device()
+           << ", \"indel_columns_host\": " << emitter.indel_columns_host();
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
     // ... --inflate device with it: the BAM files' compressed members handed to the engine instead, and their bytes

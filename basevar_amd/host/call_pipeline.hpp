@@ -20,6 +20,7 @@
 #include <cstring>
 #include <deque>
 #include <exception>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -63,6 +64,8 @@ struct Batch {
     bool cvg_device = false;
     std::string cvg_text;
     uint64_t cvg_lines_device = 0, lines_host_formatted = 0;
+    uint64_t indel_columns_device = 0;  // of the rows the device wrote: those whose indel column, not ".", it tallied too
+    uint64_t indel_columns_host = 0;    // of the rows the host formatted: those whose indel column is not "."
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -229,6 +232,8 @@ public:
     uint64_t vcf_lines_device() const { return vcf_lines_device_; }
     uint64_t cvg_lines_device() const { return cvg_lines_device_; }
     uint64_t lines_host_formatted() const { return lines_host_formatted_; }
+    uint64_t indel_columns_device() const { return indel_columns_device_; }
+    uint64_t indel_columns_host() const { return indel_columns_host_; }
     uint64_t members_deflated() const { return members_deflated_; }
     double deflate_s() const { return deflate_s_; }
 
@@ -288,6 +293,8 @@ private:
         vcf_lines_device_ += d.vcf_record.size();
         cvg_lines_device_ += d.cvg_lines_device;
         lines_host_formatted_ += d.lines_host_formatted;
+        indel_columns_device_ += d.indel_columns_device;
+        indel_columns_host_ += d.indel_columns_host;
     }
 
     const CallContext &ctx_;
@@ -299,7 +306,7 @@ private:
     uint64_t next_seq_ = 0;
     bool stopped_ = false;  // a batch failed: nothing behind it is written
     size_t n_sites_ = 0, n_variants_ = 0;
-    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, members_deflated_ = 0;
+    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, indel_columns_device_ = 0, indel_columns_host_ = 0, members_deflated_ = 0;
     double deflate_s_ = 0;
 };
 
@@ -378,12 +385,17 @@ private:
 
 // One worker thread: an engine on devices[w % G], batches from `in` (or from its turns at the raw reader) to `out`
 // --emit device: the VCF lines of the batch's variant records and its CVG rows, written on `engine` from the records
-// (bv_engine_vcf_format_records, bv_engine_cvg_format) over the rows that lie there -- row first_row + i of `slab` for record i,
-// or, with slab == nullptr, the rows the engine's text submit kept.  The few records whose numbers the device does not format
-// (BaseTypeEngine::record_text_on_device: a NaN AF), or whose place is not the batch's first CHROM and one REF character, or
-// whose indel column is too long, are formatted here and go in as host text.  The VCF text comes back as BGZF members
-// deflated there too (a *.vcf.gz, at --deflate-level) or as it is; the CVG text as it is.
-inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engine, Batch &b, const bv_slab *slab, uint32_t first_row) {
+// (bv_engine_vcf_format_records, bv_engine_cvg_format_tallied) over the rows that lie there -- row first_row + i of `slab` for
+// record i, or, with slab == nullptr, the rows the engine's text submit kept.  The rows' indel columns are tallied there too
+// (bv_engine_indel_tally): from the tokens of the engine's last pileup where they lie, keyed by position (`pileup_tokens`: how
+// to get one position's tokens to the host after all), or from the SiteTexts' tokens, handed over as host descriptors keyed by
+// the row's index in the batch.  The few records whose numbers the device does not format (BaseTypeEngine::
+// record_text_on_device: a NaN AF), or whose place is not the batch's first CHROM and one REF character, or whose row the
+// tally left to the caller, are formatted here and go in as host text, with the tally's column where it made one.  The VCF
+// text comes back as BGZF members deflated there too (a *.vcf.gz, at --deflate-level) or as it is; the CVG text as it is.
+typedef std::function<std::vector<std::string>(uint32_t pos)> PileupRowTokens;
+inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engine, Batch &b, const bv_slab *slab, uint32_t first_row,
+                                   const PileupRowTokens *pileup_tokens = nullptr) {
     b.emit_device = true;
     const size_t n = b.text.size();
     if (n == 0) return;
@@ -395,36 +407,75 @@ inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engin
     bool names_fit = !chrom.empty() && chrom.size() <= BV_RECORD_TEXT_NAME_MAX;
     for (const std::string &g : ctx.group_names) names_fit = names_fit && g.size() <= BV_RECORD_TEXT_NAME_MAX;
     std::vector<uint32_t> pos(n), site;
-    std::string ref(n, 'N'), cvg_host, indel, vcf_host;
-    std::vector<uint64_t> cvg_host_off(1, 0), indel_off(1, 0), vcf_host_off(1, 0);
+    std::string ref(n, 'N'), cvg_host, vcf_host;
+    std::vector<uint64_t> cvg_host_off(1, 0), vcf_host_off(1, 0);
     std::vector<bv_site_result> vrec;
     std::vector<bv_group_result> vgrp;
     std::vector<uint32_t> vpos, vidx;
     std::string vref;
-    // the predicate and the indel tallies (sorted host maps, as the emitter built them) on the run's host threads
-    std::vector<std::string> columns(n);
+    for (size_t i = 0; i < n; ++i) pos[i] = b.text[i].ref_pos;
+    // the indel tallies on the engine
+    std::vector<uint8_t> flagged;
+    std::vector<uint64_t> col_off;
+    if (pileup_tokens) {
+        col_off = engine.indel_tally(nullptr, pos, flagged);
+    } else {
+        // (a row of 10,000 samples brings hundreds of tokens: the descriptors are laid out on the run's host threads)
+        std::vector<uint32_t> key(n);
+        std::vector<uint64_t> token_at(n + 1, 0), text_at(n + 1, 0);
+        parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                key[i] = (uint32_t)i;
+                token_at[i + 1] = b.text[i].indel_tokens.size();
+                for (const std::string &t : b.text[i].indel_tokens) text_at[i + 1] += t.size();
+            }
+        });
+        for (size_t i = 0; i < n; ++i) { token_at[i + 1] += token_at[i]; text_at[i + 1] += text_at[i]; }
+        std::vector<bv_pileup_token> tokens(token_at[n]);
+        std::string token_text(text_at[n], '\0');
+        parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
+            for (size_t i = lo; i < hi; ++i) {
+                uint64_t k = token_at[i], at = text_at[i];
+                for (const std::string &t : b.text[i].indel_tokens) {
+                    tokens[k++] = bv_pileup_token{(uint32_t)i, 0u, at, (uint32_t)t.size(), 0u};
+                    std::memcpy(&token_text[at], t.data(), t.size());
+                    at += t.size();
+                }
+            }
+        });
+        const bv_indel_tokens tok{tokens.data(), reinterpret_cast<const uint8_t *>(token_text.data()), tokens.size(), token_text.size(), BV_MEM_HOST, 0};
+        col_off = engine.indel_tally(&tok, key, flagged);
+    }
+    // the predicate on the run's host threads
     std::vector<uint8_t> fits(n, 0);
     parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
         for (size_t i = lo; i < hi; ++i) {
             const SiteText &st = b.text[i];
-            if (!st.indel_tokens.empty()) columns[i] = indel_string(st.indel_tokens);
             fits[i] = names_fit && st.ref_id == chrom && st.ref_base.size() == 1 &&
                       BaseTypeEngine::record_text_on_device(b.result.sites[i], G ? &b.result.group(i, 0) : nullptr, G);
         }
     });
+    // the columns of the rows the host formats: the tally's, fetched once if there is such a row
+    std::string columns;
+    auto host_column = [&](size_t i) {
+        if (flagged[i]) return indel_string(pileup_tokens ? (*pileup_tokens)(pos[i]) : b.text[i].indel_tokens);
+        if (col_off[i + 1] == col_off[i]) return std::string();
+        if (columns.empty()) { columns.resize(col_off[n]); engine.indel_fetch(&columns[0], col_off[n]); }
+        return columns.substr(col_off[i], col_off[i + 1] - col_off[i]);
+    };
     for (size_t i = 0; i < n; ++i) {
         const SiteText &st = b.text[i];
         const bv_site_result &r = b.result.sites[i];
         const bv_group_result *g = G ? &b.result.group(i, 0) : nullptr;
-        pos[i] = st.ref_pos;
         if (st.ref_base.size() == 1) ref[i] = st.ref_base[0];
-        const std::string &column = columns[i];
         const bool on_device = fits[i] != 0;
         if (!on_device) ++b.lines_host_formatted;
-        if (!on_device || column.size() > BV_RECORD_TEXT_INDEL_MAX) cvg_host += format_cvg_line(st, r);
-        else if (column != ".") indel += column;
+        if (!on_device || flagged[i]) {
+            const std::string column = host_column(i), row = format_cvg_line(st, r, column);
+            if (!row.empty() && !column.empty() && column != ".") ++b.indel_columns_host;
+            cvg_host += row;
+        }
         cvg_host_off.push_back(cvg_host.size());
-        indel_off.push_back(indel.size());
         if (!b.result.has_variant(i)) continue;
         vrec.push_back(r);
         if (G) vgrp.insert(vgrp.end(), g, g + G);
@@ -466,19 +517,21 @@ inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engin
         b.vcf_text.resize(total);
         engine.vcf_fetch(&b.vcf_text[0], total);
     }
-    // the CVG rows of every record
+    // the CVG rows of every record, around the tally's columns
     in.records = b.result.sites.data(); in.groups = in.n_groups ? b.result.groups.data() : nullptr;
     in.pos = pos.data(); in.ref_char = ref.data();
     in.host_text = cvg_host.data(); in.host_text_off = cvg_host_off.data();
-    in.indel = indel.data(); in.indel_off = indel_off.data();
     in.slab = nullptr; in.site = nullptr;
     in.n_lines = (uint32_t)n;
-    const std::vector<uint64_t> coff = engine.cvg_format(in);
+    const std::vector<uint64_t> coff = engine.cvg_format_tallied(in);
     b.cvg_device = true;
     b.cvg_text.resize(coff.back());
     if (coff.back()) engine.cvg_fetch(&b.cvg_text[0], coff.back());
     for (size_t i = 0; i < n; ++i)
-        if (coff[i + 1] != coff[i] && cvg_host_off[i + 1] == cvg_host_off[i]) ++b.cvg_lines_device;
+        if (coff[i + 1] != coff[i] && cvg_host_off[i + 1] == cvg_host_off[i]) {
+            ++b.cvg_lines_device;
+            if (col_off[i + 1] != col_off[i]) ++b.indel_columns_device;
+        }
 }
 
 class EngineWorker {
@@ -700,20 +753,38 @@ private:
         bv_slab slab;
         // (short reads: the rank words carry the calls, as SlabBuilder::tag_ranks chooses on the host path)
         if (bv_engine_pileup_rows(pe, 1, &slab, pos.data(), depth.data()) != BV_OK) check(bv_engine_pileup_rows(pe, 0, &slab, pos.data(), depth.data()));
-        bv_pileup_result res{};
-        res.mem_kind = BV_MEM_HOST;
-        check(bv_engine_pileup_fetch(pe, &res, nullptr));  // (no buffers: the sizes)
-        std::vector<bv_pileup_token> tokens(res.n_tokens);
-        std::vector<uint8_t> token_text(res.text_bytes);
-        res.tokens = tokens.data(); res.text = token_text.data();
-        res.tokens_capacity = tokens.size(); res.text_capacity = token_text.size();
-        check(bv_engine_pileup_fetch(pe, &res, nullptr));
+        // the indel tokens: --emit device tallies them where they lie, and fetches them only for a row it leaves to the host
+        std::vector<bv_pileup_token> tokens;
+        std::vector<uint8_t> token_text;
+        tokens_fetched_ = false;
+        if (!ctx_.routes.emit_device) fetch_tokens(tokens, token_text);
         const double dt = StageClock::now() - tp0;
         stats_.pileup_s += dt;
         clk_.add(StageClock::PARSE, dt);
         size_t next_token = 0;
         for (uint32_t first = 0; first < n_cov && errors_.ok(); first += ctx_.batch_sites)
             call_rows(slab, ref_id, fa_seq, pos, tokens, token_text, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
+    }
+    // the last pileup's tokens and their text, to the host
+    void fetch_tokens(std::vector<bv_pileup_token> &tokens, std::vector<uint8_t> &token_text) {
+        bv_engine *pe = engine_->handle();
+        bv_pileup_result res{};
+        res.mem_kind = BV_MEM_HOST;
+        check(bv_engine_pileup_fetch(pe, &res, nullptr));  // (no buffers: the sizes)
+        tokens.resize(res.n_tokens);
+        token_text.resize(res.text_bytes);
+        res.tokens = tokens.data(); res.text = token_text.data();
+        res.tokens_capacity = tokens.size(); res.text_capacity = token_text.size();
+        check(bv_engine_pileup_fetch(pe, &res, nullptr));
+    }
+    // --emit device: the tokens of one position of the window, fetched when the first row asks
+    std::vector<std::string> row_tokens(uint32_t pos) {
+        if (!tokens_fetched_) { fetch_tokens(window_tokens_, window_token_text_); tokens_fetched_ = true; }
+        std::vector<std::string> out;
+        auto it = std::lower_bound(window_tokens_.begin(), window_tokens_.end(), pos, [](const bv_pileup_token &t, uint32_t p) { return t.pos < p; });
+        for (; it != window_tokens_.end() && it->pos == pos; ++it)
+            out.emplace_back(reinterpret_cast<const char *>(window_token_text_.data()) + it->text_off, it->text_len);
+        return out;
     }
     // rows [first, first + rows) of the window's covered positions: called where they lie, their records and planes into a batch
     // -- or, with --emit device, their records alone: the lines are written from the rows where they lie, before the next window's
@@ -740,6 +811,7 @@ private:
         for (uint32_t k = 0; k < rows; ++k) {
             SiteText st;
             st.ref_id = ref_id; st.ref_pos = pos[first + k]; st.ref_base = std::string(1, fa_seq[st.ref_pos - 1]);
+            // (--emit device: `tokens` is empty, the column is tallied on the engine)
             while (next_token < tokens.size() && tokens[next_token].pos < st.ref_pos) ++next_token;
             for (; next_token < tokens.size() && tokens[next_token].pos == st.ref_pos; ++next_token)
                 st.indel_tokens.emplace_back(reinterpret_cast<const char *>(token_text.data()) + tokens[next_token].text_off, tokens[next_token].text_len);
@@ -747,7 +819,8 @@ private:
         }
         if (emit_device) {
             const double tw0 = StageClock::now();
-            emit_records_on_device(ctx_, *engine_, *b, &slab, first);
+            const PileupRowTokens from_pileup = [this](uint32_t pos) { return row_tokens(pos); };
+            emit_records_on_device(ctx_, *engine_, *b, &slab, first, &from_pileup);
             clk_.add(StageClock::ENGINE, StageClock::now() - tw0);
         }
         out_.push(std::move(b));
@@ -762,6 +835,9 @@ private:
     std::unique_ptr<BamPool> pool_;
     Stats stats_;
     uint64_t seq_ = 0;
+    bool tokens_fetched_ = false;  // --emit device: window_tokens_ are the current window's
+    std::vector<bv_pileup_token> window_tokens_;
+    std::vector<uint8_t> window_token_text_;
 };
 
 }  // namespace bvamd

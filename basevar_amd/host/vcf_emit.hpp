@@ -66,14 +66,16 @@ inline void append_f6(std::string &s, double v) {
 }
 
 // One CVG row (the columns of _out_cvg_line, caller.cpp:1246-1257).  Empty string when the reference writes nothing.
-inline std::string format_cvg_line(const SiteText &st, const bv_site_result &r) {
+// `indel_column`: the row's indel column where the caller has it already (indel_string's text; the device's tally, whose
+// empty column prints as "."); nullptr: tallied here from the site's tokens.
+inline std::string format_cvg_line(const SiteText &st, const bv_site_result &r, const std::string *indel_column) {
     if (r.total_depth == 0) return "";
     std::string s = st.ref_id;
     s += '\t'; s += std::to_string(st.ref_pos);
     s += '\t'; s += st.ref_base;
     s += '\t'; s += std::to_string((int)r.total_depth);
     for (int b = 0; b < 4; ++b) { s += '\t'; s += std::to_string((int)r.depth[b]); }
-    s += '\t'; s += indel_string(st.indel_tokens);
+    s += '\t'; s += !indel_column ? indel_string(st.indel_tokens) : indel_column->empty() ? std::string(".") : *indel_column;
     s += '\t'; append_f6(s, r.cvg_fs);
     s += '\t'; append_f6(s, r.cvg_sor);
     s += '\t';
@@ -81,6 +83,8 @@ inline std::string format_cvg_line(const SiteText &st, const bv_site_result &r) 
     s += '\n';
     return s;
 }
+inline std::string format_cvg_line(const SiteText &st, const bv_site_result &r) { return format_cvg_line(st, r, static_cast<const std::string *>(nullptr)); }
+inline std::string format_cvg_line(const SiteText &st, const bv_site_result &r, const std::string &indel_column) { return format_cvg_line(st, r, &indel_column); }
 
 // The INFO column as a table: key, and what of the record it prints.  Order and spelling are the file format's
 // (caller.cpp:1167-1180); the three rank sums are truncated to int as the reference's caller does (:1151-1157).
