@@ -179,6 +179,9 @@ RECORD_TEXT_EXPORTS = ["bv_record_text_on_device", "bv_engine_cvg_format", "bv_e
 # every symbol include/basevar_amd_indel.h declares
 INDEL_EXPORTS = ["bv_indel_row_tokens_max", "bv_engine_indel_tally", "bv_engine_indel_fetch", "bv_engine_cvg_format_tallied"]
 
+# every symbol include/basevar_amd_text_tokens.h declares
+TEXT_TOKENS_EXPORTS = ["bv_engine_text_tokens_enable", "bv_engine_text_tokens", "bv_engine_text_tokens_fetch", "bv_engine_text_heads_fetch"]
+
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
 
@@ -319,6 +322,14 @@ def load():
     L.bv_engine_indel_fetch.argtypes = L.bv_engine_vcf_fetch.argtypes
     L.bv_engine_cvg_format_tallied.restype = C.c_int
     L.bv_engine_cvg_format_tallied.argtypes = [C.c_void_p, C.POINTER(RecordLines), C.c_void_p, C.c_void_p]
+    L.bv_engine_text_tokens_enable.restype = C.c_int
+    L.bv_engine_text_tokens_enable.argtypes = [C.c_void_p, C.c_int]
+    L.bv_engine_text_tokens.restype = C.c_int
+    L.bv_engine_text_tokens.argtypes = [C.c_void_p, C.POINTER(IndelTokens)]
+    L.bv_engine_text_tokens_fetch.restype = C.c_int
+    L.bv_engine_text_tokens_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+    L.bv_engine_text_heads_fetch.restype = C.c_int
+    L.bv_engine_text_heads_fetch.argtypes = L.bv_engine_text_rows_fetch.argtypes
     L.bv_pileup_max_rows.restype = C.c_uint32
     L.bv_pileup_max_rows.argtypes = []
     L.bv_engine_pileup_set_reference.restype = C.c_int

@@ -514,6 +514,7 @@ int bv_engine_destroy(bv_engine *e) {
     bv_ptext_state_free(e->ptext);
     bv_rtext_state_free(e->rtext);
     bv_indel_state_free(e->indel);
+    bv_text_tok_state_free(e->ttok);
     for (hipStream_t st : e->used_streams) (void)hipStreamSynchronize(st);
     for (auto &tri : e->ring)
         for (auto &ev : tri)

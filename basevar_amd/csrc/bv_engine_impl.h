@@ -38,6 +38,8 @@ struct BvIndelView {
     const uint8_t *flag = nullptr;     // host [n]
 };
 void bv_indel_view(const BvIndelState *t, BvIndelView *v);
+struct BvTextTokState;  // bv_engine_text_tokens (bv_text_tokens.hip)
+void bv_text_tok_state_free(BvTextTokState *t);
 struct BvPileupToken;   // bv_pileup_core.h
 // The last completed bv_engine_pileup and the uploaded reference, as they lie (bv_pileup.hip): have_ref / done say what is there
 struct BvPileupView {
@@ -201,6 +203,7 @@ struct bv_engine {
     BvPtextState *ptext = nullptr;     // created by the first bv_engine_pileup_text
     BvRtextState *rtext = nullptr;     // created by the first bv_engine_cvg_format / bv_engine_vcf_format_records
     BvIndelState *indel = nullptr;     // created by the first bv_engine_indel_tally
+    BvTextTokState *ttok = nullptr;    // created by the first bv_engine_text_tokens_enable that turns the mode on
     mutable std::mutex mu;
     std::string err;
 };
@@ -254,6 +257,21 @@ int try_grow_device(bv_engine *e, T **buf, size_t *bytes, size_t need) {
     }
     return BV_OK;
 }
+
+// ---- the indel tokens of parsed text rows (bv_text_tokens.hip), as the two parses of bv_text.hip drive them.  Each call does
+// nothing while the mode is off (bv_engine_text_tokens_enable); the engine's device is selected.
+struct BvTextTokRows {  // rows [row_first, row_first + n_rows) of the batch, whose text is on the device now
+    const char *text;                   // byte k is text byte chunk_base + k
+    const uint64_t *row_beg, *row_end;  // device [rows of the batch]: a row's first byte, and the byte behind its '\n'
+    const uint8_t *rowflag;             // device: BV_TEXT_INDEL as bv_text_parse_kernel left it
+    const uint32_t *foff;               // device [n_files]
+    uint64_t chunk_base;
+    uint32_t row_first, n_rows, n_files;
+};
+int bv_text_tokens_begin(bv_engine *e, uint32_t P, uint32_t F, hipStream_t st);  // a parse begins: the last list is gone
+int bv_text_tokens_rows(bv_engine *e, const BvTextTokRows &rows, hipStream_t st);  // behind the parse kernel of these rows; waits for `st`
+int bv_text_tokens_finish(bv_engine *e, const uint8_t *pos_state, uint32_t P, uint32_t F, hipStream_t st);  // the positions' final states (host [P])
+bool bv_text_tokens_stand(const bv_engine *e);  // the mode is on and the last parse's list stands (bv_engine_text_tokens would hand it out)
 
 // ---- stream ordering (bv_engine.hip): work of one engine is serialised, whatever streams the caller alternates
 int use_stream(bv_engine *e, hipStream_t st);  // before an entry point queues on `st`

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/basevar_amd_bgzf.h"
+#include "../../include/basevar_amd_text_tokens.h"
 #include "bv_inflate_core.h"
 #include "bv_chunk_stage.h"
 
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(64) void bv_text_line_scatter_kernel(const char *te
 
 // ---- bv_engine_text_rows_fetch: how much of every row the host still needs, then the bytes
 __global__ __launch_bounds__(256) void bv_text_fetch_len_kernel(const char *text, const uint64_t *row_beg, const uint64_t *row_end, const uint8_t *pos_state,
-                                                                const uint8_t *rowflag, uint32_t R, uint32_t F, uint32_t *len) {
+                                                                const uint8_t *rowflag, uint32_t R, uint32_t F, uint32_t heads, uint32_t *len) {
     const uint32_t r = blockIdx.x * 256u + threadIdx.x;
     if (r >= R) return;
     const uint32_t p = r / F, f = r - p * F;
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(256) void bv_text_fetch_len_kernel(const char *text
     uint32_t out = 0;
     if (s & BV_TEXT_SKIP) {
         out = 0;
-    } else if ((s & BV_TEXT_HOST) || (rowflag[r] & BV_TEXT_INDEL)) {
+    } else if ((s & BV_TEXT_HOST) || (!heads && (rowflag[r] & BV_TEXT_INDEL))) {  // (heads: bv_engine_text_heads_fetch)
         out = n;
     } else if (f == 0) {  // CHROM \t POS \t REF \t Depth \t
         const char *row = text + row_beg[r];
@@ -482,7 +483,7 @@ int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint
     BV_HIP(e, hipMemsetAsync(t->d_aux, 0, o_off, st));
     BV_HIP(e, hipMemcpyAsync(b->foff, t->h_foff.data(), 4ull * F, hipMemcpyHostToDevice, st));
     BV_HIP(e, hipMemcpyAsync(b->fsamp, file_samples, 4ull * F, hipMemcpyHostToDevice, st));
-    return BV_OK;
+    return bv_text_tokens_begin(e, P, F, st);
 }
 
 int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
@@ -527,6 +528,8 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
         a.depth = depth; a.pstate = pstate; a.pmax = pmax;
         hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
         BV_HIP(e, hipGetLastError());
+        // (the mode of basevar_amd_text_tokens.h: the chunk's indel tokens, while its text is here)
+        if ((rc = bv_text_tokens_rows(e, BvTextTokRows{a.text, a.row_beg, a.row_end, rowflag, foff, base, a.row_first, a.n_rows_chunk, F}, st)) != BV_OK) return rc;
         if ((rc = chunk_stage_done(e, cst, s, st)) != BV_OK) return rc;
         p0 = p1;
     }
@@ -577,6 +580,8 @@ int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t 
     t->has_gid = group_id != nullptr;
     if (group_id) t->group_id.assign(group_id, group_id + n_samples);
     else t->group_id.clear();
+    const int rc = bv_text_tokens_finish(e, t->pos_state.data(), P, F, st);
+    if (rc != BV_OK) return rc;
     t->parsed = true;
     return BV_OK;
 }
@@ -750,6 +755,7 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     t->parsed = false;
     t->bgzf_rows = false;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
+    if ((rc = bv_text_tokens_begin(e, 0, F, st)) != BV_OK) return rc;  // (a call that takes no position leaves no token list either)
     // where every member's text goes: file f's members back to back, one spare byte behind each run (16-byte aligned runs)
     const uint32_t M = mb.n_members;
     std::vector<uint64_t> out_pos(M + 1, 0);
@@ -831,6 +837,8 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     a.depth = pb.depth; a.pstate = pb.pstate; a.pmax = pb.pmax;
     hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
     BV_HIP(e, hipGetLastError());
+    rc = bv_text_tokens_rows(e, BvTextTokRows{text, row_beg, row_end, pb.rowflag, pb.foff, 0, 0, (uint32_t)R, F}, st);
+    if (rc != BV_OK) return rc;
     std::vector<uint64_t> last(F);
     BV_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
     rc = parse_finish(e, t, P, F, (uint32_t)n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
@@ -845,12 +853,15 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     return BV_OK;
 }
 
-int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream_) {
-    const char *who = "bv_engine_text_rows_fetch";
+// bv_engine_text_rows_fetch, and with `heads` bv_engine_text_heads_fetch (include/basevar_amd_text_tokens.h)
+static int text_rows_fetch(bv_engine *e, const char *who, uint32_t heads, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed,
+                           void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
     if (!bytes_needed) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null bytes_needed");
     BvTextState *t = e->text;
     if (!t || !t->bgzf_rows) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": no bv_engine_text_parse_bgzf before it");
+    // (the heads leave the marked rows' tokens behind: only where the engine holds them)
+    if (heads && !bv_text_tokens_stand(e)) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the parse did not list the tokens (bv_engine_text_tokens_enable)");
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     BV_HIP(e, hipSetDevice(t->device));
     const uint32_t P = t->n_pos, F = t->n_files;
@@ -864,7 +875,7 @@ int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uin
     uint32_t *d_len = reinterpret_cast<uint32_t *>(t->d_fetch + o_len);
     BV_HIP(e, hipMemcpyAsync(t->d_fetch, t->pos_state.data(), P, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bv_text_fetch_len_kernel, dim3((uint32_t)((R + 255) / 256)), dim3(256), 0, st, text, row_beg, row_end, (const uint8_t *)t->d_fetch, rowflag,
-                       (uint32_t)R, F, d_len);
+                       (uint32_t)R, F, heads, d_len);
     BV_HIP(e, hipGetLastError());
     std::vector<uint32_t> len(R);
     BV_HIP(e, hipMemcpyAsync(len.data(), d_len, 4 * R, hipMemcpyDeviceToHost, st));
@@ -892,6 +903,14 @@ int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uin
     BV_HIP(e, hipMemcpyAsync(buf, t->d_fetch + o_bytes, off[R], hipMemcpyDeviceToHost, st));
     BV_HIP(e, hipStreamSynchronize(st));
     return BV_OK;
+}
+
+int bv_engine_text_rows_fetch(bv_engine *e, uint8_t *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream_) {
+    return text_rows_fetch(e, "bv_engine_text_rows_fetch", 0u, buf, capacity, row_off, bytes_needed, stream_);
+}
+
+int bv_engine_text_heads_fetch(bv_engine *e, void *buf, uint64_t capacity, uint64_t *row_off, uint64_t *bytes_needed, void *stream_) {
+    return text_rows_fetch(e, "bv_engine_text_heads_fetch", 1u, static_cast<uint8_t *>(buf), capacity, row_off, bytes_needed, stream_);
 }
 
 }  // extern "C"

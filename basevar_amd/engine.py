@@ -361,7 +361,7 @@ class BaseTypeEngine:
         return BaseTypeBatch(out, gout, self.last_variant_count(), ms1, ms2)
 
     # ---- batchfile text rows, parsed on the device
-    def lrt_text(self, rows, file_samples, group_id=None, n_groups=0, host_reader=None):
+    def lrt_text(self, rows, file_samples, group_id=None, n_groups=0, host_reader=None, tokens="host"):
         """The reference's own batchfile rows in, records out (bv_engine_text_parse + bv_engine_text_submit).
 
         `rows`: one list per position of its row in every batchfile (bytes, without the line break), or a packed pair
@@ -371,7 +371,26 @@ class BaseTypeEngine:
         ref_code)` numpy rows of n_samples, or None for a skipped position; without a host_reader such a position raises.
         Returns a TextBatch: the records (one per position not skipped), `positions` (their indices), `row_state`
         [n_positions][n_files] and the returned `cell` / `phred` planes [records][n_samples].  The engine must have been
-        created with max_samples >= sum(file_samples)."""
+        created with max_samples >= sum(file_samples).  `tokens`: "host" (the default) leaves the '+SEQ' / '-SEQ' tokens of the
+        marked rows to the caller; "device" lists them on the device during the parse (text_tokens_enable for this call) and
+        the batch carries `tokens` / `token_text` as text_tokens_fetch returns them."""
+        restore = self._tokens_mode(tokens, "lrt_text")
+        try:
+            return self._lrt_text(rows, file_samples, group_id, n_groups, host_reader, tokens == "device")
+        finally:
+            restore()
+
+    def _tokens_mode(self, tokens, who):
+        """tokens="device": the mode on for one call; returns what puts it back"""
+        if tokens not in ("host", "device"):
+            raise ValueError("%s: tokens is 'host' or 'device'" % who)
+        was = getattr(self, "_text_tokens_on", False)
+        if tokens == "device" and not was:
+            self.text_tokens_enable(True)
+            return lambda: self.text_tokens_enable(False)
+        return lambda: None
+
+    def _lrt_text(self, rows, file_samples, group_id, n_groups, host_reader, device_tokens):
         fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
         F, N = int(fs.size), int(fs.sum())
         if isinstance(rows, tuple):
@@ -394,8 +413,11 @@ class BaseTypeEngine:
                                             state.ctypes.data, None)
         if rc != 0:
             raise RuntimeError("bv_engine_text_parse failed (%d): %s" % (rc, self._err()))
-        return self._text_submit("lrt_text", state, P, F, N, n_groups, host_reader,
-                                 lambda p: [bytes(text[int(off[p * F + f]):int(off[p * F + f + 1]) - 1]) for f in range(F)])
+        batch = self._text_submit("lrt_text", state, P, F, N, n_groups, host_reader,
+                                  lambda p: [bytes(text[int(off[p * F + f]):int(off[p * F + f + 1]) - 1]) for f in range(F)])
+        if device_tokens:
+            batch.tokens, batch.token_text = self.text_tokens_fetch()
+        return batch
 
     def _text_submit(self, what, state, P, F, N, n_groups, host_reader, lines_of):
         """the host positions of a parsed batch through host_reader, then bv_engine_text_submit: a TextBatch"""
@@ -443,14 +465,22 @@ class BaseTypeEngine:
 
     # ---- batchfile rows that are still compressed: inflated, split into lines and parsed on the device
     def lrt_bgzf(self, runs, file_samples, skip_bytes=None, skip_lines=None, max_positions=None, at_end=True, group_id=None, n_groups=0,
-                 host_reader=None):
+                 host_reader=None, tokens="host"):
         """lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf + bv_engine_text_rows_fetch +
         bv_engine_text_submit).  `runs`: per batchfile the list of its consecutive whole members (bytes) from where its next row
         starts; that row begins skip_bytes[f] inflated bytes into the run and skip_lines[f] lines further.  Takes
         min(max_positions, max_sites, the files' complete lines) positions; `at_end`: the runs reach the ends of their files.
         Returns what lrt_text returns plus `cursors` [n_files][2] -- (member of the run, inflated offset inside it) of every
         file's first line not taken -- and `fetched` = (bytes, row_off): the text the host needs (bv_engine_text_rows_fetch).
-        A damaged member raises RuntimeError with `.args[1] == BV_ERR_DATA`."""
+        A damaged member raises RuntimeError with `.args[1] == BV_ERR_DATA`.  `tokens`: as lrt_text's; with "device", `fetched` comes
+        from text_heads_fetch (a marked row is cut like any other) and the batch carries `tokens` / `token_text`."""
+        restore = self._tokens_mode(tokens, "lrt_bgzf")
+        try:
+            return self._lrt_bgzf(runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, tokens == "device")
+        finally:
+            restore()
+
+    def _lrt_bgzf(self, runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, device_tokens):
         fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
         F, N = int(fs.size), int(fs.sum())
         if len(runs) != F:
@@ -480,28 +510,71 @@ class BaseTypeEngine:
             batch = TextBatch(np.zeros(0, _capi.SITE_DTYPE), np.zeros((0, n_groups), _capi.GROUP_DTYPE) if n_groups else None, 0,
                               np.zeros(0, np.uint32), state, np.zeros((0, N), np.uint8), np.zeros((0, N), np.uint8))
             batch.cursors, batch.fetched = cursors, (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
+            if device_tokens:
+                batch.tokens, batch.token_text = np.zeros(0, _capi.PILEUP_TOKEN_DTYPE), np.zeros(0, np.uint8)
             return batch
-        fetched = self.text_rows_fetch(P * F)
+        fetched = self.text_heads_fetch(P * F) if device_tokens else self.text_rows_fetch(P * F)
         buf, roff = fetched
         batch = self._text_submit("lrt_bgzf", state, P, F, N, n_groups, host_reader,
                                   lambda p: [bytes(buf[int(roff[p * F + f]):int(roff[p * F + f + 1])]) for f in range(F)])
         batch.cursors, batch.fetched = cursors, fetched
+        if device_tokens:
+            batch.tokens, batch.token_text = self.text_tokens_fetch()
         return batch
 
     def text_rows_fetch(self, n_rows, capacity=None):
         """(bytes uint8, row_off uint64 [n_rows + 1]) of bv_engine_text_rows_fetch after a parse of n_rows rows; with `capacity`
         below what is needed: (None, bytes needed)"""
+        return self._rows_fetch("bv_engine_text_rows_fetch", n_rows, capacity)
+
+    def text_heads_fetch(self, n_rows, capacity=None):
+        """text_rows_fetch with every BV_TEXT_INDEL row cut like any other parsed row (bv_engine_text_heads_fetch); refused after a
+        parse that listed no tokens (text_tokens_enable), since the marked rows' tokens would be nowhere."""
+        return self._rows_fetch("bv_engine_text_heads_fetch", n_rows, capacity)
+
+    # ---- the '+SEQ' / '-SEQ' tokens of parsed rows, listed on the device (include/basevar_amd_text_tokens.h)
+    def text_tokens_enable(self, on=True):
+        """The mode for this engine's later parses (bv_engine_text_tokens_enable); the default is off."""
+        rc = self._lib.bv_engine_text_tokens_enable(self._h, 1 if on else 0)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_tokens_enable failed (%d): %s" % (rc, self._err()), rc)
+        self._text_tokens_on = bool(on)
+
+    def text_tokens(self):
+        """The last parse's tokens where they lie (bv_engine_text_tokens): ((device pointer, n_tokens), (device pointer,
+        text_bytes)), what indel_tally(key, tokens=..., text=...) takes as device tokens; pos is the position's index."""
+        T = _capi.IndelTokens()
+        rc = self._lib.bv_engine_text_tokens(self._h, C.byref(T))
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_tokens failed (%d): %s" % (rc, self._err()), rc)
+        return (int(T.tokens or 0), int(T.n_tokens)), (int(T.text or 0), int(T.text_bytes))
+
+    def text_tokens_fetch(self):
+        """The last parse's tokens in host memory (bv_engine_text_tokens_fetch): (PILEUP_TOKEN_DTYPE array, uint8 text)."""
+        n, nb = C.c_uint64(0), C.c_uint64(0)
+        rc = self._lib.bv_engine_text_tokens_fetch(self._h, None, 0, None, 0, C.byref(n), C.byref(nb), None)  # no room: the sizes
+        if rc != 0 and not (rc == _capi.BV_ERR_INVALID_ARG and n.value):
+            raise RuntimeError("bv_engine_text_tokens_fetch failed (%d): %s" % (rc, self._err()), rc)
+        tok = np.zeros(int(n.value), dtype=_capi.PILEUP_TOKEN_DTYPE)
+        text = np.zeros(int(nb.value), dtype=np.uint8)
+        if tok.size:
+            rc = self._lib.bv_engine_text_tokens_fetch(self._h, tok.ctypes.data, int(tok.size), text.ctypes.data, int(text.size), C.byref(n), C.byref(nb), None)
+            if rc != 0:
+                raise RuntimeError("bv_engine_text_tokens_fetch failed (%d): %s" % (rc, self._err()), rc)
+        return tok, text
+
+    def _rows_fetch(self, symbol, n_rows, capacity):
         need = C.c_uint64(0)
         roff = np.zeros(int(n_rows) + 1, dtype=np.uint64)
         if capacity is None:
-            rc = self._lib.bv_engine_text_rows_fetch(self._h, None, 0, roff.ctypes.data, C.byref(need), None)
+            rc = getattr(self._lib, symbol)(self._h, None, 0, roff.ctypes.data, C.byref(need), None)
             if rc != 0:
-                raise RuntimeError("bv_engine_text_rows_fetch failed (%d): %s" % (rc, self._err()))
+                raise RuntimeError("%s failed (%d): %s" % (symbol, rc, self._err()))
             capacity = int(need.value)
         buf = np.zeros(max(int(capacity), 1), dtype=np.uint8)
-        rc = self._lib.bv_engine_text_rows_fetch(self._h, buf.ctypes.data, int(capacity), roff.ctypes.data, C.byref(need), None)
+        rc = getattr(self._lib, symbol)(self._h, buf.ctypes.data, int(capacity), roff.ctypes.data, C.byref(need), None)
         if rc != 0:
-            raise RuntimeError("bv_engine_text_rows_fetch failed (%d): %s" % (rc, self._err()))
+            raise RuntimeError("%s failed (%d): %s" % (symbol, rc, self._err()))
         if int(need.value) > int(capacity):
             return None, int(need.value)
         return buf[:int(need.value)], roff

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/basevar_amd_indel.h"
+#include "../../include/basevar_amd_text_tokens.h"
 #include "../../include/basevar_amd_record_text.h"
 #include "../../include/basevar_amd_vcf.h"
 #include "vcf_emit.hpp"  // SiteText
@@ -303,19 +304,51 @@ public:
     // bool(const std::vector<std::string> &rows, size_t n_samples, SlabBuilder &, SiteText &) as parse_site_rows_fast -- in
     // position order.  When that reader throws, the positions before the offending one are delivered and `error` holds its
     // exception (the caller rethrows it after emitting them: BatchfileProducer's order).
+    enum TokenMode { TOKENS_HOST = 0, TOKENS_DEVICE = 1, TOKENS_DEVICE_KEEP = 2 };  // (text_tokens_mode, below)
     struct TextBatch {
         BaseTypeBatch batch;               // one record per position that was not skipped
         std::vector<uint32_t> position;    // ... its index in the batch
         std::vector<SiteText> text;        // ... coordinates, REF and '+'/'-' tokens (the CVG indel column)
         std::vector<uint8_t> cell, phred;  // ... [records][n_samples]: the GT:AB:SO:BP strings of format_vcf_line
         std::vector<uint8_t> row_state;    // [n_positions][n_files] as bv_engine_text_parse reported it (HOST -> SKIP where the host skipped)
+        std::vector<uint8_t> host_read;    // [records]: 1 where the host reader made the record (its tokens are the host reader's)
         uint32_t n_positions_used = 0;
+        TokenMode tokens = TOKENS_HOST;    // who took the '+'/'-' tokens of the device-parsed positions (below)
+        uint64_t tokens_device = 0;        // TOKENS_DEVICE*: the tokens the engine listed for the batch (those of positions behind n_positions_used too)
+        uint64_t fetch_bytes = 0;          // bytes the rows / heads fetch and the token fetch brought back
         std::exception_ptr error;
     };
+    // Who takes the '+SEQ' / '-SEQ' tokens of the device-parsed positions (include/basevar_amd_text_tokens.h):
+    //   TOKENS_HOST         finish_text walks the marked rows on this thread (the default: the path as it was)
+    //   TOKENS_DEVICE       the engine lists them during the parse; SiteText::indel_tokens is filled from one text_tokens_fetch
+    //   TOKENS_DEVICE_KEEP  ... and they stay there for the caller's bv_engine_indel_tally (text_tokens()): indel_tokens of the
+    //                       device-parsed positions stay empty
+    // The tokens of a host-read position are the host reader's in every mode.
+    void text_tokens_mode(TokenMode m) {
+        const bool on = m != TOKENS_HOST;
+        if (on == tokens_on_) return;
+        if (bv_engine_text_tokens_enable(e_, on ? 1 : 0) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        tokens_on_ = on;
+    }
+    bv_indel_tokens text_tokens() {
+        bv_indel_tokens t;
+        if (bv_engine_text_tokens(e_, &t) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        return t;
+    }
+    void text_tokens_fetch(std::vector<bv_pileup_token> &tokens, std::vector<uint8_t> &text) {
+        const bv_indel_tokens t = text_tokens();
+        tokens.resize((size_t)t.n_tokens);
+        text.resize((size_t)t.text_bytes);
+        uint64_t n = 0, nb = 0;
+        if (bv_engine_text_tokens_fetch(e_, tokens.data(), tokens.size(), text.data(), text.size(), &n, &nb, nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(e_));
+    }
     template <class HostReader>
     TextBatch lrt_text(const bv_text_rows &rows, HostReader &&read_host, const uint8_t *group_id = nullptr, uint32_t n_groups = 0,
-                       bool keep_planes = true) {
+                       bool keep_planes = true, TokenMode tokens = TOKENS_HOST) {
         TextBatch tb;
+        tb.tokens = tokens;
+        text_tokens_mode(tokens);
         const size_t F = rows.n_files;
         tb.row_state.resize((size_t)rows.n_positions * F);
         if (bv_engine_text_parse(e_, &rows, group_id, n_groups, tb.row_state.data(), nullptr) != BV_OK)
@@ -418,9 +451,13 @@ public:
         uint32_t n_positions = 0;
         std::vector<uint8_t> row_state;
         std::vector<bv_bgzf_cursor> cursor;
+        TokenMode tokens = TOKENS_HOST;
     };
-    BgzfParse parse_bgzf(const bv_bgzf_rows &rows, uint32_t max_sites, const uint8_t *group_id = nullptr, uint32_t n_groups = 0) {
+    BgzfParse parse_bgzf(const bv_bgzf_rows &rows, uint32_t max_sites, const uint8_t *group_id = nullptr, uint32_t n_groups = 0,
+                         TokenMode tokens = TOKENS_HOST) {
         BgzfParse bp;
+        bp.tokens = tokens;
+        text_tokens_mode(tokens);
         bp.row_state.resize((size_t)std::max<uint32_t>(1, std::min(rows.max_positions, max_sites)) * rows.n_files);
         bp.cursor.resize(rows.n_files);
         const int rc = bv_engine_text_parse_bgzf(e_, &rows, group_id, n_groups, &bp.n_positions, bp.row_state.data(), bp.cursor.data(), nullptr);
@@ -433,6 +470,7 @@ public:
     TextBatch finish_bgzf(BgzfParse &bp, const uint32_t *file_samples, size_t F, HostReader &&read_host, uint32_t n_groups = 0,
                           bool keep_planes = true) {
         TextBatch tb;
+        tb.tokens = bp.tokens;
         tb.row_state.swap(bp.row_state);
         uint32_t N = 0;
         for (size_t f = 0; f < F; ++f) N += file_samples[f];
@@ -440,9 +478,15 @@ public:
         std::vector<uint64_t> off(R + 1);
         std::vector<uint8_t> buf;
         uint64_t need = 0;
-        if (bv_engine_text_rows_fetch(e_, nullptr, 0, off.data(), &need, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        // (the tokens listed on the device: a marked row is needed no further than any other)
+        auto fetch = [&](uint8_t *dst, uint64_t cap) {
+            return tb.tokens == TOKENS_HOST ? bv_engine_text_rows_fetch(e_, dst, cap, off.data(), &need, nullptr)
+                                            : bv_engine_text_heads_fetch(e_, dst, cap, off.data(), &need, nullptr);
+        };
+        if (fetch(nullptr, 0) != BV_OK) throw std::runtime_error(bv_last_error(e_));
         buf.resize((size_t)need + 1);
-        if (bv_engine_text_rows_fetch(e_, buf.data(), need, off.data(), &need, nullptr) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        if (fetch(buf.data(), need) != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        tb.fetch_bytes += need;
         const char *text = reinterpret_cast<const char *>(buf.data());
         finish_text(tb, bp.n_positions, F, N,
                     [&](size_t p, size_t f) { return std::string(text + off[p * F + f], (size_t)(off[p * F + f + 1] - off[p * F + f])); },
@@ -464,7 +508,8 @@ public:
             uint8_t *rs = &tb.row_state[(size_t)used * F];
             if (rs[0] & BV_TEXT_SKIP) continue;
             SiteText st;
-            if (rs[0] & BV_TEXT_HOST) {
+            const bool host_read = (rs[0] & BV_TEXT_HOST) != 0;
+            if (host_read) {
                 for (size_t f = 0; f < F; ++f) lines[f] = row_text(used, f);
                 bool kept = false;
                 try { kept = read_host(lines, (size_t)N, host, st); }
@@ -477,7 +522,7 @@ public:
                 st.ref_id = r0.substr(0, t1);
                 st.ref_pos = (uint32_t)std::stoi(r0.substr(t1 + 1, t2 - t1 - 1));
                 st.ref_base = r0.substr(t2 + 1, t3 - t2 - 1);
-                for (size_t f = 0; f < F; ++f) {
+                for (size_t f = 0; f < F && tb.tokens == TOKENS_HOST; ++f) {
                     if (!(rs[f] & BV_TEXT_INDEL)) continue;
                     const char *p = row_ptr(used, f);
                     for (int k = 0; k < 5; ++k) { while (*p != '\t') ++p; ++p; }  // to Readbases (a parsed row has its 8 tabs)
@@ -491,9 +536,27 @@ public:
                 }
             }
             tb.position.push_back(used);
+            tb.host_read.push_back(host_read ? 1 : 0);
             tb.text.push_back(std::move(st));
         }
         tb.n_positions_used = used;
+        if (tb.tokens != TOKENS_HOST) {
+            // the list is in position order, as tb.position is: one pass hands every token to its record (the tokens of a
+            // position behind the one the host reader stopped at belong to no record)
+            tb.tokens_device = text_tokens().n_tokens;
+            if (tb.tokens == TOKENS_DEVICE && tb.tokens_device) {
+                std::vector<bv_pileup_token> tok;
+                std::vector<uint8_t> text;
+                text_tokens_fetch(tok, text);
+                tb.fetch_bytes += sizeof(bv_pileup_token) * tok.size() + text.size();
+                size_t i = 0;
+                for (const bv_pileup_token &t : tok) {
+                    while (i < tb.position.size() && tb.position[i] < t.pos) ++i;
+                    if (i == tb.position.size()) break;
+                    if (tb.position[i] == t.pos) tb.text[i].indel_tokens.emplace_back(reinterpret_cast<const char *>(text.data()) + t.text_off, t.text_len);
+                }
+            }
+        }
         const size_t R = tb.position.size();
         tb.batch.sites.resize(R);
         tb.batch.n_groups = n_groups;
@@ -512,6 +575,7 @@ public:
 
 private:
     bv_engine *e_ = nullptr;
+    bool tokens_on_ = false;
 };
 
 }  // namespace bvamd

@@ -47,7 +47,7 @@ using bvamd::StageClock;
 struct Options {
     std::vector<std::string> batchfiles, bams;
     std::string out_vcf, out_cvg, pop_group_file, reference = ".", regions, bam_list, devices_arg, timing_file, inflate = "host", deflate = "host",
-                deflate_level = "fast", emit = "host", pileup = "host";
+                deflate_level = "fast", emit = "host", pileup = "host", indel_tokens = "host";
     int mapq_thd = 10, threads = 4, n_gpus = 1, device = 0;  // (`-t`: 4, the reference's default, src/basetype_utils.h:33,94)
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
@@ -75,6 +75,7 @@ Options parse_options(int argc, char **argv) {
         else if (a == "--deflate-level") o.deflate_level = next();
         else if (a == "--emit") o.emit = next();
         else if (a == "--pileup") o.pileup = next();
+        else if (a == "--indel-tokens") o.indel_tokens = next();
         else if (a == "--device") o.device = std::stoi(next());
         else if (a == "--gpus") o.n_gpus = std::stoi(next());
         else if (a == "--devices") o.devices_arg = next();
@@ -102,6 +103,7 @@ void validate(Options &o) {
     if (o.deflate_level != "fast" && o.deflate_level != "small") die("[ERROR] --deflate-level wants fast or small");
     if (o.emit != "host" && o.emit != "device") die("[ERROR] --emit wants device or host");
     if (o.pileup != "host" && o.pileup != "device") die("[ERROR] --pileup wants device or host");
+    if (o.indel_tokens != "host" && o.indel_tokens != "device") die("[ERROR] --indel-tokens wants device or host");
     // (the host path is zlib at its own level: the device encoder's levels do not apply to it)
     if (o.deflate_level != "fast" && o.deflate != "device") die("[ERROR] --deflate-level small needs --deflate device");
     // one engine per entry: --devices a,b,... (an ordinal may repeat: several engines on one GPU), else device, device+1, ...
@@ -211,6 +213,12 @@ bvamd::Routes resolve_routes(const Options &o, const bvamd::BatchfileHeaders &he
         std::cerr << "[NOTE] --emit device on BAM input needs --pileup device (on one engine): the host path is taken" << std::endl;
         r.emit_device = false;
     }
+    // --indel-tokens device: the '+SEQ' / '-SEQ' tokens of batchfile rows are listed on the engine that parses the rows
+    // (bv_engine_text_tokens_enable); the mode is the engine's own, so every worker has it
+    if (o.indel_tokens == "device") {
+        if (from_bam) std::cerr << "[NOTE] --indel-tokens device applies to batchfile input: on BAM input the pileup's tokens are on the device already" << std::endl;
+        else r.indel_tokens_device = true;
+    }
     // --pileup device --inflate device: the host threads inflate nothing either
     if (from_bam && o.pileup == "device" && o.inflate == "device") {
         r.bam_inflate_device = r.device_pileup;
@@ -259,6 +267,10 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
         tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << emitter.vcf_lines_device() << ", \"cvg_lines_device\": " << emitter.cvg_lines_device()
            << ", \"lines_host_formatted\": " << emitter.lines_host_formatted() << ", \"indel_columns_device\": " << emitter.indel_columns_device()
            << ", \"indel_columns_host\": " << emitter.indel_columns_host();
+    // batchfile input: the bytes the workers' row (or head) fetches and token fetches brought back from their engines; with
+    // --indel-tokens device, the tokens the engines listed
+    if (!ctx.from_bam) tf << ", \"text_fetch_bytes\": " << emitter.text_fetch_bytes();
+    if (ctx.routes.indel_tokens_device) tf << ", \"indel_tokens\": \"device\", \"indel_tokens_device\": " << emitter.indel_tokens_device();
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
     // ... --inflate device with it: the BAM files' compressed members handed to the engine instead, and their bytes

@@ -66,6 +66,12 @@ struct Batch {
     uint64_t cvg_lines_device = 0, lines_host_formatted = 0;
     uint64_t indel_columns_device = 0;  // of the rows the device wrote: those whose indel column, not ".", it tallied too
     uint64_t indel_columns_host = 0;    // of the rows the host formatted: those whose indel column is not "."
+    // batchfile input: the records' positions in the batch and who read them (TextBatch::position, ::host_read), who took the
+    // device-parsed positions' tokens, how many the engine listed, and the bytes its row and token fetches brought back
+    std::vector<uint32_t> position;
+    std::vector<uint8_t> host_read;
+    BaseTypeEngine::TokenMode tokens = BaseTypeEngine::TOKENS_HOST;
+    uint64_t indel_tokens_device = 0, text_fetch_bytes = 0;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -150,6 +156,7 @@ struct Routes {
     bool emit_device = false;         // --emit device: the VCF lines and the CVG rows are written on the worker's / the pileup's engine
     bool device_pileup = false;       // --pileup device: produce_bam_device
     bool bam_inflate_device = false;  // ... with --inflate device: the BAM files' members reach the engine compressed
+    bool indel_tokens_device = false; // --indel-tokens device: the engine lists the '+'/'-' tokens of batchfile rows (text_tokens_mode)
 };
 
 // What every stage reads and none writes: built once before any thread starts, passed as const &
@@ -234,6 +241,8 @@ public:
     uint64_t lines_host_formatted() const { return lines_host_formatted_; }
     uint64_t indel_columns_device() const { return indel_columns_device_; }
     uint64_t indel_columns_host() const { return indel_columns_host_; }
+    uint64_t indel_tokens_device() const { return indel_tokens_device_; }
+    uint64_t text_fetch_bytes() const { return text_fetch_bytes_; }
     uint64_t members_deflated() const { return members_deflated_; }
     double deflate_s() const { return deflate_s_; }
 
@@ -277,6 +286,8 @@ private:
             for (size_t t = 0; t < nt; ++t) n_variants_ += nv[t];
         } catch (const std::exception &ex) { errors_.fail(ex.what()); }
         n_sites_ += d.text.size();
+        indel_tokens_device_ += d.indel_tokens_device;
+        text_fetch_bytes_ += d.text_fetch_bytes;
         clk_.add(StageClock::EMIT, StageClock::now() - t0);
     }
     // --emit device: the VCF lines as the worker's engine left them
@@ -306,7 +317,8 @@ private:
     uint64_t next_seq_ = 0;
     bool stopped_ = false;  // a batch failed: nothing behind it is written
     size_t n_sites_ = 0, n_variants_ = 0;
-    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, indel_columns_device_ = 0, indel_columns_host_ = 0, members_deflated_ = 0;
+    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, indel_columns_device_ = 0, indel_columns_host_ = 0, members_deflated_ = 0,
+             indel_tokens_device_ = 0, text_fetch_bytes_ = 0;
     double deflate_s_ = 0;
 };
 
@@ -323,6 +335,14 @@ inline BlockDeflater device_block_deflater(const CallContext &ctx) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- the engine workers
+
+// --indel-tokens device: who takes the tokens of a batch of batchfile rows -- listed on the worker's engine and left there for
+// its tally (--emit device), or fetched once into the SiteTexts (--emit host)
+inline BaseTypeEngine::TokenMode text_token_mode(const CallContext &ctx) {
+    return !ctx.routes.indel_tokens_device ? BaseTypeEngine::TOKENS_HOST
+           : ctx.routes.emit_device        ? BaseTypeEngine::TOKENS_DEVICE_KEEP
+                                           : BaseTypeEngine::TOKENS_DEVICE;
+}
 
 // --inflate device: BGZF batchfiles go to the engine compressed (bv_engine_text_parse_bgzf inflates, finds the lines and
 // parses).  There is no producer then: the engine workers take turns at the raw reader -- a worker reads the next runs from the
@@ -346,7 +366,7 @@ public:
                 const bv_bgzf_rows rows{runs.data.data(), runs.member_off.data(), runs.data.size(), runs.file_member.data(), ctx_.file_samples.data(),
                                         runs.skip_bytes.data(), runs.skip_lines.data(), (uint32_t)ctx_.file_samples.size(), ctx_.batch_sites,
                                         runs.at_end ? 1u : 0u, 0};
-                bp = engine.parse_bgzf(rows, ctx_.batch_sites, ctx_.group_ids(), ctx_.n_groups());
+                bp = engine.parse_bgzf(rows, ctx_.batch_sites, ctx_.group_ids(), ctx_.n_groups(), text_token_mode(ctx_));
                 clk.add(StageClock::READ, t1 - t0);
                 clk.add(StageClock::ENGINE, StageClock::now() - t1);
             } catch (const BaseTypeEngine::BgzfDataError &ex) {
@@ -417,8 +437,29 @@ inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engin
     // the indel tallies on the engine
     std::vector<uint8_t> flagged;
     std::vector<uint64_t> col_off;
+    // --indel-tokens device: the tokens of the device-parsed positions lie on this engine since its parse, keyed by the
+    // position's index in the batch; a flagged row's come over with one fetch, made when the first such row asks
+    const bool listed = !pileup_tokens && b.tokens == BaseTypeEngine::TOKENS_DEVICE_KEEP;
+    std::vector<bv_pileup_token> listed_tok;
+    std::vector<uint8_t> listed_text;
+    bool listed_fetched = false;
+    auto listed_tokens = [&](size_t i) {
+        if (!listed_fetched) {
+            engine.text_tokens_fetch(listed_tok, listed_text);
+            b.text_fetch_bytes += sizeof(bv_pileup_token) * listed_tok.size() + listed_text.size();
+            listed_fetched = true;
+        }
+        std::vector<std::string> out;
+        auto it = std::lower_bound(listed_tok.begin(), listed_tok.end(), b.position[i], [](const bv_pileup_token &t, uint32_t p) { return t.pos < p; });
+        for (; it != listed_tok.end() && it->pos == b.position[i]; ++it)
+            out.emplace_back(reinterpret_cast<const char *>(listed_text.data()) + it->text_off, it->text_len);
+        return out;
+    };
     if (pileup_tokens) {
         col_off = engine.indel_tally(nullptr, pos, flagged);
+    } else if (listed) {
+        const bv_indel_tokens tok = engine.text_tokens();
+        col_off = engine.indel_tally(&tok, b.position, flagged);
     } else {
         // (a row of 10,000 samples brings hundreds of tokens: the descriptors are laid out on the run's host threads)
         std::vector<uint32_t> key(n);
@@ -458,7 +499,8 @@ inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engin
     // the columns of the rows the host formats: the tally's, fetched once if there is such a row
     std::string columns;
     auto host_column = [&](size_t i) {
-        if (flagged[i]) return indel_string(pileup_tokens ? (*pileup_tokens)(pos[i]) : b.text[i].indel_tokens);
+        if (listed && b.host_read[i]) return indel_string(b.text[i].indel_tokens);  // (the host reader's: the list never holds them)
+        if (flagged[i]) return indel_string(pileup_tokens ? (*pileup_tokens)(pos[i]) : listed ? listed_tokens(i) : b.text[i].indel_tokens);
         if (col_off[i + 1] == col_off[i]) return std::string();
         if (columns.empty()) { columns.resize(col_off[n]); engine.indel_fetch(&columns[0], col_off[n]); }
         return columns.substr(col_off[i], col_off[i + 1] - col_off[i]);
@@ -470,7 +512,8 @@ inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engin
         if (st.ref_base.size() == 1) ref[i] = st.ref_base[0];
         const bool on_device = fits[i] != 0;
         if (!on_device) ++b.lines_host_formatted;
-        if (!on_device || flagged[i]) {
+        const bool host_tokens = listed && b.host_read[i] && !st.indel_tokens.empty();  // a host-read row with tokens: host text, as a flagged row
+        if (!on_device || flagged[i] || host_tokens) {
             const std::string column = host_column(i), row = format_cvg_line(st, r, column);
             if (!row.empty() && !column.empty() && column != ".") ++b.indel_columns_host;
             cvg_host += row;
@@ -582,7 +625,7 @@ private:
     void call_text_rows(Batch &b) {
         text_batch(b, [&]() {
             const bv_text_rows rows{b.rows.data(), b.row_off.data(), ctx_.file_samples.data(), b.rows.size(), b.n_positions, (uint32_t)ctx_.file_samples.size(), 0};
-            return engine_->lrt_text(rows, host_reader, ctx_.group_ids(), ctx_.n_groups(), !ctx_.routes.emit_device);
+            return engine_->lrt_text(rows, host_reader, ctx_.group_ids(), ctx_.n_groups(), !ctx_.routes.emit_device, text_token_mode(ctx_));
         });
         std::string().swap(b.rows);
     }
@@ -601,6 +644,11 @@ private:
         b.text = std::move(tb.text);
         b.cell = std::move(tb.cell);
         b.phred = std::move(tb.phred);
+        b.position = std::move(tb.position);
+        b.host_read = std::move(tb.host_read);
+        b.tokens = tb.tokens;
+        b.indel_tokens_device = tb.tokens_device;
+        b.text_fetch_bytes = tb.fetch_bytes;
         if (ctx_.routes.emit_device) emit_records_on_device(ctx_, *engine_, b, nullptr, 0);  // (over the rows the text submit kept)
         if (tb.error) {
             try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b.error = ex.what(); }
