@@ -27,6 +27,7 @@
 #include "../../include/basevar_amd_text_tokens.h"
 #include "../../include/basevar_amd_record_text.h"
 #include "../../include/basevar_amd_vcf.h"
+#include "indel_tokens.hpp"  // TokenList, row_indel_tokens
 #include "vcf_emit.hpp"  // SiteText
 
 namespace bvamd {
@@ -522,18 +523,8 @@ public:
                 st.ref_id = r0.substr(0, t1);
                 st.ref_pos = (uint32_t)std::stoi(r0.substr(t1 + 1, t2 - t1 - 1));
                 st.ref_base = r0.substr(t2 + 1, t3 - t2 - 1);
-                for (size_t f = 0; f < F && tb.tokens == TOKENS_HOST; ++f) {
-                    if (!(rs[f] & BV_TEXT_INDEL)) continue;
-                    const char *p = row_ptr(used, f);
-                    for (int k = 0; k < 5; ++k) { while (*p != '\t') ++p; ++p; }  // to Readbases (a parsed row has its 8 tabs)
-                    for (;;) {
-                        const char *q = p;
-                        while (*q != ' ' && *q != '\t') ++q;
-                        if (*p == '+' || *p == '-') st.indel_tokens.emplace_back(p, (size_t)(q - p));
-                        if (*q == '\t') break;
-                        p = q + 1;
-                    }
-                }
+                for (size_t f = 0; f < F && tb.tokens == TOKENS_HOST; ++f)
+                    if (rs[f] & BV_TEXT_INDEL) row_indel_tokens(row_ptr(used, f), st.indel_tokens);
             }
             tb.position.push_back(used);
             tb.host_read.push_back(host_read ? 1 : 0);
@@ -545,16 +536,11 @@ public:
             // position behind the one the host reader stopped at belong to no record)
             tb.tokens_device = text_tokens().n_tokens;
             if (tb.tokens == TOKENS_DEVICE && tb.tokens_device) {
-                std::vector<bv_pileup_token> tok;
-                std::vector<uint8_t> text;
-                text_tokens_fetch(tok, text);
-                tb.fetch_bytes += sizeof(bv_pileup_token) * tok.size() + text.size();
-                size_t i = 0;
-                for (const bv_pileup_token &t : tok) {
-                    while (i < tb.position.size() && tb.position[i] < t.pos) ++i;
-                    if (i == tb.position.size()) break;
-                    if (tb.position[i] == t.pos) tb.text[i].indel_tokens.emplace_back(reinterpret_cast<const char *>(text.data()) + t.text_off, t.text_len);
-                }
+                TokenList list;
+                text_tokens_fetch(list.tokens, list.text);
+                tb.fetch_bytes += list.bytes();
+                size_t cursor = 0;
+                list.deal(tb.position.data(), tb.position.size(), tb.text.data(), cursor);
             }
         }
         const size_t R = tb.position.size();

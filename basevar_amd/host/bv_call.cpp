@@ -207,7 +207,7 @@ bvamd::Routes resolve_routes(const Options &o, const bvamd::BatchfileHeaders &he
         else if (G > 1) std::cerr << "[NOTE] --pileup device runs on one engine (--gpus 1): the host path is taken" << std::endl;
         else r.device_pileup = true;
     }
-    // --emit device (emit_records_on_device): batches of batchfile rows parsed on the device, and BAM input piled up there
+    // --emit device (device_emit.hpp: emit_records_on_device): batches of batchfile rows parsed on the device, and BAM input piled up there
     r.emit_device = o.emit == "device";
     if (r.emit_device && from_bam && !r.device_pileup) {
         std::cerr << "[NOTE] --emit device on BAM input needs --pileup device (on one engine): the host path is taken" << std::endl;
@@ -238,6 +238,7 @@ bvamd::Routes resolve_routes(const Options &o, const bvamd::BatchfileHeaders &he
 void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, double total, const StageClock &clk, const bvamd::OrderedEmitter &emitter,
             const bvamd::BgzfRawReader &raw, const bvamd::DevicePileupProducer::Stats &pileup) {
     const size_t n_sites = emitter.n_sites(), G = ctx.devices.size();
+    const bvamd::EmitCounts &counts = emitter.counts();
     const double read_s = clk.get(StageClock::READ), parse_s = clk.get(StageClock::PARSE), engine_s = clk.get(StageClock::ENGINE), emit_s = clk.get(StageClock::EMIT);
     std::cout << "[INFO] bv_call: " << n_sites << " covered positions, " << emitter.n_variants() << " VCF records, " << ctx.n_sample()
               << " samples, " << ctx.group_names.size() << " groups, " << G << " engine(s)" << std::endl;
@@ -264,13 +265,13 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
     // device's formats do not cover: a NaN AF); and the rows whose indel column is not ".", by who wrote the row (the
     // device's own are tallied there too)
     if (ctx.routes.emit_device)
-        tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << emitter.vcf_lines_device() << ", \"cvg_lines_device\": " << emitter.cvg_lines_device()
-           << ", \"lines_host_formatted\": " << emitter.lines_host_formatted() << ", \"indel_columns_device\": " << emitter.indel_columns_device()
-           << ", \"indel_columns_host\": " << emitter.indel_columns_host();
+        tf << ", \"emit\": \"device\", \"vcf_lines_device\": " << counts.vcf_lines_device << ", \"cvg_lines_device\": " << counts.cvg_lines_device
+           << ", \"lines_host_formatted\": " << counts.lines_host_formatted << ", \"indel_columns_device\": " << counts.indel_columns_device
+           << ", \"indel_columns_host\": " << counts.indel_columns_host;
     // batchfile input: the bytes the workers' row (or head) fetches and token fetches brought back from their engines; with
     // --indel-tokens device, the tokens the engines listed
-    if (!ctx.from_bam) tf << ", \"text_fetch_bytes\": " << emitter.text_fetch_bytes();
-    if (ctx.routes.indel_tokens_device) tf << ", \"indel_tokens\": \"device\", \"indel_tokens_device\": " << emitter.indel_tokens_device();
+    if (!ctx.from_bam) tf << ", \"text_fetch_bytes\": " << counts.text_fetch_bytes;
+    if (ctx.routes.indel_tokens_device) tf << ", \"indel_tokens\": \"device\", \"indel_tokens_device\": " << counts.indel_tokens_device;
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
     // ... --inflate device with it: the BAM files' compressed members handed to the engine instead, and their bytes

@@ -12,6 +12,8 @@
 // An engine worker (EngineWorker: a thread, an engine on one GPU) shares with the emitter the to_emit queue and nothing else; all
 // stages share the CallContext (immutable), the StageClock and the ErrorSink (a mutex of their own each).  The emitter
 // (OrderedEmitter: a thread) alone writes the outputs and counts sites, VCF records and device-written lines.
+// --emit device (the lines written on the worker's / the pileup's engine) is device_emit.hpp; the host's lists of indel tokens
+// and parallel_ranges are indel_tokens.hpp.
 #pragma once
 
 #include <algorithm>
@@ -32,10 +34,28 @@
 #include "batch_producer.hpp"
 #include "bgzf_tabix.hpp"
 #include "device_pileup.hpp"
+#include "indel_tokens.hpp"
 #include "pileup.hpp"
 #include "vcf_emit.hpp"
 
 namespace bvamd {
+
+// What --timing says of the lines and tokens of a batch, summed by the emitter over the batches it wrote
+struct EmitCounts {
+    // --emit device: VCF lines and CVG rows the device wrote, and records that the host formatted because the device's number
+    // formats do not cover them
+    uint64_t vcf_lines_device = 0, cvg_lines_device = 0, lines_host_formatted = 0;
+    uint64_t indel_columns_device = 0;  // of the rows the device wrote: those whose indel column, not ".", it tallied too
+    uint64_t indel_columns_host = 0;    // of the rows the host formatted: those whose indel column is not "."
+    // batchfile input: the tokens the engine listed, and the bytes its row and token fetches brought back
+    uint64_t indel_tokens_device = 0, text_fetch_bytes = 0;
+    EmitCounts &operator+=(const EmitCounts &o) {
+        vcf_lines_device += o.vcf_lines_device; cvg_lines_device += o.cvg_lines_device; lines_host_formatted += o.lines_host_formatted;
+        indel_columns_device += o.indel_columns_device; indel_columns_host += o.indel_columns_host;
+        indel_tokens_device += o.indel_tokens_device; text_fetch_bytes += o.text_fetch_bytes;
+        return *this;
+    }
+};
 
 // One batch of consecutive sites on its way through the pipeline.
 struct Batch {
@@ -59,19 +79,15 @@ struct Batch {
     std::vector<uint64_t> vcf_line_off, vcf_member_off;
     std::vector<uint8_t> vcf_members;
     std::string vcf_text;
-    // ... and its CVG rows there too (bv_engine_cvg_format): the batch's rows back to back; rows the device wrote, and records
-    // that the host formatted because the device's number formats do not cover them
+    // ... and its CVG rows there too (bv_engine_cvg_format): the batch's rows back to back
     bool cvg_device = false;
     std::string cvg_text;
-    uint64_t cvg_lines_device = 0, lines_host_formatted = 0;
-    uint64_t indel_columns_device = 0;  // of the rows the device wrote: those whose indel column, not ".", it tallied too
-    uint64_t indel_columns_host = 0;    // of the rows the host formatted: those whose indel column is not "."
-    // batchfile input: the records' positions in the batch and who read them (TextBatch::position, ::host_read), who took the
-    // device-parsed positions' tokens, how many the engine listed, and the bytes its row and token fetches brought back
+    EmitCounts counts;
+    // batchfile input: the records' positions in the batch and who read them (TextBatch::position, ::host_read), and who took
+    // the device-parsed positions' tokens
     std::vector<uint32_t> position;
     std::vector<uint8_t> host_read;
     BaseTypeEngine::TokenMode tokens = BaseTypeEngine::TOKENS_HOST;
-    uint64_t indel_tokens_device = 0, text_fetch_bytes = 0;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -132,22 +148,6 @@ private:
     mutable std::mutex mu_;
     std::string first_;
 };
-
-// fn(t, lo, hi) over [0, n) on up to `threads` threads (contiguous ranges; the caller's thread takes the first)
-// An exception in any range (a malformed row, bad_alloc under large batches) is caught on its thread and the first one rethrown
-// on the caller's thread once all ranges are done -- the tool's "[ERROR] ..." exit path, not std::terminate.
-template <typename Fn>
-void parallel_ranges(size_t n, int threads, Fn fn) {
-    const size_t nt = std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, threads), n));
-    if (nt <= 1) { fn(0, 0, n); return; }
-    std::vector<std::thread> pool;
-    std::vector<std::exception_ptr> errs(nt);
-    for (size_t t = 1; t < nt; ++t)
-        pool.emplace_back([&, t]() { try { fn(t, n * t / nt, n * (t + 1) / nt); } catch (...) { errs[t] = std::current_exception(); } });
-    try { fn(0, 0, n / nt); } catch (...) { errs[0] = std::current_exception(); }
-    for (auto &th : pool) th.join();
-    for (auto &e : errs) if (e) std::rethrow_exception(e);
-}
 
 // Which way each stage goes, resolved from the options and the inputs before any thread starts (bv_call.cpp: resolve_routes)
 struct Routes {
@@ -236,13 +236,7 @@ public:
     // (for the thread that joined the emitter's)
     size_t n_sites() const { return n_sites_; }
     size_t n_variants() const { return n_variants_; }
-    uint64_t vcf_lines_device() const { return vcf_lines_device_; }
-    uint64_t cvg_lines_device() const { return cvg_lines_device_; }
-    uint64_t lines_host_formatted() const { return lines_host_formatted_; }
-    uint64_t indel_columns_device() const { return indel_columns_device_; }
-    uint64_t indel_columns_host() const { return indel_columns_host_; }
-    uint64_t indel_tokens_device() const { return indel_tokens_device_; }
-    uint64_t text_fetch_bytes() const { return text_fetch_bytes_; }
+    const EmitCounts &counts() const { return counts_; }
     uint64_t members_deflated() const { return members_deflated_; }
     double deflate_s() const { return deflate_s_; }
 
@@ -286,8 +280,7 @@ private:
             for (size_t t = 0; t < nt; ++t) n_variants_ += nv[t];
         } catch (const std::exception &ex) { errors_.fail(ex.what()); }
         n_sites_ += d.text.size();
-        indel_tokens_device_ += d.indel_tokens_device;
-        text_fetch_bytes_ += d.text_fetch_bytes;
+        counts_ += d.counts;
         clk_.add(StageClock::EMIT, StageClock::now() - t0);
     }
     // --emit device: the VCF lines as the worker's engine left them
@@ -301,11 +294,6 @@ private:
             vcf_.write_lines(d.vcf_text);
         }
         for (size_t i = 0; i < d.text.size(); ++i) n_variant += d.result.has_variant(i) ? 1 : 0;
-        vcf_lines_device_ += d.vcf_record.size();
-        cvg_lines_device_ += d.cvg_lines_device;
-        lines_host_formatted_ += d.lines_host_formatted;
-        indel_columns_device_ += d.indel_columns_device;
-        indel_columns_host_ += d.indel_columns_host;
     }
 
     const CallContext &ctx_;
@@ -317,8 +305,8 @@ private:
     uint64_t next_seq_ = 0;
     bool stopped_ = false;  // a batch failed: nothing behind it is written
     size_t n_sites_ = 0, n_variants_ = 0;
-    uint64_t vcf_lines_device_ = 0, cvg_lines_device_ = 0, lines_host_formatted_ = 0, indel_columns_device_ = 0, indel_columns_host_ = 0, members_deflated_ = 0,
-             indel_tokens_device_ = 0, text_fetch_bytes_ = 0;
+    EmitCounts counts_;
+    uint64_t members_deflated_ = 0;
     double deflate_s_ = 0;
 };
 
@@ -335,6 +323,10 @@ inline BlockDeflater device_block_deflater(const CallContext &ctx) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- the engine workers
+
+}  // namespace bvamd
+#include "device_emit.hpp"  // (behind Batch and CallContext)
+namespace bvamd {
 
 // --indel-tokens device: who takes the tokens of a batch of batchfile rows -- listed on the worker's engine and left there for
 // its tally (--emit device), or fetched once into the SiteTexts (--emit host)
@@ -404,179 +396,6 @@ private:
 };
 
 // One worker thread: an engine on devices[w % G], batches from `in` (or from its turns at the raw reader) to `out`
-// --emit device: the VCF lines of the batch's variant records and its CVG rows, written on `engine` from the records
-// (bv_engine_vcf_format_records, bv_engine_cvg_format_tallied) over the rows that lie there -- row first_row + i of `slab` for
-// record i, or, with slab == nullptr, the rows the engine's text submit kept.  The rows' indel columns are tallied there too
-// (bv_engine_indel_tally): from the tokens of the engine's last pileup where they lie, keyed by position (`pileup_tokens`: how
-// to get one position's tokens to the host after all), or from the SiteTexts' tokens, handed over as host descriptors keyed by
-// the row's index in the batch.  The few records whose numbers the device does not format (BaseTypeEngine::
-// record_text_on_device: a NaN AF), or whose place is not the batch's first CHROM and one REF character, or whose row the
-// tally left to the caller, are formatted here and go in as host text, with the tally's column where it made one.  The VCF
-// text comes back as BGZF members deflated there too (a *.vcf.gz, at --deflate-level) or as it is; the CVG text as it is.
-typedef std::function<std::vector<std::string>(uint32_t pos)> PileupRowTokens;
-inline void emit_records_on_device(const CallContext &ctx, BaseTypeEngine &engine, Batch &b, const bv_slab *slab, uint32_t first_row,
-                                   const PileupRowTokens *pileup_tokens = nullptr) {
-    b.emit_device = true;
-    const size_t n = b.text.size();
-    if (n == 0) return;
-    const uint32_t G = ctx.n_groups();
-    const std::string &chrom = b.text[0].ref_id;
-    std::string names;
-    std::vector<uint32_t> name_off(1, 0);
-    for (const std::string &g : ctx.group_names) { names += g; name_off.push_back((uint32_t)names.size()); }
-    bool names_fit = !chrom.empty() && chrom.size() <= BV_RECORD_TEXT_NAME_MAX;
-    for (const std::string &g : ctx.group_names) names_fit = names_fit && g.size() <= BV_RECORD_TEXT_NAME_MAX;
-    std::vector<uint32_t> pos(n), site;
-    std::string ref(n, 'N'), cvg_host, vcf_host;
-    std::vector<uint64_t> cvg_host_off(1, 0), vcf_host_off(1, 0);
-    std::vector<bv_site_result> vrec;
-    std::vector<bv_group_result> vgrp;
-    std::vector<uint32_t> vpos, vidx;
-    std::string vref;
-    for (size_t i = 0; i < n; ++i) pos[i] = b.text[i].ref_pos;
-    // the indel tallies on the engine
-    std::vector<uint8_t> flagged;
-    std::vector<uint64_t> col_off;
-    // --indel-tokens device: the tokens of the device-parsed positions lie on this engine since its parse, keyed by the
-    // position's index in the batch; a flagged row's come over with one fetch, made when the first such row asks
-    const bool listed = !pileup_tokens && b.tokens == BaseTypeEngine::TOKENS_DEVICE_KEEP;
-    std::vector<bv_pileup_token> listed_tok;
-    std::vector<uint8_t> listed_text;
-    bool listed_fetched = false;
-    auto listed_tokens = [&](size_t i) {
-        if (!listed_fetched) {
-            engine.text_tokens_fetch(listed_tok, listed_text);
-            b.text_fetch_bytes += sizeof(bv_pileup_token) * listed_tok.size() + listed_text.size();
-            listed_fetched = true;
-        }
-        std::vector<std::string> out;
-        auto it = std::lower_bound(listed_tok.begin(), listed_tok.end(), b.position[i], [](const bv_pileup_token &t, uint32_t p) { return t.pos < p; });
-        for (; it != listed_tok.end() && it->pos == b.position[i]; ++it)
-            out.emplace_back(reinterpret_cast<const char *>(listed_text.data()) + it->text_off, it->text_len);
-        return out;
-    };
-    if (pileup_tokens) {
-        col_off = engine.indel_tally(nullptr, pos, flagged);
-    } else if (listed) {
-        const bv_indel_tokens tok = engine.text_tokens();
-        col_off = engine.indel_tally(&tok, b.position, flagged);
-    } else {
-        // (a row of 10,000 samples brings hundreds of tokens: the descriptors are laid out on the run's host threads)
-        std::vector<uint32_t> key(n);
-        std::vector<uint64_t> token_at(n + 1, 0), text_at(n + 1, 0);
-        parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; ++i) {
-                key[i] = (uint32_t)i;
-                token_at[i + 1] = b.text[i].indel_tokens.size();
-                for (const std::string &t : b.text[i].indel_tokens) text_at[i + 1] += t.size();
-            }
-        });
-        for (size_t i = 0; i < n; ++i) { token_at[i + 1] += token_at[i]; text_at[i + 1] += text_at[i]; }
-        std::vector<bv_pileup_token> tokens(token_at[n]);
-        std::string token_text(text_at[n], '\0');
-        parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; ++i) {
-                uint64_t k = token_at[i], at = text_at[i];
-                for (const std::string &t : b.text[i].indel_tokens) {
-                    tokens[k++] = bv_pileup_token{(uint32_t)i, 0u, at, (uint32_t)t.size(), 0u};
-                    std::memcpy(&token_text[at], t.data(), t.size());
-                    at += t.size();
-                }
-            }
-        });
-        const bv_indel_tokens tok{tokens.data(), reinterpret_cast<const uint8_t *>(token_text.data()), tokens.size(), token_text.size(), BV_MEM_HOST, 0};
-        col_off = engine.indel_tally(&tok, key, flagged);
-    }
-    // the predicate on the run's host threads
-    std::vector<uint8_t> fits(n, 0);
-    parallel_ranges(n, ctx.threads, [&](size_t, size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i) {
-            const SiteText &st = b.text[i];
-            fits[i] = names_fit && st.ref_id == chrom && st.ref_base.size() == 1 &&
-                      BaseTypeEngine::record_text_on_device(b.result.sites[i], G ? &b.result.group(i, 0) : nullptr, G);
-        }
-    });
-    // the columns of the rows the host formats: the tally's, fetched once if there is such a row
-    std::string columns;
-    auto host_column = [&](size_t i) {
-        if (listed && b.host_read[i]) return indel_string(b.text[i].indel_tokens);  // (the host reader's: the list never holds them)
-        if (flagged[i]) return indel_string(pileup_tokens ? (*pileup_tokens)(pos[i]) : listed ? listed_tokens(i) : b.text[i].indel_tokens);
-        if (col_off[i + 1] == col_off[i]) return std::string();
-        if (columns.empty()) { columns.resize(col_off[n]); engine.indel_fetch(&columns[0], col_off[n]); }
-        return columns.substr(col_off[i], col_off[i + 1] - col_off[i]);
-    };
-    for (size_t i = 0; i < n; ++i) {
-        const SiteText &st = b.text[i];
-        const bv_site_result &r = b.result.sites[i];
-        const bv_group_result *g = G ? &b.result.group(i, 0) : nullptr;
-        if (st.ref_base.size() == 1) ref[i] = st.ref_base[0];
-        const bool on_device = fits[i] != 0;
-        if (!on_device) ++b.lines_host_formatted;
-        const bool host_tokens = listed && b.host_read[i] && !st.indel_tokens.empty();  // a host-read row with tokens: host text, as a flagged row
-        if (!on_device || flagged[i] || host_tokens) {
-            const std::string column = host_column(i), row = format_cvg_line(st, r, column);
-            if (!row.empty() && !column.empty() && column != ".") ++b.indel_columns_host;
-            cvg_host += row;
-        }
-        cvg_host_off.push_back(cvg_host.size());
-        if (!b.result.has_variant(i)) continue;
-        vrec.push_back(r);
-        if (G) vgrp.insert(vgrp.end(), g, g + G);
-        vpos.push_back(st.ref_pos);
-        vref.push_back(ref[i]);
-        vidx.push_back((uint32_t)i);
-        site.push_back(first_row + (uint32_t)i);
-        if (!on_device) vcf_host += format_vcf_head(st, r, g, ctx.group_names);
-        vcf_host_off.push_back(vcf_host.size());
-    }
-    bv_record_lines in;
-    std::memset(&in, 0, sizeof in);
-    in.mem_kind = BV_MEM_HOST;
-    in.chrom = names_fit ? chrom.data() : "-"; in.chrom_len = names_fit ? (uint32_t)chrom.size() : 1u;
-    in.n_groups = names_fit ? G : 0u;  // (names that do not fit: every line is host text, and no name is looked at)
-    in.group_names = names.data(); in.group_name_off = name_off.data();
-    // the VCF lines first: on BAM input the slab's rows are the pileup's, which the next window overwrites
-    in.records = vrec.data(); in.groups = in.n_groups ? vgrp.data() : nullptr;
-    in.pos = vpos.data(); in.ref_char = vref.data();
-    in.host_text = vcf_host.data(); in.host_text_off = vcf_host_off.data();
-    in.slab = slab; in.site = site.data();
-    in.n_lines = (uint32_t)vrec.size();
-    const std::vector<uint64_t> off = engine.vcf_format_records(in);
-    b.vcf_line_off.assign(1, 0);
-    for (size_t k = 0; k < vrec.size(); ++k) {
-        if (off[k + 1] == off[k]) continue;  // (no ALT: format_vcf_line writes nothing)
-        b.vcf_record.push_back(vidx[k]);
-        b.vcf_line_off.push_back(off[k + 1]);
-    }
-    const uint64_t total = off.back();
-    if (total && ctx.vcf_gz) {
-        const std::vector<uint64_t> block_off = bgzf_block_table(total);
-        const size_t nb = block_off.size() - 1;
-        b.vcf_members.resize(total + 31 * nb);
-        b.vcf_member_off.assign(nb + 1, 0);
-        engine.vcf_deflate(total, block_off.data(), (uint32_t)nb, b.vcf_members.data(), b.vcf_member_off.data(), ctx.deflate_level);
-        b.vcf_members.resize(b.vcf_member_off[nb]);
-    } else if (total) {
-        b.vcf_text.resize(total);
-        engine.vcf_fetch(&b.vcf_text[0], total);
-    }
-    // the CVG rows of every record, around the tally's columns
-    in.records = b.result.sites.data(); in.groups = in.n_groups ? b.result.groups.data() : nullptr;
-    in.pos = pos.data(); in.ref_char = ref.data();
-    in.host_text = cvg_host.data(); in.host_text_off = cvg_host_off.data();
-    in.slab = nullptr; in.site = nullptr;
-    in.n_lines = (uint32_t)n;
-    const std::vector<uint64_t> coff = engine.cvg_format_tallied(in);
-    b.cvg_device = true;
-    b.cvg_text.resize(coff.back());
-    if (coff.back()) engine.cvg_fetch(&b.cvg_text[0], coff.back());
-    for (size_t i = 0; i < n; ++i)
-        if (coff[i + 1] != coff[i] && cvg_host_off[i + 1] == cvg_host_off[i]) {
-            ++b.cvg_lines_device;
-            if (col_off[i + 1] != col_off[i]) ++b.indel_columns_device;
-        }
-}
-
 class EngineWorker {
 public:
     EngineWorker(const CallContext &ctx, size_t w, BatchQueue &in, BatchQueue &out, RawReaderTurns *raw, StageClock &clk, ErrorSink &errors)
@@ -636,7 +455,7 @@ private:
     // a text batch through `make`, which parses and calls it; a failure of the engine leaves the batch without records
     template <class Make>
     void text_batch(Batch &b, Make make) {
-        try { take_text_result(b, make()); } catch (const std::exception &ex) { b.error = ex.what(); b.text.clear(); b.emit_device = b.cvg_device = false; }
+        try { take_text_result(b, make()); } catch (const std::exception &ex) { b.error = ex.what(); b.text.clear(); b.emit_device = b.cvg_device = false; b.counts = EmitCounts(); }
     }
     // the records of a text batch into the batch; what the host reader threw becomes the batch's error, behind its records
     void take_text_result(Batch &b, BaseTypeEngine::TextBatch &&tb) {
@@ -647,9 +466,13 @@ private:
         b.position = std::move(tb.position);
         b.host_read = std::move(tb.host_read);
         b.tokens = tb.tokens;
-        b.indel_tokens_device = tb.tokens_device;
-        b.text_fetch_bytes = tb.fetch_bytes;
-        if (ctx_.routes.emit_device) emit_records_on_device(ctx_, *engine_, b, nullptr, 0);  // (over the rows the text submit kept)
+        b.counts.indel_tokens_device = tb.tokens_device;
+        b.counts.text_fetch_bytes = tb.fetch_bytes;
+        if (ctx_.routes.emit_device) {  // (over the rows the text submit kept)
+            LazyTokenList listed{[&](TokenList &l) { engine_->text_tokens_fetch(l.tokens, l.text); b.counts.text_fetch_bytes += l.bytes(); }};
+            emit_records_on_device(ctx_, *engine_, b, b.tokens == BaseTypeEngine::TOKENS_DEVICE_KEEP ? IndelTokenSource::engine_list(*engine_, b, listed)
+                                                                                                       : IndelTokenSource::site_texts(b.text, ctx_.threads), nullptr, 0);
+        }
         if (tb.error) {
             try { std::rethrow_exception(tb.error); } catch (const std::exception &ex) { b.error = ex.what(); }
         }
@@ -802,43 +625,32 @@ private:
         // (short reads: the rank words carry the calls, as SlabBuilder::tag_ranks chooses on the host path)
         if (bv_engine_pileup_rows(pe, 1, &slab, pos.data(), depth.data()) != BV_OK) check(bv_engine_pileup_rows(pe, 0, &slab, pos.data(), depth.data()));
         // the indel tokens: --emit device tallies them where they lie, and fetches them only for a row it leaves to the host
-        std::vector<bv_pileup_token> tokens;
-        std::vector<uint8_t> token_text;
-        tokens_fetched_ = false;
-        if (!ctx_.routes.emit_device) fetch_tokens(tokens, token_text);
+        window_tokens_.fetched = false;
+        if (!ctx_.routes.emit_device) window_tokens_.get();
         const double dt = StageClock::now() - tp0;
         stats_.pileup_s += dt;
         clk_.add(StageClock::PARSE, dt);
-        size_t next_token = 0;
+        size_t next_token = 0;  // (the window's batches take its tokens in turn)
         for (uint32_t first = 0; first < n_cov && errors_.ok(); first += ctx_.batch_sites)
-            call_rows(slab, ref_id, fa_seq, pos, tokens, token_text, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
+            call_rows(slab, ref_id, fa_seq, pos, next_token, first, std::min(ctx_.batch_sites, n_cov - first));
     }
     // the last pileup's tokens and their text, to the host
-    void fetch_tokens(std::vector<bv_pileup_token> &tokens, std::vector<uint8_t> &token_text) {
+    void fetch_tokens(TokenList &l) {
         bv_engine *pe = engine_->handle();
         bv_pileup_result res{};
         res.mem_kind = BV_MEM_HOST;
         check(bv_engine_pileup_fetch(pe, &res, nullptr));  // (no buffers: the sizes)
-        tokens.resize(res.n_tokens);
-        token_text.resize(res.text_bytes);
-        res.tokens = tokens.data(); res.text = token_text.data();
-        res.tokens_capacity = tokens.size(); res.text_capacity = token_text.size();
+        l.tokens.resize(res.n_tokens);
+        l.text.resize(res.text_bytes);
+        res.tokens = l.tokens.data(); res.text = l.text.data();
+        res.tokens_capacity = l.tokens.size(); res.text_capacity = l.text.size();
         check(bv_engine_pileup_fetch(pe, &res, nullptr));
-    }
-    // --emit device: the tokens of one position of the window, fetched when the first row asks
-    std::vector<std::string> row_tokens(uint32_t pos) {
-        if (!tokens_fetched_) { fetch_tokens(window_tokens_, window_token_text_); tokens_fetched_ = true; }
-        std::vector<std::string> out;
-        auto it = std::lower_bound(window_tokens_.begin(), window_tokens_.end(), pos, [](const bv_pileup_token &t, uint32_t p) { return t.pos < p; });
-        for (; it != window_tokens_.end() && it->pos == pos; ++it)
-            out.emplace_back(reinterpret_cast<const char *>(window_token_text_.data()) + it->text_off, it->text_len);
-        return out;
     }
     // rows [first, first + rows) of the window's covered positions: called where they lie, their records and planes into a batch
     // -- or, with --emit device, their records alone: the lines are written from the rows where they lie, before the next window's
     // pileup takes the slab's place, and only the text (or its BGZF members) comes back
-    void call_rows(const bv_slab &slab, const std::string &ref_id, const std::string &fa_seq, const std::vector<uint32_t> &pos, const std::vector<bv_pileup_token> &tokens,
-                   const std::vector<uint8_t> &token_text, size_t &next_token, uint32_t first, uint32_t rows) {
+    void call_rows(const bv_slab &slab, const std::string &ref_id, const std::string &fa_seq, const std::vector<uint32_t> &pos, size_t &next_token, uint32_t first,
+                   uint32_t rows) {
         const size_t n_sample = ctx_.n_sample();
         BatchPtr b(new Batch((uint32_t)n_sample));
         b->seq = seq_++;
@@ -859,17 +671,14 @@ private:
         for (uint32_t k = 0; k < rows; ++k) {
             SiteText st;
             st.ref_id = ref_id; st.ref_pos = pos[first + k]; st.ref_base = std::string(1, fa_seq[st.ref_pos - 1]);
-            // (--emit device: `tokens` is empty, the column is tallied on the engine)
-            while (next_token < tokens.size() && tokens[next_token].pos < st.ref_pos) ++next_token;
-            for (; next_token < tokens.size() && tokens[next_token].pos == st.ref_pos; ++next_token)
-                st.indel_tokens.emplace_back(reinterpret_cast<const char *>(token_text.data()) + tokens[next_token].text_off, tokens[next_token].text_len);
             b->text.push_back(std::move(st));
         }
-        if (emit_device) {
+        if (emit_device) {  // (the column is tallied on the engine: the SiteTexts stay without tokens)
             const double tw0 = StageClock::now();
-            const PileupRowTokens from_pileup = [this](uint32_t pos) { return row_tokens(pos); };
-            emit_records_on_device(ctx_, *engine_, *b, &slab, first, &from_pileup);
+            emit_records_on_device(ctx_, *engine_, *b, IndelTokenSource::pileup(b->text, window_tokens_), &slab, first);
             clk_.add(StageClock::ENGINE, StageClock::now() - tw0);
+        } else {
+            window_tokens_.get().deal(&pos[first], rows, b->text.data(), next_token);
         }
         out_.push(std::move(b));
     }
@@ -883,9 +692,7 @@ private:
     std::unique_ptr<BamPool> pool_;
     Stats stats_;
     uint64_t seq_ = 0;
-    bool tokens_fetched_ = false;  // --emit device: window_tokens_ are the current window's
-    std::vector<bv_pileup_token> window_tokens_;
-    std::vector<uint8_t> window_token_text_;
+    LazyTokenList window_tokens_{[this](TokenList &l) { fetch_tokens(l); }};  // the current window's: --emit device fetches them only if a row asks
 };
 
 }  // namespace bvamd

@@ -1,6 +1,7 @@
 // call_pipeline_check.cpp -- the stages of bv_call below the whole tool, WITHOUT an engine (basevar_amd/host/call_pipeline.hpp,
-// pileup.hpp, bgzf_tabix.hpp): the hand-off queue, the emitter's ordering rules, the pileup window walk, region parsing and the
-// BGZF block table.
+// pileup.hpp, bgzf_tabix.hpp, indel_tokens.hpp, device_emit.hpp): the hand-off queue, the emitter's ordering rules, the pileup
+// window walk, region parsing, the BGZF block table, the host's lists of indel tokens (TokenList) and the plan step of
+// --emit device (plan_record_lines, with csrc/bv_record_text_core.h's bv_rt_on_device as the predicate).
 //   call_pipeline_check WORKDIR
 // The records are made up from the rows themselves, the way host_fuzz.cpp makes them.  What the emitter writes into plain-text
 // outputs is held to a single-threaded format_cvg_line / format_vcf_line loop over the batches in seq order.  Ends with
@@ -12,6 +13,7 @@
 #include <iostream>
 #include <sstream>
 
+#include "../../basevar_amd/csrc/bv_record_text_core.h"
 #include "../../basevar_amd/host/call_pipeline.hpp"
 
 using namespace bvamd;
@@ -275,6 +277,157 @@ static void check_block_table() {
     CHECK(ends_in_gz("a.vcf.gz") && !ends_in_gz("a.vcf") && !ends_in_gz(".gz") && !ends_in_gz("gz"), "ends_in_gz");
 }
 
+typedef std::vector<std::string> Strs;
+
+static TokenList make_list(const std::vector<std::pair<uint32_t, std::string>> &toks) {
+    TokenList l;
+    for (const auto &t : toks) {
+        l.tokens.push_back(bv_pileup_token{t.first, 0u, l.text.size(), (uint32_t)t.second.size(), 0u});
+        l.text.insert(l.text.end(), t.second.begin(), t.second.end());
+    }
+    return l;
+}
+// the dealing walk over `keys` from `cursor` on: what every key's SiteText took
+static std::vector<Strs> dealt(const TokenList &l, const std::vector<uint32_t> &keys, size_t &cursor) {
+    std::vector<SiteText> st(keys.size());
+    l.deal(keys.data(), keys.size(), st.data(), cursor);
+    std::vector<Strs> out;
+    for (const SiteText &s : st) out.push_back(s.indel_tokens);
+    return out;
+}
+
+static void check_token_list() {
+    {
+        const TokenList none;
+        size_t cur = 0;
+        CHECK(dealt(none, {1, 2}, cur) == std::vector<Strs>({{}, {}}) && cur == 0, "TokenList, empty: nothing is dealt");
+        CHECK(none.of(1).empty() && none.bytes() == 0, "TokenList, empty: of() and bytes()");
+        const bv_indel_tokens t = none.as_indel_tokens();
+        CHECK(t.n_tokens == 0 && t.text_bytes == 0 && t.mem_kind == BV_MEM_HOST && t.reserved_ == 0, "TokenList, empty: as_indel_tokens");
+    }
+    // positions 2 .. 11, eight tokens, three of them at 5
+    const TokenList l = make_list({{2, "+A"}, {3, "-C"}, {5, "+GG"}, {5, "-T"}, {5, "+GG"}, {7, "+AC"}, {9, "-TT"}, {11, "+N"}});
+    size_t cur = 0;
+    CHECK(dealt(l, {4, 5, 6, 7}, cur) == std::vector<Strs>({{}, {"+GG", "-T", "+GG"}, {}, {"+AC"}}),
+          "TokenList: tokens below the first key are passed over, a key without a token takes none, three tokens at one key");
+    CHECK(cur == 6, "TokenList: the cursor stands behind the last key's tokens, got " << cur);
+    CHECK(dealt(l, {8, 9, 10}, cur) == std::vector<Strs>({{}, {"-TT"}, {}}) && cur == 7, "TokenList: the next range of keys goes on with the same cursor");
+    CHECK(dealt(l, {11, 12}, cur) == std::vector<Strs>({{"+N"}, {}}) && cur == 8, "TokenList: the last token, and a key behind the list's end");
+    CHECK(dealt(l, {13}, cur) == std::vector<Strs>({{}}) && cur == 8, "TokenList: a walk from the list's end");
+    cur = 0;
+    CHECK(dealt(l, {2, 3}, cur) == std::vector<Strs>({{"+A"}, {"-C"}}) && cur == 2, "TokenList: tokens beyond the last key are left where they are");
+    CHECK(l.of(2) == Strs({"+A"}) && l.of(11) == Strs({"+N"}) && l.of(6).empty() && l.of(1).empty() && l.of(12).empty(), "TokenList: of() on the first, the last and absent positions");
+    CHECK(l.of(5) == Strs({"+GG", "-T", "+GG"}) && l.view(2) == "+GG" && l.view(7) == "+N", "TokenList: of() keeps the list's order; view()");
+    CHECK(l.bytes() == 24 * 8 + 20, "TokenList: bytes() is descriptors and text, got " << l.bytes());
+    const bv_indel_tokens t = l.as_indel_tokens();
+    CHECK(t.tokens == l.tokens.data() && t.text == l.text.data() && t.n_tokens == 8 && t.text_bytes == 20 && t.mem_kind == BV_MEM_HOST && t.reserved_ == 0, "TokenList: as_indel_tokens");
+    // from_site_texts: rows without tokens between rows with them
+    const std::vector<Strs> rows = {{"+AC", "-T"}, {}, {}, {"+G"}, {}, {"-TTT", "+A", "+A"}, {}};
+    std::vector<SiteText> texts(rows.size());
+    for (size_t i = 0; i < rows.size(); ++i) texts[i].indel_tokens = rows[i];
+    const uint32_t want_pos[6] = {0, 0, 3, 5, 5, 5}, want_len[6] = {3, 2, 2, 4, 2, 2};
+    const uint64_t want_off[6] = {0, 3, 5, 7, 11, 13};
+    for (int threads : {1, 4, 16}) {
+        const TokenList none = TokenList::from_site_texts(std::vector<SiteText>(), threads);
+        CHECK(none.tokens.empty() && none.text.empty(), "from_site_texts, no row, threads " << threads);
+        const TokenList got = TokenList::from_site_texts(texts, threads);
+        bool same = got.tokens.size() == 6 && std::string(got.text.begin(), got.text.end()) == "+AC-T+G-TTT+A+A";
+        for (size_t k = 0; same && k < 6; ++k) {
+            const bv_pileup_token &d = got.tokens[k];
+            same = d.pos == want_pos[k] && d.sample == 0 && d.text_off == want_off[k] && d.text_len == want_len[k] && d.reserved_ == 0;
+        }
+        CHECK(same, "from_site_texts: descriptors keyed by the row's index, text back to back, threads " << threads);
+        bool round = true;
+        for (size_t i = 0; i < rows.size(); ++i) round = round && got.of((uint32_t)i) == rows[i];
+        CHECK(round, "from_site_texts: of(i) gives row i's strings in order, threads " << threads);
+    }
+    // a lazy list is fetched once, and only when asked
+    int fetches = 0;
+    LazyTokenList lazy{[&](TokenList &into) { ++fetches; into = make_list({{4, "+A"}}); }};
+    CHECK(fetches == 0, "LazyTokenList: nothing is fetched before a row asks");
+    CHECK(lazy.get().of(4) == Strs({"+A"}) && lazy.get().of(5).empty() && fetches == 1, "LazyTokenList: one fetch for any number of rows");
+}
+
+// One record of the plan step's batch: variant, covered, every number inside the device's formats
+static Site plan_site(uint32_t k) {
+    Site s = make_site(3, k, 5000 + 10 * k);
+    s.text.indel_tokens.clear();
+    bv_site_result &r = s.r;
+    if (!r.total_depth) { r.total_depth = 1; r.depth[s.ref] = 1; }
+    if (!r.n_alt) { r.n_alt = 1; r.alt[0] = (uint8_t)((s.ref + 1) & 3); r.af[0] = 0.125; r.caf[0] = 0.5; }
+    r.status = BV_SITE_COVERED | BV_SITE_VARIANT | BV_SITE_RANKSUM;
+    s.g.n_alt = r.n_alt;
+    for (int a = 0; a < r.n_alt; ++a) { s.g.alt[a] = r.alt[a]; s.g.af[a] = 0.5; }
+    return s;
+}
+
+static void check_plan() {
+    const uint32_t n = 12, first_row = 40;
+    std::vector<SiteText> text;
+    BaseTypeBatch result;
+    result.n_groups = 1;
+    for (uint32_t k = 0; k < n; ++k) {
+        const Site s = plan_site(k);
+        text.push_back(s.text);
+        result.sites.push_back(s.r);
+        result.groups.push_back(s.g);
+    }
+    std::vector<uint8_t> flagged(n, 0), host_read(n, 0);
+    result.sites[1].af[0] = std::nan("");                                     // refused by the predicate
+    flagged[2] = 1; text[2].indel_tokens = {"+AC", "-T"};                     // left to the caller by the tally
+    host_read[3] = 1; text[3].indel_tokens = {"+AC", "-T"};                   // host-read, with tokens
+    host_read[4] = 1;                                                         // host-read, without
+    text[5].ref_id = "chrU";                                                  // not the batch's first CHROM
+    text[6].ref_base = "AC";                                                  // two REF characters
+    result.sites[7].status = BV_SITE_COVERED;                                 // no variant
+    result.sites[8].total_depth = 0; flagged[8] = 1;                          // flagged, and the reference writes no row
+    CHECK(bv_rt_on_device(&result.sites[0], &result.groups[0], 1) && !bv_rt_on_device(&result.sites[1], &result.groups[1], 1), "plan: the predicate takes row 0 and refuses row 1");
+    const Strs column = {"", "", "+AC|1,-T|1", "+AC|1,-T|1", "", ".", "-T|2", "", "+A|1", "", "", ""};  // what host_column hands out
+    const std::vector<uint8_t> as_host = {0, 1, 1, 1, 0, 1, 1, 0, 1, 0, 0, 0}, off_device = {0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0};
+    const auto fits = [](const bv_site_result &r, const bv_group_result *g, uint32_t G) { return bv_rt_on_device(&r, g, G); };
+    for (int run = 0; run < 2; ++run) {
+        // the second run: a group name beyond BV_RECORD_TEXT_NAME_MAX -- every line is host text
+        const std::vector<std::string> groups = {run ? std::string(BV_RECORD_TEXT_NAME_MAX + 1, 'g') : std::string("g1")};
+        std::vector<size_t> asked;
+        const EmitPlan p = plan_record_lines(groups, text, result, first_row, flagged, &host_read, 3, fits, [&](size_t i) { asked.push_back(i); return column[i]; });
+        std::string cvg, vcf;
+        std::vector<uint64_t> cvg_off(1, 0), vcf_off(1, 0);
+        std::vector<uint32_t> vidx, site;
+        std::vector<size_t> want_asked;
+        uint64_t n_off = 0, n_col = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool off = run || off_device[i];
+            n_off += off;
+            if (run || as_host[i]) {
+                want_asked.push_back(i);
+                const std::string row = format_cvg_line(text[i], result.sites[i], column[i]);
+                cvg += row;
+                n_col += !row.empty() && !column[i].empty() && column[i] != ".";
+            }
+            cvg_off.push_back(cvg.size());
+            if (i == 7) continue;
+            if (off) vcf += format_vcf_head(text[i], result.sites[i], &result.groups[i], groups);
+            vcf_off.push_back(vcf.size());
+            vidx.push_back(i);
+            site.push_back(first_row + i);
+        }
+        CHECK(asked == want_asked, "plan, run " << run << ": host_column is asked for the host-text rows and no other");
+        CHECK(p.cvg_host == cvg && p.cvg_host_off == cvg_off, "plan, run " << run << ": the CVG host text and its offsets");
+        CHECK(p.vcf_host == vcf && p.vcf_host_off == vcf_off, "plan, run " << run << ": the VCF host text and its offsets");
+        CHECK(p.vidx == vidx && p.site == site && p.vrec.size() == 11 && p.vgrp.size() == 11, "plan, run " << run << ": the variant subset, its records and rows");
+        CHECK(p.lines_host_formatted == n_off && p.indel_columns_host == n_col && n_off == (run ? 12u : 3u) && n_col == 3u,
+              "plan, run " << run << ": the counters, got " << p.lines_host_formatted << " and " << p.indel_columns_host);
+        const bv_record_lines v = p.vcf_lines(nullptr), c = p.cvg_lines(result);
+        CHECK(std::string(c.chrom, c.chrom_len) == (run ? "-" : "chrT") && c.n_groups == (run ? 0u : 1u) && v.n_groups == c.n_groups && (c.groups != nullptr) == !run,
+              "plan, run " << run << ": CHROM and the groups of both calls");
+        CHECK(c.n_lines == n && v.n_lines == 11 && c.records == result.sites.data() && v.records == p.vrec.data() && v.site == p.site.data() && !c.site && !c.slab &&
+              c.host_text_off == p.cvg_host_off.data() && v.host_text_off == p.vcf_host_off.data() && c.mem_kind == BV_MEM_HOST && !c.reserved_, "plan, run " << run << ": both bv_record_lines");
+        CHECK(std::string(c.ref_char, n) == std::string("") + text[0].ref_base + text[1].ref_base + text[2].ref_base + text[3].ref_base + text[4].ref_base + text[5].ref_base + "N" +
+              text[7].ref_base + text[8].ref_base + text[9].ref_base + text[10].ref_base + text[11].ref_base && c.pos[3] == 5030 && v.pos[7] == 5080,
+              "plan, run " << run << ": positions and REF characters ('N' for a REF of two)");
+    }
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { std::cerr << "usage: call_pipeline_check WORKDIR" << std::endl; return 2; }
     try {
@@ -287,6 +440,8 @@ int main(int argc, char **argv) {
         check_walk(UINT32_MAX - 1200000, UINT32_MAX, 65536, "a region ending at 4,294,967,295");
         check_regions();
         check_block_table();
+        check_token_list();
+        check_plan();
     } catch (const std::exception &ex) {
         std::cout << "FAIL: " << ex.what() << std::endl;
         ++g_fails;

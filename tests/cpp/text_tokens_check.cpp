@@ -1,7 +1,7 @@
 // Test infrastructure (tests/ only, host code, its own main): basevar_amd/csrc/bv_text_tokens_core.h -- the code the kernels of
 // bv_text_tokens.hip compile -- held to the tokens the host collects today, byte for byte and in order:
 //   * the host reader (host/batchfile_fast.hpp, parse_site_rows_fast) on every position in state 0, and
-//   * BaseTypeEngine::finish_text's walk of a marked row (host/basetype_gpu.hpp), restated here as it stands there,
+//   * the walk of a marked row that BaseTypeEngine::finish_text makes (host/indel_tokens.hpp: row_indel_tokens),
 // on the batches tests/text_tokens_model.py writes.  The core is also run over the rows of every other position (a row it is
 // never asked about on the device may be anything: it must stay inside the row).  The list goes to a dump that the Python
 // model compares and from which tests/test_text_tokens_cpu.py asserts the corpus's reach.  Built with ASan + UBSan and run as
@@ -10,7 +10,7 @@
 //   text_tokens_check <in> <out>     exit 0: all agree
 //   text_tokens_check walk <in>      what the host route costs on one thread (tools/text_tokens_bench.py): finish_text's walk of the
 //                                    marked rows of the state-0 positions, a std::string a token, then the descriptors and the text
-//                                    laid out as bv_call's emit_records_on_device lays them out; best of 5 passes
+//                                    laid out as bv_call --emit device lays them out (TokenList::from_site_texts); best of 5 passes
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +22,7 @@
 
 #include "../../basevar_amd/csrc/bv_text_tokens_core.h"
 #include "../../basevar_amd/host/batchfile_fast.hpp"
+#include "../../basevar_amd/host/indel_tokens.hpp"
 
 namespace {
 
@@ -29,20 +30,6 @@ struct Token {
     uint32_t pos, sample, file;
     std::string text;
 };
-
-// finish_text's walk (host/basetype_gpu.hpp): to Readbases over five tabs, then token by token to the column's tab
-std::vector<std::string> finish_text_walk(const char *p) {
-    std::vector<std::string> out;
-    for (int k = 0; k < 5; ++k) { while (*p != '\t') ++p; ++p; }
-    for (;;) {
-        const char *q = p;
-        while (*q != ' ' && *q != '\t') ++q;
-        if (*p == '+' || *p == '-') out.emplace_back(p, (size_t)(q - p));
-        if (*q == '\t') break;
-        p = q + 1;
-    }
-    return out;
-}
 
 template <class T>
 T get(std::istream &in) {
@@ -106,7 +93,7 @@ int time_walk(const char *path) {
     size_t n_rows = 0, n_tokens = 0, n_text = 0;
     for (int pass = 0; pass < 5; ++pass) {
         const double t0 = now();
-        std::vector<std::vector<std::string>> per_pos(b.P);
+        std::vector<bvamd::SiteText> per_pos(b.P);
         n_rows = 0;
         for (uint32_t p = 0; p < b.P; ++p) {
             if (b.state[p]) continue;
@@ -114,30 +101,15 @@ int time_walk(const char *path) {
                 const std::string &row = b.rows[(size_t)p * b.F + f];
                 if (row.find_first_of("+-") == std::string::npos) continue;  // (the device's mark says more; a row without either byte has no token)
                 ++n_rows;
-                for (std::string &t : finish_text_walk(row.c_str())) per_pos[p].push_back(std::move(t));
+                bvamd::row_indel_tokens(row.c_str(), per_pos[p].indel_tokens);
             }
         }
         const double t1 = now();
-        std::vector<uint64_t> token_at(b.P + 1, 0), text_at(b.P + 1, 0);
-        for (uint32_t p = 0; p < b.P; ++p) {
-            token_at[p + 1] = token_at[p] + per_pos[p].size();
-            text_at[p + 1] = text_at[p];
-            for (const std::string &t : per_pos[p]) text_at[p + 1] += t.size();
-        }
-        std::vector<bv_tt_token> tokens(token_at[b.P]);
-        std::string text(text_at[b.P], '\0');
-        for (uint32_t p = 0; p < b.P; ++p) {
-            uint64_t k = token_at[p], at = text_at[p];
-            for (const std::string &t : per_pos[p]) {
-                tokens[k++] = bv_tt_token{p, 0u, at, (uint32_t)t.size(), 0u};
-                std::memcpy(&text[at], t.data(), t.size());
-                at += t.size();
-            }
-        }
+        const bvamd::TokenList list = bvamd::TokenList::from_site_texts(per_pos, 1);
         const double t2 = now();
         best_walk = std::min(best_walk, t1 - t0);
         best_layout = std::min(best_layout, t2 - t1);
-        n_tokens = tokens.size(); n_text = text.size();
+        n_tokens = list.tokens.size(); n_text = list.text.size();
     }
     std::printf("walk: rows %zu tokens %zu text %zu walk_ms %.3f layout_ms %.3f\n", n_rows, n_tokens, n_text, 1e3 * best_walk, 1e3 * best_layout);
     return 0;
@@ -183,7 +155,8 @@ int main(int argc, char **argv) {
                     ++n_rows;
                     const std::vector<Token> got = core_row(rows[f], p, f, foff[f]);  // (every row: it stays inside the row whatever the row is)
                     if (state[p]) continue;
-                    const std::vector<std::string> walk = finish_text_walk(rows[f].c_str());
+                    std::vector<std::string> walk;
+                    bvamd::row_indel_tokens(rows[f].c_str(), walk);
                     if (walk.size() != got.size()) throw std::runtime_error("batch " + std::to_string(b) + " position " + std::to_string(p) + ": the core has " +
                                                                             std::to_string(got.size()) + " tokens, finish_text's walk " + std::to_string(walk.size()));
                     for (size_t i = 0; i < got.size(); ++i)

@@ -1,7 +1,7 @@
 """CPU test (no GPU, no engine) of bv_call's stages below the whole tool (basevar_amd/host/call_pipeline.hpp and the helpers it
 shares with bv_pileup): the hand-off queue, the emitter's ordering rules -- batches finish out of order, a failed slab batch stops
-everything from itself on, a failed text batch first writes its records -- the pileup window walk, region parsing and the BGZF
-block table.  tests/cpp/call_pipeline_check.cpp is built by g++ three ways (plain, ASan + UBSan, TSan) and each is run as a
+everything from itself on, a failed text batch first writes its records -- the pileup window walk, region parsing, the BGZF
+block table, the host's lists of indel tokens (indel_tokens.hpp) and the plan step of --emit device (device_emit.hpp).  tests/cpp/call_pipeline_check.cpp is built by g++ three ways (plain, ASan + UBSan, TSan) and each is run as a
 program; nothing loaded into python runs under a sanitizer."""
 import os
 import subprocess
@@ -24,4 +24,4 @@ def test_queue_emitter_order_window_walk_regions_and_block_table(kind, tmp_path)
     work.mkdir()
     p = subprocess.run((NO_ASLR if kind == "tsan" else []) + [exe, str(work)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=ENV, timeout=300)
     assert p.returncode == 0 and b"FAILS 0" in p.stdout and not p.stderr, (p.stdout[-2000:], p.stderr[-3000:])
-    assert b"CALL_PIPELINE cases 83 " in p.stdout
+    assert b"CALL_PIPELINE cases 124 " in p.stdout

@@ -12,7 +12,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "text_tokens_check.cpp")
 CORE = os.path.join(ROOT, "basevar_amd", "csrc", "bv_text_tokens_core.h")
-DEPS = [SRC, CORE] + [os.path.join(ROOT, "basevar_amd", "host", h) for h in ("batchfile_fast.hpp", "basetype_gpu.hpp", "batchfile.hpp", "vcf_emit.hpp")]
+DEPS = [SRC, CORE] + [os.path.join(ROOT, "basevar_amd", "host", h) for h in ("batchfile_fast.hpp", "basetype_gpu.hpp", "batchfile.hpp", "vcf_emit.hpp", "indel_tokens.hpp")]
 OUT_DIR = os.path.join(ROOT, "basevar_amd", "lib", "san")
 GOLDEN_ROWS = os.path.join(ROOT, "tests", "golden", "reference_pileup_rows.txt.gz")
 SKIP, HOST, INDEL = 1, 2, 4  # BV_TEXT_*

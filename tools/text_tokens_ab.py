@@ -5,12 +5,13 @@ and this build without the flag, which must do what the parent does: wall second
 count.  A leg counts as a gain or a loss only beyond the parent's own spread.
 
     python3 tools/text_tokens_ab.py --parent DIR [--bf-samples 10000 --bf-per-file 200 --bf-sites 24000 --threads 1 4 16]
-                                    [--out profiles/text_tokens_bv_call_ab.txt]
+                                    [--parent-flag] [--out profiles/text_tokens_bv_call_ab.txt]
 
   the job        tools/indel_tally_ab.py's batchfile leg: 10,000 samples in 50 BGZF files, 24,000 positions
   flag sets      --inflate device --deflate device --emit device, and --inflate device alone
 DIR holds the parent commit's bv_call and libbasevar_amd.so.  The outputs of every triple are compared, inflated, before
-anything is reported."""
+anything is reported.  --parent-flag: the parent has the flag too and gets it -- the same flags on both sides, for a change that
+must leave the speed as it is; the run without the flag is left out then."""
 import argparse
 import json
 import os
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--bf-sites", type=int, default=24000)
     ap.add_argument("--threads", type=int, nargs="+", default=[1, 4, 16])
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--parent-flag", action="store_true", help="pass --indel-tokens device to the parent's binary too")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     new = os.path.join(ROOT, "basevar_amd", "lib")
@@ -59,21 +61,23 @@ def main():
         for t in a.threads:
             par, got, off = [], [], []
             for _ in range(a.repeats):
-                par.append(run(cmd(a.parent, t, "parent")))
+                par.append(run(cmd(a.parent, t, "parent", ["--indel-tokens", "device"] if a.parent_flag else [])))
                 got.append(run(cmd(new, t, "new", ["--indel-tokens", "device"])))
-                off.append(run(cmd(new, t, "off")))
-            same = all(digest_gz(os.path.join(d, "parent." + x)) == digest_gz(os.path.join(d, "new." + x)) == digest_gz(os.path.join(d, "off." + x))
-                       for x in ("vcf.gz", "cvg.gz"))
-            tj, oj, pj = (json.load(open(os.path.join(d, x + ".json"))) for x in ("new", "off", "parent"))
+                if not a.parent_flag:
+                    off.append(run(cmd(new, t, "off")))
+            tags = ("parent", "new") + (("off",) if off else ())
+            same = all(len(set(digest_gz(os.path.join(d, tag + "." + x)) for tag in tags)) == 1 for x in ("vcf.gz", "cvg.gz"))
+            tj, oj, pj = (json.load(open(os.path.join(d, x + ".json"))) for x in ("new", "off" if off else "new", "parent"))
             spread = max(par) - min(par)
 
             def verdict(best):
                 return "beyond the parent's spread" if abs(min(par) - best) > spread else "within the parent's spread"
-            say("  %2d thread(s): parent %s (spread %.3f); --indel-tokens device %s, best against best %+.3f s (%s); without the flag %s, %+.3f s (%s); "
+            without = "without the flag %s, %+.3f s (%s)" % (" ".join("%.3f" % x for x in off), min(off) - min(par), verdict(min(off))) if off else "the parent has the flag too"
+            say("  %2d thread(s): parent %s (spread %.3f); --indel-tokens device %s, best against best %+.3f s (%s); %s; "
                 "engine_s %.3f -> %.3f (flag) / %.3f (no flag), emit_s %.3f -> %.3f / %.3f; indel_tokens_device %s, text_fetch_bytes %s (flag) / %s (no flag); "
                 "indel_columns_device %s, indel_columns_host %s of %d sites; outputs inflate to the same bytes: %s" % (
                     t, " ".join("%.3f" % x for x in par), spread, " ".join("%.3f" % x for x in got), min(got) - min(par), verdict(min(got)),
-                    " ".join("%.3f" % x for x in off), min(off) - min(par), verdict(min(off)), pj["engine_s"], tj["engine_s"], oj["engine_s"], pj["emit_s"],
+                    without, pj["engine_s"], tj["engine_s"], oj["engine_s"], pj["emit_s"],
                     tj["emit_s"], oj["emit_s"], tj.get("indel_tokens_device"), tj.get("text_fetch_bytes"), oj.get("text_fetch_bytes"),
                     tj.get("indel_columns_device"), tj.get("indel_columns_host"), tj["sites"], same))
             if not same:

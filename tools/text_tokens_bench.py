@@ -10,7 +10,7 @@ Two shapes: the recorded job's (10,000 samples in 50 files) and 200 samples in 1
   (b) bv_engine_text_parse_bgzf with the mode off and on
   (c) after (b) with the mode on: heads fetch + text_tokens() + indel_tally over the device tokens; after (b) with the mode off:
       rows fetch; the host walk of the marked rows (a std::string a token) and the descriptor layout, on one thread, as
-      finish_text and emit_records_on_device do them (tests/cpp/text_tokens_check.cpp `walk`, built -O2); and the tally of
+      finish_text and --emit device do them (row_indel_tokens, TokenList::from_site_texts; tests/cpp/text_tokens_check.cpp `walk`, built -O2); and the tally of
       the same tokens handed in as host descriptors (the upload bv_call's default route makes).
 Every figure is the best and the worst of the passes after the first, which allocates."""
 import argparse
