@@ -139,6 +139,10 @@ class PileupText(C.Structure):  # bv_pileup_text
                 ("reserved_", C.c_uint32)]
 
 
+class PileupTextParts(C.Structure):  # bv_pileup_text_parts (include/basevar_amd_pileup_text_parts.h)
+    _fields_ = [("rows", C.POINTER(PileupText)), ("part_first", C.c_void_p), ("n_parts", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 PILEUP_TOKEN_DTYPE = np.dtype([("pos", "<u4"), ("sample", "<u4"), ("text_off", "<u8"), ("text_len", "<u4"), ("reserved_", "<u4")])  # bv_pileup_token
 assert PILEUP_TOKEN_DTYPE.itemsize == 24
 
@@ -190,6 +194,9 @@ PILEUP_BGZF_EXPORTS = ["bv_engine_pileup_bgzf"]
 
 # every symbol include/basevar_amd_pileup_text.h declares
 PILEUP_TEXT_EXPORTS = ["bv_pileup_text_tile_samples", "bv_engine_pileup_text", "bv_engine_pileup_text_fetch", "bv_engine_pileup_text_deflate"]
+
+# every symbol include/basevar_amd_pileup_text_parts.h declares
+PILEUP_TEXT_PARTS_EXPORTS = ["bv_engine_pileup_text_parts"]
 
 _lib = None
 
@@ -352,5 +359,7 @@ def load():
     L.bv_engine_pileup_text_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p]
     L.bv_engine_pileup_text_deflate.restype = C.c_int
     L.bv_engine_pileup_text_deflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.bv_engine_pileup_text_parts.restype = C.c_int
+    L.bv_engine_pileup_text_parts.argtypes = [C.c_void_p, C.POINTER(PileupTextParts), C.c_void_p, C.c_void_p]
     _lib = L
     return L

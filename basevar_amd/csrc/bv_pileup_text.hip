@@ -19,66 +19,14 @@
 //          indel tokens of any length -- the whole words are stored, the rest moves to the image's front and the list goes on; a
 //          step whose tokens exceed the image goes token by token, the wave across a token's bytes.  Tile 0 copies the head.
 // No atomics, no scratch, vector stores only.  Cells at pitch positions at or beyond n_samples are loaded with their 16-byte
-// word and never looked at.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/basevar_amd_pileup_text.h"
-#include "bv_chunk_stage.h"
-#include "bv_device_text.h"
-#include "bv_pileup_core.h"
-#include "bv_pileup_text_core.h"
-#include "bv_text_image.h"
-
-using namespace bv_impl;
+// word and never looked at.  The kernels' arguments, the tile's rows in LDS and the list writer are bv_pileup_text_impl.h's, which
+// bv_pileup_text_parts.hip (rows over sample parts of a tile) includes too.
+#include "bv_pileup_text_impl.h"
 
 static_assert(BV_PTEXT_CELL_NOCALL == BV_CELL_NOCALL && BV_PTEXT_CELL_REV == BV_CELL_REV, "bv_pileup_text_core.h restates the cell bits");
 static_assert(sizeof(BvPtextToken) == sizeof(bv_pileup_token) && sizeof(bv_pileup_token) == 24 && sizeof(BvPileupToken) == 24, "one token layout");
 
 namespace {
-
-// Samples of a tile: one 16-byte load a lane and byte plane.  The write kernel's LDS is the tile's four plane rows (5 KiB) and
-// the image (4 KiB): seventeen workgroups fit a CU's 160 KiB.
-constexpr uint32_t BV_PTEXT_TILE = 1024;
-constexpr uint32_t kImage = 4096;
-constexpr uint32_t kNoSample = 0xffffffffu;
-static_assert(BV_PTEXT_TILE == 64u * 16u, "a lane loads 16 cells of a tile");
-static_assert(kImage % 16u == 0 && kImage >= 64u * 6u + 32u, "a step of ranks fits the image behind a flush");
-
-struct PtextArgs {
-    const uint8_t *cell, *qual, *mapq;  // [.][pitch], 16-byte aligned rows; row k of the call is plane row row0 + k
-    const uint16_t *rank;
-    uint64_t pitch;
-    const BvPtextToken *tokens;         // the tokens of the call's rows, ascending by (pos, sample)
-    uint64_t n_tokens;
-    const uint8_t *tok_text;            // token t's text is tok_text[text_off ..)
-    const uint8_t *head;
-    const uint64_t *head_off;           // [n_rows + 1]
-    const uint64_t *row_off;            // [n_rows + 1] (write kernel)
-    uint4 *tile_sum;                    // [n_rows][n_tiles]: token bytes of M, B, R in the tile and its first sample without a
-                                        // token (kNoSample: none); after the scan x, y, z are those of the tiles before it
-    uint4 *row_sum;                     // [n_rows]: the row's
-    uint8_t *text;
-    uint32_t row0, pos0, n_rows, n_samples, n_tiles;
-};
-
-struct TileRows {
-    uint8_t cell[BV_PTEXT_TILE], qual[BV_PTEXT_TILE], mapq[BV_PTEXT_TILE];
-    uint16_t rank[BV_PTEXT_TILE];
-};
-
-// the tile's piece of the four plane rows to LDS; lanes beyond the tile's samples store zeros (rank 0: never looked at anyway)
-__device__ __forceinline__ void tile_stage(TileRows *t, const PtextArgs &a, uint32_t k, uint32_t tile, uint32_t cnt, uint32_t lane) {
-    const size_t at = (size_t)(a.row0 + k) * a.pitch + (size_t)tile * BV_PTEXT_TILE;
-    reinterpret_cast<uint4 *>(t->cell)[lane] = tile_load16(a.cell + at, cnt, lane);
-    reinterpret_cast<uint4 *>(t->qual)[lane] = tile_load16(a.qual + at, cnt, lane);
-    reinterpret_cast<uint4 *>(t->mapq)[lane] = tile_load16(a.mapq + at, cnt, lane);
-    tile_load16x2(a.rank + at, cnt, lane, reinterpret_cast<uint4 *>(t->rank) + 2u * lane);
-}
 
 __global__ __launch_bounds__(64) void bv_ptext_count_kernel(PtextArgs a) {
     __shared__ __attribute__((aligned(16))) TileRows rows;
@@ -120,76 +68,6 @@ __global__ __launch_bounds__(256) void bv_ptext_scan_kernel(PtextArgs a) {
     a.row_sum[k] = run;
 }
 
-// One list of the tile: LIST 0 .. 4 = M B Q R S
-template <uint32_t LIST>
-__device__ __forceinline__ void write_list(const PtextArgs &a, const TileRows &rows, uint8_t *image, uint64_t dst, uint64_t bytes, uint32_t tile, uint32_t cnt,
-                                  uint32_t pos, uint32_t lane) {
-    Piece p;
-    piece_open(p, a.text, dst, bytes);
-    for (uint32_t s0 = 0; s0 < cnt; s0 += 64u) {
-        const uint32_t s = s0 + lane, n_act = min(64u, cnt - s0), sample = tile * BV_PTEXT_TILE + s;
-        const bool active = s < cnt;
-        const uint32_t rk = active ? rows.rank[s] : 0u;
-        const uint8_t c = active ? rows.cell[s] : (uint8_t)0;
-        const uint8_t sep = bv_ptext_sep(LIST, sample, a.n_samples);
-        const uint64_t any = __ballot(rk != 0u);
-        uint32_t len = 1, at = 2u * lane, total = 2u * n_act;  // the token's bytes, its place behind the step's base, the step's bytes
-        uint32_t value = 0;       // M, R: the number; B, Q, S: the character
-        uint64_t tok_off = 0;     // B: an indel token's text
-        bool is_tok = false;
-        if (LIST == 0) value = rk ? rows.mapq[s] : 0u;
-        else if (LIST == 1) value = rk ? bv_ptext_base_char(c) : (uint8_t)'N';
-        else if (LIST == 2) value = rk ? bv_ptext_qual_char(rows.qual[s]) : (uint8_t)'!';
-        else if (LIST == 3) value = rk;
-        else value = rk ? bv_ptext_strand_char(c) : (uint8_t)'.';
-        if (any != 0ull && (LIST == 0 || LIST == 1 || LIST == 3)) {
-            if (LIST == 0 || LIST == 3) len = bv_ptext_digits(value);
-            if (LIST == 1 && rk && bv_ptext_is_indel(c)) {
-                const uint64_t t = bv_ptext_find(a.tokens, a.n_tokens, pos, sample);
-                if (t != a.n_tokens) { is_tok = true; len = a.tokens[t].text_len; tok_off = a.tokens[t].text_off; }  // (the count pass refused the row otherwise)
-            }
-            const uint32_t mine = active ? len + 1u : 0u, incl = wave_incl_scan(mine, lane);
-            at = incl - mine;
-            total = __shfl(incl, 63, 64);
-        }
-        if (p.fill + total > kImage) piece_flush(p, image, false, lane);
-        if (p.fill + total <= kImage) {
-            if (active) {
-                uint8_t *o = image + p.fill + at;
-                if (LIST == 0 || LIST == 3) bv_ptext_dec(value, o);
-                else if (LIST == 1 && is_tok) for (uint32_t i = 0; i < len; ++i) o[i] = a.tok_text[tok_off + i];
-                else o[0] = (uint8_t)value;
-                o[len] = sep;
-            }
-            p.fill += total;
-        } else if (LIST == 1) {
-            // tokens longer than the image can take in one step: sample by sample, the wave across the token's bytes
-            for (uint32_t j = 0; j < n_act; ++j) {
-                const uint32_t l1 = (uint32_t)__shfl(len, j, 64) + 1u, ch = __shfl(value, j, 64), sp = __shfl((uint32_t)sep, j, 64);
-                const bool tk = __shfl((int)is_tok, j, 64) != 0;
-                const uint64_t off = ((uint64_t)(uint32_t)__shfl((uint32_t)(tok_off >> 32), j, 64) << 32) | (uint32_t)__shfl((uint32_t)tok_off, j, 64);
-                for (uint32_t done = 0; done < l1;) {
-                    if (p.fill == kImage) {
-                        const uint32_t before = p.fill;
-                        piece_flush(p, image, false, lane);
-                        if (p.fill == before) return;  // (the piece has no bytes left to write: cannot happen behind the count pass)
-                        continue;
-                    }
-                    const uint32_t take = min(kImage - p.fill, l1 - done);
-                    for (uint32_t i = lane; i < take; i += 64u) {
-                        const uint32_t idx = done + i;
-                        image[p.fill + i] = idx + 1u == l1 ? (uint8_t)sp : tk ? a.tok_text[off + idx] : (uint8_t)ch;
-                    }
-                    p.fill += take;
-                    done += take;
-                }
-            }
-        }
-    }
-    piece_flush(p, image, true, lane);
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(64) void bv_ptext_write_kernel(PtextArgs a) {
     __shared__ __attribute__((aligned(16))) TileRows rows;
     __shared__ __attribute__((aligned(16))) uint8_t image[kImage];
@@ -214,16 +92,6 @@ __global__ __launch_bounds__(64) void bv_ptext_write_kernel(PtextArgs a) {
 
 }  // namespace
 
-// Per-engine state of bv_engine_pileup_text: the formatted text and what the kernels read beside the planes.
-struct BvPtextState {
-    DeviceText text;             // the formatted rows
-    uint8_t *d_tok = nullptr;    // the tokens of the call's rows; behind them an explicit tile's token text
-    uint8_t *d_head = nullptr;   // head_off u64 [n + 1], row_off u64 [n + 1], the heads
-    uint8_t *d_sum = nullptr;    // tile_sum uint4 [n][tiles], row_sum uint4 [n], depth + max_rank u32 [2 n], ref bytes [n]
-    uint8_t *d_rows = nullptr;   // an explicit tile's rows of the call, packed: cell, qual, mapq [n][P], rank [n][P]
-    size_t tok_cap = 0, head_cap = 0, sum_cap = 0, rows_cap = 0;
-};
-
 void bv_ptext_state_free(BvPtextState *t) {
     if (!t) return;
     (void)hipSetDevice(t->text.device);
@@ -232,20 +100,84 @@ void bv_ptext_state_free(BvPtextState *t) {
     delete t;
 }
 
-namespace {
+namespace bv_impl {
 
-// the tile of a call, resolved: device planes of the engine's pileup, or an explicit tile's host / device planes
-struct TileView {
-    const uint8_t *cell = nullptr, *qual = nullptr, *mapq = nullptr;
-    const uint16_t *rank = nullptr;
-    uint64_t pitch = 0;
-    uint32_t rows = 0, n_samples = 0, beg = 0;
-    const uint32_t *depth = nullptr;     // host [rows], or NULL: to be counted
-    const BvPtextToken *tokens = nullptr;  // host
-    uint64_t n_tokens = 0;
-    const uint8_t *h_text = nullptr, *d_text = nullptr;  // the tokens' text: an explicit tile's on the host, the pileup's on the device
-    bool explicit_tile = false, host_planes = false;
-};
+int ptext_planes(bv_engine *e, BvPtextState *t, const bv_pileup_text *in, const TileView &v, hipStream_t st, std::vector<uint8_t> &up, PtextPlanes &a) {
+    const uint32_t n = in->n_rows, N = v.n_samples;
+    a.cell = v.cell; a.qual = v.qual; a.mapq = v.mapq; a.rank = v.rank; a.pitch = v.pitch;
+    a.row0 = in->first_row;
+    if (!v.explicit_tile) return BV_OK;
+    const size_t P = up16(N), plane = (size_t)n * P;
+    const int rc = grow_device(e, &t->d_rows, &t->rows_cap, up256(5 * plane));
+    if (rc != BV_OK) return rc;
+    uint16_t *d_rank = reinterpret_cast<uint16_t *>(t->d_rows + 3 * plane);
+    const size_t r0 = (size_t)in->first_row * v.pitch;
+    if (v.host_planes) {
+        up.assign(5 * plane, 0);
+        for (uint32_t k = 0; k < n; ++k) {
+            std::memcpy(&up[(size_t)k * P], v.cell + r0 + (size_t)k * v.pitch, N);
+            std::memcpy(&up[plane + (size_t)k * P], v.qual + r0 + (size_t)k * v.pitch, N);
+            std::memcpy(&up[2 * plane + (size_t)k * P], v.mapq + r0 + (size_t)k * v.pitch, N);
+            std::memcpy(&up[3 * plane + 2 * (size_t)k * P], v.rank + r0 + (size_t)k * v.pitch, 2ull * N);
+        }
+        BV_HIP(e, hipMemcpyAsync(t->d_rows, up.data(), 5 * plane, hipMemcpyHostToDevice, st));
+    } else {
+        BV_HIP(e, hipMemsetAsync(t->d_rows, 0, 5 * plane, st));
+        BV_HIP(e, hipMemcpy2DAsync(t->d_rows, P, v.cell + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
+        BV_HIP(e, hipMemcpy2DAsync(t->d_rows + plane, P, v.qual + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
+        BV_HIP(e, hipMemcpy2DAsync(t->d_rows + 2 * plane, P, v.mapq + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
+        BV_HIP(e, hipMemcpy2DAsync(d_rank, 2 * P, v.rank + r0, 2 * v.pitch, 2ull * N, n, hipMemcpyDeviceToDevice, st));
+    }
+    a.cell = t->d_rows; a.qual = t->d_rows + plane; a.mapq = t->d_rows + 2 * plane; a.rank = d_rank; a.pitch = P;
+    a.row0 = 0;
+    return BV_OK;
+}
+
+// The checks of a bv_pileup_text that bv_engine_pileup_text and bv_engine_pileup_text_parts share, and the tile it names
+int ptext_check(bv_engine *e, const std::string &who, const bv_pileup_text *in, BvPileupView &pv, TileView &v) {
+    if (in->reserved_) return fail(e, BV_ERR_INVALID_ARG, who + "reserved_ must be zero");
+    if (!in->chrom || in->chrom_len < 1u || in->chrom_len > 255u) return fail(e, BV_ERR_INVALID_ARG, who + "chrom must have 1 to 255 bytes");
+    for (uint32_t i = 0; i < in->chrom_len; ++i)
+        if (in->chrom[i] == '\t' || in->chrom[i] == '\n' || in->chrom[i] == '\r' || in->chrom[i] == '\0')
+            return fail(e, BV_ERR_INVALID_ARG, who + "chrom must not hold a tab, a line break or a NUL");
+    bv_pileup_view(e->pileup, &pv);
+    if (const bv_pileup_tile *T = in->tile) {
+        auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
+        if (T->mem_kind != BV_MEM_HOST && T->mem_kind != BV_MEM_DEVICE) return fail(e, BV_ERR_INVALID_ARG, who + "mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
+        if (T->n_samples == 0 || T->pitch < T->n_samples || (T->pitch & 15ull)) return fail(e, BV_ERR_INVALID_ARG, who + "pitch must be >= n_samples >= 1 and a multiple of 16");
+        if (!T->cell || !T->qual || !T->mapq || !T->rank) return fail(e, BV_ERR_INVALID_ARG, who + "null plane");
+        if (misaligned(T->cell) || misaligned(T->qual) || misaligned(T->mapq) || misaligned(T->rank)) return fail(e, BV_ERR_INVALID_ARG, who + "planes must be 16-byte aligned");
+        if (T->beg == 0 || (uint64_t)T->beg + T->rows > (1ull << 32)) return fail(e, BV_ERR_INVALID_ARG, who + "positions beg .. beg + rows - 1 must be 1-based and fit 32 bits");
+        if (T->n_tokens && (!T->tokens || (!T->text && T->text_bytes))) return fail(e, BV_ERR_INVALID_ARG, who + "null tokens/text");
+        for (uint64_t k = 0; k < T->n_tokens; ++k) {
+            const bv_pileup_token &x = T->tokens[k];
+            if (k && !(T->tokens[k - 1].pos < x.pos || (T->tokens[k - 1].pos == x.pos && T->tokens[k - 1].sample < x.sample)))
+                return fail(e, BV_ERR_INVALID_ARG, who + "tokens must be strictly ascending by (pos, sample): token " + std::to_string(k) + " is not");
+            if (x.text_off > T->text_bytes || x.text_len > T->text_bytes - x.text_off)
+                return fail(e, BV_ERR_INVALID_ARG, who + "the text of token " + std::to_string(k) + " lies beyond text_bytes");
+        }
+        v.cell = T->cell; v.qual = T->qual; v.mapq = T->mapq; v.rank = T->rank; v.pitch = T->pitch;
+        v.rows = T->rows; v.n_samples = T->n_samples; v.beg = T->beg;
+        v.tokens = reinterpret_cast<const BvPtextToken *>(T->tokens); v.n_tokens = T->n_tokens; v.h_text = T->text;
+        v.explicit_tile = true; v.host_planes = T->mem_kind == BV_MEM_HOST;
+    } else {
+        if (!pv.done) return fail(e, BV_ERR_INVALID_ARG, who + "tile == NULL, and no completed bv_engine_pileup on this engine");
+        v.cell = pv.cell; v.qual = pv.qual; v.mapq = pv.mapq; v.rank = pv.rank; v.pitch = pv.pitch;
+        v.rows = pv.rows; v.n_samples = pv.n_samples; v.beg = pv.beg; v.depth = pv.depth;
+        v.tokens = reinterpret_cast<const BvPtextToken *>(pv.tokens); v.n_tokens = pv.n_tokens; v.d_text = pv.d_text;
+    }
+    if (v.beg == 0) return fail(e, BV_ERR_INVALID_ARG, who + "positions are 1-based: beg must not be 0");
+    if ((uint64_t)in->first_row + in->n_rows > v.rows)
+        return fail(e, BV_ERR_INVALID_ARG, who + "rows " + std::to_string(in->first_row) + " + " + std::to_string(in->n_rows) + " are beyond the tile's " + std::to_string(v.rows));
+    if (!pv.have_ref) return fail(e, BV_ERR_INVALID_ARG, who + "no reference set: bv_engine_pileup_set_reference comes first");
+    if (in->n_rows && (uint64_t)v.beg + in->first_row + in->n_rows - 1u > pv.ref_len)
+        return fail(e, BV_ERR_INVALID_ARG, who + "the rows end beyond the reference's " + std::to_string(pv.ref_len) + " bases");
+    return BV_OK;
+}
+
+}  // namespace bv_impl
+
+namespace {
 
 int ptext_format(bv_engine *e, BvPtextState *t, const bv_pileup_text *in, const TileView &v, const BvPileupView &pv, uint64_t *row_off, hipStream_t st) {
     const std::string who = "bv_engine_pileup_text: ";
@@ -279,37 +211,13 @@ int ptext_format(bv_engine *e, BvPtextState *t, const bv_pileup_text *in, const 
         BV_HIP(e, hipMemcpyAsync(t->d_tok, h_tok.data(), h_tok.size(), hipMemcpyHostToDevice, st));
     }
     PtextArgs a;
-    a.cell = v.cell; a.qual = v.qual; a.mapq = v.mapq; a.rank = v.rank; a.pitch = v.pitch;
-    a.row0 = in->first_row;
+    PtextPlanes pl;
     std::vector<uint8_t> up;
     uint32_t *d_depth = reinterpret_cast<uint32_t *>(t->d_sum + o_depth);
-    if (v.explicit_tile) {
-        // the call's rows, packed at pitch P with zeros behind the samples: what the depth kernel counts is the samples' alone
-        const size_t P = up16(N), plane = (size_t)n * P;
-        rc = grow_device(e, &t->d_rows, &t->rows_cap, up256(5 * plane));
-        if (rc != BV_OK) return rc;
-        uint16_t *d_rank = reinterpret_cast<uint16_t *>(t->d_rows + 3 * plane);
-        const size_t r0 = (size_t)in->first_row * v.pitch;
-        if (v.host_planes) {
-            up.assign(5 * plane, 0);
-            for (uint32_t k = 0; k < n; ++k) {
-                std::memcpy(&up[(size_t)k * P], v.cell + r0 + (size_t)k * v.pitch, N);
-                std::memcpy(&up[plane + (size_t)k * P], v.qual + r0 + (size_t)k * v.pitch, N);
-                std::memcpy(&up[2 * plane + (size_t)k * P], v.mapq + r0 + (size_t)k * v.pitch, N);
-                std::memcpy(&up[3 * plane + 2 * (size_t)k * P], v.rank + r0 + (size_t)k * v.pitch, 2ull * N);
-            }
-            BV_HIP(e, hipMemcpyAsync(t->d_rows, up.data(), 5 * plane, hipMemcpyHostToDevice, st));
-        } else {
-            BV_HIP(e, hipMemsetAsync(t->d_rows, 0, 5 * plane, st));
-            BV_HIP(e, hipMemcpy2DAsync(t->d_rows, P, v.cell + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
-            BV_HIP(e, hipMemcpy2DAsync(t->d_rows + plane, P, v.qual + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
-            BV_HIP(e, hipMemcpy2DAsync(t->d_rows + 2 * plane, P, v.mapq + r0, v.pitch, N, n, hipMemcpyDeviceToDevice, st));
-            BV_HIP(e, hipMemcpy2DAsync(d_rank, 2 * P, v.rank + r0, 2 * v.pitch, 2ull * N, n, hipMemcpyDeviceToDevice, st));
-        }
-        a.cell = t->d_rows; a.qual = t->d_rows + plane; a.mapq = t->d_rows + 2 * plane; a.rank = d_rank; a.pitch = P;
-        a.row0 = 0;
-        BV_HIP(e, bv_pileup_depth_launch(d_rank, P, n, d_depth, d_depth + n, st));
-    }
+    rc = ptext_planes(e, t, in, v, st, up, pl);
+    if (rc != BV_OK) return rc;
+    a.cell = pl.cell; a.qual = pl.qual; a.mapq = pl.mapq; a.rank = pl.rank; a.pitch = pl.pitch; a.row0 = pl.row0;
+    if (v.explicit_tile) BV_HIP(e, bv_pileup_depth_launch(a.rank, a.pitch, n, d_depth, d_depth + n, st));
     a.tokens = reinterpret_cast<const BvPtextToken *>(t->d_tok); a.n_tokens = nt;
     a.tok_text = v.explicit_tile ? t->d_tok + o_toktext : v.d_text;
     a.head = nullptr; a.head_off = nullptr; a.row_off = nullptr;
@@ -371,45 +279,9 @@ int bv_engine_pileup_text(bv_engine *e, const bv_pileup_text *in, uint64_t *row_
     // deliberately on entry, not behind the checks as in bv_engine_vcf_format: whatever comes of this call, the last text is gone
     if (e->ptext) e->ptext->text.formatted = false;
     if (!in || !row_off) return fail(e, BV_ERR_INVALID_ARG, who + "null in/row_off");
-    if (in->reserved_) return fail(e, BV_ERR_INVALID_ARG, who + "reserved_ must be zero");
-    if (!in->chrom || in->chrom_len < 1u || in->chrom_len > 255u) return fail(e, BV_ERR_INVALID_ARG, who + "chrom must have 1 to 255 bytes");
-    for (uint32_t i = 0; i < in->chrom_len; ++i)
-        if (in->chrom[i] == '\t' || in->chrom[i] == '\n' || in->chrom[i] == '\r' || in->chrom[i] == '\0')
-            return fail(e, BV_ERR_INVALID_ARG, who + "chrom must not hold a tab, a line break or a NUL");
     BvPileupView pv;
-    bv_pileup_view(e->pileup, &pv);
     TileView v;
-    if (const bv_pileup_tile *T = in->tile) {
-        auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; };
-        if (T->mem_kind != BV_MEM_HOST && T->mem_kind != BV_MEM_DEVICE) return fail(e, BV_ERR_INVALID_ARG, who + "mem_kind must be BV_MEM_HOST or BV_MEM_DEVICE");
-        if (T->n_samples == 0 || T->pitch < T->n_samples || (T->pitch & 15ull)) return fail(e, BV_ERR_INVALID_ARG, who + "pitch must be >= n_samples >= 1 and a multiple of 16");
-        if (!T->cell || !T->qual || !T->mapq || !T->rank) return fail(e, BV_ERR_INVALID_ARG, who + "null plane");
-        if (misaligned(T->cell) || misaligned(T->qual) || misaligned(T->mapq) || misaligned(T->rank)) return fail(e, BV_ERR_INVALID_ARG, who + "planes must be 16-byte aligned");
-        if (T->beg == 0 || (uint64_t)T->beg + T->rows > (1ull << 32)) return fail(e, BV_ERR_INVALID_ARG, who + "positions beg .. beg + rows - 1 must be 1-based and fit 32 bits");
-        if (T->n_tokens && (!T->tokens || (!T->text && T->text_bytes))) return fail(e, BV_ERR_INVALID_ARG, who + "null tokens/text");
-        for (uint64_t k = 0; k < T->n_tokens; ++k) {
-            const bv_pileup_token &x = T->tokens[k];
-            if (k && !(T->tokens[k - 1].pos < x.pos || (T->tokens[k - 1].pos == x.pos && T->tokens[k - 1].sample < x.sample)))
-                return fail(e, BV_ERR_INVALID_ARG, who + "tokens must be strictly ascending by (pos, sample): token " + std::to_string(k) + " is not");
-            if (x.text_off > T->text_bytes || x.text_len > T->text_bytes - x.text_off)
-                return fail(e, BV_ERR_INVALID_ARG, who + "the text of token " + std::to_string(k) + " lies beyond text_bytes");
-        }
-        v.cell = T->cell; v.qual = T->qual; v.mapq = T->mapq; v.rank = T->rank; v.pitch = T->pitch;
-        v.rows = T->rows; v.n_samples = T->n_samples; v.beg = T->beg;
-        v.tokens = reinterpret_cast<const BvPtextToken *>(T->tokens); v.n_tokens = T->n_tokens; v.h_text = T->text;
-        v.explicit_tile = true; v.host_planes = T->mem_kind == BV_MEM_HOST;
-    } else {
-        if (!pv.done) return fail(e, BV_ERR_INVALID_ARG, who + "tile == NULL, and no completed bv_engine_pileup on this engine");
-        v.cell = pv.cell; v.qual = pv.qual; v.mapq = pv.mapq; v.rank = pv.rank; v.pitch = pv.pitch;
-        v.rows = pv.rows; v.n_samples = pv.n_samples; v.beg = pv.beg; v.depth = pv.depth;
-        v.tokens = reinterpret_cast<const BvPtextToken *>(pv.tokens); v.n_tokens = pv.n_tokens; v.d_text = pv.d_text;
-    }
-    if (v.beg == 0) return fail(e, BV_ERR_INVALID_ARG, who + "positions are 1-based: beg must not be 0");
-    if ((uint64_t)in->first_row + in->n_rows > v.rows)
-        return fail(e, BV_ERR_INVALID_ARG, who + "rows " + std::to_string(in->first_row) + " + " + std::to_string(in->n_rows) + " are beyond the tile's " + std::to_string(v.rows));
-    if (!pv.have_ref) return fail(e, BV_ERR_INVALID_ARG, who + "no reference set: bv_engine_pileup_set_reference comes first");
-    if (in->n_rows && (uint64_t)v.beg + in->first_row + in->n_rows - 1u > pv.ref_len)
-        return fail(e, BV_ERR_INVALID_ARG, who + "the rows end beyond the reference's " + std::to_string(pv.ref_len) + " bases");
+    if (const int rc = ptext_check(e, who, in, pv, v); rc != BV_OK) return rc;
     // one workgroup per (row, tile): a launch's grid has room for 2^26 of them; the sums of a row are 32-bit
     if (v.n_samples >= (1u << 28) || (uint64_t)in->n_rows * ((v.n_samples + BV_PTEXT_TILE - 1u) / BV_PTEXT_TILE) >= (1ull << 26))
         return fail(e, BV_ERR_TOO_LARGE, who + "n_rows x tiles of a row reaches 2^26: format fewer rows a call");
@@ -431,3 +303,4 @@ int bv_engine_pileup_text_deflate(bv_engine *e, const uint64_t *block_off, uint3
 }
 
 }  // extern "C"
+

@@ -135,4 +135,49 @@ BV_PTEXT_FN uint64_t bv_ptext_row(const char *chrom, uint32_t chrom_len, uint32_
     return at;
 }
 
+// ROWS OF A PART (bv_engine_pileup_text_parts, include/basevar_amd_pileup_text_parts.h).  The row of position pos for the sample
+// part [s0, s1) of a tile is the row above of a tile that holds only columns s0 .. s1-1: Depth is the claimed cells among those
+// columns, the five lists run over those columns only (the part's last sample takes the list's '\t' or '\n'), and an indel cell
+// takes the token of (pos, ABSOLUTE sample): tokens keep the tile's sample numbers.  Nothing else differs.  cell / qual / mapq /
+// rank are the row's cells of the whole tile, indexed by absolute sample; columns outside [s0, s1) are not looked at.
+// Returns the row's bytes, or 0 where an indel cell of the part has no token: *bad_sample is that absolute sample then.
+BV_PTEXT_FN uint64_t bv_ptext_row_part(const char *chrom, uint32_t chrom_len, uint32_t pos, uint8_t ref, const uint8_t *cell, const uint8_t *qual,
+                                       const uint8_t *mapq, const uint16_t *rank, uint32_t s0, uint32_t s1, const BvPtextToken *tokens,
+                                       uint64_t n_tokens, const uint8_t *text, uint8_t *out, uint32_t *bad_sample) {
+    const uint32_t n = s1 - s0;
+    uint32_t depth = 0;
+    for (uint32_t s = s0; s < s1; ++s) depth += rank[s] != 0;
+    uint8_t tmp[BV_PTEXT_MAX_DEC];
+    uint64_t at = bv_ptext_head_bytes(chrom_len, pos, depth);
+    if (out) bv_ptext_head(chrom, chrom_len, pos, ref, depth, out);
+    for (uint32_t list = 0; list < BV_PTEXT_LISTS; ++list)
+        for (uint32_t s = s0; s < s1; ++s) {
+            const bool claimed = rank[s] != 0;
+            const uint8_t c = cell[s];
+            uint32_t len = 1;
+            const uint8_t *src = tmp;
+            switch (list) {
+            case 0: len = bv_ptext_dec(claimed ? mapq[s] : 0u, tmp); break;
+            case 1:
+                if (claimed && bv_ptext_is_indel(c)) {
+                    const uint64_t t = bv_ptext_find(tokens, n_tokens, pos, s);
+                    if (t == n_tokens) { *bad_sample = s; return 0; }
+                    src = text + tokens[t].text_off; len = tokens[t].text_len;
+                } else {
+                    tmp[0] = claimed ? bv_ptext_base_char(c) : (uint8_t)'N';
+                }
+                break;
+            case 2: tmp[0] = claimed ? bv_ptext_qual_char(qual[s]) : (uint8_t)'!'; break;
+            case 3: len = bv_ptext_dec(claimed ? rank[s] : 0u, tmp); break;
+            default: tmp[0] = claimed ? bv_ptext_strand_char(c) : (uint8_t)'.'; break;
+            }
+            if (out) {
+                for (uint32_t i = 0; i < len; ++i) out[at + i] = src[i];
+                out[at + len] = bv_ptext_sep(list, s - s0, n);
+            }
+            at += (uint64_t)len + 1u;
+        }
+    return at;
+}
+
 #endif  // BV_PILEUP_TEXT_CORE_H

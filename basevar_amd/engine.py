@@ -1006,13 +1006,8 @@ class BaseTypeEngine:
         return PileupBatch(out, None, self.last_variant_count() if n else 0, ms1, ms2, pos, depth, toks)
 
     # ---- batchfile rows, written on the device from piled-up planes (include/basevar_amd_pileup_text.h)
-    def pileup_text(self, chrom, first=0, n=None, tile=None):
-        """The batchfile rows of rows [first, first + n) of a tile (bv_engine_pileup_text): CHROM, pos, REF, Depth and the five
-        lists of mapq, base, quality, rank and strand tokens, as host/pileup.hpp's pileup_rows_text writes them.  `tile` None: the
-        last pileup where it lies on the device (n None: all its rows from `first`).  Else a dict: cell, qual, mapq (uint8) and
-        rank (uint16) planes [rows][pitch] as numpy arrays (host) or torch tensors on the engine's device, beg, n_samples, tokens
-        (_capi.PILEUP_TOKEN_DTYPE, ascending by (pos, sample)) and text (uint8, the tokens' text).  The text stays on the device
-        (pileup_text_fetch, pileup_text_deflate); returns row_off uint64 [n + 1]."""
+    def _pileup_text_request(self, who, chrom, first, n, tile):
+        """(bv_pileup_text, n rows, what it points to) of pileup_text's arguments"""
         chrom = chrom.encode() if isinstance(chrom, str) else bytes(chrom)
         keep, t = [], None
         if tile is not None:
@@ -1020,7 +1015,7 @@ class BaseTypeEngine:
             on_device = hasattr(planes[0], "data_ptr")
             if on_device:
                 if any(not p.is_cuda or not p.is_contiguous() for p in planes):
-                    raise ValueError("pileup_text: contiguous planes, all on the device or all numpy arrays")
+                    raise ValueError(who + ": contiguous planes, all on the device or all numpy arrays")
                 rows, pitch = int(planes[0].shape[0]), int(planes[0].shape[1])
                 ptrs = [int(p.data_ptr()) for p in planes]
             else:
@@ -1029,21 +1024,47 @@ class BaseTypeEngine:
                 ptrs = [p.ctypes.data for p in planes]
             tok = np.ascontiguousarray(tile.get("tokens", np.zeros(0, _capi.PILEUP_TOKEN_DTYPE)), _capi.PILEUP_TOKEN_DTYPE)
             text = np.ascontiguousarray(tile.get("text", np.zeros(0, np.uint8)), np.uint8)
-            keep = [planes, tok, text]
             t = _capi.PileupTile(ptrs[0], ptrs[1], ptrs[2], ptrs[3], tok.ctypes.data if tok.size else None, text.ctypes.data if text.size else None,
                                  int(tile.get("pitch", pitch)), int(tok.size), int(text.size), int(tile["beg"]), int(tile.get("rows", rows)), int(tile["n_samples"]),
                                  int(tile.get("mem_kind", _capi.BV_MEM_DEVICE if on_device else _capi.BV_MEM_HOST)))
+            keep = [planes, tok, text, t]
             total = int(t.rows)
         else:
             total = getattr(self, "_pileup_window_rows", 0)
         n = max(total - int(first), 0) if n is None else int(n)
-        req = _capi.PileupText(C.pointer(t) if t is not None else None, chrom, len(chrom), int(first), n, 0)
+        return _capi.PileupText(C.pointer(t) if t is not None else None, chrom, len(chrom), int(first), n, 0), n, keep
+
+    def pileup_text(self, chrom, first=0, n=None, tile=None):
+        """The batchfile rows of rows [first, first + n) of a tile (bv_engine_pileup_text): CHROM, pos, REF, Depth and the five
+        lists of mapq, base, quality, rank and strand tokens, as host/pileup.hpp's pileup_rows_text writes them.  `tile` None: the
+        last pileup where it lies on the device (n None: all its rows from `first`).  Else a dict: cell, qual, mapq (uint8) and
+        rank (uint16) planes [rows][pitch] as numpy arrays (host) or torch tensors on the engine's device, beg, n_samples, tokens
+        (_capi.PILEUP_TOKEN_DTYPE, ascending by (pos, sample)) and text (uint8, the tokens' text).  The text stays on the device
+        (pileup_text_fetch, pileup_text_deflate); returns row_off uint64 [n + 1]."""
+        req, n, keep = self._pileup_text_request("pileup_text", chrom, first, n, tile)
         row_off = np.zeros(n + 1, dtype=np.uint64)
         rc = self._lib.bv_engine_pileup_text(self._h, C.byref(req), row_off.ctypes.data, None)
         del keep
         if rc != 0:
             raise RuntimeError("bv_engine_pileup_text failed (%d): %s" % (rc, self._err()), rc)
         self._ptext_bytes = int(row_off[n])
+        return row_off
+
+    def pileup_text_parts(self, chrom, part_first, first=0, n=None, tile=None):
+        """pileup_text over sample parts of the tile (bv_engine_pileup_text_parts): part p is the samples [part_first[p],
+        part_first[p + 1]), and its rows are those of a tile that holds only these columns -- the Depth and the five lists are
+        the part's.  The text is part-major: part 0's n rows, then part 1's, ...; returns row_off uint64 [n_parts * n + 1], row k
+        of part p at index p * n + k.  pileup_text_fetch and pileup_text_deflate serve this text as they serve pileup_text's."""
+        req, n, keep = self._pileup_text_request("pileup_text_parts", chrom, first, n, tile)
+        pf = np.ascontiguousarray(part_first, dtype=np.uint32)
+        n_parts = max(int(pf.size) - 1, 0)
+        arg = _capi.PileupTextParts(C.pointer(req), pf.ctypes.data if pf.size else None, n_parts, 0)
+        row_off = np.zeros(n_parts * n + 1, dtype=np.uint64)
+        rc = self._lib.bv_engine_pileup_text_parts(self._h, C.byref(arg), row_off.ctypes.data, None)
+        del keep
+        if rc != 0:
+            raise RuntimeError("bv_engine_pileup_text_parts failed (%d): %s" % (rc, self._err()), rc)
+        self._ptext_bytes = int(row_off[n_parts * n])
         return row_off
 
     def pileup_text_fetch(self, dst_ptr=0, dst_capacity=0):

@@ -79,4 +79,7 @@ int bv_engine_pileup_text_deflate(bv_engine *e, const uint64_t *block_off, uint3
 }
 #endif
 
+/* rows over sample parts of one pileup, served by the fetch and deflate calls above: a header of its own */
+#include "basevar_amd_pileup_text_parts.h"
+
 #endif /* BASEVAR_AMD_PILEUP_TEXT_H */

@@ -8,6 +8,10 @@
 Whole calls, wall clock around a synchronised device; best and median of --repeat runs.
 
     python tools/pileup_text_bench.py [--repeat 5] [--no-host] [--out profiles/pileup_text_bench.txt]
+
+--parts times, instead, the rows over sample parts at 10,000 samples x 13,000 rows in one sitting, alternated --repeat times:
+pileup_text of the whole tile, pileup_text_parts with 50 parts of 200 samples, and 50 pileup_text calls on explicit 200-sample
+tiles (the planes' column slices, copied once beforehand); the lines are appended to --parts-out (profiles/pileup_batches_bench.txt).
 """
 import argparse
 import os
@@ -52,12 +56,61 @@ def timed(fn, repeat):
     return min(ts), float(np.median(ts))
 
 
+def parts_bench(a):
+    import basevar_amd as bv
+    import pileup_text_parts_model as ppm
+    import torch
+    n, rows, b = 10000, 13000, 200
+    eng = bv.BaseTypeEngine(max_sites=64, min_af_value=0.01, device=0, max_samples=16)
+    eng.pileup_set_reference(b"A" * (rows + 1))
+    tile = planes(n, rows)
+    part_first = list(range(0, n + 1, b))
+    pitch_b = (b + 15) // 16 * 16
+    slices = []
+    for s0 in part_first[:-1]:
+        sl = {k: torch.zeros((rows, pitch_b), dtype=tile[k].dtype, device="cuda") for k in ("cell", "qual", "mapq", "rank")}
+        for k in sl:
+            sl[k][:, :b] = tile[k][:, s0:s0 + b]
+        slices.append(dict(sl, beg=1, n_samples=b))
+    torch.cuda.synchronize()
+    legs = {"pileup_text, the whole tile": lambda: eng.pileup_text("chr1", tile=tile),
+            "pileup_text_parts, 50 parts of 200": lambda: eng.pileup_text_parts("chr1", part_first, tile=tile),
+            "50 pileup_text calls, 200-sample tiles": lambda: [eng.pileup_text("chr1", tile=sl) for sl in slices]}
+    # the timed parts text is the defined one: the last two rows of the last two parts against the serial restatement
+    off = eng.pileup_text_parts("chr1", part_first[-3:], rows - 2, 2, tile=tile)
+    got = eng.pileup_text_fetch().tobytes()
+    import pileup_text_model as ptm
+    last = ptm.Tile(b"chr1", rows - 1, n, *[tile[k][rows - 2:].cpu().numpy() for k in ("cell", "qual", "mapq", "rank")], {}, b"A" * (rows + 1))
+    assert got == ppm.parts_text(last, part_first[-3:])[0] and int(off[-1]) == len(got), "the device text is not the model's"
+    size = int(eng.pileup_text_parts("chr1", part_first, tile=tile)[-1])
+    for fn in legs.values():
+        fn()  # (the first calls allocate)
+    times = {k: [] for k in legs}
+    for _ in range(a.repeat):  # alternated
+        for k, fn in legs.items():
+            times[k].append(timed(fn, 1)[0])
+    lines = ["pileup_text_bench --parts: %d samples x %d rows, coverage %.2f, explicit device tiles, %d alternated runs a leg" % (n, rows, COVERAGE, a.repeat),
+             "  (each call packs its tile's rows with device copies first, as pileup_text_bench.txt's legs do; parts text %d bytes)" % size]
+    for k, ts in times.items():
+        lines.append("  %-40s best %9.2f  median %9.2f ms   runs: %s" % (k, min(ts), float(np.median(ts)), " ".join("%.2f" % t for t in ts)))
+    eng.close()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    os.makedirs(os.path.dirname(a.parts_out), exist_ok=True)
+    with open(a.parts_out, "a") as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pileup_text_bench.txt"))
+    ap.add_argument("--parts", action="store_true")
+    ap.add_argument("--parts-out", default=os.path.join(ROOT, "profiles", "pileup_batches_bench.txt"))
     a = ap.parse_args()
+    if a.parts:
+        return parts_bench(a)
     import basevar_amd as bv
     import pileup_text_model as ptm
     lines = ["pileup_text_bench: coverage %.2f, explicit device tiles, %d runs a leg (best / median ms)" % (COVERAGE, a.repeat)]
