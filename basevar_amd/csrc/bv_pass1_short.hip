@@ -309,59 +309,21 @@ __global__ __launch_bounds__(BV_WAVE *NW) void bv_p1s_stream_kernel(BvP1ShortArg
             if (lane < 12) reinterpret_cast<uint32_t *>(&a.summ[site])[lane] = w;
         }
         // ---- hand the histogram back, zeroed
-        {
-            uint4 *h4 = reinterpret_cast<uint4 *>(hist);
-#pragma unroll
-            for (int i = 0; i < BV_S_HWORDS / 4 / BV_WAVE; ++i) h4[i * BV_WAVE + lane] = make_uint4(0, 0, 0, 0);
-            if (lane < 2) h4[BV_S_HWORDS / 4 + lane] = make_uint4(0, 0, 0, 0);
-        }
+        bv_p1s_zero_hist<true>(hist, lane);
         bv_lrt_sync<0>();
-        if (n_cand == 64u) {
-            // flush this wave's candidates: one atomic reserves their places in the list
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_CANDS], n_cand);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if ((uint32_t)lane < n_cand) a.cand_list[base + (uint32_t)lane] = cand;
-            n_cand = 0;
-        }
-        if (n_easy == 64u) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_EASY], n_easy);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if ((uint32_t)lane < n_easy) a.easy_list[base + (uint32_t)lane] = easy;
-            n_easy = 0;
-        }
-        if (n_easy3 == 64u) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_EASY3], n_easy3);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if ((uint32_t)lane < n_easy3) a.easy3_list[base + (uint32_t)lane] = easy3;
-            n_easy3 = 0;
-        }
+        // a full list of this wave's candidates is flushed: one atomic reserves their places in the list
+        if (n_cand == 64u) { bv_p1s_flush_list(&a.counters[BV_CTR_CANDS], a.cand_list, cand, n_cand, lane); n_cand = 0; }
+        if (n_easy == 64u) { bv_p1s_flush_list(&a.counters[BV_CTR_EASY], a.easy_list, easy, n_easy, lane); n_easy = 0; }
+        if (n_easy3 == 64u) { bv_p1s_flush_list(&a.counters[BV_CTR_EASY3], a.easy3_list, easy3, n_easy3, lane); n_easy3 = 0; }
     }  // sites of the chunk
         if (st & N_HAVE) { c_site = n_site; c_end = n_end; st &= ~N_HAVE; }
         else st &= ~C_HAVE;
     }  // chunks
     }  // passes
     // what is left of this wave's candidate lists (the wait for an atomic's return drains the ring: empty by now)
-    if (n_cand != 0u) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_CANDS], n_cand);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if ((uint32_t)lane < n_cand) a.cand_list[base + (uint32_t)lane] = cand;
-    }
-    if (n_easy != 0u) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_EASY], n_easy);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if ((uint32_t)lane < n_easy) a.easy_list[base + (uint32_t)lane] = easy;
-    }
-    if (n_easy3 != 0u) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_EASY3], n_easy3);
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        if ((uint32_t)lane < n_easy3) a.easy3_list[base + (uint32_t)lane] = easy3;
-    }
+    if (n_cand != 0u) bv_p1s_flush_list(&a.counters[BV_CTR_CANDS], a.cand_list, cand, n_cand, lane);
+    if (n_easy != 0u) bv_p1s_flush_list(&a.counters[BV_CTR_EASY], a.easy_list, easy, n_easy, lane);
+    if (n_easy3 != 0u) bv_p1s_flush_list(&a.counters[BV_CTR_EASY3], a.easy3_list, easy3, n_easy3, lane);
 #ifdef BV_TEAM_DEBUG
     if (gridDim.x * NW <= 2048u && lane == 0) dbg_[gw] = (uint32_t)__builtin_amdgcn_s_memrealtime();
 #endif

@@ -96,10 +96,7 @@ __device__ __forceinline__ uint32_t bv_p2_fast_sweep(const BvPass2Args &a, uint3
             const uint32_t idx = base + u * NT + tid;
             if (tail && idx == n_chunks - 1) {
                 if (TAG) {
-                    vr0[u].x = bv_p2t_mask_tail(vr0[u].x, tail); vr0[u].y = bv_p2t_mask_tail(vr0[u].y, tail - 2);
-                    vr0[u].z = bv_p2t_mask_tail(vr0[u].z, tail - 4); vr0[u].w = bv_p2t_mask_tail(vr0[u].w, tail - 6);
-                    vr1[u].x = bv_p2t_mask_tail(vr1[u].x, tail - 8); vr1[u].y = bv_p2t_mask_tail(vr1[u].y, tail - 10);
-                    vr1[u].z = bv_p2t_mask_tail(vr1[u].z, tail - 12); vr1[u].w = bv_p2t_mask_tail(vr1[u].w, tail - 14);
+                    bv_p2t_mask_tail16(vr0[u], vr1[u], tail);
                 } else {
                     vb[u].x = bv_p2_mask_tail(vb[u].x, tail); vb[u].y = bv_p2_mask_tail(vb[u].y, tail - 4);
                     vb[u].z = bv_p2_mask_tail(vb[u].z, tail - 8); vb[u].w = bv_p2_mask_tail(vb[u].w, tail - 12);
@@ -110,28 +107,17 @@ __device__ __forceinline__ uint32_t bv_p2_fast_sweep(const BvPass2Args &a, uint3
                 const bv_u32x4 r0 = vr0[u], r1 = vr1[u], vmq = vm[u];
                 uint32_t c0, c1, c2, c3;
                 if (TAG) {
-                    c0 = bv_p2t_class4(L, r0.x, r0.y); c1 = bv_p2t_class4(L, r0.z, r0.w);
-                    c2 = bv_p2t_class4(L, r1.x, r1.y); c3 = bv_p2t_class4(L, r1.z, r1.w);
+                    bv_p2t_class16(L, r0, r1, c0, c1, c2, c3);
                 } else {
                     c0 = __builtin_amdgcn_perm(L, L, vb[u].x) ^ 0x80808080u; c1 = __builtin_amdgcn_perm(L, L, vb[u].y) ^ 0x80808080u;
                     c2 = __builtin_amdgcn_perm(L, L, vb[u].z) ^ 0x80808080u; c3 = __builtin_amdgcn_perm(L, L, vb[u].w) ^ 0x80808080u;
                 }
                 hi_acc |= (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) & hi_mask;
-                x[0] = bv_p2d_xm<0>(c0, vmq.x); x[1] = bv_p2d_xm<1>(c0, vmq.x); x[2] = bv_p2d_xm<2>(c0, vmq.x); x[3] = bv_p2d_xm<3>(c0, vmq.x);
-                x[4] = bv_p2d_xm<0>(c1, vmq.y); x[5] = bv_p2d_xm<1>(c1, vmq.y); x[6] = bv_p2d_xm<2>(c1, vmq.y); x[7] = bv_p2d_xm<3>(c1, vmq.y);
-                x[8] = bv_p2d_xm<0>(c2, vmq.z); x[9] = bv_p2d_xm<1>(c2, vmq.z); x[10] = bv_p2d_xm<2>(c2, vmq.z); x[11] = bv_p2d_xm<3>(c2, vmq.z);
-                x[12] = bv_p2d_xm<0>(c3, vmq.w); x[13] = bv_p2d_xm<1>(c3, vmq.w); x[14] = bv_p2d_xm<2>(c3, vmq.w); x[15] = bv_p2d_xm<3>(c3, vmq.w);
                 uint32_t y[16];
-                y[0] = bv_p2d_xr<0, 0>(c0, r0.x); y[1] = bv_p2d_xr<1, 1>(c0, r0.x); y[2] = bv_p2d_xr<2, 0>(c0, r0.y); y[3] = bv_p2d_xr<3, 1>(c0, r0.y);
-                y[4] = bv_p2d_xr<0, 0>(c1, r0.z); y[5] = bv_p2d_xr<1, 1>(c1, r0.z); y[6] = bv_p2d_xr<2, 0>(c1, r0.w); y[7] = bv_p2d_xr<3, 1>(c1, r0.w);
-                y[8] = bv_p2d_xr<0, 0>(c2, r1.x); y[9] = bv_p2d_xr<1, 1>(c2, r1.x); y[10] = bv_p2d_xr<2, 0>(c2, r1.y); y[11] = bv_p2d_xr<3, 1>(c2, r1.y);
-                y[12] = bv_p2d_xr<0, 0>(c3, r1.z); y[13] = bv_p2d_xr<1, 1>(c3, r1.z); y[14] = bv_p2d_xr<2, 0>(c3, r1.w); y[15] = bv_p2d_xr<3, 1>(c3, r1.w);
+                bv_p2d_xy16(c0, c1, c2, c3, vmq, r0, r1, x, y);
                 // (both histograms under one predicate -- the class byte is the same in x and y -- unless the row is deep and its mapq
                 // tally counts the dominant value)
-                if (DOM) {
-                    bv_lds_add16_dom<2>(x, hm, one, 0x200u, dom);
-                    bv_lds_add16<2>(y, hr, one, 0x200u);
-                } else bv_lds_add16x2<2>(x, y, hm, hr, one, 0x200u);
+                bv_p2d_add16(x, y, hm, hr, one, DOM, dom);
             }
             if (GROUPS) {
                 // the group tally of bv_p2g_stream_kernel: byte = group << 2 | base, bit 7 for "no call" / "no group"; X = byte << 8 |
@@ -708,10 +694,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2D_WAVES) void bv_pass2_dma_kernel(BvP
                     r1 = r0;
                 } else if (tail && chunk == n_chunks - 1) {
                     if (TAG) {
-                        r0.x = bv_p2t_mask_tail(r0.x, tail); r0.y = bv_p2t_mask_tail(r0.y, tail - 2);
-                        r0.z = bv_p2t_mask_tail(r0.z, tail - 4); r0.w = bv_p2t_mask_tail(r0.w, tail - 6);
-                        r1.x = bv_p2t_mask_tail(r1.x, tail - 8); r1.y = bv_p2t_mask_tail(r1.y, tail - 10);
-                        r1.z = bv_p2t_mask_tail(r1.z, tail - 12); r1.w = bv_p2t_mask_tail(r1.w, tail - 14);
+                        bv_p2t_mask_tail16(r0, r1, tail);
                     } else {
                         vb.x = bv_mask_tail_dword(vb.x, tail); vb.y = bv_mask_tail_dword(vb.y, tail - 4);
                         vb.z = bv_mask_tail_dword(vb.z, tail - 8); vb.w = bv_mask_tail_dword(vb.w, tail - 12);
@@ -721,8 +704,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2D_WAVES) void bv_pass2_dma_kernel(BvP
             // class bytes of the 16 cells (REF 0x00, ALT 0x01, neither >= 0x7F)
             uint32_t c0, c1, c2, c3;
             if (TAG) {
-                c0 = bv_p2t_class4(L, r0.x, r0.y); c1 = bv_p2t_class4(L, r0.z, r0.w);
-                c2 = bv_p2t_class4(L, r1.x, r1.y); c3 = bv_p2t_class4(L, r1.z, r1.w);
+                bv_p2t_class16(L, r0, r1, c0, c1, c2, c3);
             } else {
                 c0 = __builtin_amdgcn_perm(L, L, vb.x) ^ 0x80808080u; c1 = __builtin_amdgcn_perm(L, L, vb.y) ^ 0x80808080u;
                 c2 = __builtin_amdgcn_perm(L, L, vb.z) ^ 0x80808080u; c3 = __builtin_amdgcn_perm(L, L, vb.w) ^ 0x80808080u;
@@ -730,20 +712,9 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2D_WAVES) void bv_pass2_dma_kernel(BvP
             // ranks that do not fit the 256-rank window: remembered, the row is then re-done by sweeps (valid data has rank 0
             // in uncovered cells)
             hi_acc |= (r0.x | r0.y | r0.z | r0.w | r1.x | r1.y | r1.z | r1.w) & (TAG ? 0x1F001F00u : 0xFF00FF00u);
-            uint32_t x[16];
-            x[0] = bv_p2d_xm<0>(c0, vm.x); x[1] = bv_p2d_xm<1>(c0, vm.x); x[2] = bv_p2d_xm<2>(c0, vm.x); x[3] = bv_p2d_xm<3>(c0, vm.x);
-            x[4] = bv_p2d_xm<0>(c1, vm.y); x[5] = bv_p2d_xm<1>(c1, vm.y); x[6] = bv_p2d_xm<2>(c1, vm.y); x[7] = bv_p2d_xm<3>(c1, vm.y);
-            x[8] = bv_p2d_xm<0>(c2, vm.z); x[9] = bv_p2d_xm<1>(c2, vm.z); x[10] = bv_p2d_xm<2>(c2, vm.z); x[11] = bv_p2d_xm<3>(c2, vm.z);
-            x[12] = bv_p2d_xm<0>(c3, vm.w); x[13] = bv_p2d_xm<1>(c3, vm.w); x[14] = bv_p2d_xm<2>(c3, vm.w); x[15] = bv_p2d_xm<3>(c3, vm.w);
-            uint32_t y[16];
-            y[0] = bv_p2d_xr<0, 0>(c0, r0.x); y[1] = bv_p2d_xr<1, 1>(c0, r0.x); y[2] = bv_p2d_xr<2, 0>(c0, r0.y); y[3] = bv_p2d_xr<3, 1>(c0, r0.y);
-            y[4] = bv_p2d_xr<0, 0>(c1, r0.z); y[5] = bv_p2d_xr<1, 1>(c1, r0.z); y[6] = bv_p2d_xr<2, 0>(c1, r0.w); y[7] = bv_p2d_xr<3, 1>(c1, r0.w);
-            y[8] = bv_p2d_xr<0, 0>(c2, r1.x); y[9] = bv_p2d_xr<1, 1>(c2, r1.x); y[10] = bv_p2d_xr<2, 0>(c2, r1.y); y[11] = bv_p2d_xr<3, 1>(c2, r1.y);
-            y[12] = bv_p2d_xr<0, 0>(c3, r1.z); y[13] = bv_p2d_xr<1, 1>(c3, r1.z); y[14] = bv_p2d_xr<2, 0>(c3, r1.w); y[15] = bv_p2d_xr<3, 1>(c3, r1.w);
-            if (deep) {  // (a deep row: the dominant mapq's lanes are counted, not added one by one)
-                bv_lds_add16_dom<2>(x, h, one, 0x200u, dom);
-                bv_lds_add16<2>(y, h + 512, one, 0x200u);
-            } else bv_lds_add16x2<2>(x, y, h, h + 512, one, 0x200u);  // (both histograms under one predicate: the class byte is the same in x and y)
+            uint32_t x[16], y[16];
+            bv_p2d_xy16(c0, c1, c2, c3, vm, r0, r1, x, y);
+            bv_p2d_add16(x, y, h, h + 512, one, deep, dom);  // (a deep row: the dominant mapq's lanes are counted, not added one by one)
         }
         bv_lrt_sync<0>();
         uint32_t *hm = h, *hr = h + 512;

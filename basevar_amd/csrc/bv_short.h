@@ -1,6 +1,6 @@
 // bv_short.h -- pieces shared by the short-row pass-1 kernels (bv_pass1_short.hip: streaming kernel + solve kernel;
 // bv_pass1_fused.hip: both in one persistent kernel): the histogram geometry, the per-lane Fisher test and the one-lane
-// finish of a non-candidate site, the wave solver's scratch.
+// finish of a non-candidate site, the histogram hand-back and list flush of the streaming waves, the wave solver's scratch.
 #pragma once
 
 #include "bv_kernels.h"
@@ -146,6 +146,27 @@ __device__ __forceinline__ void bv_p1s_simple_site(const BvP1ShortArgs &a, const
     const uint4 *src = reinterpret_cast<const uint4 *>(&r);
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(r) / 16); ++i) dst[i] = src[i];
+}
+
+// ------------------------------------------------------------------------------ streaming waves: steps of a row's epilogue
+// (Its other steps -- the row's totals, the candidate test, the bins' compaction, the 12-lane summary store -- are written out in
+// bv_p1s_stream_kernel and in bv_f_stream_until_idle, the same text except where the reference base comes from and where a
+// candidate's bins go: as shared functions they moved the fused kernel's streaming loops by 2 % of their instructions, and both
+// kernels' register allocation is tuned to the instruction.  A fix to one copy goes into the other.)
+// hand a wave's histogram back zeroed: its 8 x 128 words (OVF: and the overflow rows behind them)
+template <bool OVF>
+__device__ __forceinline__ void bv_p1s_zero_hist(uint32_t *hist, int lane) {
+    uint4 *h4 = reinterpret_cast<uint4 *>(hist);
+#pragma unroll
+    for (int i = 0; i < BV_S_HWORDS / 4 / BV_WAVE; ++i) h4[i * BV_WAVE + lane] = make_uint4(0, 0, 0, 0);
+    if (OVF && lane < 2) h4[BV_S_HWORDS / 4 + lane] = make_uint4(0, 0, 0, 0);
+}
+// flush a wave's list of n <= 64 sites (lane k holds the k-th): one atomic reserves their places in `list`
+__device__ __forceinline__ void bv_p1s_flush_list(uint32_t *counter, uint32_t *list, uint32_t mine, uint32_t n, int lane) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(counter, n);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if ((uint32_t)lane < n) list[base + (uint32_t)lane] = mine;
 }
 
 // Candidates that need the wave solver (shallow sites, phred-0 calls, > 128 bins, min_af <= 0): one wave per site.

@@ -374,6 +374,29 @@ __device__ __forceinline__ uint32_t bv_p2d_xr(uint32_t cls4, uint32_t r2) {  // 
     constexpr uint32_t SEL = 0x0C0C0000u | ((4u + J) << 8) | (uint32_t)(2 * H);
     return __builtin_amdgcn_perm(cls4, r2, SEL);
 }
+// x (mapq histogram) and y (rank histogram) of a lane's 16 cells: c0..c3 their class bytes, mq their mapq bytes, r0 / r1 the rank
+// words of cells 0-7 / 8-15.  The one copy for bv_pass2_kernel, bv_pass2_dma_kernel (bv_pass2.hip: their code is unchanged by it)
+// and the fused short-row kernel's two pass-2 tallies (bv_fused_stream.h, bv_fused_p2rows.h).
+__device__ __forceinline__ void bv_p2d_xy16(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, const bv_u32x4 &mq, const bv_u32x4 &r0,
+                                            const bv_u32x4 &r1, uint32_t x[16], uint32_t y[16]) {
+    x[0] = bv_p2d_xm<0>(c0, mq.x); x[1] = bv_p2d_xm<1>(c0, mq.x); x[2] = bv_p2d_xm<2>(c0, mq.x); x[3] = bv_p2d_xm<3>(c0, mq.x);
+    x[4] = bv_p2d_xm<0>(c1, mq.y); x[5] = bv_p2d_xm<1>(c1, mq.y); x[6] = bv_p2d_xm<2>(c1, mq.y); x[7] = bv_p2d_xm<3>(c1, mq.y);
+    x[8] = bv_p2d_xm<0>(c2, mq.z); x[9] = bv_p2d_xm<1>(c2, mq.z); x[10] = bv_p2d_xm<2>(c2, mq.z); x[11] = bv_p2d_xm<3>(c2, mq.z);
+    x[12] = bv_p2d_xm<0>(c3, mq.w); x[13] = bv_p2d_xm<1>(c3, mq.w); x[14] = bv_p2d_xm<2>(c3, mq.w); x[15] = bv_p2d_xm<3>(c3, mq.w);
+    y[0] = bv_p2d_xr<0, 0>(c0, r0.x); y[1] = bv_p2d_xr<1, 1>(c0, r0.x); y[2] = bv_p2d_xr<2, 0>(c0, r0.y); y[3] = bv_p2d_xr<3, 1>(c0, r0.y);
+    y[4] = bv_p2d_xr<0, 0>(c1, r0.z); y[5] = bv_p2d_xr<1, 1>(c1, r0.z); y[6] = bv_p2d_xr<2, 0>(c1, r0.w); y[7] = bv_p2d_xr<3, 1>(c1, r0.w);
+    y[8] = bv_p2d_xr<0, 0>(c2, r1.x); y[9] = bv_p2d_xr<1, 1>(c2, r1.x); y[10] = bv_p2d_xr<2, 0>(c2, r1.y); y[11] = bv_p2d_xr<3, 1>(c2, r1.y);
+    y[12] = bv_p2d_xr<0, 0>(c3, r1.z); y[13] = bv_p2d_xr<1, 1>(c3, r1.z); y[14] = bv_p2d_xr<2, 0>(c3, r1.w); y[15] = bv_p2d_xr<3, 1>(c3, r1.w);
+}
+// both [class][256] histograms (mapq: hm, ranks: hr) from x / y.  deep (a wave-uniform choice per row: an eighth of
+// its cells are REF / ALT reads): the dominant mapq's lanes are counted, not added one by one; every other row: both histograms
+// under ONE predicate -- the class byte is the same in x and y
+__device__ __forceinline__ void bv_p2d_add16(const uint32_t x[16], const uint32_t y[16], uint32_t *hm, uint32_t *hr, uint32_t one, bool deep, uint32_t &dom) {
+    if (deep) {
+        bv_lds_add16_dom<2>(x, hm, one, 0x200u, dom);
+        bv_lds_add16<2>(y, hr, one, 0x200u);
+    } else bv_lds_add16x2<2>(x, y, hm, hr, one, 0x200u);
+}
 
 // ---- the tagged rank plane (BV_SLAB_RPR_TAGGED, include/basevar_amd.h): rank | base << 13 | nocall << 15 per 16-bit word.
 // what the OR of a row's rank dwords must not hold in the perm form (a rank >= 256), per layout
@@ -393,4 +416,15 @@ __device__ __forceinline__ uint32_t bv_p2t_class4(uint32_t L, uint32_t r01, uint
 __device__ __forceinline__ uint32_t bv_p2t_mask_tail(uint32_t r2, int keep) {
     return keep >= 2 ? r2 : (keep <= 0 ? 0x80008000u : ((r2 & 0xFFFFu) | 0x80000000u));
 }
-
+// ... of the 16 cells of a row's last chunk (r0: cells 0-7, r1: cells 8-15; tail = n_samples & 15, not 0)
+__device__ __forceinline__ void bv_p2t_mask_tail16(bv_u32x4 &r0, bv_u32x4 &r1, int tail) {
+    r0.x = bv_p2t_mask_tail(r0.x, tail); r0.y = bv_p2t_mask_tail(r0.y, tail - 2);
+    r0.z = bv_p2t_mask_tail(r0.z, tail - 4); r0.w = bv_p2t_mask_tail(r0.w, tail - 6);
+    r1.x = bv_p2t_mask_tail(r1.x, tail - 8); r1.y = bv_p2t_mask_tail(r1.y, tail - 10);
+    r1.z = bv_p2t_mask_tail(r1.z, tail - 12); r1.w = bv_p2t_mask_tail(r1.w, tail - 14);
+}
+// the class bytes of a lane's 16 cells from the tags of their rank words
+__device__ __forceinline__ void bv_p2t_class16(uint32_t L, const bv_u32x4 &r0, const bv_u32x4 &r1, uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3) {
+    c0 = bv_p2t_class4(L, r0.x, r0.y); c1 = bv_p2t_class4(L, r0.z, r0.w);
+    c2 = bv_p2t_class4(L, r1.x, r1.y); c3 = bv_p2t_class4(L, r1.z, r1.w);
+}
