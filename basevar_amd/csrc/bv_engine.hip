@@ -37,7 +37,7 @@ void set_global_error(const std::string &m) {
     g_err = m;
 }
 
-// ---- the host libm's log() table (BvTables::hostlog, bv_log_host in bv_device.h) ----------------------------------
+// ---- the host libm's log() table (BvTables::hostlog, bv_log_host in bv_hostlog.h) ----------------------------------
 // The reference's EM takes log() of per-sample marginals with the host's libm (algorithm.h:243) and compares /
 // truncates sums of them; at tie-prone shallow sites the last bit of log() decides the call.  The device replays those
 // sites with the host's own algorithm: its data table is looked up in the libm this process has loaded, and it is used

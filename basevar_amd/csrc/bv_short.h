@@ -1,6 +1,6 @@
 // bv_short.h -- pieces shared by the short-row pass-1 kernels (bv_pass1_short.hip: streaming kernel + solve kernel;
-// bv_pass1_fused.hip: both in one persistent kernel): the histogram geometry, the per-lane Fisher test and the one-lane
-// finish of a non-candidate site, the histogram hand-back and list flush of the streaming waves, the wave solver's scratch.
+// bv_pass1_fused.hip: both in one persistent kernel): the histogram geometry, the one-lane finish of a non-candidate site
+// (its per-lane Fisher test: bv_fisher.h), the histogram hand-back and list flush of the streaming waves, the wave solver's scratch.
 #pragma once
 
 #include "bv_kernels.h"
@@ -13,63 +13,6 @@
 #define BV_S_OVF 8                           /* + per-row counts of covered cells with phred >= 128 (invalid input) */
 #define BV_S_SLOT_WORDS 512                  /* one slot of U = 1: 1 KiB of calls, then 1 KiB of phreds (U x that for U chunks per lane) */
 #define BV_S_SIMPLE_MAX_TABLES 32            /* a non-candidate site's strand table has at most this many Fisher tables */
-
-
-// ------------------------------------------------------------------------------ per-lane Fisher test
-// kt_fisher_exact (two-sided), htslib/kfunc.c:245-313, one table family per LANE: the walk of kfunc.c:291-307 with its
-// incremental hypergeo_acc (kfunc.c:220-243: multiplicative update, re-seeded from log-factorials whenever n11 % 11 == 0
-// or the table's n22 is 0).  log(k!) comes from the engine's table of the host's lgamma (the reference's own values).
-struct BvHgAcc {
-    int n11, n1_, n_1, n;
-    double p;
-};
-__device__ __forceinline__ double bv_lbinom_lane(const BvLnTab &T, int n, int k) {
-    if (k == 0 || n == k) return 0;
-    return bv_lnfact(T, n) - bv_lnfact(T, k) - bv_lnfact(T, n - k);
-}
-__device__ __forceinline__ double bv_hypergeo_lane(const BvLnTab &T, int n11, int n1_, int n_1, int n) {
-    return exp(bv_lbinom_lane(T, n1_, n11) + bv_lbinom_lane(T, n - n1_, n_1 - n11) - bv_lbinom_lane(T, n, n_1));
-}
-__device__ __forceinline__ double bv_hgacc_step(const BvLnTab &T, int n11, BvHgAcc &x) {  // hypergeo_acc(n11, 0, 0, 0, aux)
-    if (n11 % 11 && n11 + x.n - x.n1_ - x.n_1) {
-        if (n11 == x.n11 + 1) {
-            x.p *= (double)(x.n1_ - x.n11) / n11 * (x.n_1 - x.n11) / (n11 + x.n - x.n1_ - x.n_1);
-            x.n11 = n11;
-            return x.p;
-        }
-        if (n11 == x.n11 - 1) {
-            x.p *= (double)x.n11 / (x.n1_ - n11) * (x.n11 + x.n - x.n1_ - x.n_1) / (x.n_1 - n11);
-            x.n11 = n11;
-            return x.p;
-        }
-    }
-    x.n11 = n11;
-    x.p = bv_hypergeo_lane(T, x.n11, x.n1_, x.n_1, x.n);
-    return x.p;
-}
-__device__ inline double bv_fisher_two_sided_lane(int n11, int n12, int n21, int n22, const BvLnTab &T) {
-    const int n1_ = n11 + n12, n_1 = n11 + n21, n = n11 + n12 + n21 + n22;
-    const int max = (n_1 < n1_) ? n_1 : n1_;
-    int min = n1_ + n_1 - n;
-    if (min < 0) min = 0;
-    if (min == max) return 1.;
-    BvHgAcc x;
-    x.n11 = n11; x.n1_ = n1_; x.n_1 = n_1; x.n = n;
-    x.p = bv_hypergeo_lane(T, n11, n1_, n_1, n);
-    const double q = x.p;
-    if (q == 0.0) return 0.0;  // kfunc.c:260-289: two = 0
-    double p, left, right;
-    int i, j;
-    p = bv_hgacc_step(T, min, x);
-    for (left = 0., i = min + 1; p < 0.99999999 * q && i <= max; ++i) { left += p; p = bv_hgacc_step(T, i, x); }
-    if (p < 1.00000001 * q) left += p;
-    p = bv_hgacc_step(T, max, x);
-    for (right = 0., j = max - 1; p < 0.99999999 * q && j >= 0; --j) { right += p; p = bv_hgacc_step(T, j, x); }
-    if (p < 1.00000001 * q) right += p;
-    double two = left + right;
-    if (two > 1.) two = 1.;
-    return two;
-}
 
 // ------------------------------------------------------------------------------ solve kernels
 // A non-candidate site (hom-ref or uncovered), finished by ONE LANE: depths, flags, one small Fisher test.
@@ -124,15 +67,8 @@ __device__ __forceinline__ void bv_p1s_simple_site(const BvP1ShortArgs &a, const
             if (b == ref) { c_rf += fwd[b]; c_rr += rev[b]; } else { c_af += fwd[b]; c_ar += rev[b]; }
         }
         if (!(a.flags & BV_FLAG_SKIP_FISHER)) {
-            // strand_bias tail, src/basetype.cpp:277-286 (see bv_strand_bias_wave for the SOR overflow note)
-            double fs = -10 * log10(bv_fisher_two_sided_lane((int)c_rf, (int)c_rr, (int)c_af, (int)c_ar, lnfact));
-            if (isinf(fs)) fs = 10000;
-            else if (fs == 0) fs = 0.0;
-            const int den = (int)(c_rr * c_af), num = (int)(c_rf * c_ar);
-            if ((unsigned long long)c_rr * c_af > 0x7fffffffull || (unsigned long long)c_rf * c_ar > 0x7fffffffull)
-                flags |= BV_SITE_SOR_OVERFLOW;
-            r.cvg_fs = fs;
-            r.cvg_sor = (c_rr != 0u && c_af != 0u) ? (double)num / (double)den : 10000;
+            bv_strand_bias_tail(bv_fisher_two_sided_lane((int)c_rf, (int)c_rr, (int)c_af, (int)c_ar, lnfact), c_rf, c_rr, c_af, c_ar,
+                                &r.cvg_fs, &r.cvg_sor, &flags);
             r.cvg_sb[0] = c_rf; r.cvg_sb[1] = c_rr; r.cvg_sb[2] = c_af; r.cvg_sb[3] = c_ar;
         }
         r.status = flags;

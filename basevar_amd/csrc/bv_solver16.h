@@ -8,221 +8,17 @@
 // registers of its 16 lanes (bin i in lane i % 16, slot i / 16: at most 8 x 16 = 128 bins -- deeper or shallower
 // candidates, or ones with a phred-0 call, keep the wave solver).
 //
-// Same reference functions, same arithmetic per term as the wave solver (bv_device.h / bv_solver.h); only the ORDER of
+// Same reference functions, same arithmetic per term as the wave solver (bv_em.h, bv_lrt.h / bv_solver.h); only the ORDER of
 // the floating-point sums over bins / tables / phred values differs (tree inside a row instead of a scan over the wave),
 // i.e. results agree with the wave solver to ~1e-15 relative, far inside the 1e-6 parity bar.
 //
 // Cross-lane rules: everything "uniform" here is uniform per GROUP and lives in VGPRs; control flow may diverge between
 // the four groups of a wave (the compiler masks), so only row-local operations are used: DPP quad_perm / row_mirror /
-// row_shr, and ballots cut to the group's 16 bits.
+// row_shr, and ballots cut to the group's 16 bits (the bv_g16_* primitives of bv_wave.h).  The group's Fisher test and rank-sum
+// window sit beside their wave forms: bv_fisher.h, bv_ranksum.h.
 #pragma once
 
 #include "bv_solver.h"
-
-
-// ------------------------------------------------------------------ row-local primitives
-#define BV_DPP_QUAD_XOR1 0xB1 /* quad_perm [1,0,3,2] */
-#define BV_DPP_QUAD_XOR2 0x4E /* quad_perm [2,3,0,1] */
-#define BV_DPP_ROW_MIRROR 0x140
-#define BV_DPP_ROW_HALF_MIRROR 0x141
-
-// All-reduce over the 16 lanes of a row.  Every step pairs lanes symmetrically (i <-> i^1, i^2, 7-i, 15-i) and IEEE
-// addition is commutative, so all 16 lanes end with the bit-identical sum -- no broadcast needed.
-// L: the lanes that own the item -- 16 (a whole DPP row), or 8 / 4 (aligned parts of one: the pop-group solver for small groups,
-// bv_p2g_solve_small_kernel): the first log2(L) steps of the same pairing.
-template <int L = 16>
-__device__ __forceinline__ double bv_g16_sum(double v) {
-    v += bv_dpp_f64<BV_DPP_QUAD_XOR1, 0xf>(v);
-    v += bv_dpp_f64<BV_DPP_QUAD_XOR2, 0xf>(v);
-    if (L >= 8) v += bv_dpp_f64<BV_DPP_ROW_HALF_MIRROR, 0xf>(v);
-    if (L >= 16) v += bv_dpp_f64<BV_DPP_ROW_MIRROR, 0xf>(v);
-    return v;
-}
-__device__ __forceinline__ uint32_t bv_g16_sum_u32(uint32_t v) {
-    v += (uint32_t)bv_dpp_i32<BV_DPP_QUAD_XOR1, 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_QUAD_XOR2, 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_HALF_MIRROR, 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_MIRROR, 0xf>(0, (int)v);
-    return v;
-}
-__device__ __forceinline__ unsigned long long bv_g16_sum_u64(unsigned long long v) {
-    v += bv_dpp_u64<BV_DPP_QUAD_XOR1, 0xf>(v);
-    v += bv_dpp_u64<BV_DPP_QUAD_XOR2, 0xf>(v);
-    v += bv_dpp_u64<BV_DPP_ROW_HALF_MIRROR, 0xf>(v);
-    v += bv_dpp_u64<BV_DPP_ROW_MIRROR, 0xf>(v);
-    return v;
-}
-__device__ __forceinline__ int bv_g16_max_i32(int v) {
-    v = max(v, bv_dpp_i32<BV_DPP_QUAD_XOR1, 0xf>(v, v));
-    v = max(v, bv_dpp_i32<BV_DPP_QUAD_XOR2, 0xf>(v, v));
-    v = max(v, bv_dpp_i32<BV_DPP_ROW_HALF_MIRROR, 0xf>(v, v));
-    v = max(v, bv_dpp_i32<BV_DPP_ROW_MIRROR, 0xf>(v, v));
-    return v;
-}
-__device__ __forceinline__ int bv_g16_min_i32(int v) {
-    v = min(v, bv_dpp_i32<BV_DPP_QUAD_XOR1, 0xf>(v, v));
-    v = min(v, bv_dpp_i32<BV_DPP_QUAD_XOR2, 0xf>(v, v));
-    v = min(v, bv_dpp_i32<BV_DPP_ROW_HALF_MIRROR, 0xf>(v, v));
-    v = min(v, bv_dpp_i32<BV_DPP_ROW_MIRROR, 0xf>(v, v));
-    return v;
-}
-// inclusive prefix PRODUCTS inside the row
-__device__ __forceinline__ double bv_g16_incl_scan_prod_f64(double v) {
-    v *= bv_dpp_f64_one<BV_DPP_ROW_SHR(1), 0xf>(v);
-    v *= bv_dpp_f64_one<BV_DPP_ROW_SHR(2), 0xf>(v);
-    v *= bv_dpp_f64_one<BV_DPP_ROW_SHR(4), 0xf>(v);
-    v *= bv_dpp_f64_one<BV_DPP_ROW_SHR(8), 0xf>(v);
-    return v;
-}
-// inclusive prefix sum inside the row (lane 15 of the row ends with the total)
-__device__ __forceinline__ uint32_t bv_g16_incl_scan_u32(uint32_t v) {
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_SHR(1), 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_SHR(2), 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_SHR(4), 0xf>(0, (int)v);
-    v += (uint32_t)bv_dpp_i32<BV_DPP_ROW_SHR(8), 0xf>(0, (int)v);
-    return v;
-}
-// the 16 ballot bits of this lane's group
-__device__ __forceinline__ uint32_t bv_g16_ballot(bool pred, int lane) {
-    return (uint32_t)(__ballot(pred) >> (lane & 48)) & 0xFFFFu;
-}
-// value held by lane `k` (0..15, uniform in the group) of this lane's group
-__device__ __forceinline__ double bv_g16_bcast_f64(double v, int k, int lane) {
-    const int src = ((lane & 48) | (k & 15)) << 2;
-    const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-// ------------------------------------------------------------------ Fisher exact test, 16 tables per round
-// kt_fisher_exact (two-sided), htslib/kfunc.c:197-313; see bv_fisher_two_sided_wave for the formulation.  `T` as there.
-__device__ inline double bv_fisher_two_sided_g16(int n11, int n12, int n21, int n22, int lane, const BvLnTab &T) {
-    const int gl = lane & 15;
-    const int n1_ = n11 + n12, n_1 = n11 + n21, n = n11 + n12 + n21 + n22;
-    const int imax = (n_1 < n1_) ? n_1 : n1_;
-    int imin = n1_ + n_1 - n;
-    if (imin < 0) imin = 0;
-    if (imin == imax) return 1.;
-    {
-        // a row margin of at most 12 reads: product form, at most 13 tables -- one per lane of the group
-        const int n2_ = n21 + n22, n_2 = n - n_1;
-        const bool alt_row = n2_ <= n1_;
-        const int m = alt_row ? n2_ : n1_, jobs = alt_row ? n21 : n11;
-        if (m <= 12) {
-            const int jmin = max(0, m - n_2), jmax = min(m, n_1);
-            const int j = jmin + gl;
-            const bool have = j <= jmax;
-            double pn = 1.0, pd = 1.0;
-            for (int t = 0; t < m; ++t) {
-                const double num = (t < j) ? (double)(n_1 - t) * (double)(m - t) : (double)(n_2 - (t - j));
-                const double den = (t < j) ? (double)(n - t) * (double)(t + 1) : (double)(n - t);
-                pn *= num;
-                pd *= den;
-            }
-            const double p = have ? pn / pd : 0.;
-            const double q = bv_g16_bcast_f64(p, jobs - jmin, lane);
-            if (q == 0.0) return 0.0;
-            const double lo = 0.99999999 * q, hi = 1.00000001 * q;
-            const bool viol = have && !(p < lo);
-            const uint32_t vm = bv_g16_ballot(viol, lane);  // never empty: the observed table is in it
-            double two = bv_g16_sum(viol ? 0. : p);
-            const double pL = bv_g16_bcast_f64(p, __builtin_ctz(vm), lane), pR = bv_g16_bcast_f64(p, 31 - __builtin_clz(vm), lane);
-            if (pL < hi) two += pL;
-            if (pR < hi) two += pR;
-            return two > 1. ? 1. : two;
-        }
-    }
-    BvHyper h;
-    bv_hyper_init(h, T, n1_, n_1, n);
-    const int R = imax - imin + 1;
-    // Up to 128 tables (no tails to skip: the blocks below are those of [imin, imax]): the lane's seed table is known here,
-    // and its four log-factorials travel with those of q instead of making a memory trip of their own after it.
-    const bool narrow = R <= 8 * 16;
-    const int i0n = imin + gl * ((R + 15) >> 4);
-    double seed_n = (narrow && i0n <= imax) ? bv_hyper_logp(h, i0n) : 0.;
-    asm volatile("" : "+v"(seed_n));  // (read here, not where it is used)
-    const double logq = bv_hyper_logp(h, n11);
-    if (exp(logq) == 0.0) return 0.0;  // kfunc.c:260-289
-    // q below 2^-511: every table is carried scaled by 2^512 (BV_FISHER_SHIFT, bv_device.h) and the sum scaled back at the end.
-    // Unscaled, a block that starts at a table of q * e^-60 (where a probed tail ends) is seeded with exp() == 0 once q nears
-    // the smallest double, and stays 0 while the true terms rise past q: the tail's sum was lost, and with it the observed
-    // table when it lay in that block (found by tests/test_gpu_strand_tables.py, "probed R=max q300": p came out halved).
-    const double shift = bv_fisher_shift(logq);
-    const double q = exp(logq + shift);
-    const double lo = 0.99999999 * q, hi = 1.00000001 * q;
-    const int INF = 0x7fffffff;
-    int wl = imin, wr = imax;
-    if (!narrow) {
-        // many tables: skip the far tails whose terms are below q * 2^-86 (16-point probes on either side)
-        const double cut = logq - 60.0;
-        {
-            const int span = n11 - imin, step = span / 15 + 1;
-            const int i = imin + gl * step;
-            const bool below = (i <= n11) && (bv_hyper_logp(h, min(i, n11)) < cut);
-            const int last = bv_g16_max_i32(below ? i : -1);
-            if (last >= 0) wl = last;
-        }
-        {
-            const int span = imax - n11, step = span / 15 + 1;
-            const int i = imax - gl * step;
-            const bool below = (i >= n11) && (bv_hyper_logp(h, max(i, n11)) < cut);
-            const int first = bv_g16_min_i32(below ? i : INF);
-            if (first != INF) wr = first;
-        }
-    }
-    // The tables of [wl, wr] in 16 consecutive blocks, one per lane: the lane seeds its first table from log-factorials and
-    // walks its block with the multiplicative step of the reference's own walk (hypergeo_acc, kfunc.c:226-231) -- at most
-    // ~25 steps from an exact seed (the reference re-seeds every 11).  Per table: one division and a few multiplies on ONE
-    // lane, against a 16-lane prefix product, two broadcasts and a ballot per 16 tables in the round form this replaces
-    // (the Fisher tests were 45 % of the solver's instructions).
-    const int Lb = (wr - wl + 16) >> 4;  // tables per lane
-    int i0 = wl + gl * Lb;
-    const int i1 = min(i0 + Lb - 1, wr);
-    const bool mine = i0 <= wr;
-    double ls = (narrow ? seed_n : bv_hyper_logp(h, mine ? i0 : wr)) + shift;
-    if (mine && ls < BV_FISHER_LIVE) {
-        // a block that starts below the double range and rises (bv_fisher_first_live, bv_device.h): it starts where its tables do
-        const int top = min(i1, bv_fisher_mode(n1_, n_1, n));
-        if (i0 < top) {
-            i0 = bv_fisher_first_live(h, i0 + 1, top, shift);
-            ls = bv_hyper_logp(h, i0) + shift;
-        }
-    }
-    double p = mine ? exp(ls) : 0.;
-    double tail = 0., pfirst = 0., plast = 0.;
-    bool seen = false;
-    for (int t = 0; t < Lb; ++t) {
-        const int i = i0 + t;
-        const bool in = mine && i <= i1;
-        const bool viol = in && !(p < lo);
-        tail += (in && !viol) ? p : 0.;
-        if (viol && !seen) pfirst = p;
-        if (viol) { plast = p; seen = true; }
-        p *= bv_hyper_ratio(h, i);
-    }
-    const uint32_t vm = bv_g16_ballot(seen, lane);  // never empty: the observed table lies inside [wl, wr]
-    double two = bv_g16_sum(tail);
-    const double pL = bv_g16_bcast_f64(pfirst, __builtin_ctz(vm | 0x10000u), lane);
-    const double pR = bv_g16_bcast_f64(plast, 31 - __builtin_clz(vm | 1u), lane);
-    if (vm != 0u) {
-        if (pL < hi) two += pL;
-        if (pR < hi) two += pR;
-    }
-    two = bv_fisher_unshift(two, shift);
-    return two > 1. ? 1. : two;
-}
-
-// strand_bias tail, src/basetype.cpp:277-286 (see bv_strand_bias_wave for the SOR overflow note)
-__device__ inline void bv_strand_bias_g16(uint32_t ref_fwd, uint32_t ref_rev, uint32_t alt_fwd, uint32_t alt_rev, int lane,
-                                          const BvLnTab &T, double *fs_out, double *sor_out, uint32_t *flags) {
-    double fs = -10 * log10(bv_fisher_two_sided_g16((int)ref_fwd, (int)ref_rev, (int)alt_fwd, (int)alt_rev, lane, T));
-    if (isinf(fs)) fs = 10000;
-    else if (fs == 0) fs = 0.0;
-    int den = (int)(ref_rev * alt_fwd), num = (int)(ref_fwd * alt_rev);
-    if ((unsigned long long)ref_rev * alt_fwd > 0x7fffffffull || (unsigned long long)ref_fwd * alt_rev > 0x7fffffffull)
-        *flags |= BV_SITE_SOR_OVERFLOW;
-    *fs_out = fs;
-    *sor_out = (ref_rev != 0u && alt_fwd != 0u) ? (double)num / (double)den : 10000;
-}
 
 // ------------------------------------------------------------------ EM on the group's bins (in registers)
 // bin word = code << 16 | count (code = base << 7 | phred), 0 for an empty slot; bins with phred > 93 carry no likelihood
@@ -476,17 +272,6 @@ __device__ inline void bv_lrt_g16(const BvG16Bins &B, const uint32_t depth[4], u
     o.af[0] = af0; o.af[1] = af1; o.af[2] = af2; o.af[3] = af3;
 }
 
-// ------------------------------------------------------------------ Wilcoxon rank sum, 16 values per window
-__device__ inline unsigned long long bv_ranksum_window_g16(uint32_t ref_v, uint32_t alt_v, unsigned long long n,
-                                                           unsigned long long &below) {
-    const uint32_t t = ref_v + alt_v;
-    const uint32_t incl = bv_g16_incl_scan_u32(t);
-    const unsigned long long below_v = below + (incl - t);
-    const unsigned long long term = (unsigned long long)ref_v * (2ull * n - 2ull * below_v - t + 1ull);
-    const unsigned long long s = bv_g16_sum_u64(term);
-    below += (unsigned long long)bv_g16_sum_u32(t);
-    return s;
-}
 
 // ------------------------------------------------------------------ one site on one group, in two phases
 // The solve of a candidate is split over two kernels so that each kernel's code fits the instruction cache (64 KB per pair

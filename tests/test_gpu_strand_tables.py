@@ -9,7 +9,7 @@ corpus of a row length populates is asserted on the oracle's records in tests/te
 
 The corpus tables named "probed R=max q300, left / right of the mode" (q ~ 1e-300 inside a long family) are the ones
 that found the seed of a probed tail underflowing to 0: the 16-lane form gave half the reference's p, the wave form
-p = 0 (FS 10000), on every row length.  Both forms now carry such families scaled (bv_fisher_shift, csrc/bv_device.h).
+p = 0 (FS 10000), on every row length.  Both forms now carry such families scaled (bv_fisher_shift, csrc/bv_fisher.h).
 The "steep end" tables (the family's first table below e^-760 beside an ordinary q) found the same zero in the wave form's
 first round: FS 10000 for the reference's 0.9 at (250, 5, 15835, 295); walks now start at their first live table."""
 import numpy as np
