@@ -43,25 +43,13 @@ __device__ __forceinline__ uint32_t bv_f_take(uint32_t *q, uint32_t pos) {
     *e = BV_F_EMPTY;
     return s;  // (BV_F_EMPTY after a time-out: the caller flags it)
 }
-// What the rank sums of pass 2 need of a variant site (bv_pass2_dma_kernel forms the same from the record): the class of
-// every base -- byte b of L: 0x80 REF, 0x81 ALT, 0xFF neither (caller.cpp:1151-1157) --, the 2-bit form of it for the window
-// sweeps, and the REF / ALT depths.  aw0 / aw1: the record's bytes n_alt, alt[0..3] as stored at bv_site_result::n_alt.
+// What the rank sums of pass 2 need of a variant site (bv_p2_site_facts, bv_pass2_sweep.h), the REF / ALT depths packed as the
+// variant queue carries them: n1 | n2 << 16, both at most the row length (<= 49,152).
 __device__ __forceinline__ void bv_f_p2_facts(int ref, const uint32_t depth[4], uint32_t aw0, uint32_t aw1, uint32_t &L, uint32_t &n12,
                                               uint32_t &lut) {
-    L = 0xFFFFFFFFu; lut = 0xAAu;
-    uint32_t n1 = 0, n2 = 0;
-    const int n_alt = (int)(aw0 & 0xFFu);
-    if (ref < 4) { L = (L & ~(0xFFu << (8 * ref))) | (0x80u << (8 * ref)); lut &= ~(3u << (2 * ref)); n1 = bv_sel4u(depth, ref); }
-#pragma unroll
-    for (int t = 0; t < BV_MAX_ALT; ++t) {
-        if (t < n_alt) {
-            const int b = (int)((t < 3 ? (aw0 >> (8 * (t + 1))) : aw1) & 3u);
-            L = (L & ~(0xFFu << (8 * b))) | (0x81u << (8 * b));
-            lut = (lut & ~(3u << (2 * b))) | (1u << (2 * b));
-            n2 += bv_sel4u(depth, b);
-        }
-    }
-    n12 = n1 | (n2 << 16);  // both at most the row length (<= 49,152)
+    uint32_t n1, n2;
+    bv_p2_site_facts(ref, depth, aw0, aw1, L, lut, n1, n2);
+    n12 = n1 | (n2 << 16);
 }
 // Variant sites into the workgroup's variant queue; called by the WHOLE wave, `want` marks the lanes that have one (their
 // records are complete in memory).  The queue in LDS takes them while it is at most BV_F_QV_ROOM full: the positions are

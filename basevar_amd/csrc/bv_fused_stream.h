@@ -56,9 +56,9 @@ __device__ __forceinline__ void bv_f_publish(const BvP1ShortArgs &a, BvFusedShar
         bv_f_push((bv_lds_vu32 *)sh.q2, (bv_lds_u32 *)&sh.ctl[BV_FC_Q2_TAIL], site, a.counters, (a.flags & BV_FLAG_FAULT_LOST_HANDOFF) != 0u, lane);
     }
 }
-// A variant row with a read-position rank beyond the 256-rank window of the fast tally (long reads): the exact window sweeps of
-// bv_pass2_sweep.h -- plain loads, as bv_pass2_dma_kernel falls back to them -- into the wave's histogram, the two rank sums
-// stored at once.  Rare, and not inlined: the streaming loop keeps its registers; the loads' waits drain the ring.
+// A variant row with a read-position rank beyond the 256-rank window of the fast tally (long reads): the exact re-do of
+// bv_pass2_sweep.h (bv_p2_wave_exact) -- plain loads, as bv_pass2_dma_kernel falls back to it -- into the wave's histogram, the two
+// rank sums stored at once.  Rare, and not inlined: the streaming loop keeps its registers; the loads' waits drain the ring.
 __device__ __attribute__((noinline)) void bv_f_p2_redo(const uint8_t *bs_, const uint8_t *mapq_, const uint16_t *rpr_, bv_site_result *out_, uint64_t pitch,
                                                        uint32_t n_samples, uint32_t site_, uint32_t lut_, uint32_t n12_, uint32_t hist_lds_) {
     const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -73,43 +73,7 @@ __device__ __attribute__((noinline)) void bv_f_p2_redo(const uint8_t *bs_, const
     as.rpr = (const uint16_t *)(__attribute__((address_space(1))) const uint16_t *)rpr_;
     as.q = nullptr; as.group_id = nullptr; as.pitch = pitch; as.n_samples = n_samples; as.n_groups = 0;
     const unsigned long long n1 = n12 & 0xFFFFu, n2 = n12 >> 16;
-    uint32_t *hm = h, *hr = h + 512;
-    auto zero = [&](uint32_t *p, int words) {
-        uint4 *z = reinterpret_cast<uint4 *>(p);
-        for (int i = lane; i < words / 4; i += BV_WAVE) z[i] = make_uint4(0, 0, 0, 0);
-    };
-    zero(h, 4 * 256);
-    bv_lrt_sync<0>();
-    BvP2Ctx cx;
-    cx.hm = hm; cx.hr = hr; cx.hg = nullptr; cx.lut = lut; cx.win_lo = 0; cx.n_groups = 0; cx.maxr = 0; cx.half = false;
-    cx.rmask = bv_rpr_rank_mask(lut_tag >> 31);
-    bv_p2_sweep<BV_WAVE, true, true, false, 256>(cx, as, site, lane);
-    const uint32_t maxr = (uint32_t)bv_wave_max_i32((int)cx.maxr);
-    bv_lrt_sync<0>();
-    {
-        unsigned long long below = 0, twoR = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) twoR += bv_ranksum_window(hm[w * 64 + lane], hm[256 + w * 64 + lane], n1 + n2, below, lane);
-        const double ph = bv_ranksum_phred(twoR, n1, n2);
-        if (lane == 0) out[site].mq_ranksum = ph;
-    }
-    unsigned long long below = 0, twoR = 0;
-    for (uint32_t win_lo = 0;; win_lo += 256u) {
-        const int nblk = (maxr < win_lo + 256u) ? (int)((maxr - win_lo) >> 6) + 1 : 4;
-        for (int w = 0; w < nblk; ++w) twoR += bv_ranksum_window(hr[w * 64 + lane], hr[256 + w * 64 + lane], n1 + n2, below, lane);
-        if (maxr < win_lo + 256u) break;
-        bv_lrt_sync<0>();
-        zero(hr, 2 * 256);
-        bv_lrt_sync<0>();
-        cx.win_lo = win_lo + 256u;
-        bv_p2_sweep<BV_WAVE, true, false, false, 256>(cx, as, site, lane);
-        bv_lrt_sync<0>();
-    }
-    const double ph = bv_ranksum_phred(twoR, n1, n2);
-    if (lane == 0) {
-        out[site].rpr_ranksum = ph;
-        atomicOr(&out[site].status, BV_SITE_RANKSUM);
-    }
+    bv_p2_wave_exact<256>(as, out, site, lut, bv_rpr_rank_mask(lut_tag >> 31), n1, n2, h, h + 512, lane);
     bv_lrt_sync<0>();
 }
 

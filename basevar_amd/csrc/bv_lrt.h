@@ -71,6 +71,21 @@ __device__ __forceinline__ void bv_team_barrier(BvLrtShared *sh, uint32_t target
     }
 }
 
+// [toupper(REF)] + alts (caller.cpp:750-753), the list a pop-group's LRT starts from, as bv_lrt / bv_lrt_g16 take it: 3 bits per
+// entry, `nc` entries.  ref: the reference base, clamped to 4; n_alt, alt: the site record's.
+__device__ __forceinline__ int bv_lrt_ref_alts(int ref, int n_alt, const uint8_t *alt, int &nc) {
+    int comb = ref;
+    nc = 1;
+#pragma unroll
+    for (int k = 0; k < BV_MAX_ALT; ++k) {
+        if (k < n_alt) {
+            comb |= (alt[k] & 3) << (3 * nc);
+            ++nc;
+        }
+    }
+    return comb;
+}
+
 // `specific_packed`: the candidate bases in reference order, 3 bits each (value 4 = a base
 // that is not ACGT, never active); `nspec` of them.
 template <int NW>

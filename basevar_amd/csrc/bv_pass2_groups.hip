@@ -119,10 +119,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2GS_WAVES) void bv_p2g_stream_kernel(B
                 if (chunk >= n_chunks) {  // not loaded: stale bytes
                     vb = bv_u32x4{0x08080808u, 0x08080808u, 0x08080808u, 0x08080808u};
                     vq = bv_u32x4{0u, 0u, 0u, 0u};
-                } else if (tail && chunk == n_chunks - 1) {
-                    vb.x = bv_mask_tail_dword(vb.x, tail); vb.y = bv_mask_tail_dword(vb.y, tail - 4);
-                    vb.z = bv_mask_tail_dword(vb.z, tail - 8); vb.w = bv_mask_tail_dword(vb.w, tail - 12);
-                }
+                } else if (tail && chunk == n_chunks - 1) bv_mask_tail16(vb, tail);
             }
             // call bytes above 15 and phred bytes above 127 (invalid input) do not fit the packed index: cell by cell then
             const uint32_t odd = ((vb.x | vb.y | vb.z | vb.w) & 0xF0F0F0F0u) | ((vq.x | vq.y | vq.z | vq.w) & 0x80808080u);
@@ -262,15 +259,8 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2GH_WAVES) void bv_p2g_hard_kernel(BvP
             const bv_site_result *res = &outp[site];
             int ref = refp[site];
             if (ref > 4) ref = 4;
-            const int n_alt = res->n_alt;
-            int comb = ref, nc = 1;  // caller.cpp:750-753: [toupper(REF)] + alts, 3 bits per entry
-#pragma unroll
-            for (int k = 0; k < BV_MAX_ALT; ++k) {
-                if (k < n_alt) {
-                    comb |= (res->alt[k] & 3) << (3 * nc);
-                    ++nc;
-                }
-            }
+            int nc;
+            const int comb = bv_lrt_ref_alts(ref, res->n_alt, res->alt, nc);  // caller.cpp:750-753: [toupper(REF)] + alts
             uint32_t gdepth[4] = {it[1], it[2], it[3], it[4]};
             const uint32_t gtotal = gdepth[0] + gdepth[1] + gdepth[2] + gdepth[3], q0_mask = it[5];
             for (uint32_t i = (uint32_t)lane; i < nb; i += BV_WAVE) {
@@ -381,18 +371,11 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2G_NW, BV_P2G_OCC) void bv_p2g_solve16
         const bv_site_result *res = &outp[site];
         int ref = refp[site];
         if (ref > 4) ref = 4;
-        const int n_alt = res->n_alt;
-        int comb = ref, nc = 1;  // caller.cpp:750-753: [toupper(REF)] + alts, 3 bits per entry
+        int nc;
+        const int comb = bv_lrt_ref_alts(ref, res->n_alt, res->alt, nc);  // caller.cpp:750-753: [toupper(REF)] + alts
         // (Tried, round 6: site and [REF] + alts riding in the item, so that a job starts from one load instead of the chain
         // variant list -> record -> reference base: no change, 60.4 against 60.2 M sites/s at 32 groups -- the kernel is bound by
         // its FP64 instructions, not by these loads.)
-#pragma unroll
-        for (int k = 0; k < BV_MAX_ALT; ++k) {
-            if (k < n_alt) {
-                comb |= (res->alt[k] & 3) << (3 * nc);
-                ++nc;
-            }
-        }
         uint32_t gdepth[4] = {it[1], it[2], it[3], it[4]};
         const uint32_t gtotal = gdepth[0] + gdepth[1] + gdepth[2] + gdepth[3];
         BvG16Bins B;
@@ -486,15 +469,8 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2G_NW, BV_P2G_OCC) void bv_p2g_solve_s
         const bv_site_result *res = &outp[site];
         int ref = refp[site];
         if (ref > 4) ref = 4;
-        const int n_alt = res->n_alt;
-        int comb = ref, nc = 1;  // caller.cpp:750-753: [toupper(REF)] + alts, 3 bits per entry
-#pragma unroll
-        for (int k = 0; k < BV_MAX_ALT; ++k) {
-            if (k < n_alt) {
-                comb |= (res->alt[k] & 3) << (3 * nc);
-                ++nc;
-            }
-        }
+        int nc;
+        const int comb = bv_lrt_ref_alts(ref, res->n_alt, res->alt, nc);  // caller.cpp:750-753: [toupper(REF)] + alts
         uint32_t gdepth[4] = {it[1], it[2], it[3], it[4]};
         const uint32_t gtotal = gdepth[0] + gdepth[1] + gdepth[2] + gdepth[3];
         BvG16Bins B;

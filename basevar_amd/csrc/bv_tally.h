@@ -321,6 +321,21 @@ __device__ __forceinline__ uint32_t bv_mask_tail_dword(uint32_t w, int keep) {
     uint32_t low = (1u << (8 * keep)) - 1u;
     return (w & low) | (0x08080808u & ~low);
 }
+// ... of the 16 call bytes of a row's last chunk (tail = n_samples & 15, not 0).  (bv_pass1.hip and bv_pass1_short.hip keep the four
+// assignments written out: through this function the code of their kernels moved, profiles/pass2_split_codehash.txt 3b.)
+__device__ __forceinline__ void bv_mask_tail16(bv_u32x4 &vb, int tail) {
+    vb.x = bv_mask_tail_dword(vb.x, tail); vb.y = bv_mask_tail_dword(vb.y, tail - 4);
+    vb.z = bv_mask_tail_dword(vb.z, tail - 8); vb.w = bv_mask_tail_dword(vb.w, tail - 12);
+}
+// one wave zeroes WORDS words of LDS at a 16-byte aligned `p`: 16 bytes per lane and store, UNROLL stores per trip (all of them
+// where every row passes; 1, a loop, on the rare paths -- smaller code, and bv_f_p2_redo keeps the registers its callers count on)
+template <int WORDS, int UNROLL = WORDS / 4 / BV_WAVE>
+__device__ __forceinline__ void bv_wave_zero(uint32_t *p, int lane) {
+    static_assert(WORDS % (4 * BV_WAVE) == 0, "whole stores of the whole wave");
+    uint4 *z = reinterpret_cast<uint4 *>(p);
+#pragma unroll UNROLL
+    for (int i = lane; i < WORDS / 4; i += BV_WAVE) z[i] = make_uint4(0, 0, 0, 0);
+}
 
 // ------------------------------------------------------------------------------ LDS-DMA
 // 64 lanes x 16 bytes from base + voff into LDS at lds_dst + lane * 16 (M0 saved / restored); counted on vmcnt like any load,
@@ -359,9 +374,14 @@ __device__ __forceinline__ const uint8_t *bv_uniform_ptr(const uint8_t *p) {
     return (const uint8_t *)(uintptr_t)(((uint64_t)hi << 32) | lo);
 }
 
-// ---- the perm form of the rank-sum tally (see bv_pass2_dma_kernel, bv_pass2.hip, for the derivation; also used by bv_pass1_fused.hip): class byte J << 8 | mapq byte J, and
-// rank_hi << 16 | class byte J << 8 | rank_lo (rank H of the dword r2); "< 0x200" is the whole predicate, the value the word
-// of a [class][256] histogram
+// ---- the perm form of the rank-sum tally (bv_pass2_kernel, bv_pass2_dma_kernel, the fused short-row kernel), per cell:
+//   * one v_perm_b32 per FOUR cells turns the call bytes into class bytes: the call byte itself is the selector into a
+//     4-byte table (0x80 REF, 0x81 ALT, 0xFF neither; strand bit folded by giving both sources the same table); N / + / -
+//     (8..10) select a sign-replication of table bytes whose top bit is always set -> 0xFF, garbage -> 0x00 / 0xFF: neither;
+//   * after an XOR with 0x80808080, X = class << 8 | mapq and X' = rank_hi << 16 | class << 8 | rank_lo are glued by one
+//     v_perm each; "X < 0x200" is the whole predicate (REF/ALT class, and rank < 256) and X the histogram word: 3 VALU + one
+//     EXEC-predicated ds_add_u32 per cell and plane (bv_lds_add16), against ~20 VALU per cell in the branchy form.
+// bv_p2d_xm: class byte J << 8 | mapq byte J; bv_p2d_xr: class byte J << 8 | rank_lo (rank H of the dword r2).
 template <int J>
 __device__ __forceinline__ uint32_t bv_p2d_xm(uint32_t cls4, uint32_t mq4) {  // class byte J << 8 | mapq byte J
     constexpr uint32_t SEL = 0x0C0C0000u | ((4u + J) << 8) | (uint32_t)J;

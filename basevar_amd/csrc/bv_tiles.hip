@@ -175,17 +175,16 @@ __global__ __launch_bounds__(BV_WAVE) void bv_tile_finish_kernel(BvTileFinishArg
     uint32_t depth[4] = {sh.sc.res.depth[0], sh.sc.res.depth[1], sh.sc.res.depth[2], sh.sc.res.depth[3]};
     uint32_t alt_mask = 0;
     unsigned long long n1 = (ref < 4) ? bv_sel4u(depth, ref) : 0ull, n2 = 0;
-    int comb = ref, nc = 1;
 #pragma unroll
     for (int k = 0; k < BV_MAX_ALT; ++k) {
         if (k < n_alt) {
             const int b = sh.sc.res.alt[k] & 3;
             alt_mask |= 1u << b;
             n2 += bv_sel4u(depth, b);
-            comb |= b << (3 * nc);
-            ++nc;
         }
     }
+    int nc;
+    const int comb = bv_lrt_ref_alts(ref, n_alt, sh.sc.res.alt, nc);
     __builtin_amdgcn_s_waitcnt(0);  // the record store of the solver has been issued before the field updates below
 
     if (a.have_ranks) {

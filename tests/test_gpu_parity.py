@@ -1331,25 +1331,32 @@ def test_tile_job_interleaved_with_row_submits_and_abandoned_jobs(bv, restatemen
 
 
 @pytest.mark.parametrize("n,flags,groups", [(60000, 0, 0), (6000, 0, 0), (6000, 1 << 16, 0), (70, 0, 0), (1500, 0, 0),
-                                            (60000, 0, 3), (6000, 0, 3), (6000, 1 << 16, 2), (6000, 0, 9), (1500, 0, 2), (70, 0, 2)],
+                                            (60000, 0, 3), (6000, 0, 3), (6000, 1 << 16, 2), (6000, 0, 9), (1500, 0, 2), (70, 0, 2),
+                                            (3000, 0, 0), (6000, 10 << 12, 0)],
                          ids=["long_rows", "short_rows", "short_rows_one_workgroup", "shallow_rows", "rows_of_1500",
                               "long_rows_groups", "short_rows_groups", "short_rows_groups_one_workgroup", "short_rows_9_groups",
-                              "rows_of_1500_groups", "shallow_rows_groups"])
+                              "rows_of_1500_groups", "shallow_rows_groups", "dma_rows", "short_rows_pass2_own_launch"])
 def test_chained_submit_equals_separate_submits(bv, n, flags, groups):
     """bv_engine_submit_many(_g): several device slabs, one launch per pass (the site tickets / site ranges span the queue) --
     every record must be the one a submit of its own slab writes (byte for byte: which workgroup solves a site has no
     influence).  Long rows: every kernel looks its segment up per site; short rows: planes per row, reference bases and
     records through the engine's contiguous copies (with BV_FLAG_GRID_LIMIT(1) every wave walks sites of many segments);
     rows of <= 2048 samples and pop-groups (one cohort: one group_id array for the queue; the streaming group tally, the
-    workgroup-per-row kernels, the four-per-wave and the one-wave group solvers) chain too since round 3."""
+    workgroup-per-row kernels, the four-per-wave and the one-wave group solvers) chain too since round 3.
+    dma_rows: rows of 3,000 samples, bv_pass2_dma_kernel as a launch of its own; short_rows_pass2_own_launch: form 10
+    (BV_FLAG_SHORT_ROW_FORM), the fused pass 1 with pass 2 as that kernel -- the chained engine carries the flag, the single
+    submits run with default flags (records do not depend on the form).  Both re-do a long-read row of a later segment exactly
+    (the segment's planes looked up per site, bv_p2_wave_exact)."""
     import torch
     sizes = [96, 17, 200, 64, 1, 130, 48, 77, 33, 120, 5, 5, 60, 41, 9, 88, 150, 3, 70]  # 19 slabs: two chained launches (16 + 3)
     slabs = [make_slab(s, n, seed=300 + k, coverage=(0.05 + 0.02 * (k % 3)) if n > 1000 else 0.4,
                        class_af=[(0.0, 0.0), (0.3, 0.0), (0.2, 0.1)]) for k, s in enumerate(sizes)]
     if n == 6000:
-        # a shallow site (ordered gather from the segment's planes) and a long read (rank-window sweeps) in later segments
+        # a shallow site (ordered gather from the segment's planes) in a later segment
         sl = slabs[5]
         sl["base_strand"][7, :] = 8; sl["base_strand"][7, [11, 500, 4000]] = [0, 1, 6]; sl["qual"][7, [11, 500, 4000]] = 20
+    if n in (3000, 6000):
+        # a long read (rank-window sweeps) in a later segment
         sl = slabs[9]
         sl["rpr"][3, np.nonzero(sl["base_strand"][3] < 8)[0][:3]] = 700
     maf = bv.min_af(n)

@@ -163,10 +163,12 @@ def test_tagged_tile_job_with_fewer_samples_than_announced(bv):
     eng.close()
 
 
-@pytest.mark.parametrize("n,groups", [(60000, 0), (6000, 0), (6000, 3), (1500, 0)], ids=["long_rows", "short_rows", "short_rows_groups", "rows_of_1500"])
+@pytest.mark.parametrize("n,groups", [(60000, 0), (6000, 0), (6000, 3), (1500, 0), (3000, 0)],
+                         ids=["long_rows", "short_rows", "short_rows_groups", "rows_of_1500", "dma_rows"])
 def test_tagged_chained_submit(bv, n, groups):
     """bv_engine_submit_many on device slabs of the tagged layout = the plain layout's separate submits, byte for byte; a queue
-    that mixes the layouts is submitted slab by slab and still gives them."""
+    that mixes the layouts is submitted slab by slab and still gives them.  dma_rows: bv_pass2_dma_kernel<TAG> as a launch of its
+    own, its long-read row re-done from the segment's planes."""
     import torch
     sizes = [96, 17, 200, 64, 1, 130, 48]
     slabs = [make_slab(s, n, seed=300 + k, coverage=0.05 + 0.02 * (k % 3), class_af=[(0.0, 0.0), (0.3, 0.0), (0.2, 0.1)]) for k, s in enumerate(sizes)]
