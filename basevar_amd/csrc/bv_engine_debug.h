@@ -109,7 +109,7 @@ static void bv_fused_debug_report(const uint32_t *h) {
 }
 #endif
 #ifdef BV_TEAM_DEBUG
-// the stamps of bv_pass1_kernel's team form (see BV_TEAM_STAMP in bv_pass1.hip): distribution over the workgroups, and per XCD
+// the stamps of bv_pass1_kernel's team form (see BV_TEAM_STAMP in bv_pass1_team.h): distribution over the workgroups, and per XCD
 static void bv_team_debug_report(const uint32_t *h) {
     fprintf(stderr, "[team debug] team jobs %u (mean %.0f cycles)  solo solves %u (mean %.0f cycles)\n", h[BV_CTR_CANDS],
             h[BV_CTR_CANDS] ? 64.0 * h[BV_CTR_CANDS + 1] / h[BV_CTR_CANDS] : 0., h[BV_CTR_EASY3],

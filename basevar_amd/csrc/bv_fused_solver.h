@@ -1,7 +1,7 @@
 // bv_fused_solver.h -- the solver side of the fused short-row kernel: claiming candidates from the LDS queues, the 16-lane and the
 // wave-solver jobs, the variant queue and its overflow list, and one unit of solver work (bv_f_solver_step).
-// Included by bv_pass1_fused.hip alone, behind bv_fused_shared.h and bv_fused_lds.h; the kernel shell calls bv_f_solver_step and
-// bv_f_flush_vl.
+// Included by bv_pass1_fused.hip alone, behind bv_fused_shared.h and bv_fused_lds.h; the kernel shell calls bv_f_solver_step;
+// the variant-list flush and the wave-solver job on a site's exported bins are bv_short.h's.
 #pragma once
 
 // ------------------------------------------------------------------------------ the solver side
@@ -13,15 +13,6 @@ struct BvFusedSolver {
     BvP1sWaveScratch *big;  // the wave solver's scratch, or NULL: this wave cannot take the hard candidates
     bool fuse2;      // variant sites also go to the workgroup's variant queue (their pass-2 rows are streamed by this kernel)
 };
-__device__ __forceinline__ void bv_f_flush_vl(const BvP1ShortArgs &a, BvFusedSolver &v, int lane) {
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_VARIANTS], v.n_vl);
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    bv_lrt_sync<0>();
-    if ((uint32_t)lane < v.n_vl) a.var_list[base + (uint32_t)lane] = v.vl[lane];
-    bv_lrt_sync<0>();
-    v.n_vl = 0;
-}
 // claim `least` to `most` entries of a queue: returns the number claimed (0: too few there, or another wave was faster) and
 // the first position
 __device__ __forceinline__ uint32_t bv_f_claim(uint32_t *ctl, int tail_i, int head_i, uint32_t least, uint32_t most, uint32_t &first, int lane) {
@@ -182,7 +173,7 @@ __device__ __forceinline__ void bv_f_job16(const BvP1ShortArgs &a, BvFusedShared
         bv_site_tail_g16(v.sa, site, S, src, nb, scratch, lane, &pre, w2);
     }
     BV_JP(4);  // phase 2: rank sum, QUAL, strand-bias tests
-    if (v.n_vl > 56u) bv_f_flush_vl(a, v, lane);
+    if (v.n_vl > 56u) bv_p1s_flush_vl(a, v.vl, v.n_vl, lane);
 #ifdef BV_PHASE_DEBUG
     if (lane == 0) for (int i = 0; i < 5; ++i) atomicAdd(&a.counters[BV_CTR_WORDS + 4250 + i], jp_[i] >> 4);
 #endif
@@ -190,9 +181,6 @@ __device__ __forceinline__ void bv_f_job16(const BvP1ShortArgs &a, BvFusedShared
 }
 // one candidate that needs the wave solver (shallow site: ordered replay; phred-0 calls; more than 128 bins; min_af <= 0)
 __device__ __forceinline__ void bv_f_job_hard(const BvP1ShortArgs &a, BvFusedShared &sh, BvFusedSolver &v, uint32_t B0, uint32_t site, int lane) {
-    uint32_t *bin_code = v.big->w.raw, *bin_cnt = bin_code + BV_SLOTS * BV_WAVE, *hq = bin_code + 2 * BV_SLOTS * BV_WAVE;
-    BvSolverScratch *sv = &v.big->w.sc;
-    constexpr int REC_WORDS = (int)(sizeof(bv_site_result) / 4);
     uint4 s0, s1, s2;
     bv_load3_l2(&a.summ[site], s0, s1, s2);
     BvSiteSums S;
@@ -201,37 +189,7 @@ __device__ __forceinline__ void bv_f_job_hard(const BvP1ShortArgs &a, BvFusedSha
     const uint32_t sm_nb = s2.x;
     S.q0_mask = s2.y & BV_SUM_Q0_MASK;
     S.badq = (s2.y & BV_SUM_BADQ) ? 1u : 0u;
-    if (lane < REC_WORDS) reinterpret_cast<uint32_t *>(&sv->res)[lane] = 0u;
-    {
-        uint4 *z = reinterpret_cast<uint4 *>(hq);
-#pragma unroll
-        for (int i = 0; i < 4 * 128 / 4 / BV_WAVE; ++i) z[i * BV_WAVE + lane] = make_uint4(0, 0, 0, 0);
-    }
-    bv_lrt_sync<0>();
-    // exported bins -> merged counts for the rank sum (all of them) and the EM's bins (phred <= 93), order kept
-    const uint32_t *src = a.bins + (size_t)site * BV_S_BIN_STRIDE;
-    uint32_t nb = 0;
-    for (uint32_t i0 = 0; i0 < sm_nb; i0 += BV_WAVE) {
-        const uint32_t i = i0 + (uint32_t)lane;
-        const bool have = i < sm_nb;
-        const uint32_t w = have ? src[i] : 0u;
-        const uint32_t code = w >> 16, cnt = w & 0xFFFFu;
-        if (have) hq[code] = cnt;
-        const bool valid = have && (code & 127u) < BV_NQ_VALID;
-        const unsigned long long m = __ballot(valid);
-        const uint32_t pos = nb + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (valid) { bin_code[pos] = code; bin_cnt[pos] = cnt; }
-        nb += (uint32_t)__popcll(m);
-    }
-    S.nb = nb;
-    bv_lrt_sync<0>();
-    BvHqMerged H{hq};
-    if (a.ch != nullptr) {  // chained launch: the ordered gather of a shallow site reads the segment's (biased) planes
-        const BvChainC ch = bv_chain_const(a.ch);
-        const uint32_t sg = bv_chain_seg(ch, (uint32_t)__builtin_amdgcn_readfirstlane((int)site));
-        v.sa.bs = ch->bs[sg]; v.sa.q = ch->q[sg];
-    }
-    if (bv_site_solve<false, BvHqMerged, true>(v.sa, site, S, bin_code, bin_cnt, H, sv, sh.tab_hit, sh.tab_miss, lane)) {
+    if (bv_p1s_hard_site(a, v.sa, site, S, sm_nb, v.big, sh.tab_hit, sh.tab_miss, lane)) {
         if (lane == 0) v.vl[v.n_vl] = site;
         ++v.n_vl;
         if (v.fuse2) {
@@ -248,7 +206,7 @@ __device__ __forceinline__ void bv_f_job_hard(const BvP1ShortArgs &a, BvFusedSha
             bv_f_p2_facts(ref, depth, aw0, aw1, pL, pn12, plut);
             bv_f_push_variants(a, sh, B0, lane == 0, site, pL, pn12, plut, lane);
         }
-        if (v.n_vl > 56u) bv_f_flush_vl(a, v, lane);
+        if (v.n_vl > 56u) bv_p1s_flush_vl(a, v.vl, v.n_vl, lane);
     }
     bv_lrt_sync<0>();
 }
@@ -337,7 +295,7 @@ __device__ __forceinline__ int bv_f_solver_step(const BvP1ShortArgs &a, BvFusedS
                             bv_f_lds_read_u(&sh.ctl[BV_FC_Q2_TAIL]) != bv_f_lds_read_u(&sh.ctl[BV_FC_Q2_HEAD]) ||
                             (v.big != nullptr && bv_f_lds_read_u(&sh.ctl[BV_FC_QH_TAIL]) != bv_f_lds_read_u(&sh.ctl[BV_FC_QH_HEAD])) ||
                             bv_f_lds_read_u(&sh.ctl[BV_FC_BLK_HEAD]) < n_blocks;
-        if (!q_left && v.n_vl) bv_f_flush_vl(a, v, lane);
+        if (!q_left && v.n_vl) bv_p1s_flush_vl(a, v.vl, v.n_vl, lane);
         return q_left ? 1 : 2;
     }
     return 0;

@@ -58,6 +58,10 @@ __device__ __forceinline__ uint32_t bv_chain_seg(BvChainC c, uint32_t site) {
     for (int i = 1; i < BV_MAX_CHAIN; ++i) k += ((uint32_t)i < n && site >= c->first[i]) ? 1u : 0u;
     return k;
 }
+// ... of a site every lane of the wave has the same number of: the look-up is scalar
+__device__ __forceinline__ uint32_t bv_chain_seg_uniform(BvChainC c, uint32_t site) {
+    return bv_chain_seg(c, (uint32_t)__builtin_amdgcn_readfirstlane((int)site));
+}
 #endif
 
 struct BvPass1Args {

@@ -9,7 +9,7 @@
 //            its waves: no s_barrier); results meet in LDS behind a counting barrier in `sh` (which must then be a
 //            BvLrtTeamShared shared by the team), every wave replays the cheap, uniform argmin / threshold decision.
 //            Each run is the same one-wave arithmetic as in wave mode, so the outcome is bit-identical to it.
-//            (Used at the tail of a long-row launch, bv_pass1.hip: the idle tally waves join the solver wave.)
+//            (Used at the tail of a long-row launch, bv_pass1_team.h: the idle tally waves join the solver wave.)
 //   NW == 0: "wave mode"  -- the calling wave does every run itself (used for the pop-group
 //            calls of pass 2, where each wave owns a different group); `sh` is wave-private.
 struct BvLrtShared {

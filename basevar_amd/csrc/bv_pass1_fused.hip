@@ -150,7 +150,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_F_NW) void bv_p1s_fused_kernel(BvP1Shor
         asm volatile("" : "+v"(ln));
         if (go) {
             // (the wave's variant sites since its last flush sit in its ring's LDS: out before rows stream through it again)
-            if (v.n_vl) bv_f_flush_vl(a, v, ln);
+            if (v.n_vl) bv_p1s_flush_vl(a, v.vl, v.n_vl, ln);
             // past its pass-1 rows a wave tallies the variant sites' rows from registers (bv_f_p2_rows); until then -- and with
             // BV_FLAG_P2_TAIL_DMA always -- rows go through the ring
             if (p2_regs && (sst & BV_FS_CUR_DONE) && (sst & BV_FS_P1_FIN)) {
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_F_NW) void bv_p1s_fused_kernel(BvP1Shor
             if (bv_f_lds_read_u(&sh.ctl[BV_FC_NDONE]) == (uint32_t)BV_F_NS) {
                 if (bv_f_lds_read_u(&sh.ctl[BV_FC_QV_TAIL]) != bv_f_lds_read_u(&sh.ctl[BV_FC_QV_HEAD]) ||
                     bv_f_lds_read_u(&sh.ctl[BV_FC_OV_TAIL]) != bv_f_lds_read_u(&sh.ctl[BV_FC_OV_HEAD])) {
-                    if (v.n_vl) bv_f_flush_vl(a, v, ln);
+                    if (v.n_vl) bv_p1s_flush_vl(a, v.vl, v.n_vl, ln);
                     bv_p1s_zero_hist<false>(v.grp, ln);
                     bv_lrt_sync<0>();
                     bv_f_p2_rows((uint32_t)ka_ptr, (uint32_t)(ka_ptr >> 32), sh_lds, (uint32_t)(uintptr_t)(bv_lds_u32 *)v.grp, B0);

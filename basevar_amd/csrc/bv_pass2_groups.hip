@@ -252,7 +252,7 @@ __global__ __launch_bounds__(BV_WAVE *BV_P2GH_WAVES) void bv_p2g_hard_kernel(BvP
             bv_group_result *goutp = a.gout;
             if (a.ch != nullptr) {
                 const BvChainC ch = bv_chain_const(a.ch);
-                const uint32_t sg = bv_chain_seg(ch, (uint32_t)__builtin_amdgcn_readfirstlane((int)site));
+                const uint32_t sg = bv_chain_seg_uniform(ch, site);
                 if (!a.ch_cat) { outp = ch->out[sg]; refp = ch->ref_base[sg]; }
                 bsp = ch->bs[sg]; qp = ch->q[sg]; goutp = ch->gout[sg];
             }

@@ -330,7 +330,7 @@ __global__ __launch_bounds__(NT) void bv_pass2_kernel(BvPass2Args a) {
     const uint32_t site = a.var_list[v];
     if (a.ch != nullptr) {  // a chained launch: the segment's (biased) planes and records
         const BvChainC ch = bv_chain_const(a.ch);
-        const uint32_t sg = bv_chain_seg(ch, (uint32_t)__builtin_amdgcn_readfirstlane((int)site));
+        const uint32_t sg = bv_chain_seg_uniform(ch, site);
         a.bs = ch->bs[sg]; a.q = ch->q[sg]; a.mapq = ch->mapq[sg]; a.rpr = ch->rpr[sg];
         if (!a.ch_cat) { a.ref_base = ch->ref_base[sg]; a.out = ch->out[sg]; }
         if (GROUPS) a.gout = ch->gout[sg];

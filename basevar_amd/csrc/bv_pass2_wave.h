@@ -19,7 +19,7 @@ __device__ __forceinline__ BvPass2Args bv_p2_site_planes(const BvPass2Args &a, u
     BvPass2Args as = a;
     if (a.ch != nullptr) {
         const BvChainC ch = bv_chain_const(a.ch);
-        const uint32_t sg = bv_chain_seg(ch, (uint32_t)__builtin_amdgcn_readfirstlane((int)site));
+        const uint32_t sg = bv_chain_seg_uniform(ch, site);
         as.bs = ch->bs[sg]; as.mapq = ch->mapq[sg]; as.rpr = ch->rpr[sg];
     }
     return as;

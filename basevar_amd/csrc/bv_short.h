@@ -1,6 +1,7 @@
 // bv_short.h -- pieces shared by the short-row pass-1 kernels (bv_pass1_short.hip: streaming kernel + solve kernel;
 // bv_pass1_fused.hip: both in one persistent kernel): the histogram geometry, the one-lane finish of a non-candidate site
-// (its per-lane Fisher test: bv_fisher.h), the histogram hand-back and list flush of the streaming waves, the wave solver's scratch.
+// (its per-lane Fisher test: bv_fisher.h), the streaming waves' histogram hand-back
+// and list flush, the solver waves' variant-list flush, the wave solver's scratch and its job on a site's exported bins.
 #pragma once
 
 #include "bv_kernels.h"
@@ -88,7 +89,9 @@ __device__ __forceinline__ void bv_p1s_simple_site(const BvP1ShortArgs &a, const
 // (Its other steps -- the row's totals, the candidate test, the bins' compaction, the 12-lane summary store -- are written out in
 // bv_p1s_stream_kernel and in bv_f_stream_until_idle, the same text except where the reference base comes from and where a
 // candidate's bins go: as shared functions they moved the fused kernel's streaming loops by 2 % of their instructions, and both
-// kernels' register allocation is tuned to the instruction.  A fix to one copy goes into the other.)
+// kernels' register allocation is tuned to the instruction.  Tried again with the pass-1 split (profiles/pass1_split_codehash.txt):
+// the totals as a function cost bv_p1s_stream_kernel a VGPR, the other three steps 1.5-2.3 % of its run time.  A fix to one copy
+// goes into the other.)
 // hand a wave's histogram back zeroed: its 8 x 128 words (OVF: and the overflow rows behind them)
 template <bool OVF>
 __device__ __forceinline__ void bv_p1s_zero_hist(uint32_t *hist, int lane) {
@@ -105,6 +108,18 @@ __device__ __forceinline__ void bv_p1s_flush_list(uint32_t *counter, uint32_t *l
     if ((uint32_t)lane < n) list[base + (uint32_t)lane] = mine;
 }
 
+// ------------------------------------------------------------------------------ solver waves
+// flush a wave's variant sites vl[0 .. n_vl) into the launch's variant list: one atomic reserves their places
+__device__ __forceinline__ void bv_p1s_flush_vl(const BvP1ShortArgs &a, const uint32_t *vl, uint32_t &n_vl, int lane) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(&a.counters[BV_CTR_VARIANTS], n_vl);
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    bv_lrt_sync<0>();
+    if ((uint32_t)lane < n_vl) a.var_list[base + (uint32_t)lane] = vl[lane];
+    bv_lrt_sync<0>();
+    n_vl = 0;
+}
+
 // Candidates that need the wave solver (shallow sites, phred-0 calls, > 128 bins, min_af <= 0): one wave per site.
 #define BV_P1S_RAW_WORDS (2 * BV_SLOTS * BV_WAVE + 4 * 128)  /* the wave solver's per-wave bins: codes [384], counts [384], merged counts [4][128] */
 // per wave: the four groups' scratch of the 16-lane solver -- or, while the wave works off the (rare) candidates that need the
@@ -116,3 +131,42 @@ union __attribute__((aligned(16))) BvP1sWaveScratch {
         BvSolverScratch sc;
     } w;
 };
+// One such candidate on one wave, from what its summary says (S: the strand totals, q0_mask, badq; sm_nb exported bins): the
+// solver of bv_solver.h on the bins.  Returns whether the site is a variant site (the caller lists it).
+__device__ __forceinline__ bool bv_p1s_hard_site(const BvP1ShortArgs &a, BvSolveArgs &sa, uint32_t site, BvSiteSums &S, uint32_t sm_nb,
+                                                 BvP1sWaveScratch *ws, const double *tab_hit, const double *tab_miss, int lane) {
+    uint32_t *bin_code = ws->w.raw, *bin_cnt = bin_code + BV_SLOTS * BV_WAVE, *hq = bin_code + 2 * BV_SLOTS * BV_WAVE;
+    BvSolverScratch *sv = &ws->w.sc;
+    constexpr int REC_WORDS = (int)(sizeof(bv_site_result) / 4);
+    if (lane < REC_WORDS) reinterpret_cast<uint32_t *>(&sv->res)[lane] = 0u;
+    {
+        uint4 *z = reinterpret_cast<uint4 *>(hq);
+#pragma unroll
+        for (int i = 0; i < 4 * 128 / 4 / BV_WAVE; ++i) z[i * BV_WAVE + lane] = make_uint4(0, 0, 0, 0);
+    }
+    bv_lrt_sync<0>();
+    // exported bins -> merged counts for the rank sum (all of them) and the EM's bins (phred <= 93), order kept
+    const uint32_t *src = a.bins + (size_t)site * BV_S_BIN_STRIDE;
+    uint32_t nb = 0;
+    for (uint32_t i0 = 0; i0 < sm_nb; i0 += BV_WAVE) {
+        const uint32_t i = i0 + (uint32_t)lane;
+        const bool have = i < sm_nb;
+        const uint32_t w = have ? src[i] : 0u;
+        const uint32_t code = w >> 16, cnt = w & 0xFFFFu;
+        if (have) hq[code] = cnt;
+        const bool valid = have && (code & 127u) < BV_NQ_VALID;
+        const unsigned long long m = __ballot(valid);
+        const uint32_t pos = nb + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (valid) { bin_code[pos] = code; bin_cnt[pos] = cnt; }
+        nb += (uint32_t)__popcll(m);
+    }
+    S.nb = nb;
+    bv_lrt_sync<0>();
+    BvHqMerged H{hq};
+    if (a.ch != nullptr) {  // chained launch: the ordered gather of a shallow site reads the segment's (biased) planes
+        const BvChainC ch = bv_chain_const(a.ch);
+        const uint32_t sg = bv_chain_seg_uniform(ch, site);
+        sa.bs = ch->bs[sg]; sa.q = ch->q[sg];
+    }
+    return bv_site_solve<false, BvHqMerged, true>(sa, site, S, bin_code, bin_cnt, H, sv, tab_hit, tab_miss, lane);
+}

@@ -96,6 +96,18 @@ struct BvSolveArgs {
     uint64_t pitch;
     uint32_t n_samples;
 };
+// ... from a row kernel's launch arguments (BvPass1Args, BvP1ShortArgs)
+// (bv_tile_finish_kernel fills its own, field by field: through this function, in any shape, it takes two VGPRs more)
+template <class ARGS>
+__device__ __forceinline__ BvSolveArgs bv_solve_args(const ARGS &a) {
+    BvSolveArgs sa;
+    sa.ref_base = a.ref_base; sa.out = a.out; sa.var_list = a.var_list; sa.counters = a.counters;
+    sa.min_af = a.min_af; sa.flags = a.flags;
+    sa.lnfact.t = a.tables->lnfact; sa.lnfact.n = (int)a.tables->lnfact_n;
+    sa.loghit = a.tables->loghit; sa.logmiss = a.tables->logmiss;
+    sa.bs = a.bs; sa.q = a.q; sa.pitch = a.pitch; sa.n_samples = a.n_samples;
+    return sa;
+}
 
 #define BV_LDS __attribute__((address_space(3)))
 
@@ -120,7 +132,7 @@ struct BvSiteSums {
 };
 
 // WHO runs a site's EM runs and its two Fisher tests.  BvSoloWork: the calling wave itself (every kernel; the arithmetic of a
-// site is defined by this form).  bv_pass1.hip adds a team form for the last sites of a long-row launch, where the same
+// site is defined by this form).  bv_pass1_team.h adds a team form for the last sites of a long-row launch, where the same
 // one-wave runs are dealt to the workgroup's idle waves -- same values, shorter critical path.
 struct BvSoloWork {
     __device__ __forceinline__ void lrt(const BvBins &B, const uint32_t depth[4], uint32_t total, int nspec, int ref,

@@ -321,7 +321,7 @@ __device__ __forceinline__ uint32_t bv_mask_tail_dword(uint32_t w, int keep) {
     uint32_t low = (1u << (8 * keep)) - 1u;
     return (w & low) | (0x08080808u & ~low);
 }
-// ... of the 16 call bytes of a row's last chunk (tail = n_samples & 15, not 0).  (bv_pass1.hip and bv_pass1_short.hip keep the four
+// ... of the 16 call bytes of a row's last chunk (tail = n_samples & 15, not 0).  (bv_pass1_row.h and bv_short_stream.h keep the four
 // assignments written out: through this function the code of their kernels moved, profiles/pass2_split_codehash.txt 3b.)
 __device__ __forceinline__ void bv_mask_tail16(bv_u32x4 &vb, int tail) {
     vb.x = bv_mask_tail_dword(vb.x, tail); vb.y = bv_mask_tail_dword(vb.y, tail - 4);

@@ -125,6 +125,37 @@ def test_short_row_kernel_variants_agree(bv, restatement, flags):
     assert np.allclose(ref_run.sites["qual"], got.sites["qual"], rtol=1e-9, atol=0, equal_nan=True)
 
 
+@pytest.mark.parametrize("n,form", [(4097, 0), (6144, 0x9000)], ids=["fused_4097", "two_kernels_6144"])
+def test_wave_solver_job_keeps_invalid_phreds_out_of_the_em(bv, n, form):
+    """The wave-solver job on a site's exported bins (bv_p1s_hard_site, bv_short.h: one definition under the solve kernel and
+    the fused kernel) unpacks every bin into the merged counts of the rank sum, and only the bins of valid phreds (< 94) into
+    the EM's -- as the four-per-wave solver does on the same bins (bv_solver16.h).  Deep sites with thirty calls of phred 94
+    (the first invalid value; the exported bins reach 127) through both solvers: with BV_FLAG_WAVE_SOLVER every candidate takes
+    the job, from the fused kernel at 4,097 samples and from the solve kernel (BV_FLAG_SHORT_ROW_FORM(9)) at 6,144.  The two
+    solvers agree to rounding, not to the byte: integer fields equal, QUAL and the allele frequencies to 1e-9 relative, the
+    bound test_short_row_kernel_variants_agree holds them to.  Thirty reads more in the EM move either by far more."""
+    S = 48
+    slab = make_slab(S, n, seed=94 + n, coverage=0.15, class_af=[(0.3, 0.0), (0.2, 0.1), (0.05, 0.0)])
+    touched = list(range(1, S, 3))
+    for r in touched:
+        cov = np.nonzero(slab["base_strand"][r, :n] < 8)[0]
+        assert len(cov) > 200
+        slab["qual"][r, cov[:30]] = 94
+    maf = bv.min_af(n)
+    res = []
+    for flags in (form, form | 0x10):
+        eng = bv.BaseTypeEngine(max_sites=S, min_af_value=maf, device=0, flags=flags)
+        res.append(eng.lrt(slab))
+        eng.close()
+    a, b = res
+    assert ((b.sites["status"][touched] & 0x4) != 0).all() and ((b.sites["status"] & 0x4) != 0).sum() == len(touched)
+    assert a.n_variant == b.n_variant and ((a.sites["status"][touched] & 0x2) != 0).sum() > 5
+    for f in ("depth", "total_depth", "cvg_sb", "var_sb", "n_alt", "alt", "status"):
+        assert np.array_equal(a.sites[f], b.sites[f]), f
+    for f in ("qual", "af"):
+        assert np.allclose(a.sites[f], b.sites[f], rtol=1e-9, atol=0, equal_nan=True), f
+
+
 def test_streaming_kernel_range_larger_than_its_reference_base_buffer(bv):
     """The short-row streaming kernel keeps the reference bases of a workgroup's sites in LDS, 4,096 at a time; a workgroup with
     more sites than that goes through its range in passes (barrier, refill, cursor reset).  BV_FLAG_GRID_LIMIT(1): one
@@ -1332,10 +1363,11 @@ def test_tile_job_interleaved_with_row_submits_and_abandoned_jobs(bv, restatemen
 
 @pytest.mark.parametrize("n,flags,groups", [(60000, 0, 0), (6000, 0, 0), (6000, 1 << 16, 0), (70, 0, 0), (1500, 0, 0),
                                             (60000, 0, 3), (6000, 0, 3), (6000, 1 << 16, 2), (6000, 0, 9), (1500, 0, 2), (70, 0, 2),
-                                            (3000, 0, 0), (6000, 10 << 12, 0)],
+                                            (3000, 0, 0), (6000, 10 << 12, 0), (6000, 9 << 12, 0), (6000, (9 << 12) | 0x10, 0)],
                          ids=["long_rows", "short_rows", "short_rows_one_workgroup", "shallow_rows", "rows_of_1500",
                               "long_rows_groups", "short_rows_groups", "short_rows_groups_one_workgroup", "short_rows_9_groups",
-                              "rows_of_1500_groups", "shallow_rows_groups", "dma_rows", "short_rows_pass2_own_launch"])
+                              "rows_of_1500_groups", "shallow_rows_groups", "dma_rows", "short_rows_pass2_own_launch",
+                              "short_rows_two_kernels", "short_rows_two_kernels_wave_solver"])
 def test_chained_submit_equals_separate_submits(bv, n, flags, groups):
     """bv_engine_submit_many(_g): several device slabs, one launch per pass (the site tickets / site ranges span the queue) --
     every record must be the one a submit of its own slab writes (byte for byte: which workgroup solves a site has no
@@ -1346,7 +1378,11 @@ def test_chained_submit_equals_separate_submits(bv, n, flags, groups):
     dma_rows: rows of 3,000 samples, bv_pass2_dma_kernel as a launch of its own; short_rows_pass2_own_launch: form 10
     (BV_FLAG_SHORT_ROW_FORM), the fused pass 1 with pass 2 as that kernel -- the chained engine carries the flag, the single
     submits run with default flags (records do not depend on the form).  Both re-do a long-read row of a later segment exactly
-    (the segment's planes looked up per site, bv_p2_wave_exact)."""
+    (the segment's planes looked up per site, bv_p2_wave_exact).
+    short_rows_two_kernels: form 9, the streaming kernel and the solve kernel at a row length the fused kernel would otherwise
+    take -- the solve kernel runs the wave-solver job on exported bins (bv_p1s_hard_site, shared with the fused kernel) with its
+    chain-plane patch on the shallow site of a later segment; ..._wave_solver: the same with BV_FLAG_WAVE_SOLVER, every
+    candidate through that job -- against single submits that keep that bit and run the job from the fused kernel."""
     import torch
     sizes = [96, 17, 200, 64, 1, 130, 48, 77, 33, 120, 5, 5, 60, 41, 9, 88, 150, 3, 70]  # 19 slabs: two chained launches (16 + 3)
     slabs = [make_slab(s, n, seed=300 + k, coverage=(0.05 + 0.02 * (k % 3)) if n > 1000 else 0.4,
@@ -1387,7 +1423,9 @@ def test_chained_submit_equals_separate_submits(bv, n, flags, groups):
     gchained = [g_.cpu().numpy().copy() for g_ in gouts]
     n_var_chain = eng.last_variant_count()
     eng.close()
-    eng = bv.BaseTypeEngine(max_sites=sum(sizes), min_af_value=maf, device=0)  # the single submits: default launch shapes
+    # the single submits: default launch shapes; which SOLVER takes a candidate stays (BV_FLAG_WAVE_SOLVER: the one-wave and the
+    # 16-lane solver agree to rounding, not to the byte -- test_short_row_kernel_variants_agree)
+    eng = bv.BaseTypeEngine(max_sites=sum(sizes), min_af_value=maf, device=0, flags=flags & 0x10)
     total_var = 0
     for k, sl in enumerate(slabs):
         outs[k].zero_()
