@@ -80,6 +80,10 @@ class BgzfCursor(C.Structure):  # bv_bgzf_cursor
     _fields_ = [("member", C.c_uint32), ("offset", C.c_uint32)]
 
 
+class TextRegion(C.Structure):  # bv_text_region (include/basevar_amd_region.h)
+    _fields_ = [("name", C.c_char_p), ("name_len", C.c_uint32), ("beg", C.c_uint32), ("end", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class VcfLines(C.Structure):  # bv_vcf_lines (include/basevar_amd_vcf.h)
     _fields_ = [("slab", C.POINTER(Slab)), ("site", C.c_void_p), ("head", C.c_void_p), ("head_off", C.c_void_p), ("gt", C.c_void_p),
                 ("n_lines", C.c_uint32), ("reserved_", C.c_uint32)]
@@ -173,6 +177,9 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
 
 # every symbol include/basevar_amd_bgzf.h declares
 BGZF_EXPORTS = ["bv_engine_bgzf_inflate", "bv_engine_text_parse_bgzf", "bv_engine_text_rows_fetch", "bv_engine_bgzf_deflate", "bv_engine_bgzf_deflate_level"]
+
+# every symbol include/basevar_amd_region.h declares
+REGION_EXPORTS = ["bv_engine_text_parse_bgzf_region"]
 
 # every symbol include/basevar_amd_vcf.h declares
 VCF_EXPORTS = ["bv_engine_vcf_format", "bv_engine_vcf_fetch", "bv_engine_vcf_deflate"]
@@ -295,6 +302,9 @@ def load():
     L.bv_engine_bgzf_inflate.argtypes = [C.c_void_p, C.POINTER(BgzfMembers), C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.bv_engine_text_parse_bgzf.restype = C.c_int
     L.bv_engine_text_parse_bgzf.argtypes = [C.c_void_p, C.POINTER(BgzfRows), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.bv_engine_text_parse_bgzf_region.restype = C.c_int
+    L.bv_engine_text_parse_bgzf_region.argtypes = [C.c_void_p, C.POINTER(BgzfRows), C.POINTER(TextRegion), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p,
+                                                   C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     L.bv_engine_text_rows_fetch.restype = C.c_int
     L.bv_engine_text_rows_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
     L.bv_engine_bgzf_deflate.restype = C.c_int

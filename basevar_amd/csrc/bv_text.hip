@@ -23,8 +23,10 @@
 
 #include "../../include/basevar_amd_bgzf.h"
 #include "../../include/basevar_amd_text_tokens.h"
+#include "../../include/basevar_amd_region.h"
 #include "bv_inflate_core.h"
 #include "bv_chunk_stage.h"
+#include "bv_text_region_core.h"
 
 using namespace bv_impl;
 
@@ -353,6 +355,81 @@ __global__ __launch_bounds__(64) void bv_text_line_scatter_kernel(const char *te
     }
 }
 
+// ---- the rows of a region (bv_engine_text_parse_bgzf_region, include/basevar_amd_region.h; the definition and the walk stand at
+// the head of bv_text_region_core.h).  Between the line scan and the scatter: one wave per tile reads the head of every line
+// that begins behind one of the tile's line breaks -- the lane that holds the line break reads on inside the run, across the
+// tile's edge where the head crosses it -- and folds the steps' masks into the tile's summary (bv_text_region_head_kernel); one
+// thread per file folds its tiles, and one thread decides P, region_done and the refusal (bv_text_region_combine_kernel).  The
+// scatter then runs on a copy of the LineFiles with skip_lines + first[f], for P + 1 rows: the begin of row (P, f) is the
+// cursor.  bv_text_region_pos_kernel holds POS of every taken row to file 0's.
+__global__ __launch_bounds__(64) void bv_text_region_head_kernel(const char *text, const LineFile *fl, uint32_t F, uint32_t at_end, const uint32_t *tile_pre,
+                                                                 bv_tr_region rg, bv_tr_tile *out) {
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const LineFile L = fl[line_file_of(fl, F, tile)];
+    const uint64_t end = line_run_end(text, L, at_end);
+    const uint64_t lo = L.skip + (uint64_t)(tile - L.tile_first) * kLineTile, hi = lo + kLineTile < end ? lo + kLineTile : end;
+    const char *run = text + L.base;
+    bv_tr_tile t = bv_tr_tile_init();
+    const uint32_t pre = tile_pre[tile];  // line breaks of this run before the tile
+    uint32_t ord = pre, pos = 0;
+    if (tile == L.tile_first && L.skip_lines == 0) {  // the run's first line: a step of its own
+        const uint32_t c = lane == 0 ? bv_tr_head(run + L.skip, end - L.skip, rg, &pos) : 0u;
+        bv_tr_step(t, 1ull, __ballot((c & BV_TR_REACHED) != 0), __ballot(lane == 0 && !(c & BV_TR_IN)), __ballot((c & BV_TR_MAL) != 0), 0u);
+    }
+    const uint64_t lt = (1ull << lane) - 1ull;
+    for (uint64_t x0 = lo; x0 < hi; x0 += 64u) {
+        const uint64_t x = x0 + lane;
+        const bool nl = x < hi && run[x] == '\n';
+        const uint64_t B = __ballot(nl);
+        // line break number j of the run begins line j + 1, whose ordinal is j + 1 - skip_lines
+        const bool has = nl && ord + (uint32_t)__popcll(B & lt) + 1u >= L.skip_lines;
+        const uint64_t LS = __ballot(has);
+        if (LS) {
+            const uint32_t c = has ? bv_tr_head(run + x + 1u, end - (x + 1u), rg, &pos) : 0u;
+            const uint32_t q0 = ord + (uint32_t)__popcll(B & bv_tr_below(bv_tr_low(LS))) + 1u - L.skip_lines;
+            bv_tr_step(t, LS, __ballot(has && (c & BV_TR_REACHED)), __ballot(has && !(c & BV_TR_IN)), __ballot(has && (c & BV_TR_MAL)), q0);
+        }
+        ord += (uint32_t)__popcll(B);
+    }
+    t.cnt = ord - pre;
+    if (lane == 0) out[tile] = t;
+}
+
+// files[f], the LineFile the scatter takes for file f, and *res
+__global__ __launch_bounds__(256) void bv_text_region_combine_kernel(const LineFile *fl, uint32_t F, const bv_tr_tile *tiles, uint32_t cap, uint32_t at_end,
+                                                                    bv_tr_file *files, LineFile *fl_sel, bv_tr_result *res) {
+    for (uint32_t f = threadIdx.x; f < F; f += 256u) {
+        LineFile L = fl[f];
+        bv_tr_file s = bv_tr_file_init();
+        uint32_t breaks = 0;
+        for (uint32_t k = 0; k < L.n_tiles; ++k) {
+            const bv_tr_tile t = tiles[L.tile_first + k];
+            bv_tr_file_add(s, t);
+            breaks += t.cnt;
+        }
+        bv_tr_file_finish(s, breaks, L.skip_lines);
+        files[f] = s;
+        L.skip_lines += s.first;
+        fl_sel[f] = L;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) *res = bv_tr_decide(files, F, cap, at_end);
+}
+
+// *err (set to BV_TR_NONE before) -> the lowest row r = p * F + f whose POS is not row (p, 0)'s
+__global__ __launch_bounds__(256) void bv_text_region_pos_kernel(const char *text, const uint64_t *row_beg, const uint64_t *row_end, uint32_t R, uint32_t F,
+                                                                uint32_t *err) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= R) return;
+    const uint32_t r0 = r - r % F;
+    if (r == r0) return;
+    const bv_tr_region any{nullptr, 0u, 0u, 0u};  // (heads of taken rows are well-formed: only POS is read)
+    uint32_t pos = 0, pos0 = 0;
+    (void)bv_tr_head(text + row_beg[r], row_end[r] - row_beg[r], any, &pos);
+    (void)bv_tr_head(text + row_beg[r0], row_end[r0] - row_beg[r0], any, &pos0);
+    if (pos != pos0) atomicMin(err, r);
+}
+
 // ---- bv_engine_text_rows_fetch: how much of every row the host still needs, then the bytes
 __global__ __launch_bounds__(256) void bv_text_fetch_len_kernel(const char *text, const uint64_t *row_beg, const uint64_t *row_end, const uint8_t *pos_state,
                                                                 const uint8_t *rowflag, uint32_t R, uint32_t F, uint32_t heads, uint32_t *len) {
@@ -421,6 +498,8 @@ struct BvTextState {
     size_t lines_bytes = 0;
     uint8_t *d_fetch = nullptr;             // rows_fetch: pos_state [n_pos], len u32 [n_rows], off u64 [n_rows + 1], the bytes
     size_t fetch_bytes = 0;
+    uint8_t *d_rrows = nullptr;             // _parse_bgzf_region: row begins, then row ends, of (n_pos + 1) * n_files rows
+    size_t rrows_bytes = 0;
 };
 
 bool bv_text_kept_rows(const BvTextState *t, BvKeptRows *rows) {
@@ -435,7 +514,7 @@ void bv_text_state_free(BvTextState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     chunk_stage_free(t->chunks);
-    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch})
+    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch, t->d_rrows})
         if (b) (void)hipFree(b);
     delete t;
 }
@@ -727,17 +806,40 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     return BV_OK;
 }
 
-int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
-                              uint8_t *row_state, bv_bgzf_cursor *cursor, void *stream_) {
-    const char *who = "bv_engine_text_parse_bgzf";
-    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
-    if (!rows || !row_state || !n_positions || !cursor) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
+// What bv_engine_text_parse_bgzf and bv_engine_text_parse_bgzf_region (include/basevar_amd_region.h) share: the runs checked,
+// inflated back to back and their line breaks counted per tile (bgzf_runs_begin), and the rows of a line index parsed
+// (bgzf_rows_parse).  Between the two each takes its rows its own way.
+namespace {
+struct BgzfRuns {
+    uint32_t F = 0, n_samples = 0, tiles = 0, Pmax = 0;
+    std::vector<BvBgzfMember> hd;
+    std::vector<LineFile> fl;
+    BvTextState *t = nullptr;
+    hipStream_t st = nullptr;
+    LineFile *d_fl = nullptr;
+    uint32_t *d_cnt = nullptr, *d_npos = nullptr;
+    size_t lines_end = 0;  // bytes of d_lines that the line index takes; a caller's own arrays lie behind them
+    const char *text = nullptr;
+    // inflated offset x of file f's run -> (member, offset)
+    void cursor_at(const bv_bgzf_rows *rows, bv_bgzf_cursor *cursor, uint32_t f, uint64_t x) const {
+        uint32_t k = rows->file_member[f];
+        const uint32_t k1 = rows->file_member[f + 1];
+        uint64_t base = 0;
+        while (k < k1 && base + hd[k].isize <= x) base += hd[k++].isize;
+        cursor[f].member = k - rows->file_member[f];
+        cursor[f].offset = k < k1 ? (uint32_t)(x - base) : 0u;
+    }
+};
+
+// r.tiles == 0 afterwards: no text behind the skips, nothing was launched.  `extra`: bytes of d_lines behind the line index
+int bgzf_runs_begin(bv_engine *e, const char *who, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
+                    bv_bgzf_cursor *cursor, void *stream_, size_t extra, BgzfRuns &r) {
     if (!rows->member_off || !rows->file_member || !rows->file_samples || !rows->skip_bytes || !rows->skip_lines)
         return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null member_off/file_member/file_samples/skip_bytes/skip_lines");
     if (rows->reserved_ || rows->at_end > 1u) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": reserved_ must be zero, at_end 0 or 1");
     if (rows->n_files == 0 || rows->max_positions == 0)
         return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": n_files and max_positions must be > 0");
-    const uint32_t F = rows->n_files;
+    const uint32_t F = r.F = rows->n_files;
     uint64_t n_samples = 0;
     if (rows->file_member[0] != 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member[0] must be 0");
     for (uint32_t f = 0; f < F; ++f)
@@ -747,7 +849,7 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     if (rc != BV_OK) return rc;
     *n_positions = 0;
     bv_bgzf_members mb{rows->data, rows->member_off, rows->data_bytes, rows->file_member[F], 0};
-    std::vector<BvBgzfMember> hd;
+    std::vector<BvBgzfMember> &hd = r.hd;
     std::vector<uint8_t> pre;
     rc = bv_bgzf_headers(e, who, &mb, hd, pre);
     if (rc != BV_OK) return rc;
@@ -759,7 +861,8 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     // where every member's text goes: file f's members back to back, one spare byte behind each run (16-byte aligned runs)
     const uint32_t M = mb.n_members;
     std::vector<uint64_t> out_pos(M + 1, 0);
-    std::vector<LineFile> fl(F);
+    std::vector<LineFile> &fl = r.fl;
+    fl.assign(F, LineFile());
     uint64_t at = 0;
     uint32_t tiles = 0;
     for (uint32_t f = 0; f < F; ++f) {
@@ -794,61 +897,170 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
                                                           " of its run: BGZF status " + std::to_string(status[k]) +
                                                           (status[k] == BV_BGZF_BAD_HEADER ? " (bad header)" : status[k] == BV_BGZF_BAD_DEFLATE ? " (invalid DEFLATE stream)"
                                                            : status[k] == BV_BGZF_BAD_SIZE ? " (inflated size is not ISIZE)" : " (CRC32 mismatch)"));
-    auto start_cursor = [&](uint32_t f, uint64_t x) {  // inflated offset x of file f's run -> (member, offset)
-        uint32_t k = rows->file_member[f];
-        const uint32_t k1 = rows->file_member[f + 1];
-        uint64_t base = 0;
-        while (k < k1 && base + hd[k].isize <= x) base += hd[k++].isize;
-        cursor[f].member = k - rows->file_member[f];
-        cursor[f].offset = k < k1 ? (uint32_t)(x - base) : 0u;
-    };
-    for (uint32_t f = 0; f < F; ++f) start_cursor(f, fl[f].skip);
-    const uint32_t Pmax = std::min(rows->max_positions, e->cfg.max_sites);
-    if (tiles == 0) return BV_OK;  // no text behind the skips: no position
+    r.n_samples = (uint32_t)n_samples; r.tiles = tiles; r.t = t; r.st = st;
+    for (uint32_t f = 0; f < F; ++f) r.cursor_at(rows, cursor, f, fl[f].skip);
+    r.Pmax = std::min(rows->max_positions, e->cfg.max_sites);
+    if (tiles == 0) return BV_OK;
     // the line index
     const size_t o_cnt = up256(sizeof(LineFile) * F), o_npos = o_cnt + up256(4ull * tiles);
-    rc = grow_device(e, &t->d_lines, &t->lines_bytes, o_npos + 256);
+    r.lines_end = o_npos + 256;
+    rc = grow_device(e, &t->d_lines, &t->lines_bytes, r.lines_end + extra + (extra ? up256(sizeof(bv_tr_tile) * tiles) : 0));
     if (rc != BV_OK) return rc;
-    LineFile *d_fl = reinterpret_cast<LineFile *>(t->d_lines);
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(t->d_lines + o_cnt), *d_npos = reinterpret_cast<uint32_t *>(t->d_lines + o_npos);
-    const char *text = reinterpret_cast<const char *>(t->d_btext);
-    BV_HIP(e, hipMemcpyAsync(d_fl, fl.data(), sizeof(LineFile) * F, hipMemcpyHostToDevice, st));
-    BV_HIP(e, hipMemcpyAsync(d_npos, &Pmax, 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(bv_text_line_pad_kernel, dim3((F + 63u) / 64u), dim3(64), 0, st, (char *)t->d_btext, (const LineFile *)d_fl, F);
-    hipLaunchKernelGGL(bv_text_line_count_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, d_cnt);
-    hipLaunchKernelGGL(bv_text_line_scan_kernel, dim3(1), dim3(256), 0, st, (const LineFile *)d_fl, F, d_cnt, d_npos);
+    r.d_fl = reinterpret_cast<LineFile *>(t->d_lines);
+    r.d_cnt = reinterpret_cast<uint32_t *>(t->d_lines + o_cnt);
+    r.d_npos = reinterpret_cast<uint32_t *>(t->d_lines + o_npos);
+    r.text = reinterpret_cast<const char *>(t->d_btext);
+    BV_HIP(e, hipMemcpyAsync(r.d_fl, fl.data(), sizeof(LineFile) * F, hipMemcpyHostToDevice, st));
+    BV_HIP(e, hipMemcpyAsync(r.d_npos, &r.Pmax, 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_line_pad_kernel, dim3((F + 63u) / 64u), dim3(64), 0, st, (char *)t->d_btext, (const LineFile *)r.d_fl, F);
+    hipLaunchKernelGGL(bv_text_line_count_kernel, dim3(tiles), dim3(64), 0, st, r.text, (const LineFile *)r.d_fl, F, rows->at_end, r.d_cnt);
+    hipLaunchKernelGGL(bv_text_line_scan_kernel, dim3(1), dim3(256), 0, st, (const LineFile *)r.d_fl, F, r.d_cnt, r.d_npos);
     BV_HIP(e, hipGetLastError());
-    uint32_t P = 0;
-    BV_HIP(e, hipMemcpyAsync(&P, d_npos, 4, hipMemcpyDeviceToHost, st));
-    BV_HIP(e, hipStreamSynchronize(st));
-    if (P == 0) return BV_OK;
-    ParseBufs pb;
-    rc = parse_begin(e, t, P, F, rows->file_samples, (uint32_t)n_samples, st, &pb);
-    if (rc != BV_OK) return rc;
+    return BV_OK;
+}
+
+// the P * F rows of (row_beg, row_end) parsed; last[f] = the end of file f's last row
+int bgzf_rows_parse(bv_engine *e, const BgzfRuns &r, uint32_t P, uint64_t *row_beg, uint64_t *row_end, const ParseBufs &pb, const uint8_t *group_id,
+                    uint32_t n_groups, uint8_t *row_state, std::vector<uint64_t> &last) {
+    const uint32_t F = r.F;
+    hipStream_t st = r.st;
     const size_t R = (size_t)P * F;
-    uint64_t *row_beg = pb.d_off, *row_end = pb.d_off + R;
-    hipLaunchKernelGGL(bv_text_line_scatter_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_fl, F, rows->at_end, (const uint32_t *)d_cnt, P,
-                       row_beg, row_end);
-    BV_HIP(e, hipGetLastError());
     TextParseArgs a;
-    a.text = text; a.row_beg = row_beg; a.row_end = row_end; a.foff = pb.foff; a.fsamp = pb.fsamp; a.chunk_base = 0;
+    a.text = r.text; a.row_beg = row_beg; a.row_end = row_end; a.foff = pb.foff; a.fsamp = pb.fsamp; a.chunk_base = 0;
     a.row_first = 0; a.n_rows_chunk = (uint32_t)R; a.n_files = F; a.pitch = pb.pitch;
     a.bs = pb.bs; a.q = pb.q; a.mq = pb.mq; a.st = pb.stp; a.ref = pb.ref; a.rowflag = pb.rowflag; a.rp = pb.rp;
     a.depth = pb.depth; a.pstate = pb.pstate; a.pmax = pb.pmax;
     hipLaunchKernelGGL(bv_text_parse_kernel, dim3((a.n_rows_chunk + 3u) / 4u), dim3(256), 0, st, a);
     BV_HIP(e, hipGetLastError());
-    rc = bv_text_tokens_rows(e, BvTextTokRows{text, row_beg, row_end, pb.rowflag, pb.foff, 0, 0, (uint32_t)R, F}, st);
+    int rc = bv_text_tokens_rows(e, BvTextTokRows{r.text, row_beg, row_end, pb.rowflag, pb.foff, 0, 0, (uint32_t)R, F}, st);
     if (rc != BV_OK) return rc;
-    std::vector<uint64_t> last(F);
+    last.resize(F);
     BV_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
-    rc = parse_finish(e, t, P, F, (uint32_t)n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
+    rc = parse_finish(e, r.t, P, F, r.n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
     if (rc != BV_OK) {
-        t->parsed = false;
+        r.t->parsed = false;
         return rc;
     }
-    for (uint32_t f = 0; f < F; ++f) start_cursor(f, std::min(last[f] - fl[f].base, fl[f].len));
-    t->bz_row_beg = row_beg; t->bz_row_end = row_end; t->bz_rowflag = pb.rowflag;
-    t->bgzf_rows = true;
+    r.t->bz_row_beg = row_beg; r.t->bz_row_end = row_end; r.t->bz_rowflag = pb.rowflag;
+    r.t->bgzf_rows = true;
+    return BV_OK;
+}
+}  // namespace
+
+int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint32_t *n_positions,
+                              uint8_t *row_state, bv_bgzf_cursor *cursor, void *stream_) {
+    const char *who = "bv_engine_text_parse_bgzf";
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!rows || !row_state || !n_positions || !cursor) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
+    BgzfRuns r;
+    int rc = bgzf_runs_begin(e, who, rows, group_id, n_groups, n_positions, cursor, stream_, 0, r);
+    if (rc != BV_OK || r.tiles == 0) return rc;  // (no text behind the skips: no position)
+    const uint32_t F = r.F;
+    hipStream_t st = r.st;
+    uint32_t P = 0;
+    BV_HIP(e, hipMemcpyAsync(&P, r.d_npos, 4, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
+    if (P == 0) return BV_OK;
+    ParseBufs pb;
+    rc = parse_begin(e, r.t, P, F, rows->file_samples, r.n_samples, st, &pb);
+    if (rc != BV_OK) return rc;
+    const size_t R = (size_t)P * F;
+    uint64_t *row_beg = pb.d_off, *row_end = pb.d_off + R;
+    hipLaunchKernelGGL(bv_text_line_scatter_kernel, dim3(r.tiles), dim3(64), 0, st, r.text, (const LineFile *)r.d_fl, F, rows->at_end, (const uint32_t *)r.d_cnt, P,
+                       row_beg, row_end);
+    BV_HIP(e, hipGetLastError());
+    std::vector<uint64_t> last;
+    rc = bgzf_rows_parse(e, r, P, row_beg, row_end, pb, group_id, n_groups, row_state, last);
+    if (rc != BV_OK) return rc;
+    for (uint32_t f = 0; f < F; ++f) r.cursor_at(rows, cursor, f, std::min(last[f] - r.fl[f].base, r.fl[f].len));
+    *n_positions = P;
+    return BV_OK;
+}
+
+// The rows of a region (bv_text_region_core.h): behind the line index the heads are read and folded, the scatter runs from each
+// file's first reached line, POS is held equal across the files, and the rows are parsed as bv_engine_text_parse_bgzf's are.
+int bv_engine_text_parse_bgzf_region(bv_engine *e, const bv_bgzf_rows *rows, const bv_text_region *region, const uint8_t *group_id, uint32_t n_groups,
+                                     uint32_t *n_positions, uint8_t *row_state, bv_bgzf_cursor *cursor, uint32_t *region_done, void *stream_) {
+    const char *who = "bv_engine_text_parse_bgzf_region";
+    if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, std::string(who) + ": null engine");
+    if (!rows || !row_state || !n_positions || !cursor) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null rows/n_positions/row_state/cursor");
+    if (!region || !region_done) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null region/region_done");
+    if (!region->name || region->name_len == 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the region needs a name");
+    if (region->beg == 0 || region->beg > region->end) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the region needs 1 <= beg <= end");
+    if (region->reserved_) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": the region's reserved_ must be zero");
+    *region_done = 0;
+    BgzfRuns r;
+    const uint32_t F0 = rows->n_files;
+    // behind the line index: file results, the scatter's LineFiles, the result and the POS check's word, the name -- and the tile summaries
+    const size_t o_file = 0, o_sel = o_file + up256(sizeof(bv_tr_file) * F0), o_res = o_sel + up256(sizeof(LineFile) * F0), o_name = o_res + 256,
+                 o_tile = o_name + up256(region->name_len);
+    int rc = bgzf_runs_begin(e, who, rows, group_id, n_groups, n_positions, cursor, stream_, o_tile, r);
+    if (rc != BV_OK) return rc;
+    if (r.tiles == 0) {  // no text behind the skips: no position
+        *region_done = rows->at_end;
+        return BV_OK;
+    }
+    const uint32_t F = r.F, tiles = r.tiles;
+    BvTextState *t = r.t;
+    hipStream_t st = r.st;
+    const char *text = r.text;
+    uint8_t *mine = t->d_lines + r.lines_end;
+    bv_tr_file *d_file = reinterpret_cast<bv_tr_file *>(mine + o_file);
+    LineFile *d_sel = reinterpret_cast<LineFile *>(mine + o_sel);
+    bv_tr_result *d_res = reinterpret_cast<bv_tr_result *>(mine + o_res);
+    uint32_t *d_err = reinterpret_cast<uint32_t *>(d_res + 1);
+    char *d_name = reinterpret_cast<char *>(mine + o_name);
+    bv_tr_tile *d_tile = reinterpret_cast<bv_tr_tile *>(mine + o_tile);
+    BV_HIP(e, hipMemcpyAsync(d_name, region->name, region->name_len, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_region_head_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)r.d_fl, F, rows->at_end, (const uint32_t *)r.d_cnt,
+                       bv_tr_region{d_name, region->name_len, region->beg, region->end}, d_tile);
+    hipLaunchKernelGGL(bv_text_region_combine_kernel, dim3(1), dim3(256), 0, st, (const LineFile *)r.d_fl, F, (const bv_tr_tile *)d_tile, r.Pmax, rows->at_end, d_file,
+                       d_sel, d_res);
+    BV_HIP(e, hipGetLastError());
+    bv_tr_result res;
+    std::vector<bv_tr_file> sel(F);
+    BV_HIP(e, hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(sel.data(), d_file, sizeof(bv_tr_file) * F, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
+    if (res.err == BV_TR_ERR_HEAD)
+        return fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(res.err_file) + ", line " + std::to_string(res.err_line) +
+                                        " behind its skip: the head is not CHROM, a tab, POS of 1 to 10 digits <= 4294967295, a tab");
+    if (res.err == BV_TR_ERR_COUNT)
+        return fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(res.err_file) + ", line " + std::to_string(res.err_line) +
+                                        " behind its skip: the file's lines of the region end here, file " + std::to_string(res.err_file2) + " has more");
+    const uint32_t P = res.P;
+    // the taken rows and one more, whose begin is the cursor
+    const size_t R1 = ((size_t)P + 1) * F;
+    rc = grow_device(e, &t->d_rrows, &t->rrows_bytes, up256(16 * R1));
+    if (rc != BV_OK) return rc;
+    uint64_t *row_beg = reinterpret_cast<uint64_t *>(t->d_rrows), *row_end = row_beg + R1;
+    const uint32_t none = BV_TR_NONE;
+    BV_HIP(e, hipMemcpyAsync(d_err, &none, 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bv_text_line_scatter_kernel, dim3(tiles), dim3(64), 0, st, text, (const LineFile *)d_sel, F, rows->at_end, (const uint32_t *)r.d_cnt, P + 1u,
+                       row_beg, row_end);
+    if (P && F > 1)
+        hipLaunchKernelGGL(bv_text_region_pos_kernel, dim3((uint32_t)(((size_t)P * F + 255) / 256)), dim3(256), 0, st, text, (const uint64_t *)row_beg,
+                           (const uint64_t *)row_end, (uint32_t)((size_t)P * F), F, d_err);
+    BV_HIP(e, hipGetLastError());
+    uint32_t bad = BV_TR_NONE;
+    std::vector<uint64_t> next(F);
+    BV_HIP(e, hipMemcpyAsync(&bad, d_err, 4, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipMemcpyAsync(next.data(), row_beg + (size_t)P * F, 8ull * F, hipMemcpyDeviceToHost, st));
+    BV_HIP(e, hipStreamSynchronize(st));
+    if (bad != BV_TR_NONE)
+        return fail(e, BV_ERR_DATA, std::string(who) + ": file " + std::to_string(bad % F) + ", position " + std::to_string(bad / F) + " of the region's rows (line " +
+                                        std::to_string(sel[bad % F].first + bad / F) + " behind its skip): POS differs from file 0's");
+    // a file without a line stays where it was; every other one goes to its line first + P
+    for (uint32_t f = 0; f < F; ++f)
+        if (sel[f].n_lines) r.cursor_at(rows, cursor, f, std::min(next[f] - r.fl[f].base, r.fl[f].len));
+    *region_done = res.done;
+    if (P == 0) return BV_OK;
+    ParseBufs pb;
+    rc = parse_begin(e, t, P, F, rows->file_samples, r.n_samples, st, &pb);
+    if (rc != BV_OK) return rc;
+    std::vector<uint64_t> last;
+    rc = bgzf_rows_parse(e, r, P, row_beg, row_end, pb, group_id, n_groups, row_state, last);
+    if (rc != BV_OK) return rc;
     *n_positions = P;
     return BV_OK;
 }

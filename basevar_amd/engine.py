@@ -465,7 +465,7 @@ class BaseTypeEngine:
 
     # ---- batchfile rows that are still compressed: inflated, split into lines and parsed on the device
     def lrt_bgzf(self, runs, file_samples, skip_bytes=None, skip_lines=None, max_positions=None, at_end=True, group_id=None, n_groups=0,
-                 host_reader=None, tokens="host"):
+                 host_reader=None, tokens="host", region=None):
         """lrt_text for rows that are still BGZF members (bv_engine_text_parse_bgzf + bv_engine_text_rows_fetch +
         bv_engine_text_submit).  `runs`: per batchfile the list of its consecutive whole members (bytes) from where its next row
         starts; that row begins skip_bytes[f] inflated bytes into the run and skip_lines[f] lines further.  Takes
@@ -473,14 +473,18 @@ class BaseTypeEngine:
         Returns what lrt_text returns plus `cursors` [n_files][2] -- (member of the run, inflated offset inside it) of every
         file's first line not taken -- and `fetched` = (bytes, row_off): the text the host needs (bv_engine_text_rows_fetch).
         A damaged member raises RuntimeError with `.args[1] == BV_ERR_DATA`.  `tokens`: as lrt_text's; with "device", `fetched` comes
-        from text_heads_fetch (a marked row is cut like any other) and the batch carries `tokens` / `token_text`."""
+        from text_heads_fetch (a marked row is cut like any other) and the batch carries `tokens` / `token_text`.
+        `region` = (name, beg, end), 1-based inclusive: the rows are the region's lines (bv_engine_text_parse_bgzf_region,
+        include/basevar_amd_region.h) -- lines in front of it are consumed, POS is held equal across the files -- and the batch
+        carries `region_done` as well; a malformed head, files that disagree on the region's lines or on POS raise RuntimeError
+        with `.args[1] == BV_ERR_DATA`.  Without `region`, exactly the calls above."""
         restore = self._tokens_mode(tokens, "lrt_bgzf")
         try:
-            return self._lrt_bgzf(runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, tokens == "device")
+            return self._lrt_bgzf(runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, tokens == "device", region)
         finally:
             restore()
 
-    def _lrt_bgzf(self, runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, device_tokens):
+    def _lrt_bgzf(self, runs, file_samples, skip_bytes, skip_lines, max_positions, at_end, group_id, n_groups, host_reader, device_tokens, region=None):
         fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
         F, N = int(fs.size), int(fs.sum())
         if len(runs) != F:
@@ -500,10 +504,19 @@ class BaseTypeEngine:
         state = np.zeros((max(cap, 1), F), dtype=np.uint8)
         n_pos = C.c_uint32(0)
         cursors = np.zeros((F, 2), dtype=np.uint32)
-        rc = self._lib.bv_engine_text_parse_bgzf(self._h, C.byref(br), None if gid is None else gid.ctypes.data, int(n_groups), C.byref(n_pos),
-                                                 state.ctypes.data, cursors.ctypes.data, None)
-        if rc != 0:
-            raise RuntimeError("bv_engine_text_parse_bgzf failed (%d): %s" % (rc, self._err()), rc)
+        done = C.c_uint32(0)
+        if region is None:
+            rc = self._lib.bv_engine_text_parse_bgzf(self._h, C.byref(br), None if gid is None else gid.ctypes.data, int(n_groups), C.byref(n_pos),
+                                                     state.ctypes.data, cursors.ctypes.data, None)
+            if rc != 0:
+                raise RuntimeError("bv_engine_text_parse_bgzf failed (%d): %s" % (rc, self._err()), rc)
+        else:
+            name = None if region[0] is None else (region[0].encode() if isinstance(region[0], str) else bytes(region[0]))
+            rg = _capi.TextRegion(name, len(name) if name else 0, int(region[1]), int(region[2]), int(region[3]) if len(region) > 3 else 0)
+            rc = self._lib.bv_engine_text_parse_bgzf_region(self._h, C.byref(br), C.byref(rg), None if gid is None else gid.ctypes.data, int(n_groups),
+                                                            C.byref(n_pos), state.ctypes.data, cursors.ctypes.data, C.byref(done), None)
+            if rc != 0:
+                raise RuntimeError("bv_engine_text_parse_bgzf_region failed (%d): %s" % (rc, self._err()), rc)
         P = int(n_pos.value)
         state = np.ascontiguousarray(state.reshape(-1)[:P * F].reshape(P, F))
         if P == 0:
@@ -512,6 +525,8 @@ class BaseTypeEngine:
             batch.cursors, batch.fetched = cursors, (np.zeros(0, np.uint8), np.zeros(1, np.uint64))
             if device_tokens:
                 batch.tokens, batch.token_text = np.zeros(0, _capi.PILEUP_TOKEN_DTYPE), np.zeros(0, np.uint8)
+            if region is not None:
+                batch.region_done = bool(done.value)
             return batch
         fetched = self.text_heads_fetch(P * F) if device_tokens else self.text_rows_fetch(P * F)
         buf, roff = fetched
@@ -520,6 +535,8 @@ class BaseTypeEngine:
         batch.cursors, batch.fetched = cursors, fetched
         if device_tokens:
             batch.tokens, batch.token_text = self.text_tokens_fetch()
+        if region is not None:
+            batch.region_done = bool(done.value)
         return batch
 
     def text_rows_fetch(self, n_rows, capacity=None):

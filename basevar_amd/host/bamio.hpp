@@ -65,6 +65,26 @@ public:
         }
         return true;
     }
+    // the next line without its '\n' (a last line without one counts); false at the end of the file
+    bool getline(std::string &line) {
+        line.clear();
+        for (;;) {
+            if (!have_block_ || pos_ == data_.size()) {
+                if (!load_block(have_block_ ? next_addr_ : 0)) return !line.empty();
+                continue;
+            }
+            const uint8_t *b = data_.data() + pos_;
+            const void *nl = std::memchr(b, '\n', data_.size() - pos_);
+            if (nl) {
+                const size_t n = (size_t)(static_cast<const uint8_t *>(nl) - b);
+                line.append(reinterpret_cast<const char *>(b), n);
+                pos_ += n + 1;
+                return true;
+            }
+            line.append(reinterpret_cast<const char *>(b), data_.size() - pos_);
+            pos_ = data_.size();
+        }
+    }
 
 private:
     bool load_block(uint64_t addr) {

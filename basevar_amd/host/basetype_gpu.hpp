@@ -26,6 +26,7 @@
 #include "../../include/basevar_amd_indel.h"
 #include "../../include/basevar_amd_text_tokens.h"
 #include "../../include/basevar_amd_record_text.h"
+#include "../../include/basevar_amd_region.h"
 #include "../../include/basevar_amd_vcf.h"
 #include "indel_tokens.hpp"  // TokenList, row_indel_tokens
 #include "vcf_emit.hpp"  // SiteText
@@ -453,6 +454,7 @@ public:
         std::vector<uint8_t> row_state;
         std::vector<bv_bgzf_cursor> cursor;
         TokenMode tokens = TOKENS_HOST;
+        bool region_done = false;  // parse_bgzf_region
     };
     BgzfParse parse_bgzf(const bv_bgzf_rows &rows, uint32_t max_sites, const uint8_t *group_id = nullptr, uint32_t n_groups = 0,
                          TokenMode tokens = TOKENS_HOST) {
@@ -465,6 +467,25 @@ public:
         if (rc == BV_ERR_DATA) throw BgzfDataError(bv_last_error(e_));
         if (rc != BV_OK) throw std::runtime_error(bv_last_error(e_));
         bp.row_state.resize((size_t)bp.n_positions * rows.n_files);
+        return bp;
+    }
+    // parse_bgzf() on the lines of a region (bv_engine_text_parse_bgzf_region, include/basevar_amd_region.h): bp.region_done says
+    // whether the region has further rows; BgzfDataError also for a malformed head and for files that disagree on the region's
+    // lines or on POS.  finish_bgzf() runs unchanged behind it.
+    BgzfParse parse_bgzf_region(const bv_bgzf_rows &rows, const bv_text_region &region, uint32_t max_sites, const uint8_t *group_id = nullptr,
+                                uint32_t n_groups = 0, TokenMode tokens = TOKENS_HOST) {
+        BgzfParse bp;
+        bp.tokens = tokens;
+        text_tokens_mode(tokens);
+        bp.row_state.resize((size_t)std::max<uint32_t>(1, std::min(rows.max_positions, max_sites)) * rows.n_files);
+        bp.cursor.resize(rows.n_files);
+        uint32_t done = 0;
+        const int rc = bv_engine_text_parse_bgzf_region(e_, &rows, &region, group_id, n_groups, &bp.n_positions, bp.row_state.data(), bp.cursor.data(), &done,
+                                                        nullptr);
+        if (rc == BV_ERR_DATA) throw BgzfDataError(bv_last_error(e_));
+        if (rc != BV_OK) throw std::runtime_error(bv_last_error(e_));
+        bp.row_state.resize((size_t)bp.n_positions * rows.n_files);
+        bp.region_done = done != 0;
         return bp;
     }
     template <class HostReader>

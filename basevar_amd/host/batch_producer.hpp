@@ -709,6 +709,38 @@ public:
             members_passed += m;
         }
     }
+    // ---- a region call (bv_call --batchfiles ... --regions; bv_engine_text_parse_bgzf_region).  File f's next run starts at
+    // the virtual offset its index gave for the region (host/tabix_query.hpp): no header line lies behind such a place.
+    void seek(size_t f, uint64_t voff) { files_[f].pos = voff >> 16; files_[f].skip_bytes = voff & 0xffffu; files_[f].skip_lines = 0; }
+    // ... at its first row (a file without an index is scanned for every region) ...
+    void rewind(size_t f, size_t header_lines) { files_[f].pos = 0; files_[f].skip_bytes = 0; files_[f].skip_lines = (uint32_t)header_lines; }
+    // ... or nowhere: the index holds no line of the region, the run is empty and ends the file
+    void seek_end(size_t f) {
+        File &x = files_[f];
+        if (std::fseek(x.fp, 0, SEEK_END) != 0) throw std::runtime_error("[ERROR] cannot seek in a batchfile");
+        x.pos = (uint64_t)std::ftell(x.fp); x.skip_bytes = 0; x.skip_lines = 0;
+    }
+    // advance() behind a region parse: a file whose cursor is where its run started had no complete line behind its skip and
+    // keeps its skip_lines; returns whether any file moved
+    bool advance_region(const BgzfRawRuns &r, const uint32_t *member, const uint32_t *offset) {
+        bool any = false;
+        for (size_t f = 0; f < files_.size(); ++f) {
+            File &x = files_[f];
+            const size_t n = r.member_pos[f].size() - 1, m = std::min<size_t>(member[f], n);
+            uint64_t at = offset[f];  // inflated bytes of the run in front of the cursor
+            for (size_t k = 0; k < m; ++k) {
+                const unsigned char *t = &r.data[r.member_off[r.file_member[f] + k + 1] - 4];
+                at += (uint64_t)t[0] | ((uint64_t)t[1] << 8) | ((uint64_t)t[2] << 16) | ((uint64_t)t[3] << 24);
+            }
+            const bool moved = at != r.skip_bytes[f];
+            x.pos = r.member_pos[f][m];
+            x.skip_bytes = offset[f];
+            if (moved) x.skip_lines = 0;
+            any = any || moved;
+            members_passed += m;
+        }
+        return any;
+    }
 
 private:
     struct File {

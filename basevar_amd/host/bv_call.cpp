@@ -17,6 +17,8 @@
 //           [--pileup device|host]   (BAM input; with it, --inflate device also hands the BAM files' BGZF members to the engine compressed)
 //           [--gpus G] [--devices 0,1,... | --device 0]
 //           [--reference ref.fa --contig NAME:LENGTH ...]
+//           [--regions CHR[:BEG[-END]][,...]]   (batchfile input: the regions in the order given, each from where the file's .tbi
+//                                                says it may begin -- a seek, not a scan)
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
 //           [--thread T] ...   (same outputs)
 //
@@ -55,6 +57,7 @@ struct Options {
     // what validate() makes of them
     std::vector<int> devices;            // one engine per entry
     std::vector<bvamd::Region> region_list;
+    std::vector<bvamd::BatchRegion> batch_regions;  // --regions on batchfile input
     bool from_bam() const { return !bams.empty(); }
 };
 
@@ -123,6 +126,51 @@ void validate(Options &o) {
         if (!bvamd::parse_region(rg, r)) die("--regions wants CHR:BEG-END[,CHR:BEG-END...]");
         o.region_list.push_back(r);
     }
+    // batchfile input: "CHR", "CHR:BEG", "CHR:BEG-END" as tabix reads them (the list is cut at commas, so numbers carry none).
+    // With --inflate device the rows are selected on the device, where the inflated text lies
+    // (bv_engine_text_parse_bgzf_region); the host reader selects them by the same definition.
+    for (const std::string &rg : !o.from_bam() && !o.regions.empty() ? bvamd::pieces(o.regions, ',') : std::vector<std::string>()) {
+        bvamd::BatchRegion r;
+        if (!bvamd::parse_batch_region(rg, r)) die("[ERROR] --regions on batchfiles wants CHR, CHR:BEG or CHR:BEG-END (1 <= BEG <= END <= 2^29), not '" + rg + "'");
+        o.batch_regions.push_back(r);
+    }
+    // a *.gz output is indexed as it is written, which takes sorted lines: the regions of a contig together, ascending, apart
+    if (bvamd::ends_in_gz(o.out_vcf) || bvamd::ends_in_gz(o.out_cvg)) {
+        for (size_t i = 0; i < o.batch_regions.size(); ++i)
+            for (size_t j = 0; j < i; ++j) {
+                const bvamd::BatchRegion &a = o.batch_regions[j], &b = o.batch_regions[i];
+                if (a.name != b.name) continue;
+                if (o.batch_regions[i - 1].name != b.name || a.end >= b.beg)
+                    die("[ERROR] --regions with a *.gz output: the regions of " + b.name + " must stand together, ascending and without overlap ('" +
+                        b.name + ":" + std::to_string(b.beg) + "-" + std::to_string(b.end) + "' does not)");
+            }
+    }
+}
+
+// --regions on batchfiles: every file's index, read before any engine exists.  A file without one, and a plain or plain-gzip
+// file (no virtual offset leads into it), is scanned from its first row for every region (one note for all of them); a contig
+// that no index knows fails as the reference does (caller.cpp:566).
+void load_region_indexes(const Options &o, const bvamd::BatchfileHeaders &headers, bvamd::RegionIndexes &idx) {
+    const size_t F = o.batchfiles.size();
+    idx.index.resize(F);
+    idx.indexed.assign(F, 0);
+    idx.header_lines = headers.header_lines;
+    std::string scanned;
+    for (size_t f = 0; f < F; ++f) {
+        unsigned char h[18];
+        std::FILE *fp = std::fopen(o.batchfiles[f].c_str(), "rb");
+        const bool bgzf = fp && std::fread(h, 1, 18, fp) == 18 && bvamd::bgzf_member_header(h);
+        if (fp) std::fclose(fp);
+        try { idx.indexed[f] = bgzf && idx.index[f].load(o.batchfiles[f] + ".tbi") ? 1 : 0; } catch (const std::exception &ex) { die(ex.what()); }
+        if (!idx.indexed[f]) scanned += (scanned.empty() ? "" : ", ") + o.batchfiles[f];
+    }
+    if (!scanned.empty()) std::cerr << "[NOTE] --regions: no .tbi beside " << scanned << " (or no BGZF file): scanned from the first row for every region" << std::endl;
+    for (const bvamd::BatchRegion &rg : o.batch_regions)
+        for (size_t f = 0; f < F; ++f) {
+            uint64_t voff = 0;
+            if (idx.indexed[f] && idx.index[f].query(rg.name, rg.beg, rg.end, &voff) == bvamd::TabixReader::UNKNOWN_NAME)
+                die("[ERROR] load data in " + rg.name + ":" + std::to_string(rg.beg) + "-" + std::to_string(rg.end) + " failed. Check input file: " + o.batchfiles[f]);
+        }
 }
 
 // Pop groups (caller.cpp:372-410): sample -> group, later rows override; groups iterate by name
@@ -271,6 +319,7 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
     // batchfile input: the bytes the workers' row (or head) fetches and token fetches brought back from their engines; with
     // --indel-tokens device, the tokens the engines listed
     if (!ctx.from_bam) tf << ", \"text_fetch_bytes\": " << counts.text_fetch_bytes;
+    if (!ctx.regions.empty()) tf << ", \"regions\": " << ctx.regions.size();  // --regions on batchfiles
     if (ctx.routes.indel_tokens_device) tf << ", \"indel_tokens\": \"device\", \"indel_tokens_device\": " << counts.indel_tokens_device;
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
@@ -298,6 +347,8 @@ int main(int argc, char **argv) {
         }
     } catch (const std::exception &ex) { die(ex.what()); }
     if (ctx.n_sample() == 0) die("[ERROR] no ##SampleIDs= header found in the batchfiles");
+    bvamd::RegionIndexes region_indexes;
+    if (!o.batch_regions.empty()) load_region_indexes(o, headers, region_indexes);
     if (o.from_bam()) o.batchfiles.clear();
     read_pop_groups(o.pop_group_file, ctx);
     bvamd::TextOut VCF, CVG;
@@ -313,6 +364,7 @@ int main(int argc, char **argv) {
     ctx.deflate_level = o.deflate_level == "small" ? BV_DEFLATE_SMALL : BV_DEFLATE_FAST;
     ctx.from_bam = o.from_bam();
     ctx.vcf_gz = bvamd::ends_in_gz(o.out_vcf);
+    ctx.regions = o.batch_regions;
     const bvamd::BamInput bam_input{o.bams, o.reference, o.region_list, o.mapq_thd};
     // batchfile input: a batch is one block of rows as text, ~10 B per cell.  32 MiB blocks, the size of the host reader's
     // blocks: larger ones left the read tasks waiting on the packing of the few blocks in flight (measured: 512 MiB blocks on
@@ -327,7 +379,8 @@ int main(int argc, char **argv) {
     StageClock clk;
     bvamd::ErrorSink errors;
     const double t_start = StageClock::now();
-    bvamd::RawReaderTurns raw_turns(ctx, raw, std::max<size_t>(text_block_bytes / std::max<size_t>(1, o.batchfiles.size()), 1));
+    bvamd::RawReaderTurns raw_turns(ctx, raw, std::max<size_t>(text_block_bytes / std::max<size_t>(1, o.batchfiles.size()), 1),
+                                     ctx.regions.empty() ? nullptr : &region_indexes);
     std::deque<bvamd::EngineWorker> workers;
     std::vector<std::thread> worker_threads;
     for (size_t w = 0; w < W; ++w) {
@@ -341,6 +394,8 @@ int main(int argc, char **argv) {
     try {
         if (ctx.routes.device_pileup) device_pileup.run();
         else if (ctx.from_bam) bvamd::produce_bam_host(ctx, bam_input, to_gpu, clk, errors);
+        else if (!ctx.routes.device_inflate && !ctx.regions.empty())
+            bvamd::produce_batchfile_regions_host(ctx, o.batchfiles, region_indexes, text_block_bytes, to_gpu, clk, errors);
         else if (!ctx.routes.device_inflate)  // (else the engine workers read the files themselves: RawReaderTurns)
             bvamd::produce_batchfile_text(ctx, headers, o.batchfiles, text_block_bytes, to_gpu, clk, errors);
     } catch (const std::exception &ex) { errors.fail(ex.what()); }

@@ -36,6 +36,8 @@
 #include "device_pileup.hpp"
 #include "indel_tokens.hpp"
 #include "pileup.hpp"
+#include "tabix_query.hpp"
+#include "../csrc/bv_text_region_core.h"  // the definition of a region's rows, for the host reader
 #include "vcf_emit.hpp"
 
 namespace bvamd {
@@ -159,6 +161,41 @@ struct Routes {
     bool indel_tokens_device = false; // --indel-tokens device: the engine lists the '+'/'-' tokens of batchfile rows (text_tokens_mode)
 };
 
+// One region of batchfile input ("CHR", "CHR:BEG", "CHR:BEG-END" as tabix reads them; open ends reach to 2^29), and where the
+// files' indexes say it may begin: index[f] is file f's .tbi where indexed[f], else the file is scanned from its first row
+struct BatchRegion {
+    std::string name;
+    uint32_t beg = 1, end = 1u << 29;
+};
+struct RegionIndexes {
+    std::vector<TabixReader> index;
+    std::vector<char> indexed;
+    std::vector<size_t> header_lines;
+};
+// "CHR[:BEG[-END]]"; false for anything else (an empty name, signs, BEG of 0, END < BEG, values beyond 2^29)
+inline bool parse_batch_region(const std::string &s, BatchRegion &out) {
+    auto number = [](const std::string &t, uint32_t &v) {
+        if (t.empty() || t.size() > 9) return false;
+        uint32_t x = 0;
+        for (char c : t) {
+            if (c < '0' || c > '9') return false;
+            x = x * 10u + (uint32_t)(c - '0');
+        }
+        v = x;
+        return x >= 1u && x <= (1u << 29);
+    };
+    out = BatchRegion();
+    const size_t colon = s.rfind(':');
+    out.name = s.substr(0, colon);
+    if (out.name.empty()) return false;
+    if (colon == std::string::npos) return true;
+    const std::string span = s.substr(colon + 1);
+    const size_t dash = span.find('-');
+    if (!number(span.substr(0, dash), out.beg)) return false;
+    if (dash == std::string::npos) return true;
+    return number(span.substr(dash + 1), out.end) && out.end >= out.beg;
+}
+
 // What every stage reads and none writes: built once before any thread starts, passed as const &
 struct CallContext {
     std::vector<std::string> sample_ids, group_names;
@@ -171,6 +208,7 @@ struct CallContext {
     int deflate_level = BV_DEFLATE_FAST;
     bool from_bam = false, vcf_gz = false;
     Routes routes;
+    std::vector<BatchRegion> regions;    // batchfile input with --regions: called in this order (empty: the whole files)
     size_t n_sample() const { return sample_ids.size(); }
     uint32_t n_groups() const { return (uint32_t)group_names.size(); }
     const uint8_t *group_ids() const { return group_names.empty() ? nullptr : group_id.data(); }
@@ -342,31 +380,55 @@ inline BaseTypeEngine::TokenMode text_token_mode(const CallContext &ctx) {
 // reader, submit and records overlap the next worker's parse.
 class RawReaderTurns {
 public:
-    RawReaderTurns(const CallContext &ctx, BgzfRawReader &raw, size_t target) : ctx_(ctx), raw_(raw), target_(target) {}
+    RawReaderTurns(const CallContext &ctx, BgzfRawReader &raw, size_t target, const RegionIndexes *idx = nullptr)
+        : ctx_(ctx), raw_(raw), target_(target), target0_(target), idx_(idx), seek_(!ctx.regions.empty()) {}
     // One turn: the next batch, numbered and parsed on `engine` (`bp`: for its finish_bgzf), or with the error that ends the
     // file; nullptr when the files are at their end or the run has failed.
+    // With ctx.regions: per region every file is sought to where its index says the region may begin, then next / parse-region
+    // / advance alternate until the parse says the region is done; the batches carry on in sequence.
     BatchPtr take(BaseTypeEngine &engine, BaseTypeEngine::BgzfParse &bp, StageClock &clk, const ErrorSink &errors) {
         std::lock_guard<std::mutex> lk(mu_);
+        const bool by_region = !ctx_.regions.empty();
         while (!done_) {
             if (!errors.ok()) { done_ = true; break; }
             std::string error;
             BgzfRawRuns runs;
             try {
+                if (by_region && seek_ && !seek_region()) continue;  // (no index holds a line of it: the next region)
+                if (done_) break;
                 const double t0 = StageClock::now();
                 raw_.next(runs, target_);
                 const double t1 = StageClock::now();
                 const bv_bgzf_rows rows{runs.data.data(), runs.member_off.data(), runs.data.size(), runs.file_member.data(), ctx_.file_samples.data(),
                                         runs.skip_bytes.data(), runs.skip_lines.data(), (uint32_t)ctx_.file_samples.size(), ctx_.batch_sites,
                                         runs.at_end ? 1u : 0u, 0};
-                bp = engine.parse_bgzf(rows, ctx_.batch_sites, ctx_.group_ids(), ctx_.n_groups(), text_token_mode(ctx_));
+                if (by_region) {
+                    const BatchRegion &rg = ctx_.regions[region_];
+                    bp = engine.parse_bgzf_region(rows, bv_text_region{rg.name.data(), (uint32_t)rg.name.size(), rg.beg, rg.end, 0}, ctx_.batch_sites, ctx_.group_ids(),
+                                                  ctx_.n_groups(), text_token_mode(ctx_));
+                } else {
+                    bp = engine.parse_bgzf(rows, ctx_.batch_sites, ctx_.group_ids(), ctx_.n_groups(), text_token_mode(ctx_));
+                }
                 clk.add(StageClock::READ, t1 - t0);
                 clk.add(StageClock::ENGINE, StageClock::now() - t1);
             } catch (const BaseTypeEngine::BgzfDataError &ex) {
-                // the message the host reader has for such a file
-                error = std::strstr(ex.what(), "bad header") ? "[ERROR] not a BGZF member where one was expected (truncated or damaged batchfile)"
-                                                            : "[ERROR] a BGZF member does not inflate to its recorded size";
+                // the message the host reader has for such a file; what a region parse refuses is said as it is
+                error = std::strstr(ex.what(), "bad header")  ? "[ERROR] not a BGZF member where one was expected (truncated or damaged batchfile)"
+                        : std::strstr(ex.what(), "BGZF status") ? "[ERROR] a BGZF member does not inflate to its recorded size"
+                                                                : std::string("[ERROR] ") + ex.what();
             } catch (const std::exception &ex) { error = ex.what(); }
-            if (error.empty() && bp.n_positions == 0) {
+            if (error.empty() && by_region) {
+                std::vector<uint32_t> cm(bp.cursor.size()), co(bp.cursor.size());
+                for (size_t f = 0; f < bp.cursor.size(); ++f) { cm[f] = bp.cursor[f].member; co[f] = bp.cursor[f].offset; }
+                const bool moved = raw_.advance_region(runs, cm.data(), co.data());
+                if (bp.region_done) {
+                    seek_ = true;
+                    if (++region_ == ctx_.regions.size()) done_ = true;
+                } else if (bp.n_positions == 0 && !moved) {
+                    target_ *= 2;  // not one complete line in some run: longer runs
+                }
+                if (bp.n_positions == 0) continue;
+            } else if (error.empty() && bp.n_positions == 0) {
                 if (runs.at_end) { done_ = true; break; }
                 target_ *= 2;  // not one complete row in every run: longer runs
                 continue;
@@ -377,7 +439,7 @@ public:
             if (!error.empty()) {
                 b->error = error;
                 done_ = true;
-            } else {
+            } else if (!by_region) {
                 std::vector<uint32_t> cm(bp.cursor.size()), co(bp.cursor.size());
                 for (size_t f = 0; f < bp.cursor.size(); ++f) { cm[f] = bp.cursor[f].member; co[f] = bp.cursor[f].offset; }
                 raw_.advance(runs, cm.data(), co.data());
@@ -387,12 +449,39 @@ public:
         return nullptr;
     }
 private:
+    // every file to the start of ctx_.regions[region_]; false (and the next region, or the end) when no file has a line there.
+    // A file whose index holds nothing of the region beside files whose indexes do starts at the linear index's offset for the
+    // region's first window: the selection finds its terminating line there at once (or its end), and the files' disagreement
+    // is refused by the parse, not waited for.
+    bool seek_region() {
+        const BatchRegion &rg = ctx_.regions[region_];
+        size_t nothing = 0;
+        target_ = target0_;
+        for (size_t f = 0; f < raw_.n_files(); ++f) {
+            uint64_t voff = 0;
+            bool window = false;
+            if (!idx_ || !idx_->indexed[f]) { raw_.rewind(f, idx_ ? idx_->header_lines[f] : 0); continue; }
+            const TabixReader::Hit h = idx_->index[f].query(rg.name, rg.beg, rg.end, &voff, &window);  // (an unknown name was refused before the run began)
+            if (h != TabixReader::FOUND && !window) raw_.seek_end(f);
+            else if (voff == 0) raw_.rewind(f, idx_->header_lines[f]);
+            else raw_.seek(f, voff);
+            nothing += h != TabixReader::FOUND;
+        }
+        seek_ = false;
+        if (nothing < raw_.n_files()) return true;
+        seek_ = true;
+        if (++region_ == ctx_.regions.size()) done_ = true;
+        return false;
+    }
     const CallContext &ctx_;
     BgzfRawReader &raw_;
     std::mutex mu_;
     bool done_ = false;
     uint64_t seq_ = 0;
-    size_t target_;
+    size_t target_, target0_ = 0;
+    const RegionIndexes *idx_;
+    size_t region_ = 0;
+    bool seek_;
 };
 
 // One worker thread: an engine on devices[w % G], batches from `in` (or from its turns at the raw reader) to `out`
@@ -519,6 +608,118 @@ inline void produce_batchfile_text(const CallContext &ctx, BatchfileHeaders &hea
         to_gpu.push(std::move(b));
         return errors.ok();
     }, block_bytes, ctx.batch_sites);
+}
+
+// --regions with the host reader (--inflate host, and whatever --inflate device cannot take: plain and plain-gzip files, more
+// than one engine).  The rows of a region by the definition of csrc/bv_text_region_core.h, read as a stream: an indexed BGZF file
+// starts at the virtual offset its index gives, any other file at its first row; lines are dropped until one is reached, then
+// one line per file per position is taken while all are IN, with POS held equal across the files; the same refusals, naming
+// file and line.  One thread reads; the batches are text batches as produce_batchfile_text makes them.
+class RegionLineSource {
+public:
+    RegionLineSource(const std::string &path, bool indexed, size_t header_lines) : path_(path), indexed_(indexed), header_lines_(header_lines) {}
+    // at the file's first row, or at virtual offset voff
+    void start(bool seek, uint64_t voff) {
+        line_no_ = 0;
+        if (indexed_ && seek) {
+            if (!bg_) bg_.reset(new BgzfReader(path_));
+            bg_->seek(voff);
+            use_bg_ = true;
+            return;
+        }
+        use_bg_ = false;
+        gz_.reset(new GzLineReader());
+        if (!gz_->open(path_)) throw std::runtime_error("[ERROR] " + path_ + " open failure.");
+        std::string skip;
+        for (size_t k = 0; k < header_lines_; ++k) gz_->getline(skip);
+    }
+    void start_empty() { use_bg_ = false; gz_.reset(); }
+    bool next(std::string &line) {
+        const bool got = use_bg_ ? bg_->getline(line) : gz_ ? gz_->getline(line) : false;
+        line_no_ += got ? 1 : 0;
+        return got;
+    }
+    size_t line_no() const { return line_no_ - 1; }  // of the line next() gave last, from where the file was started
+    const std::string &path() const { return path_; }
+private:
+    std::string path_;
+    bool indexed_, use_bg_ = false;
+    size_t header_lines_, line_no_ = 0;
+    std::unique_ptr<BgzfReader> bg_;
+    std::unique_ptr<GzLineReader> gz_;
+};
+
+inline void produce_batchfile_regions_host(const CallContext &ctx, const std::vector<std::string> &batchfiles, const RegionIndexes &idx, size_t block_bytes,
+                                           BatchQueue &to_gpu, StageClock &clk, const ErrorSink &errors) {
+    const size_t F = batchfiles.size();
+    std::vector<std::unique_ptr<RegionLineSource>> src;
+    for (size_t f = 0; f < F; ++f) src.emplace_back(new RegionLineSource(batchfiles[f], idx.indexed[f] != 0, idx.header_lines[f]));
+    uint64_t seq = 0;
+    BatchPtr cur;
+    auto flush = [&]() {
+        if (cur && cur->n_positions) to_gpu.push(std::move(cur));
+        cur.reset();
+    };
+    std::vector<std::string> line(F);
+    std::vector<uint32_t> cls(F), pos(F);
+    for (const BatchRegion &rg : ctx.regions) {
+        if (!errors.ok()) break;
+        const double t0 = StageClock::now();
+        const bv_tr_region key{rg.name.data(), (uint32_t)rg.name.size(), rg.beg, rg.end};
+        // the head of file f's next line: 0 at the end of the file, else BV_TR_* bits (| 8: a line); a malformed head is thrown
+        auto read = [&](size_t f) {
+            if (!src[f]->next(line[f])) { cls[f] = 0; return; }
+            line[f].push_back('\n');
+            const uint32_t c = bv_tr_head(line[f].data(), line[f].size(), key, &pos[f]);
+            if (c & BV_TR_MAL)
+                throw std::runtime_error("[ERROR] " + src[f]->path() + ", line " + std::to_string(src[f]->line_no()) + " behind the region's start: the head is not CHROM, a tab, POS, a tab");
+            cls[f] = c | 8u;
+        };
+        size_t nothing = 0;
+        std::vector<char> empty(F, 0);
+        for (size_t f = 0; f < F; ++f) {
+            uint64_t voff = 0;
+            bool window = false;
+            if (!idx.indexed[f]) { src[f]->start(false, 0); continue; }
+            const TabixReader::Hit h = idx.index[f].query(rg.name, rg.beg, rg.end, &voff, &window);
+            if (h == TabixReader::FOUND || window) src[f]->start(voff != 0, voff);
+            else { src[f]->start_empty(); empty[f] = 1; }
+            nothing += h != TabixReader::FOUND;
+        }
+        if (nothing == F) continue;  // no index holds a line of it
+        for (size_t f = 0; f < F; ++f)
+            do read(f); while (cls[f] && !(cls[f] & BV_TR_REACHED));  // the lines in front of the region
+        for (size_t p = 0; errors.ok(); ++p) {
+            size_t in = 0, first_out = F, first_in = F;
+            for (size_t f = 0; f < F; ++f) {
+                const bool is_in = (cls[f] & BV_TR_IN) != 0;
+                in += is_in;
+                if (is_in && first_in == F) first_in = f;
+                if (!is_in && first_out == F) first_out = f;
+            }
+            if (in == 0) break;
+            if (in < F)
+                throw std::runtime_error("[ERROR] " + src[first_out]->path() + ": the file's lines of " + rg.name + ":" + std::to_string(rg.beg) + "-" + std::to_string(rg.end) +
+                                         " end behind " + std::to_string(p) + " positions, " + src[first_in]->path() + " has more");
+            for (size_t f = 1; f < F; ++f)
+                if (pos[f] != pos[0])
+                    throw std::runtime_error("[ERROR] " + src[f]->path() + ", position " + std::to_string(p) + " of " + rg.name + ":" + std::to_string(rg.beg) + "-" +
+                                             std::to_string(rg.end) + ": POS " + std::to_string(pos[f]) + " differs from " + src[0]->path() + "'s " + std::to_string(pos[0]));
+            if (!cur) {
+                cur = new_slab_batch(ctx, seq++);
+                cur->from_text = true;
+                cur->row_off.assign(1, 0);
+            }
+            for (size_t f = 0; f < F; ++f) {
+                cur->rows += line[f];
+                cur->row_off.push_back(cur->rows.size());
+            }
+            if (++cur->n_positions == ctx.batch_sites || cur->rows.size() >= block_bytes) flush();
+            for (size_t f = 0; f < F; ++f) read(f);
+        }
+        clk.add(StageClock::READ, StageClock::now() - t0);
+    }
+    flush();
 }
 
 // fn(region, fa_seq) for the regions in the order given ("-r chr:beg-end[,chr:beg-end ...]", caller.cpp:311-356), with the

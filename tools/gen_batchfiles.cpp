@@ -1,6 +1,6 @@
 // gen_batchfiles.cpp -- synthetic batchfiles in the reference's format (BaseVarBatchFile_v1.0) for host-pipeline measurements:
 //   gen_batchfiles OUT_DIR N_SAMPLES SAMPLES_PER_FILE N_SITES [COVERAGE=0.08] [SEED=1]
-// writes OUT_DIR/bf_000.gz ... (BGZF, deflate level 1), each holding SAMPLES_PER_FILE samples of every site (the reference's
+// writes OUT_DIR/bf_000.gz ... (BGZF, deflate level 1) and a tabix index OUT_DIR/bf_000.gz.tbi ... beside each, each holding SAMPLES_PER_FILE samples of every site (the reference's
 // --batch-count), with the cell statistics of SURVEY.md section 8d (coverage, phred ~ N(32, 6), 10 % of the sites carry an ALT).
 // g++ -O2 -std=c++17 tools/gen_batchfiles.cpp -lz -o gen_batchfiles
 #include <zlib.h>
@@ -24,10 +24,13 @@ int main(int argc, char **argv) {
     auto uni = [&]() { return (double)(rnd() >> 11) * 0x1p-53; };
     const uint32_t nf = (n + per - 1) / per;
     std::vector<bvamd::BgzfWriter> out(nf);  // BGZF, as the reference writes its batchfiles (src/basetype_caller.cpp:428)
+    std::vector<bvamd::TabixIndex> index(nf);
+    std::vector<std::string> path(nf);
     for (uint32_t f = 0; f < nf; ++f) {
         char name[64];
         std::snprintf(name, sizeof name, "/bf_%03u.gz", f);
-        out[f].open(dir + name, 1);
+        path[f] = dir + name;
+        out[f].open(path[f], 1);
         std::string h = "##fileformat=BaseVarBatchFile_v1.0\n##SampleIDs=";
         for (uint32_t i = f * per; i < std::min(n, (f + 1) * per); ++i) { if (i != f * per) h += ','; h += "S" + std::to_string(i); }
         h += "\n#CHROM\tPOS\tREF\tDepth(CoveredSample)\tMappingQuality\tReadbases\tReadbasesQuality\tReadPositionRank\tStrand\n";
@@ -57,9 +60,11 @@ int main(int argc, char **argv) {
                 } else { mq += '0'; bs += 'N'; qs += '!'; rk += '0'; sd += '.'; }
             }
             row = "chr1\t" + std::to_string(1000 + s) + "\t" + ref + "\t" + std::to_string(covered) + "\t" + mq + "\t" + bs + "\t" + qs + "\t" + rk + "\t" + sd + "\n";
+            const uint64_t at = out[f].tell();
             out[f].write(row);
+            index[f].add_line("chr1", 1000 + (int64_t)s, at, out[f].tell());
         }
     }
-    for (auto &f : out) f.close();
+    for (uint32_t f = 0; f < nf; ++f) { out[f].close(); index[f].write(path[f] + ".tbi"); }
     return 0;
 }
