@@ -172,7 +172,7 @@ EXPORTS = ["bv_version", "bv_min_af", "bv_engine_create", "bv_engine_destroy", "
            "bv_engine_tiles_begin", "bv_engine_tiles_add", "bv_engine_tiles_add_many", "bv_engine_tiles_add_sparse", "bv_engine_tiles_add_sparse_many", "bv_sparse_tile_packed_layout", "bv_engine_tiles_finish", "bv_tile_packed_layout", "bv_engine_stream",
            "bv_engine_kernel_ms", "bv_engine_timing_reset", "bv_engine_timing_get", "bv_engine_timing_get_ex",
            "bv_host_log_probe", "bv_host_log_eval", "bv_engine_host_log_exact", "bv_engine_host_log_eval",
-           "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form",
+           "bv_engine_last_variant_count", "bv_last_error", "bv_synth_fill", "bv_device_numa_node", "bv_bind_thread_to_device_node", "bv_engine_last_launch_form", "bv_engine_text_last_layout",
            "bv_engine_text_parse", "bv_engine_text_submit", "bv_engine_deflate_code_lengths", "bv_vcf_tile_samples"]
 
 # every symbol include/basevar_amd_bgzf.h declares
@@ -192,6 +192,9 @@ INDEL_EXPORTS = ["bv_indel_row_tokens_max", "bv_engine_indel_tally", "bv_engine_
 
 # every symbol include/basevar_amd_text_tokens.h declares
 TEXT_TOKENS_EXPORTS = ["bv_engine_text_tokens_enable", "bv_engine_text_tokens", "bv_engine_text_tokens_fetch", "bv_engine_text_heads_fetch"]
+
+# every symbol include/basevar_amd_text_job.h declares
+TEXT_JOB_EXPORTS = ["bv_engine_text_job_begin", "bv_engine_text_job_add", "bv_engine_text_job_finish"]
 
 # every symbol include/basevar_amd_pileup.h declares
 PILEUP_EXPORTS = ["bv_pileup_max_rows", "bv_engine_pileup_set_reference", "bv_engine_pileup", "bv_engine_pileup_fetch", "bv_engine_pileup_rows", "bv_engine_pileup_submit"]
@@ -339,6 +342,14 @@ def load():
     L.bv_engine_indel_fetch.argtypes = L.bv_engine_vcf_fetch.argtypes
     L.bv_engine_cvg_format_tallied.restype = C.c_int
     L.bv_engine_cvg_format_tallied.argtypes = [C.c_void_p, C.POINTER(RecordLines), C.c_void_p, C.c_void_p]
+    L.bv_engine_text_last_layout.restype = C.c_int
+    L.bv_engine_text_last_layout.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.bv_engine_text_job_begin.restype = C.c_int
+    L.bv_engine_text_job_begin.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.bv_engine_text_job_add.restype = C.c_int
+    L.bv_engine_text_job_add.argtypes = [C.c_void_p, C.POINTER(TextRows), C.c_uint32, C.c_void_p, C.c_void_p]
+    L.bv_engine_text_job_finish.restype = C.c_int
+    L.bv_engine_text_job_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.bv_engine_text_tokens_enable.restype = C.c_int
     L.bv_engine_text_tokens_enable.argtypes = [C.c_void_p, C.c_int]
     L.bv_engine_text_tokens.restype = C.c_int

@@ -267,10 +267,23 @@ struct BvTextTokRows {  // rows [row_first, row_first + n_rows) of the batch, wh
     const uint32_t *foff;               // device [n_files]
     uint64_t chunk_base;
     uint32_t row_first, n_rows, n_files;
+    // the rows of a parse job's add (bv_text_job.hip) of files [first_file, first_file + add_files): row_beg, row_end, row_first and
+    // n_rows count the add's rows, add row p * add_files + k being row p * n_files + first_file + k of the batch.  add_files == 0: not so
+    uint32_t first_file, add_files;
 };
+// ... and the store's device arrays, for the strided kernels of such an add (bv_text_job.hip), which bv_text_tokens_rows launches
+// through these two: the count and the scan (base_* written from run_tok / run_txt on, totals[0 .. 2) the sums), and the write
+struct BvTextTokStore {
+    uint32_t *cnt_tok, *cnt_txt;            // [rows of the batch]
+    uint64_t *base_tok, *base_txt, *totals;
+    uint8_t *tok, *ttext;                   // descriptors (bv_pileup_token) and text
+};
+void text_job_tokens_count_scan(const BvTextTokRows &rows, const BvTextTokStore &s, uint64_t run_tok, uint64_t run_txt, hipStream_t st);
+void text_job_tokens_write(const BvTextTokRows &rows, const BvTextTokStore &s, hipStream_t st);
 int bv_text_tokens_begin(bv_engine *e, uint32_t P, uint32_t F, hipStream_t st);  // a parse begins: the last list is gone
 int bv_text_tokens_rows(bv_engine *e, const BvTextTokRows &rows, hipStream_t st);  // behind the parse kernel of these rows; waits for `st`
 int bv_text_tokens_finish(bv_engine *e, const uint8_t *pos_state, uint32_t P, uint32_t F, hipStream_t st);  // the positions' final states (host [P])
+bool bv_text_tokens_on(const bv_engine *e);  // the mode is on
 bool bv_text_tokens_stand(const bv_engine *e);  // the mode is on and the last parse's list stands (bv_engine_text_tokens would hand it out)
 
 // ---- stream ordering (bv_engine.hip): work of one engine is serialised, whatever streams the caller alternates

@@ -24,57 +24,14 @@
 #include "../../include/basevar_amd_bgzf.h"
 #include "../../include/basevar_amd_text_tokens.h"
 #include "../../include/basevar_amd_region.h"
+#include "../../include/basevar_amd_diag.h"
 #include "bv_inflate_core.h"
-#include "bv_chunk_stage.h"
+#include "bv_text_rows.h"
 #include "bv_text_region_core.h"
 
 using namespace bv_impl;
 
 namespace {
-
-constexpr uint32_t kPrefixFail = 1u;  // d_pstate bits: the field count or the first four fields are not the strict form
-constexpr uint32_t kTokenFail = 2u;   //                a per-sample token is not the strict form
-constexpr uint32_t kMaxPrefix = 512;  // bytes of CHROM \t POS \t REF \t Depth \t the device looks at; longer -> host
-constexpr size_t kChunkBytes = (size_t)128 << 20;  // text bytes per staged chunk (two chunks in flight)
-
-struct TextParseArgs {
-    const char *text;          // the chunk: byte k is text byte chunk_base + k
-    const uint64_t *row_beg;   // [n_rows] absolute offset of every row's first byte (device) ...
-    const uint64_t *row_end;   // [n_rows] ... and of the byte behind its '\n' (bv_engine_text_parse: row_beg + 1, rows are contiguous)
-    const uint32_t *foff;      // [n_files] sample offset of file f inside the row
-    const uint32_t *fsamp;     // [n_files]
-    uint64_t chunk_base;
-    uint32_t row_first, n_rows_chunk, n_files;
-    uint64_t pitch;
-    uint8_t *bs, *q, *mq, *st, *ref, *rowflag;
-    uint16_t *rp;
-    uint32_t *depth, *pstate, *pmax;
-};
-
-__device__ __forceinline__ bool is_digit(char c) { return c >= '0' && c <= '9'; }
-__device__ __forceinline__ bool is_sep(char c) { return c == ' ' || c == '\t' || c == '\n'; }
-
-// digits [p, first separator): 1..max_digits of them, value <= max_value -> value, else -1
-__device__ __forceinline__ int parse_uint_token(const char *p, int max_digits, int max_value) {
-    int v = 0, n = 0;
-    for (;; ++n) {
-        const char c = p[n];
-        if (is_sep(c)) break;
-        if (!is_digit(c) || n == max_digits) return -1;
-        v = v * 10 + (c - '0');
-    }
-    return (n == 0 || v > max_value) ? -1 : v;
-}
-
-__device__ __forceinline__ uint8_t base_code_dev(char c) {
-    switch (c) {
-        case 'A': case 'a': return BV_BASE_A;
-        case 'C': case 'c': return BV_BASE_C;
-        case 'G': case 'g': return BV_BASE_G;
-        case 'T': case 't': return BV_BASE_T;
-        default: return BV_BASE_OTHER;
-    }
-}
 
 // One wave per (position, file) row; four rows per workgroup.
 __global__ __launch_bounds__(256) void bv_text_parse_kernel(TextParseArgs a) {
@@ -89,137 +46,7 @@ __global__ __launch_bounds__(256) void bv_text_parse_kernel(TextParseArgs a) {
     const uint32_t len = (uint32_t)(a.row_end[r] - a.row_beg[r]);  // the last byte is '\n' (checked by the host / the line index)
     const uint32_t len0 = (uint32_t)(a.row_end[r0] - a.row_beg[r0]);
 
-    // ---- CHROM \t POS \t REF \t Depth \t: one lane (they are a few bytes)
-    uint32_t start = 0, ok = 1, dep = 0;
-    if (lane == 0) {
-        uint32_t tabs = 0, i = 0, pos_digits = 0, dep_digits = 0, ref_at = 0;
-        const uint32_t lim = min(min(len, len0), kMaxPrefix);
-        for (; i < lim && tabs < 3; ++i) {  // CHROM, POS, REF: byte-equal to file 0's, POS decimal
-            const char c = row[i];
-            if (c != row0[i] || c == '\n') { ok = 0; break; }
-            if (c == '\t') { if (++tabs == 2) ref_at = i + 1; continue; }
-            if (tabs == 1) {
-                if (!is_digit(c) || ++pos_digits > 9) { ok = 0; break; }
-            }
-        }
-        ok = ok && tabs == 3 && pos_digits > 0;
-        if (ok) {
-            for (;; ++i) {  // Depth
-                if (i >= min(len, kMaxPrefix)) { ok = 0; break; }
-                const char c = row[i];
-                if (c == '\t') { ++i; break; }
-                if (!is_digit(c) || ++dep_digits > 9) { ok = 0; break; }
-                dep = dep * 10u + (uint32_t)(c - '0');
-            }
-            ok = ok && dep_digits > 0;
-        }
-        start = i;
-        if (ok && f == 0)  // toupper(REF[0]), 'N' when REF is empty (SlabBuilder::commit_row)
-            a.ref[p] = base_code_dev(row[ref_at] == '\t' ? 'N' : row[ref_at]);
-        if (ok) atomicAdd(&a.depth[p], dep);  // (wraps as the host reader's uint32_t sum does)
-        else atomicOr(&a.pstate[p], kPrefixFail);
-    }
-    ok = __shfl(ok, 0);
-    if (!ok) return;
-    start = __shfl(start, 0);
-
-    // ---- the five per-sample columns, 64 bytes per step
-    const uint32_t ns = a.fsamp[f];
-    const size_t cell0 = (size_t)p * a.pitch + a.foff[f];
-    const uint64_t lt = (1ull << lane) - 1ull;
-    uint32_t fld = 4, tok = 0, prev_sep = 1, bad = 0, indel = 0, maxr = 0;
-    for (uint32_t b = start; b < len; b += 64u) {
-        const uint32_t i = b + lane;
-        const bool valid = i < len;
-        const char c = valid ? row[i] : '\0';
-        const uint64_t T = __ballot(valid && c == '\t');
-        const uint64_t S = __ballot(valid && c == ' ');
-        const uint64_t SEP = T | S | __ballot(valid && c == '\n');
-        const uint64_t tb = T & lt;
-        const uint32_t my_fld = fld + (uint32_t)__popcll(tb);
-        uint32_t my_tok;
-        if (tb) {
-            const uint32_t t = 63u - (uint32_t)__clzll(tb);
-            my_tok = (uint32_t)__popcll(S & lt & ~((2ull << t) - 1ull));
-        } else {
-            my_tok = tok + (uint32_t)__popcll(S & lt);
-        }
-        const bool after_sep = lane ? ((SEP >> (lane - 1)) & 1ull) != 0 : prev_sep != 0;
-        if (valid) {
-            if (c == '\n' && i != len - 1) bad = 1;  // a line break inside the row
-            if (is_sep(c)) {
-                // a separator ends token my_tok of field my_fld: an empty token, a tab past field 8, a row that ends early,
-                // or a column whose token count is not the file's sample count are not the strict form
-                if (after_sep) bad = 1;
-                if (c == ' ' && my_tok + 1u >= ns) bad = 1;
-                if (c == '\t' && (my_fld >= 8u || my_tok + 1u != ns)) bad = 1;
-                if (c == '\n' && (my_fld != 8u || my_tok + 1u != ns)) bad = 1;
-            } else if (after_sep && my_fld <= 8u && my_tok < ns) {
-                const char *t = row + i;
-                const size_t cell = cell0 + my_tok;
-                switch (my_fld) {
-                    case 4: {  // MappingQuality
-                        const int v = parse_uint_token(t, 3, 255);
-                        if (v < 0) bad = 1; else a.mq[cell] = (uint8_t)v;
-                        break;
-                    }
-                    case 5: {  // Readbases: the strand goes in at finish
-                        uint8_t code;
-                        if (c == '+' || c == '-') {
-                            code = c == '+' ? BV_CELL_INS : BV_CELL_DEL;
-                            indel = 1;
-                        } else if (!is_sep(t[1])) {
-                            bad = 1; code = BV_CELL_N;
-                        } else if (c == 'N') {
-                            code = BV_CELL_N;
-                        } else {
-                            code = c == 'A' ? BV_BASE_A : c == 'C' ? BV_BASE_C : c == 'G' ? BV_BASE_G : c == 'T' ? BV_BASE_T : 0xFFu;
-                            if (code == 0xFFu) { bad = 1; code = BV_CELL_N; }
-                        }
-                        a.bs[cell] = code;
-                        break;
-                    }
-                    case 6:  // ReadbasesQuality: one character, phred = char - 33
-                        if (!is_sep(t[1])) bad = 1; else a.q[cell] = (uint8_t)(c - 33);
-                        break;
-                    case 7: {  // ReadPositionRank
-                        const int v = parse_uint_token(t, 5, 65535);
-                        if (v < 0) bad = 1; else { a.rp[cell] = (uint16_t)v; maxr = max(maxr, (uint32_t)v); }
-                        break;
-                    }
-                    default: {  // Strand
-                        const uint8_t s = c == '+' ? 0u : c == '-' ? 1u : c == '.' ? 2u : 3u;
-                        if (s == 3u || !is_sep(t[1])) bad = 1; else a.st[cell] = s;
-                        break;
-                    }
-                }
-            } else if (after_sep) {
-                bad = 1;  // a token beyond the sample count, or in a tenth field
-            }
-        }
-        fld += (uint32_t)__popcll(T);
-        if (T) {
-            const uint32_t t = 63u - (uint32_t)__clzll(T);
-            tok = t == 63u ? 0u : (uint32_t)__popcll(S & ~((2ull << t) - 1ull));
-        } else {
-            tok += (uint32_t)__popcll(S);
-        }
-        prev_sep = (uint32_t)((SEP >> 63) & 1ull);
-    }
-    if (fld != 8u) {  // not 9 fields: the host reader refuses the row before it looks at Depth (a skip would be wrong)
-        if (lane == 0) atomicOr(&a.pstate[p], kPrefixFail);
-        return;
-    }
-    if (__ballot(bad)) {
-        if (lane == 0) atomicOr(&a.pstate[p], kTokenFail);
-        return;
-    }
-    const bool any_indel = __ballot(indel) != 0;
-    for (int o = 32; o > 0; o >>= 1) maxr = max(maxr, (uint32_t)__shfl_xor((int)maxr, o));
-    if (lane == 0) {
-        a.rowflag[r] = any_indel ? (uint8_t)BV_TEXT_INDEL : (uint8_t)0;
-        atomicMax(&a.pmax[p], maxr);
-    }
+#include "bv_text_row_walk_body.h"
 }
 
 // After the last chunk: the strand of every covered call goes into its cell (REV for '-'); a covered call with strand '.'
@@ -462,46 +289,6 @@ __global__ __launch_bounds__(256) void bv_text_fetch_copy_kernel(const char *tex
 
 }  // namespace
 
-// Per-engine state of the text path: the parsed planes of the last bv_engine_text_parse, the slab handed to the calling kernels,
-// the staging of the text chunks (bv_chunk_stage.h) and what the host learnt from the parse.
-struct BvTextState {
-    int device = 0;
-    ChunkStage chunks;
-    uint8_t *d_planes = nullptr;            // parsed rows: bs, q, mq, st [cap][pitch], rp [cap][pitch] u16, ref [cap]
-    size_t planes_bytes = 0;
-    uint8_t *d_sub = nullptr;               // the submitted slab: bs, q, mq [cap][pitch], rp [cap][pitch] u16, ref [cap]
-    size_t sub_bytes = 0;
-    uint32_t sub_rows = 0, sub_samples = 0; // rows of the last submit that stand in d_sub (bv_text_kept_rows); 0: none
-    uint64_t sub_pitch = 0;
-    uint8_t *d_aux = nullptr;               // depth, pstate, pmax [n_pos] u32, rowflag [n_rows], row_off [n_rows + 1], foff/fsamp
-    size_t aux_bytes = 0;
-    uint8_t *d_misc = nullptr;              // submit: src [n] i32, host rows, records
-    size_t misc_bytes = 0;
-    uint8_t *d_gid = nullptr;
-    size_t gid_bytes = 0;
-    // the pending parse
-    bool parsed = false;
-    uint32_t n_pos = 0, n_files = 0, n_samples = 0, n_groups = 0;
-    uint64_t pitch = 0;
-    std::vector<uint8_t> pos_state;         // BV_TEXT_SKIP / BV_TEXT_HOST / 0 per position
-    std::vector<uint32_t> pos_max_rank;
-    std::vector<uint8_t> group_id;
-    bool has_gid = false;
-    std::vector<uint32_t> h_foff;           // sample offset of every file (what parse_begin uploads)
-    // bv_engine_text_parse_bgzf: the inflated runs, the line index, and what bv_engine_text_rows_fetch gathers
-    bool bgzf_rows = false;                 // the last parse was a _parse_bgzf: d_btext and the row begins / ends stand
-    const uint64_t *bz_row_beg = nullptr, *bz_row_end = nullptr;  // ... where they stand (inside d_aux) ...
-    const uint8_t *bz_rowflag = nullptr;    // ... and the rows' BV_TEXT_INDEL flags
-    uint8_t *d_btext = nullptr;             // file f's run inflated back to back, one spare byte behind each run
-    size_t btext_bytes = 0;
-    uint8_t *d_lines = nullptr;             // LineFile [n_files], newline counts / prefixes per tile, n_pos
-    size_t lines_bytes = 0;
-    uint8_t *d_fetch = nullptr;             // rows_fetch: pos_state [n_pos], len u32 [n_rows], off u64 [n_rows + 1], the bytes
-    size_t fetch_bytes = 0;
-    uint8_t *d_rrows = nullptr;             // _parse_bgzf_region: row begins, then row ends, of (n_pos + 1) * n_files rows
-    size_t rrows_bytes = 0;
-};
-
 bool bv_text_kept_rows(const BvTextState *t, BvKeptRows *rows) {
     if (!t || !t->sub_rows) return false;
     rows->cell = t->d_sub;
@@ -514,28 +301,20 @@ void bv_text_state_free(BvTextState *t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     chunk_stage_free(t->chunks);
-    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch, t->d_rrows})
+    for (uint8_t *b : {t->d_planes, t->d_sub, t->d_aux, t->d_misc, t->d_gid, t->d_btext, t->d_lines, t->d_fetch, t->d_rrows, t->d_heads})
         if (b) (void)hipFree(b);
     delete t;
 }
 
-namespace {
-// The device arrays of one parse of P positions x F files.
-struct ParseBufs {
-    uint8_t *bs, *q, *mq, *stp, *ref, *rowflag;
-    uint16_t *rp;
-    uint32_t *depth, *pstate, *pmax, *foff, *fsamp;
-    uint64_t *d_off;  // [2 * (P * F + 1)]: row_off [P * F + 1] of bv_engine_text_parse; row begins [P * F], then row ends, of _parse_bgzf
-    uint64_t pitch;
-};
-
+namespace bv_impl {
 // Sized, cleared (a parsed row is all 'N' where the text leaves nothing) and with the files' sample offsets in place.
-int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint32_t *file_samples, uint32_t n_samples, hipStream_t st,
-                ParseBufs *b) {
+int text_parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint32_t *file_samples, uint32_t n_samples, hipStream_t st,
+                     ParseBufs *b) {
     const size_t R = (size_t)P * F;
     const uint64_t pitch = (n_samples + 255ull) & ~255ull;
     t->parsed = false;
     t->bgzf_rows = false;
+    t->job.open = false;
     BV_HIP(e, hipSetDevice(t->device));
     // device buffers: planes, then the small per-position / per-row arrays
     const size_t cells = (size_t)P * pitch;
@@ -565,15 +344,12 @@ int parse_begin(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, const uint
     return bv_text_tokens_begin(e, P, F, st);
 }
 
-int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
-                 uint8_t *row_state, hipStream_t st, const ParseBufs &b);
-
-int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
-               hipStream_t st, uint32_t n_samples) {
+static int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uint8_t *group_id, uint32_t n_groups, uint8_t *row_state,
+                      hipStream_t st, uint32_t n_samples) {
     const uint32_t P = rows->n_positions, F = rows->n_files;
     const size_t R = (size_t)P * F;
     ParseBufs pb;
-    int rc = parse_begin(e, t, P, F, rows->file_samples, n_samples, st, &pb);
+    int rc = text_parse_begin(e, t, P, F, rows->file_samples, n_samples, st, &pb);
     if (rc != BV_OK) return rc;
     const uint64_t pitch = pb.pitch;
     uint8_t *bs = pb.bs, *q = pb.q, *mq = pb.mq, *stp = pb.stp, *ref = pb.ref, *rowflag = pb.rowflag;
@@ -612,12 +388,12 @@ int text_parse(bv_engine *e, BvTextState *t, const bv_text_rows *rows, const uin
         if ((rc = chunk_stage_done(e, cst, s, st)) != BV_OK) return rc;
         p0 = p1;
     }
-    return parse_finish(e, t, P, F, n_samples, group_id, n_groups, row_state, st, pb);
+    return text_parse_finish(e, t, P, F, n_samples, group_id, n_groups, row_state, st, pb);
 }
 
-// What both parse entry points ask of file_samples and group_id / n_groups; *n_samples = the samples of all files.
-int check_samples_groups(bv_engine *e, const char *who, const uint32_t *file_samples, uint32_t F, const uint8_t *group_id, uint32_t n_groups,
-                         uint64_t *n_samples) {
+// What every parse entry point asks of file_samples and group_id / n_groups; *n_samples = the samples of all files.
+int text_check_samples_groups(bv_engine *e, const char *who, const uint32_t *file_samples, uint32_t F, const uint8_t *group_id, uint32_t n_groups,
+                              uint64_t *n_samples) {
     *n_samples = 0;
     for (uint32_t f = 0; f < F; ++f) {
         if (file_samples[f] == 0) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_samples[f] == 0");
@@ -631,8 +407,8 @@ int check_samples_groups(bv_engine *e, const char *who, const uint32_t *file_sam
 }
 
 // The strands into the cells, then what the host needs to know of every position.
-int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
-                 uint8_t *row_state, hipStream_t st, const ParseBufs &b) {
+int text_parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t n_samples, const uint8_t *group_id, uint32_t n_groups,
+                      uint8_t *row_state, hipStream_t st, const ParseBufs &b) {
     const size_t R = (size_t)P * F;
     hipLaunchKernelGGL(bv_text_strand_kernel, dim3(P), dim3(256), 0, st, b.bs, (const uint8_t *)b.stp, (const uint32_t *)b.depth, b.pstate, b.pitch,
                        n_samples);
@@ -664,7 +440,31 @@ int parse_finish(bv_engine *e, BvTextState *t, uint32_t P, uint32_t F, uint32_t 
     t->parsed = true;
     return BV_OK;
 }
-}  // namespace
+
+// What every call that takes a bv_text_rows asks of it: the pointers, reserved_ and the counts ...
+int text_check_rows_head(bv_engine *e, const char *who, const bv_text_rows *rows) {
+    if (!rows->text || !rows->row_off || !rows->file_samples)
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null text/row_off/file_samples");
+    if (rows->reserved_) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": reserved_ must be zero");
+    if (rows->n_positions == 0 || rows->n_files == 0)
+        return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": n_positions and n_files must be > 0");
+    return BV_OK;
+}
+// ... and the rows in order, inside the text, each ending in '\n'
+int text_check_rows_off(bv_engine *e, const char *who, const bv_text_rows *rows) {
+    const size_t R = (size_t)rows->n_positions * rows->n_files;
+    for (size_t r = 0; r < R; ++r) {
+        const uint64_t a = rows->row_off[r], b = rows->row_off[r + 1];
+        if (b <= a || b > rows->text_bytes || rows->text[b - 1] != '\n')
+            return fail(e, BV_ERR_INVALID_ARG,
+                        std::string(who) + ": row " + std::to_string(r) + ": row_off outside text_bytes, out of order, or no final '\\n'");
+        if (b - a > 0xFFFFFFFFull) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": a row is longer than 4 GiB");
+    }
+    return BV_OK;
+}
+
+BvTextState *text_state(bv_engine *e) { return engine_state(e, e->text); }
+}  // namespace bv_impl
 
 extern "C" {
 
@@ -672,24 +472,14 @@ int bv_engine_text_parse(bv_engine *e, const bv_text_rows *rows, const uint8_t *
                          void *stream_) {
     if (!e) return fail(nullptr, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null engine");
     if (!rows || !row_state) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null rows/row_state");
-    if (!rows->text || !rows->row_off || !rows->file_samples)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: null text/row_off/file_samples");
-    if (rows->reserved_) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: reserved_ must be zero");
-    if (rows->n_positions == 0 || rows->n_files == 0)
-        return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions and n_files must be > 0");
+    int rc = text_check_rows_head(e, "bv_engine_text_parse", rows);
+    if (rc != BV_OK) return rc;
     if (rows->n_positions > e->cfg.max_sites)
         return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: n_positions exceeds cfg.max_sites");
     uint64_t n_samples = 0;
-    int rc = check_samples_groups(e, "bv_engine_text_parse", rows->file_samples, rows->n_files, group_id, n_groups, &n_samples);
+    rc = text_check_samples_groups(e, "bv_engine_text_parse", rows->file_samples, rows->n_files, group_id, n_groups, &n_samples);
     if (rc != BV_OK) return rc;
-    const size_t R = (size_t)rows->n_positions * rows->n_files;
-    for (size_t r = 0; r < R; ++r) {  // rows in order, inside the text, each ending in '\n'
-        const uint64_t a = rows->row_off[r], b = rows->row_off[r + 1];
-        if (b <= a || b > rows->text_bytes || rows->text[b - 1] != '\n')
-            return fail(e, BV_ERR_INVALID_ARG,
-                                  "bv_engine_text_parse: row " + std::to_string(r) + ": row_off outside text_bytes, out of order, or no final '\\n'");
-        if (b - a > 0xFFFFFFFFull) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_parse: a row is longer than 4 GiB");
-    }
+    if ((rc = text_check_rows_off(e, "bv_engine_text_parse", rows)) != BV_OK) return rc;
     BvTextState *t = engine_state(e, e->text);
     rc = text_parse(e, t, rows, group_id, n_groups, row_state, stream_ ? (hipStream_t)stream_ : e->stream, (uint32_t)n_samples);
     if (rc != BV_OK) t->parsed = false;
@@ -802,7 +592,7 @@ int bv_engine_text_submit(bv_engine *e, const uint8_t *row_state, const bv_slab 
     if (cell) BV_HIP(e, hipMemcpy2DAsync(cell, N, a.bs, P, N, n_out, hipMemcpyDeviceToHost, st));
     if (phred) BV_HIP(e, hipMemcpy2DAsync(phred, N, a.q, P, N, n_out, hipMemcpyDeviceToHost, st));
     BV_HIP(e, hipStreamSynchronize(st));
-    t->sub_rows = n_out; t->sub_samples = N; t->sub_pitch = P;  // (d_sub stands until the next submit, whatever is parsed meanwhile)
+    t->sub_rows = n_out; t->sub_samples = N; t->sub_pitch = P; t->sub_layout = s.layout;  // (d_sub stands until the next submit, whatever is parsed meanwhile)
     return BV_OK;
 }
 
@@ -845,7 +635,7 @@ int bgzf_runs_begin(bv_engine *e, const char *who, const bv_bgzf_rows *rows, con
     for (uint32_t f = 0; f < F; ++f)
         if (rows->file_member[f + 1] < rows->file_member[f]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": file_member out of order");
     if (!rows->data && rows->file_member[F]) return fail(e, BV_ERR_INVALID_ARG, std::string(who) + ": null data");
-    int rc = check_samples_groups(e, who, rows->file_samples, F, group_id, n_groups, &n_samples);
+    int rc = text_check_samples_groups(e, who, rows->file_samples, F, group_id, n_groups, &n_samples);
     if (rc != BV_OK) return rc;
     *n_positions = 0;
     bv_bgzf_members mb{rows->data, rows->member_off, rows->data_bytes, rows->file_member[F], 0};
@@ -856,6 +646,7 @@ int bgzf_runs_begin(bv_engine *e, const char *who, const bv_bgzf_rows *rows, con
     BvTextState *t = engine_state(e, e->text);
     t->parsed = false;
     t->bgzf_rows = false;
+    t->job.open = false;
     hipStream_t st = stream_ ? (hipStream_t)stream_ : e->stream;
     if ((rc = bv_text_tokens_begin(e, 0, F, st)) != BV_OK) return rc;  // (a call that takes no position leaves no token list either)
     // where every member's text goes: file f's members back to back, one spare byte behind each run (16-byte aligned runs)
@@ -936,7 +727,7 @@ int bgzf_rows_parse(bv_engine *e, const BgzfRuns &r, uint32_t P, uint64_t *row_b
     if (rc != BV_OK) return rc;
     last.resize(F);
     BV_HIP(e, hipMemcpyAsync(last.data(), row_end + (R - F), 8ull * F, hipMemcpyDeviceToHost, st));
-    rc = parse_finish(e, r.t, P, F, r.n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
+    rc = text_parse_finish(e, r.t, P, F, r.n_samples, group_id, n_groups, row_state, st, pb);  // (synchronises: `last` is there)
     if (rc != BV_OK) {
         r.t->parsed = false;
         return rc;
@@ -962,7 +753,7 @@ int bv_engine_text_parse_bgzf(bv_engine *e, const bv_bgzf_rows *rows, const uint
     BV_HIP(e, hipStreamSynchronize(st));
     if (P == 0) return BV_OK;
     ParseBufs pb;
-    rc = parse_begin(e, r.t, P, F, rows->file_samples, r.n_samples, st, &pb);
+    rc = text_parse_begin(e, r.t, P, F, rows->file_samples, r.n_samples, st, &pb);
     if (rc != BV_OK) return rc;
     const size_t R = (size_t)P * F;
     uint64_t *row_beg = pb.d_off, *row_end = pb.d_off + R;
@@ -1056,7 +847,7 @@ int bv_engine_text_parse_bgzf_region(bv_engine *e, const bv_bgzf_rows *rows, con
     *region_done = res.done;
     if (P == 0) return BV_OK;
     ParseBufs pb;
-    rc = parse_begin(e, t, P, F, rows->file_samples, r.n_samples, st, &pb);
+    rc = text_parse_begin(e, t, P, F, rows->file_samples, r.n_samples, st, &pb);
     if (rc != BV_OK) return rc;
     std::vector<uint64_t> last;
     rc = bgzf_rows_parse(e, r, P, row_beg, row_end, pb, group_id, n_groups, row_state, last);
@@ -1114,6 +905,13 @@ static int text_rows_fetch(bv_engine *e, const char *who, uint32_t heads, uint8_
     BV_HIP(e, hipGetLastError());
     BV_HIP(e, hipMemcpyAsync(buf, t->d_fetch + o_bytes, off[R], hipMemcpyDeviceToHost, st));
     BV_HIP(e, hipStreamSynchronize(st));
+    return BV_OK;
+}
+
+int bv_engine_text_last_layout(bv_engine *e, uint32_t *layout) {
+    if (!e || !layout) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_last_layout: null engine/layout");
+    if (!e->text || !e->text->sub_rows) return fail(e, BV_ERR_INVALID_ARG, "bv_engine_text_last_layout: no bv_engine_text_submit that called a position");
+    *layout = e->text->sub_layout;
     return BV_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "../../include/basevar_amd_text_tokens.h"
 #include "bv_engine_impl.h"
 #include "bv_text_tokens_core.h"
+#include "bv_text_tokens_walk.h"
 
 using namespace bv_impl;
 
@@ -26,117 +27,24 @@ static_assert(sizeof(bv_tt_token) == sizeof(bv_pileup_token) && sizeof(bv_tt_tok
 
 namespace {
 
-struct TokArgs {
-    const char *text;          // byte k is text byte chunk_base + k
-    const uint64_t *row_beg, *row_end;
-    const uint8_t *rowflag;
-    const uint32_t *foff;
-    uint64_t chunk_base;
-    uint32_t row_first, n_rows, n_files;
-    uint32_t *cnt_tok, *cnt_txt;            // [rows of the batch]
-    const uint64_t *base_tok, *base_txt;    // [rows of the batch] (the write pass)
-    bv_tt_token *tok;
-    uint8_t *ttext;
-};
-
-// One wave walks row r.  WRITE: the lanes store what the masks give them, below the row's counts (a row that counted n tokens
-// and m bytes stores nothing at or beyond them, whatever it reads).
-template <bool WRITE>
-__device__ __forceinline__ void walk_row(const TokArgs &a, uint32_t r, uint32_t lane) {
-    if (!(a.rowflag[r] & BV_TEXT_INDEL)) {
-        if (!WRITE && lane == 0) { a.cnt_tok[r] = 0; a.cnt_txt[r] = 0; }
-        return;
-    }
-    const char *row = a.text + (a.row_beg[r] - a.chunk_base);
-    const uint32_t len = (uint32_t)(a.row_end[r] - a.row_beg[r]);
-    const uint32_t p = r / a.n_files, f = r - p * a.n_files;
-    const uint32_t sample0 = a.foff[f];
-    uint32_t lim_tok = 0, lim_txt = 0;
-    uint64_t at_tok = 0, at_txt = 0;
-    if (WRITE) { lim_tok = a.cnt_tok[r]; lim_txt = a.cnt_txt[r]; at_tok = a.base_tok[r]; at_txt = a.base_txt[r]; }
-    bv_tt_carry c = bv_tt_carry_init();
-    for (uint32_t b = 0; b < len && !bv_tt_done(c); b += 64u) {
-        const uint32_t i = b + lane;
-        const bool valid = i < len;
-        const char ch = valid ? row[i] : '\0';
-        const uint64_t T = __ballot(valid && ch == '\t');
-        const uint64_t S = __ballot(valid && ch == ' ');
-        const uint64_t SEP = T | S | __ballot(valid && ch == '\n');
-        const uint64_t V = __ballot(valid);
-        const uint64_t F5 = __ballot(bv_tt_field_at(c, T, lane) == BV_TT_FIELD);
-        const uint64_t PM = __ballot(valid && (ch == '+' || ch == '-'));
-        const bv_tt_masks m = bv_tt_step_masks(c, SEP, V, F5, PM);
-        if (WRITE) {
-            const uint64_t bit = 1ull << lane;
-            if (m.M & bit) {
-                const uint32_t x = bv_tt_text_at(c, m, lane);
-                if (x < lim_txt) a.ttext[at_txt + x] = (uint8_t)ch;
-                if (m.IS & bit) {
-                    const uint32_t o = bv_tt_start_ord_at(c, m, lane);
-                    if (o < lim_tok) {
-                        bv_tt_token *t = a.tok + at_tok + o;
-                        t->pos = p; t->sample = sample0 + bv_tt_tok_at(c, T, S, lane); t->text_off = at_txt + x; t->reserved_ = 0;
-                    }
-                }
-            } else if (m.EN & bit) {
-                const uint32_t o = bv_tt_end_ord_at(c, m, lane);
-                if (o < lim_tok) a.tok[at_tok + o].text_len = bv_tt_end_len_at(c, m, lane);
-            }
-        }
-        c = bv_tt_carry_next(c, m, T, S, SEP);
-    }
-    if (!WRITE && lane == 0) { a.cnt_tok[r] = c.n_tok; a.cnt_txt[r] = c.n_txt; }
-}
-
 // One wave per row of the chunk; four rows per workgroup.
 __global__ __launch_bounds__(256) void bv_tt_count_kernel(TokArgs a) {
     const uint32_t local = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (local >= a.n_rows) return;
-    walk_row<false>(a, a.row_first + local, threadIdx.x & 63u);
+    walk_row<false>(a, a.row_first + local, a.row_first + local, threadIdx.x & 63u);
 }
 __global__ __launch_bounds__(256) void bv_tt_write_kernel(TokArgs a) {
     const uint32_t local = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (local >= a.n_rows) return;
-    walk_row<true>(a, a.row_first + local, threadIdx.x & 63u);
+    walk_row<true>(a, a.row_first + local, a.row_first + local, threadIdx.x & 63u);
 }
 
-// Rows [first, first + n): out_a[r] = start_a + the counts ca of the rows before r, out_b the same for cb; with pos_state, a
-// row of a position not in state 0 counts nothing.  totals[0 .. 2) = the sums behind the last row.  One workgroup: every thread
-// sums a run of rows, the runs' sums are scanned in LDS, and every thread walks its run again.
-constexpr uint32_t kScanThreads = 1024;
+// Rows [first, first + n) scanned (scan_rows of bv_text_tokens_walk.h).  One workgroup.
 __global__ __launch_bounds__(kScanThreads) void bv_tt_scan_kernel(const uint32_t *ca, const uint32_t *cb, const uint8_t *pos_state, uint32_t F, uint32_t first,
                                                                   uint32_t n, uint64_t start_a, uint64_t start_b, uint64_t *out_a, uint64_t *out_b,
                                                                   uint64_t *totals) {
-    __shared__ uint64_t sa[kScanThreads], sb[kScanThreads];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (n + kScanThreads - 1u) / kScanThreads;
-    const uint32_t lo = min(n, tid * per), hi = min(n, lo + per);
-    uint64_t a = 0, b = 0;
-    for (uint32_t k = lo; k < hi; ++k) {
-        const uint32_t r = first + k;
-        const bool keep = !pos_state || pos_state[r / F] == 0;
-        a += keep ? ca[r] : 0u;
-        b += keep ? cb[r] : 0u;
-    }
-    sa[tid] = a; sb[tid] = b;
-    __syncthreads();
-    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {
-        const uint64_t va = tid >= o ? sa[tid - o] : 0u, vb = tid >= o ? sb[tid - o] : 0u;
-        __syncthreads();
-        sa[tid] += va; sb[tid] += vb;
-        __syncthreads();
-    }
-    uint64_t ra = start_a + sa[tid] - a, rb = start_b + sb[tid] - b;
-    for (uint32_t k = lo; k < hi; ++k) {
-        const uint32_t r = first + k;
-        const bool keep = !pos_state || pos_state[r / F] == 0;
-        out_a[r] = ra; out_b[r] = rb;
-        ra += keep ? ca[r] : 0u;
-        rb += keep ? cb[r] : 0u;
-    }
-    if (tid == kScanThreads - 1u) { totals[0] = start_a + sa[tid]; totals[1] = start_b + sb[tid]; }
+    scan_rows<false>(ca, cb, pos_state, F, first, n, start_a, start_b, out_a, out_b, totals, 0u, 0u);
 }
-
 // The rows of positions in state 0 into the caller's list: one wave per row moves its descriptors and its text.
 struct PackArgs {
     const uint32_t *cnt_tok, *cnt_txt;
@@ -219,6 +127,7 @@ int grow_keep(bv_engine *e, uint8_t **buf, size_t *bytes, size_t need, size_t us
 namespace bv_impl {
 
 bool bv_text_tokens_stand(const bv_engine *e) { return e->ttok && e->ttok->on && e->ttok->valid; }
+bool bv_text_tokens_on(const bv_engine *e) { return e->ttok && e->ttok->on; }
 
 int bv_text_tokens_begin(bv_engine *e, uint32_t P, uint32_t F, hipStream_t st) {
     BvTextTokState *t = e->ttok;
@@ -236,16 +145,25 @@ int bv_text_tokens_begin(bv_engine *e, uint32_t P, uint32_t F, hipStream_t st) {
 int bv_text_tokens_rows(bv_engine *e, const BvTextTokRows &rows, hipStream_t st) {
     BvTextTokState *t = e->ttok;
     if (!t || !t->on || rows.n_rows == 0) return BV_OK;
-    if ((uint64_t)rows.row_first + rows.n_rows > t->n_rows) return fail(e, BV_ERR_INVALID_ARG, "bv_text_tokens_rows: rows beyond the batch");
+    const bool job = rows.add_files != 0;  // the rows of a parse job's add: row_first and n_rows count the add's rows
+    const uint64_t last = (uint64_t)rows.row_first + rows.n_rows - 1u;  // the last row, and with a job its place in the batch
+    if (job && (uint64_t)rows.first_file + rows.add_files > rows.n_files) return fail(e, BV_ERR_INVALID_ARG, "bv_text_tokens_rows: files beyond the batch");
+    if ((job ? last / rows.add_files * rows.n_files + rows.first_file + last % rows.add_files : last) >= t->n_rows)
+        return fail(e, BV_ERR_INVALID_ARG, "bv_text_tokens_rows: rows beyond the batch");
     TokArgs a;
     a.text = rows.text; a.row_beg = rows.row_beg; a.row_end = rows.row_end; a.rowflag = rows.rowflag; a.foff = rows.foff;
     a.chunk_base = rows.chunk_base; a.row_first = rows.row_first; a.n_rows = rows.n_rows; a.n_files = rows.n_files;
     a.cnt_tok = t->cnt_tok(); a.cnt_txt = t->cnt_txt(); a.base_tok = t->u64(0); a.base_txt = t->u64(1);
     a.tok = nullptr; a.ttext = nullptr;
     const dim3 grid((rows.n_rows + 3u) / 4u);
-    hipLaunchKernelGGL(bv_tt_count_kernel, grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(bv_tt_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)a.cnt_tok, (const uint32_t *)a.cnt_txt, (const uint8_t *)nullptr,
-                       rows.n_files, rows.row_first, rows.n_rows, t->run_tok, t->run_txt, t->u64(0), t->u64(1), t->u64(4));
+    BvTextTokStore store{t->cnt_tok(), t->cnt_txt(), t->u64(0), t->u64(1), t->u64(4), nullptr, nullptr};
+    if (job) {  // (the strided kernels live with the job: bv_text_job.hip)
+        text_job_tokens_count_scan(rows, store, t->run_tok, t->run_txt, st);
+    } else {
+        hipLaunchKernelGGL(bv_tt_count_kernel, grid, dim3(256), 0, st, a);
+        hipLaunchKernelGGL(bv_tt_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, (const uint32_t *)a.cnt_tok, (const uint32_t *)a.cnt_txt,
+                           (const uint8_t *)nullptr, rows.n_files, rows.row_first, rows.n_rows, t->run_tok, t->run_txt, t->u64(0), t->u64(1), t->u64(4));
+    }
     BV_HIP(e, hipGetLastError());
     uint64_t sums[2] = {0, 0};
     BV_HIP(e, hipMemcpyAsync(sums, t->u64(4), 16, hipMemcpyDeviceToHost, st));
@@ -255,7 +173,9 @@ int bv_text_tokens_rows(bv_engine *e, const BvTextTokRows &rows, hipStream_t st)
     if (rc == BV_OK) rc = grow_keep(e, &t->d_ttext, &t->ttext_bytes, sums[1], t->run_txt, st);
     if (rc != BV_OK) return rc;
     a.tok = reinterpret_cast<bv_tt_token *>(t->d_tok); a.ttext = t->d_ttext;
-    hipLaunchKernelGGL(bv_tt_write_kernel, grid, dim3(256), 0, st, a);
+    store.tok = t->d_tok; store.ttext = t->d_ttext;
+    if (job) text_job_tokens_write(rows, store, st);
+    else hipLaunchKernelGGL(bv_tt_write_kernel, grid, dim3(256), 0, st, a);
     BV_HIP(e, hipGetLastError());
     t->run_tok = sums[0]; t->run_txt = sums[1];
     return BV_OK;

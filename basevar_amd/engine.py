@@ -393,19 +393,7 @@ class BaseTypeEngine:
     def _lrt_text(self, rows, file_samples, group_id, n_groups, host_reader, device_tokens):
         fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
         F, N = int(fs.size), int(fs.sum())
-        if isinstance(rows, tuple):
-            text, off = rows
-            text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
-            off = np.ascontiguousarray(off, dtype=np.uint64)
-            P = (off.size - 1) // F
-        else:
-            P = len(rows)
-            flat = [bytes(r) + b"\n" for pos in rows for r in pos]
-            if any(len(pos) != F for pos in rows):
-                raise ValueError("lrt_text: every position needs one row per batchfile")
-            off = np.zeros(len(flat) + 1, dtype=np.uint64)
-            off[1:] = np.cumsum([len(r) for r in flat])
-            text = np.frombuffer(b"".join(flat), dtype=np.uint8)
+        text, off, P = self._pack_rows(rows, F, "lrt_text")
         gid = None if group_id is None else np.ascontiguousarray(group_id, dtype=np.uint8)
         tr = _capi.TextRows(text.ctypes.data, off.ctypes.data, fs.ctypes.data, int(text.size), int(P), F, 0)
         state = np.zeros((P, F), dtype=np.uint8)
@@ -462,6 +450,94 @@ class BaseTypeEngine:
             self.wait()
             n_variant = self.last_variant_count()
         return TextBatch(out, gout, n_variant, positions, state, cell, phred)
+
+    # ---- batchfile text rows, parsed a few files at a time (include/basevar_amd_text_job.h)
+    @staticmethod
+    def _pack_rows(rows, F, who):
+        """rows of lrt_text -> (text uint8, row_off uint64, P)"""
+        if isinstance(rows, tuple):
+            text, off = rows
+            text = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            return text, off, (off.size - 1) // F
+        if any(len(pos) != F for pos in rows):
+            raise ValueError("%s: every position needs one row per batchfile" % who)
+        flat = [bytes(r) + b"\n" for pos in rows for r in pos]
+        off = np.zeros(len(flat) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(r) for r in flat])
+        return np.frombuffer(b"".join(flat), dtype=np.uint8), off, len(rows)
+
+    def text_job_begin(self, n_positions, file_samples, group_id=None, n_groups=0):
+        """bv_engine_text_job_begin: a parse job of n_positions x len(file_samples) rows"""
+        fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
+        gid = None if group_id is None else np.ascontiguousarray(group_id, dtype=np.uint8)
+        rc = self._lib.bv_engine_text_job_begin(self._h, int(n_positions), int(fs.size), fs.ctypes.data, None if gid is None else gid.ctypes.data,
+                                                int(n_groups), None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_job_begin failed (%d): %s" % (rc, self._err()))
+
+    def text_job_add(self, rows, file_samples, first_file, want_flags=True):
+        """bv_engine_text_job_add: the rows of files [first_file, first_file + len(file_samples)), as lrt_text takes rows.
+        Returns the add's BV_TEXT_INDEL marks [n_positions][files of the add] (None without want_flags)."""
+        fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
+        K = int(fs.size)
+        text, off, P = self._pack_rows(rows, K, "text_job_add")
+        tr = _capi.TextRows(text.ctypes.data, off.ctypes.data, fs.ctypes.data, int(text.size), int(P), K, 0)
+        flags = np.zeros((P, K), dtype=np.uint8) if want_flags else None
+        rc = self._lib.bv_engine_text_job_add(self._h, C.byref(tr), int(first_file), flags.ctypes.data if want_flags else None, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_job_add failed (%d): %s" % (rc, self._err()))
+        return flags
+
+    def text_job_finish(self, n_positions, n_files):
+        """bv_engine_text_job_finish: row_state [n_positions][n_files] of the whole job"""
+        state = np.zeros((int(n_positions), int(n_files)), dtype=np.uint8)
+        rc = self._lib.bv_engine_text_job_finish(self._h, state.ctypes.data, None)
+        if rc != 0:
+            raise RuntimeError("bv_engine_text_job_finish failed (%d): %s" % (rc, self._err()))
+        return state
+
+    def lrt_text_job(self, adds, file_samples, group_id=None, n_groups=0, host_reader=None, tokens="host"):
+        """lrt_text with the files delivered in groups (bv_engine_text_job_begin / _add / _finish + bv_engine_text_submit).
+
+        `adds`: a list of (first_file, rows) in any file order; `rows` as lrt_text takes them, for the adjacent files
+        first_file .. first_file + K, K being the rows per position (list form) -- a packed pair is given as
+        (first_file, (text, row_off), K).  Every file of `file_samples` is added exactly once.  Returns what lrt_text returns
+        for the rows of all files joined position-major; host_reader gets a host position's rows of all files, in file order."""
+        restore = self._tokens_mode(tokens, "lrt_text_job")
+        try:
+            fs = np.ascontiguousarray(file_samples, dtype=np.uint32)
+            F, N = int(fs.size), int(fs.sum())
+            packed = []
+            for add in adds:
+                first, rows = int(add[0]), add[1]
+                K = int(add[2]) if len(add) > 2 else (len(rows[0]) if len(rows) else 0)
+                if K <= 0 or first < 0 or first + K > F:
+                    raise ValueError("lrt_text_job: an add of files %d .. %d does not lie in the %d files" % (first, first + K, F))
+                packed.append((first, K) + self._pack_rows(rows, K, "lrt_text_job"))
+            if not packed:
+                raise ValueError("lrt_text_job: no add")
+            P = packed[0][4]
+            self.text_job_begin(P, fs, group_id, n_groups)
+            where = {}  # file -> (text, row_off, K, k): the host reader's lines come from the adds' own rows
+            for first, K, text, off, _ in packed:
+                self.text_job_add((text, off), fs[first:first + K], first, want_flags=False)
+                for k in range(K):
+                    where[first + k] = (text, off, K, k)
+            state = self.text_job_finish(P, F)
+
+            def lines_of(p):
+                out = []
+                for f in range(F):
+                    text, off, K, k = where[f]
+                    out.append(bytes(text[int(off[p * K + k]):int(off[p * K + k + 1]) - 1]))
+                return out
+            batch = self._text_submit("lrt_text_job", state, P, F, N, n_groups, host_reader, lines_of)
+            if tokens == "device":
+                batch.tokens, batch.token_text = self.text_tokens_fetch()
+            return batch
+        finally:
+            restore()
 
     # ---- batchfile rows that are still compressed: inflated, split into lines and parsed on the device
     def lrt_bgzf(self, runs, file_samples, skip_bytes=None, skip_lines=None, max_positions=None, at_end=True, group_id=None, n_groups=0,

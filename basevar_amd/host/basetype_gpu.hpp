@@ -28,6 +28,7 @@
 #include "../../include/basevar_amd_record_text.h"
 #include "../../include/basevar_amd_region.h"
 #include "../../include/basevar_amd_vcf.h"
+#include "../../include/basevar_amd_text_job.h"
 #include "indel_tokens.hpp"  // TokenList, row_indel_tokens
 #include "vcf_emit.hpp"  // SiteText
 
@@ -361,7 +362,8 @@ public:
             const uint64_t a = rows.row_off[p * F + f], b = rows.row_off[p * F + f + 1];
             return std::string(rows.text + a, (size_t)(b - a - 1));
         };
-        finish_text(tb, rows.n_positions, F, N, row_text, [&](size_t p, size_t f) { return rows.text + rows.row_off[p * F + f]; }, read_host, n_groups,
+        finish_text(tb, rows.n_positions, F, N, row_text,
+                    [&](size_t p, size_t f, std::vector<std::string> &out) { row_indel_tokens(rows.text + rows.row_off[p * F + f], out); }, read_host, n_groups,
                     keep_planes);
         return tb;
     }
@@ -512,16 +514,16 @@ public:
         const char *text = reinterpret_cast<const char *>(buf.data());
         finish_text(tb, bp.n_positions, F, N,
                     [&](size_t p, size_t f) { return std::string(text + off[p * F + f], (size_t)(off[p * F + f + 1] - off[p * F + f])); },
-                    [&](size_t p, size_t f) { return text + off[p * F + f]; }, read_host, n_groups, keep_planes);
+                    [&](size_t p, size_t f, std::vector<std::string> &out) { row_indel_tokens(text + off[p * F + f], out); }, read_host, n_groups, keep_planes);
         return tb;
     }
 
     // The host's part of a parsed batch and its submit (shared by lrt_text and lrt_bgzf): row_text(p, f) is a row without its
     // line break (whole for the positions left to the host, through its fourth tab at least for file 0's row of any other),
-    // row_ptr(p, f) the first byte of a whole row flagged BV_TEXT_INDEL.  keep_planes = false: the records' cell / phred rows are
+    // row_tokens(p, f, out) appends the '+'/'-' tokens of a row flagged BV_TEXT_INDEL, in sample order.  keep_planes = false: the records' cell / phred rows are
     // not copied back (tb.cell / tb.phred stay empty); they stand on the device for vcf_format().
-    template <class RowText, class RowPtr, class HostReader>
-    void finish_text(TextBatch &tb, uint32_t P, size_t F, uint32_t N, RowText &&row_text, RowPtr &&row_ptr, HostReader &&read_host, uint32_t n_groups,
+    template <class RowText, class RowTokens, class HostReader>
+    void finish_text(TextBatch &tb, uint32_t P, size_t F, uint32_t N, RowText &&row_text, RowTokens &&row_tokens, HostReader &&read_host, uint32_t n_groups,
                      bool keep_planes = true) {
         SlabBuilder host(N);
         std::vector<std::string> lines(F);
@@ -545,7 +547,7 @@ public:
                 st.ref_pos = (uint32_t)std::stoi(r0.substr(t1 + 1, t2 - t1 - 1));
                 st.ref_base = r0.substr(t2 + 1, t3 - t2 - 1);
                 for (size_t f = 0; f < F && tb.tokens == TOKENS_HOST; ++f)
-                    if (rs[f] & BV_TEXT_INDEL) row_indel_tokens(row_ptr(used, f), st.indel_tokens);
+                    if (rs[f] & BV_TEXT_INDEL) row_tokens(used, f, st.indel_tokens);
             }
             tb.position.push_back(used);
             tb.host_read.push_back(host_read ? 1 : 0);
@@ -583,6 +585,72 @@ public:
 private:
     bv_engine *e_ = nullptr;
     bool tokens_on_ = false;
+};
+
+// lrt_text with the files delivered in groups (include/basevar_amd_text_job.h): a job over P positions of F files; add() takes
+// the rows of a run of adjacent files, in any file order, and may free them when it returns; finish() returns what lrt_text
+// returns for the rows of all files joined position-major.  What finish_text wants of the rows is kept at add time: the
+// coordinates of every position (CHROM, POS, REF of whichever row came first -- they are equal in every row of a position that
+// ends parsed) and, with TOKENS_HOST, the '+'/'-' tokens of the rows the add's row_flag marks, per (position, file).
+class TextJob {
+public:
+    TextJob(BaseTypeEngine &eng, uint32_t n_positions, const std::vector<uint32_t> &file_samples, const uint8_t *group_id, uint32_t n_groups,
+            BaseTypeEngine::TokenMode tokens)
+        : eng_(eng), P_(n_positions), fs_(file_samples), tokens_(tokens), head_(n_positions) {
+        eng_.text_tokens_mode(tokens);
+        if (bv_engine_text_job_begin(eng_.handle(), P_, (uint32_t)fs_.size(), fs_.data(), group_id, n_groups, nullptr) != BV_OK)
+            throw std::runtime_error(bv_last_error(eng_.handle()));
+        if (tokens_ == BaseTypeEngine::TOKENS_HOST) row_tokens_.resize((size_t)P_ * fs_.size());
+    }
+    void add(const bv_text_rows &rows, uint32_t first_file) {
+        const size_t K = rows.n_files;
+        flag_.assign((size_t)P_ * K, 0);
+        if (bv_engine_text_job_add(eng_.handle(), &rows, first_file, flag_.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(eng_.handle()));
+        for (size_t p = 0; p < P_; ++p) {
+            if (!have_head_) {  // through the third tab (a row without one belongs to a position the host reads)
+                const char *r = rows.text + rows.row_off[p * K], *end = rows.text + rows.row_off[p * K + 1];
+                const char *t = r;
+                for (int tabs = 0; t < end && tabs < 3; ++t) tabs += *t == '\t';
+                head_[p].assign(r, (size_t)(t - r));
+            }
+            for (size_t k = 0; k < K && tokens_ == BaseTypeEngine::TOKENS_HOST; ++k)
+                if (flag_[p * K + k] & BV_TEXT_INDEL) row_indel_tokens(rows.text + rows.row_off[p * K + k], row_tokens_[p * fs_.size() + first_file + k]);
+        }
+        have_head_ = true;
+    }
+    // reread(p): position p's F lines (without their line breaks), for the positions left to the host reader -- in position
+    // order, and none behind the one at which the reader throws.  n_used <= P: the positions that have a row in every file.
+    template <class Reread, class HostReader>
+    BaseTypeEngine::TextBatch finish(Reread &&reread, HostReader &&read_host, uint32_t n_groups, bool keep_planes = true, uint32_t n_used = UINT32_MAX) {
+        BaseTypeEngine::TextBatch tb;
+        tb.tokens = tokens_;
+        const size_t F = fs_.size();
+        tb.row_state.resize((size_t)P_ * F);
+        if (bv_engine_text_job_finish(eng_.handle(), tb.row_state.data(), nullptr) != BV_OK) throw std::runtime_error(bv_last_error(eng_.handle()));
+        uint32_t N = 0;
+        for (uint32_t n : fs_) N += n;
+        size_t have = (size_t)-1;
+        std::vector<std::string> lines;
+        auto row_text = [&](size_t p, size_t f) -> std::string {
+            if (!(tb.row_state[p * F] & BV_TEXT_HOST)) return head_[p];  // (asked of file 0 only: the coordinates)
+            if (have != p) { lines = reread(p); have = p; }
+            return lines[f];
+        };
+        eng_.finish_text(tb, std::min(P_, n_used), F, N, row_text,
+                         [&](size_t p, size_t f, std::vector<std::string> &out) { const auto &t = row_tokens_[p * F + f]; out.insert(out.end(), t.begin(), t.end()); },
+                         read_host, n_groups, keep_planes);
+        return tb;
+    }
+
+private:
+    BaseTypeEngine &eng_;
+    uint32_t P_;
+    std::vector<uint32_t> fs_;
+    BaseTypeEngine::TokenMode tokens_;
+    std::vector<std::string> head_;
+    bool have_head_ = false;
+    std::vector<uint8_t> flag_;
+    std::vector<std::vector<std::string>> row_tokens_;  // TOKENS_HOST: [P][F]
 };
 
 }  // namespace bvamd

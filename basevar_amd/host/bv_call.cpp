@@ -19,6 +19,11 @@
 //           [--reference ref.fa --contig NAME:LENGTH ...]
 //           [--regions CHR[:BEG[-END]][,...]]   (batchfile input: the regions in the order given, each from where the file's .tbi
 //                                                says it may begin -- a seek, not a scan)
+//           [--files-per-pass K]   (batchfile input: the files are read K at a time, a window of --batch-sites positions at a
+//                                   time, and parsed as one job per window -- never more than K batchfiles are open, so a
+//                                   cohort may have more files than the process may hold descriptors; one engine, host inflate,
+//                                   no --regions; INTEGRATION.md section 2q.  The window's default is the plane budget's:
+//                                   2^28 cells / samples, at most 65536 -- the text-block size of the default route does not cut it)
 //   bv_call -I a.bam [-I b.bam ...] [-L bam.list] -R ref.fa[.gz] --regions CHR:BEG-END[,CHR:BEG-END...] [--mapq 10]
 //           [--thread T] ...   (same outputs)
 //
@@ -54,6 +59,8 @@ struct Options {
     std::vector<bvamd::Contig> contigs;
     float user_min_af = 0.01f;  // BaseTypeARGS default, src/basetype_utils.h:94
     uint32_t batch_sites = 0;   // 0 = from a cell budget once the sample count is known
+    uint32_t files_per_pass = 0;  // batchfile input: > 0 reads the files file-major, this many at a time (file_major.hpp)
+    size_t fm_passes = 0, fm_max_open = 0;  // ... what that route counted, for --timing
     // what validate() makes of them
     std::vector<int> devices;            // one engine per entry
     std::vector<bvamd::Region> region_list;
@@ -72,6 +79,10 @@ Options parse_options(int argc, char **argv) {
         else if (a == "--pop-group") o.pop_group_file = next();
         else if (a == "--min-af") o.user_min_af = std::stof(next());
         else if (a == "--batch-sites") o.batch_sites = (uint32_t)std::stoul(next());
+        else if (a == "--files-per-pass") {
+            o.files_per_pass = (uint32_t)std::stoul(next());
+            if (o.files_per_pass == 0) die("[ERROR] --files-per-pass wants a number >= 1");
+        }
         else if (a == "--timing") o.timing_file = next();
         else if (a == "--inflate") o.inflate = next();
         else if (a == "--deflate") o.deflate = next();
@@ -119,6 +130,19 @@ void validate(Options &o) {
     if ((o.batchfiles.empty() && !o.from_bam()) || o.out_vcf.empty() || o.out_cvg.empty() || (o.from_bam() && (o.regions.empty() || o.reference == ".")))
         die("usage: bv_call (--batchfiles a,b,... | -I a.bam [-I ...] -R ref.fa --regions CHR:BEG-END [--mapq Q]) --output-vcf FILE "
             "--output-cvg FILE [--pop-group FILE] [--min-af F] [--gpus G]");
+    // --files-per-pass: batchfiles, whole files, one engine, inflated on the host
+    if (o.files_per_pass) {
+        if (o.from_bam()) die("[ERROR] --files-per-pass applies to batchfile input, not to BAM input");
+        if (!o.regions.empty()) die("[ERROR] --files-per-pass with --regions is not built: the file-major route reads whole files");
+        if (o.devices.size() > 1) {
+            std::cerr << "[NOTE] --files-per-pass runs on one engine: device " << o.devices[0] << " is taken" << std::endl;
+            o.devices.resize(1);
+        }
+        if (o.inflate == "device") {
+            std::cerr << "[NOTE] --files-per-pass reads and inflates on the host: --inflate host is taken" << std::endl;
+            o.inflate = "host";
+        }
+    }
     // "-r chr:beg-end[,chr:beg-end ...]" (caller.cpp:311-356): the syntax here, before any engine exists; whether a region lies
     // inside its contig takes the contig's sequence (for_each_bam_region)
     for (const std::string &rg : o.from_bam() ? bvamd::pieces(o.regions, ',') : std::vector<std::string>()) {
@@ -320,6 +344,8 @@ void report(const Options &o, const bvamd::CallContext &ctx, size_t n_workers, d
     // --indel-tokens device, the tokens the engines listed
     if (!ctx.from_bam) tf << ", \"text_fetch_bytes\": " << counts.text_fetch_bytes;
     if (!ctx.regions.empty()) tf << ", \"regions\": " << ctx.regions.size();  // --regions on batchfiles
+    // --files-per-pass: groups of files read (windows x groups), and the most batchfiles the producer had open at once
+    if (o.files_per_pass) tf << ", \"files_per_pass\": " << o.files_per_pass << ", \"passes\": " << o.fm_passes << ", \"max_open_batchfiles\": " << o.fm_max_open;
     if (ctx.routes.indel_tokens_device) tf << ", \"indel_tokens\": \"device\", \"indel_tokens_device\": " << counts.indel_tokens_device;
     // --pileup device: bytes of raw BAM records handed to the engine, and the producer's seconds inside the pileup calls (part of parse_pack_s)
     if (ctx.routes.device_pileup) tf << ", \"pileup\": \"device\", \"reads_bytes\": " << pileup.reads_bytes << ", \"pileup_s\": " << pileup.pileup_s;
@@ -338,9 +364,14 @@ int main(int argc, char **argv) {
     // ---- headers: sample ids in batchfile order (caller.cpp:637-665), or the BAM files' sample names; pop groups; outputs
     bvamd::CallContext ctx;
     bvamd::BatchfileHeaders headers;
+    bvamd::FileMajorHeaders fm_headers;
     try {
         for (const auto &b : o.bams) ctx.sample_ids.push_back(bvamd::BamFile(b, false).sample_name());
-        if (!o.from_bam()) {
+        if (o.files_per_pass) {  // (file by file, each closed again)
+            bvamd::scan_batchfile_headers_closing(o.batchfiles, fm_headers);
+            ctx.sample_ids = fm_headers.sample_ids;
+            ctx.file_samples = fm_headers.file_samples;
+        } else if (!o.from_bam()) {
             bvamd::scan_batchfile_headers(o.batchfiles, headers);
             ctx.sample_ids = headers.sample_ids;
             ctx.file_samples = headers.file_samples;
@@ -374,7 +405,8 @@ int main(int argc, char **argv) {
     // ---- the pipeline: producer (this thread) -> engine workers -> emitter, results written in batch order
     // batchfile input: three engine workers per GPU -- a text batch has host work on its worker (the rows into pinned staging,
     // the host reader for the positions the device leaves to it, the records and planes back), which the other two overlap
-    const size_t W = (ctx.from_bam ? 1 : 3) * ctx.devices.size();
+    // (--files-per-pass: one worker, whose engine holds the window's job from its first add to its finish)
+    const size_t W = o.files_per_pass ? 1 : (ctx.from_bam ? 1 : 3) * ctx.devices.size();
     bvamd::BatchQueue to_gpu(W + 1), to_emit(2 * W + 2);
     StageClock clk;
     bvamd::ErrorSink errors;
@@ -391,8 +423,13 @@ int main(int argc, char **argv) {
     std::thread emitter_thread(&bvamd::OrderedEmitter::run, &emitter, std::ref(to_emit));
 
     bvamd::DevicePileupProducer device_pileup(ctx, bam_input, to_emit, clk, errors);
+    std::unique_ptr<bvamd::FileMajorReader> file_major;
     try {
-        if (ctx.routes.device_pileup) device_pileup.run();
+        if (o.files_per_pass) {
+            file_major.reset(new bvamd::FileMajorReader(o.batchfiles, fm_headers.header_lines, o.files_per_pass, ctx.threads));
+            bvamd::produce_batchfile_file_major(ctx, *file_major, to_gpu, clk, errors);
+        }
+        else if (ctx.routes.device_pileup) device_pileup.run();
         else if (ctx.from_bam) bvamd::produce_bam_host(ctx, bam_input, to_gpu, clk, errors);
         else if (!ctx.routes.device_inflate && !ctx.regions.empty())
             bvamd::produce_batchfile_regions_host(ctx, o.batchfiles, region_indexes, text_block_bytes, to_gpu, clk, errors);
@@ -404,6 +441,7 @@ int main(int argc, char **argv) {
     for (auto &t : worker_threads) t.join();
     to_emit.close();
     emitter_thread.join();  // (the emitter has closed both outputs)
+    if (file_major) { o.fm_passes = file_major->passes(); o.fm_max_open = file_major->max_open(); }
     if (!errors.ok()) die(errors.first());
     report(o, ctx, W, StageClock::now() - t_start, clk, emitter, raw, device_pileup.stats());
     return 0;

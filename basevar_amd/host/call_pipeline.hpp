@@ -32,6 +32,7 @@
 
 #include "basetype_gpu.hpp"
 #include "batch_producer.hpp"
+#include "file_major.hpp"
 #include "bgzf_tabix.hpp"
 #include "device_pileup.hpp"
 #include "indel_tokens.hpp"
@@ -90,6 +91,12 @@ struct Batch {
     std::vector<uint32_t> position;
     std::vector<uint8_t> host_read;
     BaseTypeEngine::TokenMode tokens = BaseTypeEngine::TOKENS_HOST;
+    // --files-per-pass: `rows` are those of files [job_first_file, job_first_file + job_files) for the n_positions of a window, one
+    // add of the worker's parse job (basetype_gpu.hpp: TextJob).  The window's last part carries its records on to the emitter:
+    // job_used positions have a row in every file, reread(p) brings a position's lines again for the host reader
+    bool job_part = false, job_last = false;
+    uint32_t job_first_file = 0, job_files = 0, job_used = 0;
+    std::function<std::vector<std::string>(size_t)> reread;
     explicit Batch(uint32_t n_samples) : slab(n_samples) {}
     const uint8_t *cell_row(size_t i, size_t n) const { return from_text ? &cell[i * n] : slab.cell_row(i); }
     const uint8_t *phred_row(size_t i, size_t n) const { return from_text ? &phred[i * n] : slab.phred_row(i); }
@@ -500,9 +507,12 @@ public:
         for (BatchPtr b; (b = in_.pop());) {
             if (engine_) {
                 const double t0 = StageClock::now();
-                if (b->from_text) call_text_rows(*b);
+                bool passes_on = true;
+                if (b->job_part) passes_on = call_job_part(*b);
+                else if (b->from_text) call_text_rows(*b);
                 else call_slab(*b);
                 clk_.add(StageClock::ENGINE, StageClock::now() - t0);
+                if (!passes_on) continue;  // (an add of a window that has more to come)
             } else {
                 b->error = "no engine on device " + std::to_string(device_);
             }
@@ -536,6 +546,27 @@ private:
             return engine_->lrt_text(rows, host_reader, ctx_.group_ids(), ctx_.n_groups(), !ctx_.routes.emit_device, text_token_mode(ctx_));
         });
         std::string().swap(b.rows);
+    }
+    // --files-per-pass: one add of the window's job; the window's last part finishes it and takes the records.  What an add threw
+    // is the window's error.  Returns whether the batch goes on to the emitter.
+    bool call_job_part(Batch &b) {
+        try {
+            if (!job_) {
+                job_error_.clear();
+                job_.reset(new TextJob(*engine_, b.n_positions, ctx_.file_samples, ctx_.group_ids(), ctx_.n_groups(), text_token_mode(ctx_)));
+            }
+            if (job_error_.empty()) {
+                const bv_text_rows rows{b.rows.data(), b.row_off.data(), ctx_.file_samples.data() + b.job_first_file, b.rows.size(), b.n_positions, b.job_files, 0};
+                job_->add(rows, b.job_first_file);
+            }
+        } catch (const std::exception &ex) { if (job_error_.empty()) job_error_ = ex.what(); }
+        std::string().swap(b.rows);
+        if (!b.job_last) return false;
+        b.from_text = true;
+        if (job_error_.empty()) text_batch(b, [&]() { return job_->finish(b.reread, host_reader, ctx_.n_groups(), !ctx_.routes.emit_device, b.job_used); });
+        else b.error = job_error_;
+        job_.reset();
+        return true;
     }
     // (the producer's choice of layout: short reads -> the rank words carry the calls, basetype_gpu.hpp)
     void call_slab(Batch &b) {
@@ -573,6 +604,8 @@ private:
     StageClock &clk_;
     ErrorSink &errors_;
     std::unique_ptr<BaseTypeEngine> engine_;
+    std::unique_ptr<TextJob> job_;  // --files-per-pass: the window under way
+    std::string job_error_;
 };
 
 // --------------------------------------------------------------------------------------------------------------- the producers
@@ -608,6 +641,45 @@ inline void produce_batchfile_text(const CallContext &ctx, BatchfileHeaders &hea
         to_gpu.push(std::move(b));
         return errors.ok();
     }, block_bytes, ctx.batch_sites);
+}
+
+// --files-per-pass K: the batchfiles read file-major (file_major.hpp), a window of ctx.batch_sites positions at a time and K files
+// at a time within it; every group of files goes to the one engine worker as an add of the window's parse job, the last one with
+// what the worker needs to finish the window.  A window that a file ends in is the run's last.
+inline void produce_batchfile_file_major(const CallContext &ctx, FileMajorReader &reader, BatchQueue &to_gpu, StageClock &clk, const ErrorSink &errors) {
+    const size_t G = reader.groups();
+    for (uint64_t seq = 0; errors.ok(); ++seq) {
+        double t0 = StageClock::now();
+        FileMajorReader::Group g;
+        const size_t P = reader.begin(ctx.batch_sites, g);
+        if (P == 0) break;
+        std::vector<BatchPtr> parts;
+        for (size_t gi = 0; gi < G; ++gi) {
+            if (gi) reader.group(gi, g);
+            BatchPtr b(new Batch((uint32_t)ctx.n_sample()));
+            b->seq = seq;
+            b->job_part = true;
+            b->job_first_file = (uint32_t)g.first_file; b->job_files = (uint32_t)g.n_files;
+            b->rows.swap(g.text);
+            b->row_off.swap(g.row_off);
+            b->n_positions = (uint32_t)P;
+            clk.add(StageClock::READ, StageClock::now() - t0);  // (wall seconds of the group's read and pack on this thread and its helpers)
+            if (gi + 1 < G) {
+                to_gpu.push(std::move(b));
+                t0 = StageClock::now();
+                continue;
+            }
+            const size_t used = reader.used();
+            b->job_last = true;
+            b->job_used = (uint32_t)used;
+            const std::vector<FileMajorReader::Cursor> start = reader.window_start();
+            FileMajorReader *rd = &reader;
+            b->reread = [rd, start](size_t p) { return rd->reread_at(start, p); };
+            reader.end();
+            to_gpu.push(std::move(b));
+            if (used < P || P < ctx.batch_sites) return;  // a file ended in this window
+        }
+    }
 }
 
 // --regions with the host reader (--inflate host, and whatever --inflate device cannot take: plain and plain-gzip files, more

@@ -49,6 +49,9 @@ extern "C" {
                                      clear: bv_p1s_stream_kernel + bv_p1s_solve16_kernel                                       */
 #define BV_FORM_PASS2_FUSED 0x4u  /* ... and that kernel streamed the variant sites' rank-sum rows too (no pass-2 launch)       */
 int bv_engine_last_launch_form(bv_engine *e, uint32_t *form);
+/* bv_slab.layout of the slab the last bv_engine_text_submit handed to the calling kernels: BV_SLAB_RPR_TAGGED where no rank of a
+ * called position is above BV_RPR_TAG_MAX_RANK (tests).  BV_ERR_INVALID_ARG before a submit that called a position. */
+int bv_engine_text_last_layout(bv_engine *e, uint32_t *layout);
 
 /* ---- per-pass HIP-event timings (bench.py) --------------------------------------------------------------------- */
 /* HIP-event timings (ms) of the last submit's kernels on the stream they ran on:

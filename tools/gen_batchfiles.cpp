@@ -2,6 +2,8 @@
 //   gen_batchfiles OUT_DIR N_SAMPLES SAMPLES_PER_FILE N_SITES [COVERAGE=0.08] [SEED=1]
 // writes OUT_DIR/bf_000.gz ... (BGZF, deflate level 1) and a tabix index OUT_DIR/bf_000.gz.tbi ... beside each, each holding SAMPLES_PER_FILE samples of every site (the reference's
 // --batch-count), with the cell statistics of SURVEY.md section 8d (coverage, phred ~ N(32, 6), 10 % of the sites carry an ALT).
+// More than 256 files are written 256 at a time, the generator run again from its seed for every such pass: the bytes are those of one
+// pass, and a cohort may have more files than the process may hold descriptors (bv_call --files-per-pass reads such a cohort).
 // g++ -O2 -std=c++17 tools/gen_batchfiles.cpp -lz -o gen_batchfiles
 #include <zlib.h>
 
@@ -19,14 +21,19 @@ int main(int argc, char **argv) {
     const std::string dir = argv[1];
     const uint32_t n = (uint32_t)std::atoi(argv[2]), per = (uint32_t)std::atoi(argv[3]), sites = (uint32_t)std::atoi(argv[4]);
     const double cov = argc > 5 ? std::atof(argv[5]) : 0.08;
-    uint64_t st = argc > 6 ? (uint64_t)std::atoll(argv[6]) * 0x9E3779B97F4A7C15ull + 1 : 0x9E3779B97F4A7C15ull;
+    const uint64_t st0 = argc > 6 ? (uint64_t)std::atoll(argv[6]) * 0x9E3779B97F4A7C15ull + 1 : 0x9E3779B97F4A7C15ull;
+    uint64_t st = st0;
     auto rnd = [&]() { st ^= st << 13; st ^= st >> 7; st ^= st << 17; return st; };
     auto uni = [&]() { return (double)(rnd() >> 11) * 0x1p-53; };
     const uint32_t nf = (n + per - 1) / per;
     std::vector<bvamd::BgzfWriter> out(nf);  // BGZF, as the reference writes its batchfiles (src/basetype_caller.cpp:428)
     std::vector<bvamd::TabixIndex> index(nf);
     std::vector<std::string> path(nf);
-    for (uint32_t f = 0; f < nf; ++f) {
+    const uint32_t kOpen = 256;  // files open at once
+    for (uint32_t lo = 0; lo < nf; lo += kOpen) {
+    const uint32_t hi = std::min(nf, lo + kOpen);
+    st = st0;
+    for (uint32_t f = lo; f < hi; ++f) {
         char name[64];
         std::snprintf(name, sizeof name, "/bf_%03u.gz", f);
         path[f] = dir + name;
@@ -59,12 +66,14 @@ int main(int argc, char **argv) {
                     sd += (rnd() & 1) ? '+' : '-';
                 } else { mq += '0'; bs += 'N'; qs += '!'; rk += '0'; sd += '.'; }
             }
+            if (f < lo || f >= hi) continue;
             row = "chr1\t" + std::to_string(1000 + s) + "\t" + ref + "\t" + std::to_string(covered) + "\t" + mq + "\t" + bs + "\t" + qs + "\t" + rk + "\t" + sd + "\n";
             const uint64_t at = out[f].tell();
             out[f].write(row);
             index[f].add_line("chr1", 1000 + (int64_t)s, at, out[f].tell());
         }
     }
-    for (uint32_t f = 0; f < nf; ++f) { out[f].close(); index[f].write(path[f] + ".tbi"); }
+    for (uint32_t f = lo; f < hi; ++f) { out[f].close(); index[f].write(path[f] + ".tbi"); }
+    }
     return 0;
 }
