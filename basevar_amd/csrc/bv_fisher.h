@@ -331,13 +331,15 @@ __device__ __forceinline__ void bv_strand_bias_tail(double two, uint32_t ref_fwd
     if (isinf(fs)) fs = 10000;
     else if (fs == 0) fs = 0.0;
     // basetype.cpp:286 multiplies `int`s; past 2^31 that is UB in the reference.  Its compiled
-    // form (gcc -O3 x86-64, pinned by tests/golden/deep_sor.npz) folds the guard
-    // `ref_rev * alt_fwd > 0` into "both factors non-zero" and divides the 32-bit wrapped products.
+    // form (gcc -O3 x86-64, pinned by tests/golden/deep_sor.npz and sor_wrap.npz) divides the 32-bit
+    // wrapped products and folds the guard `ref_rev * alt_fwd > 0` into "the wrapped product is not
+    // zero": a denominator that wraps negative is divided by, one that is a multiple of 2^32
+    // (65536 x 65536, 524288 x 8192) gives 10000 -- "both factors non-zero" divided by 0 there (inf, nan).
     // Reproduced exactly, and flagged so that a caller can tell such a value is not meaningful.
     int den = (int)(ref_rev * alt_fwd), num = (int)(ref_fwd * alt_rev);
     if ((unsigned long long)ref_rev * alt_fwd > 0x7fffffffull || (unsigned long long)ref_fwd * alt_rev > 0x7fffffffull)
         *flags |= BV_SITE_SOR_OVERFLOW;
-    double sor = (ref_rev != 0u && alt_fwd != 0u) ? (double)num / (double)den : 10000;
+    double sor = (den != 0) ? (double)num / (double)den : 10000;
     *fs_out = fs;
     *sor_out = sor;
 }

@@ -64,7 +64,7 @@ typedef enum bv_mem_kind {
 #define BV_SITE_BAD_QUAL 0x4u  /* a covered cell had phred > 93                        */
 #define BV_SITE_ZERO_FREQ 0x8u /* reference would throw at basetype.cpp:113-115        */
 #define BV_SITE_RANKSUM 0x10u  /* mapq/rpr rank sums were computed (planes present)    */
-#define BV_SITE_SOR_OVERFLOW 0x20u /* int product in SOR exceeded 2^31 (basetype.cpp:286 is UB there) */
+#define BV_SITE_SOR_OVERFLOW 0x20u /* int product in SOR exceeded 2^31 (basetype.cpp:286 is UB there; SOR is then the compiled reference's: wrapped products, 10000 where the denominator wraps to 0) */
 #define BV_SITE_RPR_RANGE 0x40u    /* per-site-tally tile jobs only: the site has > 2,048 read-position ranks beyond the announced bound, or the
                                       job > 4 Mi such cells: rpr_ranksum is NaN (fewer take an exact path at finish) */
 #define BV_SITE_LOG_APPROX 0x80u   /* a shallow site was replayed in the reference's per-sample order with the DEVICE library's log()

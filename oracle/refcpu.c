@@ -475,13 +475,18 @@ static void o_strand_bias(int ref_code, unsigned alt_mask, const uint8_t *bs, ui
     else if (fs == 0) fs = 0.0;
     /* basetype.cpp:286 multiplies `int`s.  Once a product reaches 2^31 that is signed overflow
      * (undefined behaviour); what the reference AS COMPILED (gcc -O3, x86-64: oracle/_ref) does is
-     * pinned by tests/golden/deep_sor.npz: the guard `ref_rev * alt_fwd > 0` is folded under the
-     * no-overflow assumption into "both factors non-zero", while the quotient uses the 32-bit
-     * wrapped products (imul r32).  Written out explicitly here so that this file does not depend
-     * on how a compiler treats the UB. */
+     * pinned by tests/golden/deep_sor.npz and tests/golden/sor_wrap.npz.  Observed there: the
+     * quotient uses the 32-bit wrapped products (imul r32), and the guard `ref_rev * alt_fwd > 0`
+     * behaves as "the wrapped product is not zero" -- counts being non-negative, `> 0` is folded
+     * under the no-overflow assumption into `!= 0` of that same imul.  A product that wraps
+     * negative passes it ((1000, 65537, 65535, 1000): the denominator wraps to -1, SOR -1e6), a
+     * product that is a multiple of 2^32 does not ((1000, 65536, 65536, 1000) and
+     * (0, 65536, 65536, 0) both give 10000, where "both factors non-zero" would divide by 0:
+     * inf and nan).  Written out explicitly here so that this file does not depend on how a
+     * compiler treats the UB. */
     int num = (int)((uint32_t)ref_fwd * (uint32_t)alt_rev);
     int den = (int)((uint32_t)ref_rev * (uint32_t)alt_fwd);
-    double sor = (ref_rev > 0 && alt_fwd > 0) ? (double)num / (double)den : 10000;
+    double sor = (den != 0) ? (double)num / (double)den : 10000;
     cnt[0] = ref_fwd; cnt[1] = ref_rev; cnt[2] = alt_fwd; cnt[3] = alt_rev;
     *fs_out = fs;
     *sor_out = sor;

@@ -4,6 +4,7 @@
 Run in the build container (where /root/reference exists):
 
     make -C oracle ref && python tests/golden/make_golden.py          # the fixtures below + known_answers.json
+    make -C oracle ref && python tests/golden/make_golden.py sor_wrap # that fixture alone (any names of FIXTURES)
     make -C oracle ref && python tests/golden/make_golden.py fresh    # reference_fresh/: records only (see write_fresh)
     make -C oracle ref && python tests/golden/make_golden.py pileup_rows  # reference_pileup_rows.txt.gz (see write_pileup_rows)
 
@@ -105,6 +106,30 @@ def deep_sor_slab():
             "ref_base": np.array([s[0] for s in sites], np.uint8)}
 
 
+def sor_wrap_slab():
+    """Strand-count products of SOR around 2^31 and 2^32 at 140,000 samples (the SOR tables of tests/strand_tables.py): just
+    below and just above 2^31 in the numerator and in the denominator, 65537 x 65535 (wraps to -1), 65537 x 65537 (to 131073)
+    and 65536 x 65536, which wraps to exactly 0 -- where the guard of basetype.cpp:286 as compiled gives 10000, with a
+    numerator of 0 too.  One site has a third base that only the CVG table counts.  Run-structured like deep_sor_slab."""
+    n = 140000
+    #            A+      A-      G+      G-    T+  T-   (ref A, alt G, a third base T; rest uncovered)
+    layouts = [(3, 46340, 46341, 5, 0, 0), (3, 46341, 46341, 5, 0, 0), (46340, 9, 11, 46341, 0, 0), (46341, 9, 11, 46341, 0, 0),
+               (1000, 65536, 65536, 1000, 0, 0), (65536, 9, 11, 65536, 0, 0), (0, 65536, 65536, 0, 0, 0),
+               (1000, 65537, 65535, 1000, 0, 0), (1000, 65537, 65537, 1000, 0, 0), (3, 46341, 46340, 5, 1, 0)]
+    S = len(layouts)
+    bs = np.full((S, n), N, np.uint8); q = np.zeros((S, n), np.uint8); mq = np.zeros((S, n), np.uint8); rp = np.zeros((S, n), np.uint16)
+    for s, l in enumerate(layouts):
+        o = 0
+        for k, cnt in enumerate(l):
+            bs[s, o:o + cnt] = (A, G, T)[k // 2] | (REV if k & 1 else 0)
+            q[s, o:o + cnt] = 30 + (k % 3)
+            mq[s, o:o + cnt] = 60 - k
+            rp[s, o:o + cnt] = 10 + 5 * k
+            o += cnt
+    return {"n_sites": S, "n_samples": n, "pitch": n, "n_groups": 0, "base_strand": bs, "qual": q, "mapq": mq, "rpr": rp,
+            "ref_base": np.full(S, A, np.uint8)}
+
+
 def real_bam_slab():
     """Real sequencing data: the reference's own 100-BAM test set (tests/data/140k_thalassemia_brca_bam, work.log.sh:8),
     piled up by basevar_amd/lib/bv_pileup over chr11:5246595-5248428 and the first 6 kb of the chr17 region, covered
@@ -167,6 +192,7 @@ FIXTURES = {
     # name: (slab factory, user min_af)
     "edge16": (edge_slab, 0.01),
     "deep_sor": (deep_sor_slab, 0.01),
+    "sor_wrap": (sor_wrap_slab, 0.01),
     "dense_64x500": (lambda: make_slab(64, 500, seed=11, coverage=0.6, n_groups=2, ref_n_frac=0.05), 0.01),
     "nipt_96x4000": (lambda: make_slab(96, 4000, seed=12, coverage=0.08, n_groups=2), 0.01),
     "ragged_40x1003": (lambda: make_slab(40, 1003, seed=13, coverage=0.25, n_groups=3, pitch=1008), 0.01),
@@ -233,10 +259,12 @@ def write_pileup_rows():
     print("%s (%d bytes)" % (os.path.basename(PILEUP_ROWS), os.path.getsize(PILEUP_ROWS)))
 
 
-def main():
+def main(only=()):
     ref = oracle.Reference()
     res = oracle.Restatement()
     for name, (factory, user_af) in FIXTURES.items():
+        if only and name not in only:
+            continue
         slab = factory()
         maf = res.min_af(slab["n_samples"], user_af)
         sites, groups = ref.run(slab, maf)
@@ -251,6 +279,8 @@ def main():
         np.savez_compressed(path, **out)
         print("%-16s sites=%d variants=%d -> %s (%d bytes)" % (
             name, len(sites), int(((sites["status"] & 2) != 0).sum()), os.path.basename(path), os.path.getsize(path)))
+    if only:
+        return
 
     ka = {
         "source": "reference functions of src/algorithm.h called through oracle/_ref (inputs: tests/io/test_algorithm.cpp:13-31 and SURVEY.md section 4)",
@@ -268,4 +298,7 @@ def main():
 
 
 if __name__ == "__main__":
-    {"fresh": write_fresh, "pileup_rows": write_pileup_rows}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()
+    if len(sys.argv) > 1 and sys.argv[1] in FIXTURES:
+        main(only=sys.argv[1:])
+    else:
+        {"fresh": write_fresh, "pileup_rows": write_pileup_rows}.get(sys.argv[1] if len(sys.argv) > 1 else "", main)()

@@ -1,4 +1,4 @@
-"""Strand-bias tables built by construction for the short-row Fisher tests (a test helper, not a conftest).
+"""Strand-bias tables built by construction for the Fisher tests of short and long rows (a test helper, not a conftest).
 
 FS and SOR of a short row (<= 49,152 samples) come from one of three realisations of kt_fisher_exact: the 16-lane form
 with its three regimes (candidates, four sites to a wave), the one-lane serial walk (hom-ref sites of at most 32 tables)
@@ -14,8 +14,17 @@ sits in its family, how unlikely it is -- and sized to the reads a row length ho
   exact_two_sided()   the two-sided rule in 60-digit decimal arithmetic over an exact hypergeometric pmf;
   serial_walk()       the rule as htslib walks it, in Python's doubles.
 
-BV_SITE_SOR_OVERFLOW needs a product of two cells above 2^31, i.e. more than 92,682 reads in a row: out of reach of
-short rows, it stays with tests/golden/deep_sor.npz.
+Long rows (> 49,152 samples), tile jobs and the shallow / phred-0 sites of short rows take the wave form, whose boundaries
+are its own -- one table per lane up to 64, rounds of 64 without probes up to 256, probes at span // 63 + 1 beyond:
+
+  classify_wave()   a plain-Python model of that walk (regime, probe steps, window, rounds, lanes, shift, live floor);
+  corpus_long()     corpus() plus the wave-form targets, for the row lengths of LONG_ROWS; corpus_million() a short list
+                    at 1,000,000 samples;
+  wave_labels(), required_wave_classes(), wave_site_classes()   the classes of those targets.
+
+BV_SITE_SOR_OVERFLOW needs a product of two cells above 2^31, i.e. more than 92,682 reads in a row, and a product that
+wraps to 0 more than 131,072: out of reach of short rows, they are in the long corpora (the SOR tables of _add_wave_tables)
+and in tests/golden/deep_sor.npz and sor_wrap.npz.
 """
 import decimal
 import functools
@@ -110,6 +119,198 @@ def classify(table, n_samples, min_af, depths=None, phred0=False):
             "position": "imin" if rf == imin else "imax" if rf == imax else "interior",
             "candidate": candidate, "hom_ref": hom_ref, "n_active": sum(active), "solver": solver,
             "jmin": max(0, m - n_2), "small_row": "alt" if n - n1_ <= n1_ else "ref"}
+
+
+# ------------------------------------------------------------------------------------------------ the wave form
+WAVE = 64                  # tables per round: one per lane
+WAVE_ROUNDS_MAX = 256      # more tables: a probe of log p per lane on either side first
+WAVE_PROBES = 63           # steps between the probe points of a side
+CUT_NATS = 60.0            # a tail below q * e^-60 is skipped
+SHIFT_LOG = -354.0         # ln q below this: the family is carried scaled by 2^512
+SHIFT = 512 * math.log(2.0)
+LIVE_FLOOR = -700.0        # a walk whose first table has ln p + shift below this starts at the first table that reaches it
+LNFACT_TABLE_MIN = 65536   # the engine's log-factorial table never has fewer entries; arguments beyond a table take the series
+EXP_ZERO = -745.14         # exp() of less is 0
+
+
+def log_p(t, i):
+    """ln of the hypergeometric probability of the table n11 = i in the family of t, from math.lgamma."""
+    _, _, n1_, n_1, n = family(t)
+    return _lbinom(n1_, i) + _lbinom(n - n1_, n_1 - i) - _lbinom(n, n_1)
+
+
+def classify_wave(table):
+    """How the wave form (one family on the 64 lanes of a wave: every site of a long row, every tile job, shallow and
+    phred-0 sites of short rows) walks one (n11, n12, n21, n22) table: a plain-Python model written from the comments of
+    csrc/bv_fisher.h, sharing no code with the kernels.
+
+    regime      degenerate (imin == imax), product (a row margin <= 12), lanes (R <= 64: one table per lane),
+                rounds (65..256: rounds of 64 tables over the whole family), probed (> 256: tails skipped first);
+    q0          rounds / probed: exp(ln q) is 0, the test returns before any walk (the keys below are then absent);
+    steps       probed: (span // 63 + 1) of [imin, n11] and of [n11, imax];
+    probe_window  probed: [wl, wr] as the probes leave it -- wl the last probe point of the left side below
+                ln q - 60, wr the first of the right side;
+    shifted     ln q < -354: every table carried scaled by 2^512;
+    below_floor the first table of the window has ln p + shift < -700: the walk starts at the first live table instead;
+    window      [wl, wr] as walked; rounds: its rounds of 64; lane: the lane of the observed table in its round;
+    lstar, rstar  the first table from the left / right with p >= 0.99999999 q; same_round: both in one round;
+    series      some log-factorial argument reaches 65,536 (beyond the smallest table the engine builds);
+    series_mixed  the four cells of the observed table lie on both sides of 65,536: one log p mixes table and series."""
+    t = tuple(int(x) for x in table)
+    n11 = t[0]
+    imin, imax, n1_, n_1, n = family(t)
+    R = imax - imin + 1
+    m = min(n1_, n - n1_)
+    args = (n1_, n - n1_, n, n_1, n - n_1) + t
+    out = {"R": R, "m": m, "imin": imin, "imax": imax, "series": max(args) >= LNFACT_TABLE_MIN,
+           "series_mixed": max(t) >= LNFACT_TABLE_MIN > min(t)}
+    if imin == imax:
+        out["regime"] = "degenerate"
+        return out
+    if m <= PRODUCT_MAX_MARGIN:
+        out.update(regime="product", rounds=1)
+        return out
+    if R <= WAVE:
+        out.update(regime="lanes", rounds=1, lane=n11 - imin, window=(imin, imax))
+        return out
+    out["regime"] = "rounds" if R <= WAVE_ROUNDS_MAX else "probed"
+    lq = log_p(t, n11)
+    out["q0"] = lq < EXP_ZERO
+    if out["q0"]:
+        return out
+    shift = SHIFT if lq < SHIFT_LOG else 0.0
+    wl, wr = imin, imax
+    if out["regime"] == "probed":
+        cut = lq - CUT_NATS
+        sl, sr = (n11 - imin) // WAVE_PROBES + 1, (imax - n11) // WAVE_PROBES + 1
+        below = [i for i in (imin + g * sl for g in range(WAVE)) if i <= n11 and log_p(t, i) < cut]
+        if below:
+            wl = max(below)
+        below = [i for i in (imax - g * sr for g in range(WAVE)) if i >= n11 and log_p(t, i) < cut]
+        if below:
+            wr = min(below)
+        out.update(steps=(sl, sr), probe_window=(wl, wr))
+    mode = (n1_ + 1) * (n_1 + 1) // (n + 2)
+    out["shifted"] = shift != 0.0
+    out["below_floor"] = log_p(t, wl) + shift < LIVE_FLOOR
+    if out["below_floor"]:
+        top = min(wr, mode)
+        if wl < top:
+            lo, hi = wl + 1, top
+            while lo < hi:
+                mid = lo + (hi - lo) // 2
+                if log_p(t, mid) + shift >= LIVE_FLOOR:
+                    hi = mid
+                else:
+                    lo = mid + 1
+            wl = lo
+    # L* / R*: the pmf is unimodal, the tables of at least 0.99999999 q are those of one interval around n11 and the mode
+    lo_log = lq + math.log(0.99999999)
+    a, b = wl, max(wl, min(n11, mode))
+    while a < b:
+        mid = (a + b) // 2
+        if log_p(t, mid) >= lo_log:
+            b = mid
+        else:
+            a = mid + 1
+    lstar = min(a, n11)
+    a, b = min(wr, max(n11, mode)), wr
+    while a < b:
+        mid = (a + b + 1) // 2
+        if log_p(t, mid) >= lo_log:
+            a = mid
+        else:
+            b = mid - 1
+    rstar = max(a, n11)
+    out.update(window=(wl, wr), rounds=(wr - wl) // WAVE + 1, lane=(n11 - wl) % WAVE, lstar=lstar, rstar=rstar,
+               same_round=(lstar - wl) // WAVE == (rstar - wl) // WAVE)
+    return out
+
+
+WAVE_R = (2, 63, 64, 65, 255, 256, 257)
+WAVE_SPANS = (62, 63, 64)          # span // 63 + 1 goes from 1 to 2 at 63
+WAVE_STEEP_R = (3001, 20001)
+FAR_ROUNDS = 8                     # L* and R* at least this many rounds apart
+LONG_WINDOW_ROUNDS = 100
+SOR_PAIRS = {(46340, 46341): "46340x46341", (46341, 46341): "46341x46341", (65535, 65537): "65537x65535",
+             (65537, 65537): "65537x65537"}
+
+
+def wave_labels(t, w):
+    """The wave-form classes of table t with the model's account w (classify_wave)."""
+    rf, rr, af, ar = (int(x) for x in t)
+    L = set()
+    reg = w["regime"]
+    if reg in ("lanes", "rounds", "probed") and w["R"] in WAVE_R:
+        L.add("wave:R=%d:%s" % (w["R"], reg))
+    if reg == "probed":
+        for side, d in (("left", rf - w["imin"]), ("right", w["imax"] - rf)):
+            if d in WAVE_SPANS:
+                L.add("wave:span:%s=%d:%s" % (side, d, "q0" if w["q0"] else "live"))
+    if reg in ("rounds", "probed") and not w["q0"]:
+        wl, wr = w["window"]
+        if (wr - wl + 1) % WAVE in (0, 1, 63):
+            L.add("wave:window%%64=%d" % ((wr - wl + 1) % WAVE))
+        if w["lane"] in (0, 63):
+            L.add("wave:lane=%d" % w["lane"])
+        if w["same_round"]:
+            L.add("wave:LR:same_round")
+        elif (w["rstar"] - wl) // WAVE - (w["lstar"] - wl) // WAVE >= FAR_ROUNDS:
+            L.add("wave:LR:far_apart")
+        if w["rounds"] >= LONG_WINDOW_ROUNDS:
+            L.add("wave:rounds>=100")
+        if reg == "probed" and w["R"] in WAVE_STEEP_R and 4 * w["m"] <= sum(t) and min(log_p(t, w["imin"]), log_p(t, w["imax"])) < STEEP_LOG:
+            _, _, n1_, n_1, n = family(t)
+            if abs(rf - (n1_ + 1) * (n_1 + 1) // (n + 2)) <= 1:
+                L.add("wave:steep:R=%d" % w["R"])
+        if reg == "probed" and w["below_floor"] and w["shifted"] and w["probe_window"][0] > w["imin"]:
+            L.add("wave:shifted_below_floor_after_probe")
+        if w["series_mixed"]:
+            L.add("wave:series_mixed")
+    num, den = tuple(sorted((rf, ar))), tuple(sorted((rr, af)))
+    if num in SOR_PAIRS:
+        L.add("sor:num=" + SOR_PAIRS[num])
+    if den in SOR_PAIRS:
+        L.add("sor:den=" + SOR_PAIRS[den])
+    nz, dz = rf * ar > 0 and rf * ar % 2 ** 32 == 0, rr * af > 0 and rr * af % 2 ** 32 == 0
+    if dz:
+        L.add("sor:wrap0:" + ("both" if rf * ar == 0 else "den"))
+    elif nz:
+        L.add("sor:wrap0:num")
+    return L
+
+
+def required_wave_classes():
+    """Every wave-form class a long corpus is asked to populate (what a length cannot hold is subtracted by the caller)."""
+    req = {"wave:R=%d:%s" % (R, "lanes" if R <= WAVE else "rounds" if R <= WAVE_ROUNDS_MAX else "probed") for R in WAVE_R}
+    req |= {"wave:span:%s=%d:%s" % (s, d, q) for s in ("left", "right") for d in WAVE_SPANS for q in ("live", "q0")}
+    req |= {"wave:window%64=0", "wave:window%64=1", "wave:window%64=63", "wave:lane=0", "wave:lane=63", "wave:LR:same_round",
+            "wave:LR:far_apart", "wave:rounds>=100", "wave:shifted_below_floor_after_probe", "wave:series_mixed"}
+    req |= {"wave:steep:R=%d" % R for R in WAVE_STEEP_R}
+    req |= {"sor:%s=%s" % (s, p) for s in ("num", "den") for p in ("46340x46341", "46341x46341")}
+    req |= {"sor:den=65537x65535", "sor:den=65537x65537", "sor:wrap0:den", "sor:wrap0:num", "sor:wrap0:both", "sor:vcf_cvg_differ"}
+    return req
+
+
+def overflows(t):
+    """BV_SITE_SOR_OVERFLOW of one four-column table: a product of SOR's quotient is above 2^31 - 1."""
+    return t[0] * t[3] > 0x7fffffff or t[1] * t[2] > 0x7fffffff
+
+
+def wave_site_classes(exp):
+    """The wave-form classes the oracle's records `exp` of a long corpus slab populate: every CVG table, every VCF table of
+    a variant site, and the site whose two tables differ in BV_SITE_SOR_OVERFLOW."""
+    got = set()
+    for rec in exp:
+        cv = tuple(int(x) for x in rec["cvg_sb"])
+        got |= wave_labels(cv, classify_wave(cv))
+        if rec["n_alt"] > 0:
+            vv = tuple(int(x) for x in rec["var_sb"])
+            if vv != cv:
+                got |= wave_labels(vv, classify_wave(vv))
+                if overflows(vv) != overflows(cv):
+                    got.add("sor:vcf_cvg_differ")
+    return got
 
 
 # ------------------------------------------------------------------------------------------------ classes
@@ -441,6 +642,144 @@ def corpus(n_samples):
     return C
 
 
+# ------------------------------------------------------------------------------------------------ long rows
+LONG_ROWS = (100000, 140000)   # the smallest round lengths that hold a product above 2^31 and a 65536 x 65536 wrap
+MILLION = 1000000
+
+
+def _walk_is_exact(t):
+    """The rule of the q300 tables of corpus(): the reference's own walk is the exact rule's value to 5e-10."""
+    e = exact_two_sided(t)
+    return e > 0 and abs((decimal.Decimal(serial_walk(t)) - e) / e) < decimal.Decimal("5e-10")
+
+
+def _add_wave_tables(C, exact_filter=True):
+    """The wave-form targets of a long row, added to C: regimes, probe spans, round geometry, steep families with probes,
+    the SOR products.  What the row length cannot hold goes to C.unreachable, by name."""
+    N = C.n_samples
+    # ---- R = 2, 63, 64 | 65, 255, 256 | 257: one table per lane, rounds, probes.  R - 1 ALT reads beside many REF reads is a row
+    # margin of R - 1 (> 12 from R = 14 on); R = 2 takes a column margin of 1 so that no row margin is small
+    C.add("wave R=2 (a column margin of 1)", (300, 1, 280, 0))
+    for R in WAVE_R[1:]:
+        a = R - 1
+        C.add("wave R=%d at the mode" % R, (400, 394, (a + 1) // 2, a // 2))
+    # ---- probe spans 62 | 63 | 64 on either side, q = 0 (the symmetric family) and q live (the mode beside the observed table)
+    K = 999
+    for d in WAVE_SPANS:
+        for live in (False, True):
+            W = max(d, min(N - 2 * K + d, K * K // d - 2 * K + d)) if live else d
+            C.add("wave probed R=1000, %d tables from imin, %s" % (d, "q live" if live else "q = 0"), (d, K - d, K - d, W))
+            C.add("wave probed R=1000, %d tables from imax, %s" % (d, "q live" if live else "q = 0"), (K - d, d, W, K - d))
+    # ---- round geometry on whole families (65..256 tables: the window is the family): its length mod 64, the observed table's lane
+    for R, d in ((128, 64), (129, 63), (191, 128), (255, 127), (256, 64), (193, 96)):
+        K = R - 1
+        C.add("wave rounds R=%d, observed table on lane %d" % (R, d % WAVE), (d, K - d, K - d + 300, d + 300))
+    # ---- steep families with probes: row 1 holds K reads, small against N, column 2 two thousand more; the observed table at the
+    # mode.  ln p(imin) ~ -ln C(N, K) is thousands of nats below the double range; a probe step is ~5 sigma of the family, so the
+    # probes still leave a live first table (the model says so: below_floor is False on these)
+    for R in WAVE_STEEP_R:
+        K = R - 1
+        n_2 = K + 2000
+        y = max(1, (K * n_2 + N // 2) // N)
+        t = (K - y, y, N - n_2 - (K - y), n_2 - y)
+        for end, tt in (("imin", t), ("imax", (t[1], t[0], t[3], t[2]))):
+            C.add("wave steep R=%d with probes, ln p(%s) below the double range, observed table at the mode" % (R, end), tt)
+    # ---- a window of at least 100 rounds, and the shifted family whose window starts below the live floor after a probe: both
+    # need a tiny live q inside the longest family; searched with the model over the symmetric family, kept where the
+    # reference's own walk is the exact rule (as the q300 tables of corpus())
+    K = N // 2
+    for want, name in (("wave:rounds>=100", "a window of at least 100 rounds"),
+                       ("wave:shifted_below_floor_after_probe", "shifted, first table below the live floor after a probe")):
+        found = None
+        lo_d = next(d for d in range(K // 2, 0, -1) if log10_q((d, K - d, K - d, d)) < -200.0)
+        for d in range(lo_d, 0, -max(1, K // 20000)):
+            t = (d, K - d, K - d, d)
+            lq = log10_q(t)
+            if lq < -300.0:
+                break
+            if want in wave_labels(t, classify_wave(t)) and (not exact_filter or _walk_is_exact(t)):
+                found = t
+                break
+        if found is None:
+            C.unreachable.append("wave %s: no table of the R=%d family with 1e-300 < q < 1e-200 has it" % (name, K + 1))
+        else:
+            C.add("wave %s, left of the mode" % name, found)
+            C.add("wave %s, right of the mode" % name, (found[1], found[0], found[3], found[2]))
+    # ---- SOR: products of two cells around 2^31 and 2^32 in the numerator (ref_fwd x alt_rev) and the denominator (ref_rev x alt_fwd)
+    C.add("SOR den 46340 x 46341: below 2^31, no flag", (3, 46340, 46341, 5))
+    C.add("SOR den 46341 x 46341: wraps negative", (3, 46341, 46341, 5))
+    C.add("SOR num 46340 x 46341: below 2^31, no flag", (46340, 9, 11, 46341))
+    C.add("SOR num 46341 x 46341: wraps negative", (46341, 9, 11, 46341))
+    C.add("SOR den 65536 x 65536: wraps to 0", (1000, 65536, 65536, 1000))
+    C.add("SOR num 65536 x 65536: wraps to 0", (65536, 9, 11, 65536))
+    C.add("SOR den 65536 x 65536 wraps to 0 over a numerator of 0", (0, 65536, 65536, 0))
+    C.add("SOR den 65537 x 65535: wraps to -1", (1000, 65537, 65535, 1000))
+    C.add("SOR den 65537 x 65537: wraps to 131073", (1000, 65537, 65537, 1000))
+    C.add("SOR: the CVG table overflows (46341 x 46341), the VCF table does not (46341 x 46340)", (3, 46341, 46340, 5, 1, 0))
+    return C
+
+
+@functools.lru_cache(maxsize=None)
+def corpus_long(n_samples):
+    """corpus(n_samples) plus the wave-form targets of a long row (a Corpus, built once and shared: leave it unchanged)."""
+    base = corpus(n_samples)
+    C = Corpus(int(n_samples))
+    for name, t in zip(base.names, base):
+        C.append(t)
+        C.names.append(name)
+    C.unreachable = list(base.unreachable)
+    return _add_wave_tables(C)
+
+
+@functools.lru_cache(maxsize=None)
+def corpus_million():
+    """At most 12 tables of 1,000,000 samples: the longest family at the mode and at q ~ 1e-200 on both sides, (k, 0, 0, k), a
+    steep family with probes, 524288 x 8192 in SOR's denominator, and the shifted family whose window starts below the live
+    floor after a probe (one probe step spans ~600 nats here).  The exact rule is too slow at this length: the tiny-q tables
+    keep ln q above -520, where every term that matters to 1e-9 is a normal double in the reference's own walk."""
+    N = MILLION
+    C = Corpus(N)
+    K = N // 2
+    C.add("million R=max at the mode", (K // 2, K - K // 2, K - K // 2, K // 2))
+
+    def sym(d):
+        return (d, K - d, K - d, d)
+
+    def first_d(pred):   # the largest d below the mode whose table satisfies pred (log10 q falls as d does)
+        lo, hi = 1, K // 2
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if pred(sym(mid)):
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    t = sym(first_d(lambda t: log10_q(t) <= -200.0))
+    C.add("million R=max q200, left of the mode", t)
+    C.add("million R=max q200, right of the mode", (t[1], t[0], t[3], t[2]))
+    C.add("million (k, 0, 0, k) k=500000", (K, 0, 0, K))
+    Ks, n_2 = 20000, 22000
+    y = (Ks * n_2 + N // 2) // N
+    C.add("million steep R=20001 with probes", (Ks - y, y, N - n_2 - (Ks - y), n_2 - y))
+    C.add("million SOR den 524288 x 8192: wraps to 0", (1000, 524288, 8192, 1000))
+    found = None
+    for d in range(first_d(lambda t: log10_q(t) <= -205.0), 0, -25):
+        t = sym(d)
+        if log_p(t, d) < -520.0:
+            break
+        if "wave:shifted_below_floor_after_probe" in wave_labels(t, classify_wave(t)):
+            found = t
+            break
+    if found is None:
+        C.unreachable.append("million shifted, first table below the live floor after a probe: no table with -520 < ln q < -472")
+    else:
+        C.add("million shifted, first table below the live floor after a probe, left of the mode", found)
+        # (the mirror's left span is the longer one: its probes leave a live first table, the same q on the other lanes)
+        C.add("million, the mirror of that table", (found[1], found[0], found[3], found[2]))
+    return C
+
+
 def slab(tables, n_samples, order=None):
     """One site per (ref_fwd, ref_rev, alt_fwd, alt_rev[, other_fwd, other_rev]) table: ref A, alt C, a third base G for the
     optional pair (it makes the all-sites CVG table differ from the VCF one), every read at phred 30.  `order`: site i
@@ -591,8 +930,17 @@ def serial_walk(t):
 
 
 def exact_two_sided(t):
-    """kt_fisher_exact's two-sided value of t = (n11, n12, n21, n22) in 60-digit decimal arithmetic: the first table's
-    probability from exact binomials, every next one by the exact ratio, the walk from either end up to the first table of
+    """_exact_two_sided, computed once per family and observed table: swapping the columns reverses the family and leaves the
+    two-sided sum as it is, so a table and its mirror (n12, n11, n22, n21) share one value."""
+    t = tuple(int(x) for x in t)
+    return _exact_two_sided(min(t, (t[1], t[0], t[3], t[2])))
+
+
+@functools.lru_cache(maxsize=None)
+def _exact_two_sided(t):
+    """kt_fisher_exact's two-sided value of t = (n11, n12, n21, n22) in 60-digit decimal arithmetic: every table's weight from
+    the one before by the exact ratio, the weights normalised by their sum (Vandermonde: the family's probabilities sum to 1; the
+    binomials of 100,000 reads as integers of 40,000 digits cost ten times the walk), the walk from either end up to the first table of
     at least 0.99999999 q, which is added when it is below 1.00000001 q (the doubles of those two literals)."""
     imin, imax, n1_, n_1, n = family(t)
     if imin == imax:
@@ -601,12 +949,14 @@ def exact_two_sided(t):
         ctx.prec = 60
         ctx.Emin, ctx.Emax = -10 ** 9, 10 ** 9
         D = decimal.Decimal
-        p = D(math.comb(n1_, imin) * math.comb(n - n1_, n_1 - imin)) / D(math.comb(n, n_1))
+        p = D(1)
         P = [p]
         n22 = imin + n - n1_ - n_1
         for i in range(imin, imax):
             p = p * ((n1_ - i) * (n_1 - i)) / ((i + 1) * (n22 + (i - imin) + 1))
             P.append(p)
+        total = sum(P)
+        P = [p / total for p in P]
         q = P[t[0] - imin]
         lo, hi = D(0.99999999) * q, D(1.00000001) * q
         i = 0

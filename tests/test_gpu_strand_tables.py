@@ -11,7 +11,14 @@ The corpus tables named "probed R=max q300, left / right of the mode" (q ~ 1e-30
 that found the seed of a probed tail underflowing to 0: the 16-lane form gave half the reference's p, the wave form
 p = 0 (FS 10000), on every row length.  Both forms now carry such families scaled (bv_fisher_shift, csrc/bv_fisher.h).
 The "steep end" tables (the family's first table below e^-760 beside an ordinary q) found the same zero in the wave form's
-first round: FS 10000 for the reference's 0.9 at (250, 5, 15835, 295); walks now start at their first live table."""
+first round: FS 10000 for the reference's 0.9 at (250, 5, 15835, 295); walks now start at their first live table.
+
+Long rows (the second half of this file) take the wave form on every site: the corpora of 100,000 and 140,000 samples and
+the list of 1,000,000 (strand_tables.corpus_long, corpus_million) hold its own boundaries -- 64 | 65 and 256 | 257 tables,
+probe spans 62 | 63 | 64, windows of a hundred rounds, a shifted family whose window starts below the live floor after a
+probe, log-factorial arguments on both sides of the table's end -- and the products of SOR around 2^31 and 2^32.  The
+tables "SOR den 65536 x 65536" (and 524288 x 8192 at a million samples) found SOR = inf and nan where the reference as
+compiled writes 10000: its guard is "the wrapped denominator is not 0" (bv_strand_bias_tail, csrc/bv_fisher.h)."""
 import numpy as np
 import pytest
 
@@ -23,7 +30,7 @@ from basevar_amd.synth import tag_ranks
 from test_gpu_parity import bv, check, oracle_run  # noqa: F401  (bv: the module fixture)
 from test_gpu_tagged import same
 from test_gpu_text_rows import check as text_check
-from test_gpu_value_domain import P2_TAIL_DMA, TILE_STATE, WAVE_SOLVER, expected_form, lrt, short_row_form
+from test_gpu_value_domain import P2_TAIL_DMA, TILE_STATE, WAVE_SOLVER, expected_form, long_row_form, lrt, short_row_form
 
 ROWS = (1500, 2048, 4096, 4097, 16385, 49152, 49153)
 _built = {}
@@ -169,3 +176,121 @@ def test_tables_as_text_rows(bv, restatement):
     got = text_check(slab, [512] * 4)
     assert got.positions.size == slab["n_sites"]
     hold(got, exp)
+
+
+# ------------------------------------------------------------------------------------------------ long rows: the wave form
+SOR_OVERFLOW = 0x20  # BV_SITE_SOR_OVERFLOW
+
+
+def built_long(restatement, n, tables=None, key=None):
+    """(corpus, slab, the oracle's (records, group records, margins)) of a long corpus (or of `tables` at n samples, cached
+    under `key`): built and solved by the oracle once per session, shared and left unchanged."""
+    key = key or n
+    if key not in _built:
+        C = tables if tables is not None else st.corpus_million() if n == st.MILLION else st.corpus_long(n)
+        slab = st.slab(C, n)
+        exp = oracle_run(restatement, slab, restatement.min_af(n), n_threads=16)
+        e = exp[0]
+        wrapped = 0
+        for i, t in enumerate(C):
+            cv = cvg_table(t)
+            assert tuple(e["cvg_sb"][i]) == cv
+            if cv[1] * cv[2] % 2 ** 32 == 0:    # an empty cell, or a product that wraps to 0: no division
+                assert e["cvg_sor"][i] == 10000.0, t
+                wrapped += cv[1] * cv[2] > 0
+            assert bool(e["status"][i] & SOR_OVERFLOW) == (st.overflows(cv) or (e["n_alt"][i] > 0 and st.overflows(tuple(int(x) for x in e["var_sb"][i])))), t
+        assert wrapped >= (1 if n >= 133072 and tables is None else 0)
+        assert np.isfinite(e["cvg_sor"]).all()
+        _built[key] = (C, slab, exp)
+    return _built[key]
+
+
+def hold_long(got, exp):
+    """The oracle's records, no site excused as a tie, and BV_SITE_SOR_OVERFLOW the oracle's on every site (which the
+    status mask of tests/parity.py leaves out)."""
+    hold(got, exp)
+    assert np.array_equal(got.sites["status"] & SOR_OVERFLOW, exp[0]["status"] & SOR_OVERFLOW), \
+        np.nonzero((got.sites["status"] ^ exp[0]["status"]) & SOR_OVERFLOW)[0].tolist()
+
+
+@pytest.mark.parametrize("n", st.LONG_ROWS)
+def test_long_tables_with_and_without_the_team_tail(bv, restatement, n):
+    """The long corpora through the long-row kernel.  With ~150 sites every deep site of the default launch is a team job: its
+    Fisher tests run on a helper wave, the VCF table crossing to it through the team's shared block (csrc/bv_pass1_team.h);
+    under BV_FLAG_LONG_ROW_FORM(2) the solver wave runs them alone.  Both the oracle's records, and each other's byte for byte."""
+    C, slab, exp = built_long(restatement, n)
+    base, form = lrt(bv, slab)
+    assert form == expected_form(n), "form 0x%x" % form
+    hold_long(base, exp)
+    alone, form = lrt(bv, slab, long_row_form(2))
+    assert form == expected_form(n)
+    hold_long(alone, exp)
+    same(base, alone)
+
+
+@pytest.mark.parametrize("n", st.LONG_ROWS)
+def test_long_tables_beyond_the_log_factorial_table(bv, restatement, n):
+    """An engine created for 1,000 samples keeps a log-factorial table of 65,536 entries: every argument beyond it takes the
+    series, and the tables whose cells lie on both sides of 65,536 mix the two inside one log p.  Held to the oracle at the
+    parity bar (not to the full table's bytes: the series is its own rounding)."""
+    C, slab, exp = built_long(restatement, n)
+    assert sum(st.classify_wave(cvg_table(t))["series_mixed"] for t in C) >= 8
+    eng = bv.BaseTypeEngine(max_sites=slab["n_sites"], min_af_value=bv.min_af(n), device=0, max_samples=1000)
+    try:
+        got = eng.lrt(slab)
+    finally:
+        eng.close()
+    hold_long(got, exp)
+
+
+def test_long_tables_in_tile_jobs(bv, restatement):
+    """The corpus of 100,000 samples as tile jobs of width 25,000: joined rows are the row submit's records byte for byte; the
+    per-site-tally finish has Fisher and SOR call sites of its own and is held to the oracle."""
+    n = 100000
+    C, slab, exp = built_long(restatement, n)
+    for flags in (0, TILE_STATE):
+        eng = bv.BaseTypeEngine(max_sites=slab["n_sites"], min_af_value=bv.min_af(n), device=0, flags=flags)
+        try:
+            t = eng.lrt_tiles(slab, 25000)
+        finally:
+            eng.close()
+        hold_long(t, exp)
+        if flags == 0:
+            same(lrt(bv, slab)[0], t)
+
+
+def test_million_sample_tables_as_rows_and_tiles(bv, restatement):
+    """strand_tables.corpus_million: the family of 500,001 tables at the mode and at q ~ 1e-200, probe steps of ~4,000 tables
+    and windows of ~300 rounds, the shifted family whose window starts below the live floor after a probe, 524288 x 8192
+    in SOR's denominator -- as one row submit and as tile jobs of width 50,000 in both realisations."""
+    n = st.MILLION
+    C, slab, exp = built_long(restatement, n)
+    rows, form = lrt(bv, slab)
+    assert form == expected_form(n)
+    hold_long(rows, exp)
+    for flags in (0, TILE_STATE):
+        eng = bv.BaseTypeEngine(max_sites=slab["n_sites"], min_af_value=bv.min_af(n), device=0, flags=flags)
+        try:
+            t = eng.lrt_tiles(slab, 50000)
+        finally:
+            eng.close()
+        hold_long(t, exp)
+        if flags == 0:
+            same(rows, t)
+
+
+def test_wave_tables_under_the_wave_solver_on_short_rows(bv, restatement):
+    """The wave form is the short rows' form too, for shallow sites and phred-0 calls: the wave-regime, probe-span and
+    round-geometry tables that fit 16,385 reads, every candidate on the one-site-per-wave solver (BV_FLAG_WAVE_SOLVER)."""
+    n = 16385
+    L = st.corpus_long(st.LONG_ROWS[0])
+    tables = [t for name, t in zip(L.names, L) if name.startswith("wave") and sum(t) <= n]
+    got = set()
+    for t in tables:
+        got |= st.wave_labels(t, st.classify_wave(t))
+        assert st.classify(t, n, restatement.min_af(n))["candidate"], t
+    assert got >= {c for c in st.required_wave_classes() if c.startswith(("wave:R=", "wave:span:", "wave:window", "wave:lane"))}
+    C, slab, exp = built_long(restatement, n, tables=tables, key=(n, "wave tables"))
+    base, form = lrt(bv, slab, WAVE_SOLVER)
+    assert form == expected_form(n, WAVE_SOLVER)
+    hold_long(base, exp)
